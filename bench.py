@@ -18,6 +18,11 @@ accumulate, WGAN-GP double backward, Gaussian noise, Adam.  Weak scaling: every 
 own 128 images; the clipped+noised gradients are all-reduced over RCCL.
 
 Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for the roofline accounting).
+
+A plain run sets up, warms up, times the --steps steps of the headline step and prints the line (metric, value, unit, ms_per_step,
+dtype, configuration).  --full adds everything else the line has carried: the launch-by-launch instrumented warm-up steps
+(per-kernel tables, roofline figures), the eagerly launched region, the other arithmetic and the bf16 128x128 variant, the full
+train() loop and the CPU baseline.  --dump-outputs DIR writes what the timed step computed in its last step as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -111,6 +116,45 @@ def cpu_baseline():
             "sample": "%d oracle D-step(s) (config 3) at bs=128 after a bs=8 warm-up, %.1f s" % (n_steps, dt)}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_outputs(tr):
+    """What a caller of the timed step holds after its last step: the step's observables (Trainer.last: losses, critic scores,
+    generated images, clip statistics) and the critic's updated parameters, by name."""
+    out = {}
+    for k, v in sorted(tr.last.items()):
+        if torch.is_tensor(v):
+            out["last." + k] = v
+        elif isinstance(v, (list, tuple)):
+            out.update(("last.%s.%d" % (k, i), t) for i, t in enumerate(v) if torch.is_tensor(t))
+    out.update(("D." + n, p) for n, p in tr.D.named_parameters())
+    return out
+
+
+def dump_outputs(outputs, out_dir, limit=DUMP_LIMIT_BYTES):
+    """Write every tensor of `outputs` as out_dir/<name>.npy: float64 stays float64, every other type becomes float32.  Above
+    `limit` bytes in all, the arrays are visited smallest first and one larger than its share of the bytes still free keeps a fixed
+    sample of that share (flat indices drawn by a generator seeded from its name, sorted), so that two runs write the same elements
+    and small outputs stay whole.  Returns {name: shape written}."""
+    import zlib
+    import numpy as np
+    arrs = {k: t.detach().to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32).numpy() for k, t in outputs.items()}
+    free = limit - 256 * len(arrs)                     # .npy headers
+    if sum(x.nbytes for x in arrs.values()) > free:
+        keys = sorted(arrs, key=lambda k: (arrs[k].nbytes, k))
+        for i, k in enumerate(keys):
+            x, share = arrs[k], free // (len(keys) - i)
+            if x.nbytes > share:
+                idx = np.sort(np.random.default_rng(zlib.crc32(k.encode())).choice(x.size, share // x.itemsize, replace=False))
+                arrs[k] = x.reshape(-1)[idx]
+            free -= arrs[k].nbytes
+    os.makedirs(out_dir, exist_ok=True)
+    for k, x in arrs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), x)
+    return {k: x.shape for k, x in arrs.items()}
+
+
 def _free_port():
     import socket
     with socket.socket() as sk:
@@ -154,10 +198,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--loop-steps", type=int, default=10, help="iterations of the full train() loop timed for the secondary metric (0 = skip)")
-    ap.add_argument("--no-variants", action="store_true", help="skip the hip_graph / fp32_auto variant passes (profiling runs)")
-    ap.add_argument("--dump-shapes", type=str, default="", help="write the per-kernel, per-shape launch table (HIP-event times) to this file")
+    ap.add_argument("--full", action="store_true", help="besides the headline, measure what a plain run leaves out: instrumented warm-up "
+                    "steps (per-kernel tables, roofline), the eager region, the variants, the train() loop and the CPU baseline")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR", help="after the timed steps, write what the timed step "
+                    "computed in its last step (Trainer.last, the critic's parameters) as DIR/<name>.npy, float32, at most 64 MB")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--loop-steps", type=int, default=10, help="(--full) iterations of the full train() loop timed for the secondary metric (0 = skip)")
+    ap.add_argument("--no-variants", action="store_true", help="(--full) skip the hip_graph / fp32_auto variant passes (profiling runs)")
+    ap.add_argument("--dump-shapes", type=str, default="", help="(--full) write the per-kernel, per-shape launch table (HIP-event times) to this file")
     ap.add_argument("--opt", type=str, default="", help="extra train.py flags for experiments, e.g. '--grad_sample_dtype bf16' "
                     "(the headline line is the run WITHOUT this)")
     ap.add_argument("--compute", type=str, default="fp32_auto", choices=["fp32_auto", "fp32"],
@@ -166,6 +214,8 @@ def main():
                          "everywhere: the round 1-3 headline, reported as variants.fp32_exact otherwise)")
     ap.add_argument("--launcher-selftest", type=str, default="", choices=["", "ok", "fail"], help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.dump_shapes and not a.full:
+        ap.error("--dump-shapes needs --full (the launch table comes from its instrumented warm-up steps)")
 
     in_torchrun = "WORLD_SIZE" in os.environ and "RANK" in os.environ
     if a.gpus > 1 and not in_torchrun:
@@ -210,123 +260,146 @@ def main():
             dt_ = float(t)
         return dt_
 
-    # Warm-up.  Its last steps are instrumented launch by launch (HIP events on the launch stream): they name the dominant
-    # device kernel and give the per-kernel tables.  Inside the eager TIMED region only that kernel's launches carry events — two
-    # event records per launch cost the host ~5 us, i.e. ~1 ms per step if every one of the ~170 launches were watched.
-    n_probe = min(3, a.warmup)
-    for _ in range(a.warmup - n_probe):
-        step()
-    torch.cuda.synchronize()
-    probe = ops.LaunchTimer()
-    ops.set_launch_timer(probe)
-    # the per-kernel tables are ISOLATED measurements: the step's second stream (gradient-penalty branch beside the critic pass) is
-    # and the clip phase's second stream are switched off for these steps only — with them, concurrent kernels share the CUs and each one's event time is stretched
-    saved_env = {k: os.environ.get(k) for k in ("CSLGAN_GP_STREAM", "CSLGAN_CLIP_STREAM")}
-    os.environ.update({k: "0" for k in saved_env})
-    for _ in range(n_probe):
-        # A few milliseconds of head start for the host: an event pair brackets the launch CALL, so on an idle GPU the pair also times the
-        # host's way from the first record to the launch (the generator's first small kernels read 0.3-0.6 ms for 10-30 us of work).
-        # With the queue ahead of the device every pair times its kernel.
-        torch.cuda._sleep(int(6e-3 * 2.1e9))
-        step()
-    torch.cuda.synchronize()
-    for k, v in saved_env.items():
-        if v is None:
-            del os.environ[k]
-        else:
-            os.environ[k] = v
-    ops.set_launch_timer(None)
-    pk = {k: v for k, v in probe.summary(by_kernel=True).items() if v["exec_flop"] > 0}
-    dom_name = max(pk.values(), key=lambda k: k["ms"])["name"] if pk else None
-    # Region A — the step launched eagerly, the dominant kernel's launches bracketed by HIP events (the roofline figure)
-    timer = ops.LaunchTimer(only=probe.keys_of_kernel(dom_name) if dom_name else set())
-    ops.set_launch_timer(timer)
-    dt_eager = time_region(step, a.steps)
-    ops.set_launch_timer(None)
+    # --full only.  A plain run warms up on the headline step itself (below) and times nothing else.
+    probe = timer = dom_name = dt_eager = None
+    n_probe = 0
+    if a.full:
+        # Warm-up.  Its last steps are instrumented launch by launch (HIP events on the launch stream): they name the dominant
+        # device kernel and give the per-kernel tables.  Inside the eager TIMED region only that kernel's launches carry events — two
+        # event records per launch cost the host ~5 us, i.e. ~1 ms per step if every one of the ~170 launches were watched.
+        n_probe = min(3, a.warmup)
+        for _ in range(a.warmup - n_probe):
+            step()
+        torch.cuda.synchronize()
+        probe = ops.LaunchTimer()
+        ops.set_launch_timer(probe)
+        # the per-kernel tables are ISOLATED measurements: the step's second stream (gradient-penalty branch beside the critic pass) is
+        # and the clip phase's second stream are switched off for these steps only — with them, concurrent kernels share the CUs and each one's event time is stretched
+        saved_env = {k: os.environ.get(k) for k in ("CSLGAN_GP_STREAM", "CSLGAN_CLIP_STREAM")}
+        os.environ.update({k: "0" for k in saved_env})
+        for _ in range(n_probe):
+            # A few milliseconds of head start for the host: an event pair brackets the launch CALL, so on an idle GPU the pair also times the
+            # host's way from the first record to the launch (the generator's first small kernels read 0.3-0.6 ms for 10-30 us of work).
+            # With the queue ahead of the device every pair times its kernel.
+            torch.cuda._sleep(int(6e-3 * 2.1e9))
+            step()
+        torch.cuda.synchronize()
+        for k, v in saved_env.items():
+            if v is None:
+                del os.environ[k]
+            else:
+                os.environ[k] = v
+        ops.set_launch_timer(None)
+        pk = {k: v for k, v in probe.summary(by_kernel=True).items() if v["exec_flop"] > 0}
+        dom_name = max(pk.values(), key=lambda k: k["ms"])["name"] if pk else None
+        # Region A — the step launched eagerly, the dominant kernel's launches bracketed by HIP events (the roofline figure)
+        timer = ops.LaunchTimer(only=probe.keys_of_kernel(dom_name) if dom_name else set())
+        ops.set_launch_timer(timer)
+        dt_eager = time_region(step, a.steps)
+        ops.set_launch_timer(None)
     def finish(dt, launch_mode, graph_err, variant, loop, with_cpu=True):
         """Assemble and print the ONE JSON line (rank 0) from the instrumented / eager regions plus whatever came after them."""
         if rank != 0:
             return
         ips = world * B * a.steps / dt
-        n_pr = max(n_probe, 1)
-        entries = probe.summary()                                   # per-kernel tables: the instrumented warm-up steps
-        kernels = probe.summary(by_kernel=True)
-        shapes = probe.summary(by_kernel=True, by_shape=True)
-        timed = timer.summary(by_kernel=True)                       # the dominant kernel, inside the timed region
-        timed_shapes = timer.summary(by_kernel=True, by_shape=True)
-        # roofline: the dominant device KERNEL by summed HIP-event time (names as rocprofv3 lists them)
-        dom = timed.get(dom_name) if dom_name else None
-        roof = None
-        if dom:
-            traffic, traffic_src = None, None
-            try:        # fabric bytes per launch of that kernel from the newest committed rocprofv3 PMC passes (scripts/collect_profiles.sh)
-                import glob
-                src = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_traffic.json")))[-1]
-                with open(src) as f:
-                    pk = {k.replace(" ", ""): v for k, v in json.load(f)["per_kernel"].items()}
-                v = pk.get(dom["name"].replace(" ", ""))
-                traffic = None if v is None else round((v["fetch_MB_per_launch"] + v["write_MB_per_launch"]) * 1e6)
-                traffic_src = "profiles/" + os.path.basename(src) + " (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, not measured in this run)"
-            except Exception:
-                traffic = None
-            # a bf16x3 kernel issues SIX bf16 MFMAs per logical fp32 multiply-add step: its executed matrix FLOP are 6x the logical
-            x3_kernel = "bf16x3" in dom["name"] or ("igemm_x3" in dom["name"] and ",3," in dom["name"])
-            mfma_mult = 6.0 if x3_kernel else 1.0
-            ach = mfma_mult * dom["exec_flop"] / (dom["ms"] * 1e-3) / 1e12
-            # bf16 matrix-core kernels: the fp32-tensor family of csrc/igemm_bf16.hip and the bf16-stored family of csrc/igemm_bf16s.hip
-            on_bf16 = "bf16" in dom["name"] or any(t in dom["name"] for t in ("igemm_kcs_kernel", "igemm_mcs_kernel", "igemm_mcs_tr_kernel", "igemm_halos_kernel",
-                                                                             "igemm_x3h_kernel", "igemm_x3w_kernel"))
-            peak = PEAK_BF16_MFMA_TFLOPS if on_bf16 else PEAK_FP32_MFMA_TFLOPS
-            worst = sorted((v for k, v in timed_shapes.items() if k.startswith(dom["name"])), key=lambda v: -v["ms"])
-            roof = {"bound": "mfma", "kernel": dom["name"], "achieved": round(ach, 2), "peak": peak, "unit": "TFLOP/s",
-                    "frac": round(ach / peak, 4), "traffic": traffic, "traffic_from": traffic_src,
-                    "algorithmic_bytes_per_launch": round(dom["bytes"] / dom["n"]),
-                    "flop_per_launch_executed": round(mfma_mult * dom["exec_flop"] / dom["n"]),
-                    "logical_fp32_tflops": round(dom["exec_flop"] / (dom["ms"] * 1e-3) / 1e12, 2),
-                    "reference_algorithmic_tflops": round(dom["flop"] / (dom["ms"] * 1e-3) / 1e12, 2),
-                    "note": "achieved = FLOP the kernel executes / its summed HIP-event time" + (
-                                " — a three-piece (x3) kernel issues SIX bf16 MFMAs per logical fp32 multiply-add step, so its executed matrix FLOP are "
-                                "6x logical_fp32_tflops and the peak is the dense bf16 MFMA rate" if x3_kernel else "") +
-                            "; reference_algorithmic_tflops charges the UpsampleConv layers at the reference's 4x redundant channel count and "
-                            "is NOT a roofline fraction",
-                    "launches_per_step": dom["n"] / a.steps, "avg_launch_ms": round(dom["ms"] / dom["n"], 4),
-                    "share_of_step": round(dom["ms"] / (dt_eager * 1e3), 3),
-                    "measured_in": "HIP events around this kernel's launches over the %d eagerly launched timed steps (%.3f ms/step)%s" % (
-                        a.steps, dt_eager / a.steps * 1e3,
-                        "; the headline region replays the same launches from a HIP graph, where events cannot be placed" if launch_mode.startswith("hip_graph") else ""),
-                    "launch_shapes": {v["name"][len(dom["name"]) + 1:]: {"n_per_step": v["n"] / a.steps, "avg_ms": round(v["ms"] / v["n"], 4),
-                                                                         "tflops": round(v["exec_flop"] / (v["ms"] * 1e-3) / 1e12, 1)}
-                                      for v in worst[:8]}}
-        # the HBM group (SURVEY.md §8d): clip_accum_noise over the materialised per-sample gradients / slabs, from the instrumented steps
-        roof_hbm = None
-        ck = kernels.get("clip_accum_noise_kernel<float>")
-        if ck and ck["ms"] > 0:
-            gbs = ck["bytes"] / (ck["ms"] * 1e-3) / 1e9
-            roof_hbm = {"bound": "hbm", "kernel": "clip_accum_noise_kernel<float>", "achieved": round(gbs, 1), "peak": PEAK_HBM_GBPS, "unit": "GB/s",
-                        "frac": round(gbs / PEAK_HBM_GBPS, 4), "launches_per_step": ck["n"] / n_pr, "MB_per_step": round(ck["bytes"] / n_pr / 1e6, 1),
-                        "avg_launch_us": round(ck["ms"] / ck["n"] * 1e3, 2),
-                        "note": "algorithmic bytes of each launch (rows x row length read once + one output row) / HIP-event time, instrumented "
-                                "warm-up steps; SURVEY §8d's materialised-path figure is 34.5 MB/img/clipped pass — ghost clipping materialises only "
-                                "conv1 + conv2 (5 %% of the parameters), so the kernel moves %.1f MB per step instead of 4.4 GB and is launch-latency "
-                                "sized" % (ck["bytes"] / n_pr / 1e6)}
-        exec_flop_step = sum(v["exec_flop"] for v in kernels.values()) / n_pr
-        if a.dump_shapes:
-            with open(a.dump_shapes, "w") as f:
-                f.write("# HIP-event times of the launch-by-launch instrumented steps (eager, one stream, %d step(s)).  An event pair brackets the launch\n"
-                        "# CALL: for a few short launches at the head of the generator (its first linear layer, the first 1x1 / 5x5 convs after a\n"
-                        "# normalisation) the pair reads 0.2-0.6 ms where rocprofv3 --kernel-trace of the same command shows 10-250 us\n"
-                        "# (profiles/*kernel_stats*.csv, authoritative for kernel durations; the headline region replays a HIP graph).\n" % n_pr)
-                for k, v in sorted(shapes.items(), key=lambda kv: -kv[1]["ms"]):
-                    f.write("%-78s n/step %5.1f  avg_ms %8.4f  ms/step %7.3f  %s\n" % (
-                        k, v["n"] / n_pr, v["ms"] / v["n"], v["ms"] / n_pr,
-                        ("%6.1f TF" % (v["exec_flop"] / (v["ms"] * 1e-3) / 1e12)) if v["exec_flop"] else ("%7.1f GB/s" % (v["bytes"] / (v["ms"] * 1e-3) / 1e9))))
         bf16 = getattr(opt, "compute_dtype", "fp32") == "bf16"
-        step_peak = PEAK_BF16_MFMA_TFLOPS if bf16 else PEAK_FP32_MFMA_TFLOPS
-        # mixed arithmetic (fp32_auto / bf16x3): a launch on a three-piece kernel executes 6 bf16 MFMA FLOP per logical fp32 FLOP and is
-        # priced against the dense bf16 peak, every other launch against the fp32 MFMA peak; the sum is the step's matrix-pipe floor
-        is_x3 = lambda k: "bf16x3" in k or ("igemm_x3" in k and ",3," in k)
-        x3_flop = sum(v["exec_flop"] for k, v in kernels.items() if is_x3(k)) / n_pr
-        mfma_floor_s = 6.0 * x3_flop / (PEAK_BF16_MFMA_TFLOPS * 1e12) + (exec_flop_step - x3_flop) / (step_peak * 1e12)
+        fig, tables = {}, {}
+        if a.full:          # the instrumented warm-up steps and the eager region A: per-kernel tables, roofline, step FLOP
+            n_pr = max(n_probe, 1)
+            entries = probe.summary()                                   # per-kernel tables: the instrumented warm-up steps
+            kernels = probe.summary(by_kernel=True)
+            shapes = probe.summary(by_kernel=True, by_shape=True)
+            timed = timer.summary(by_kernel=True)                       # the dominant kernel, inside the timed region
+            timed_shapes = timer.summary(by_kernel=True, by_shape=True)
+            # roofline: the dominant device KERNEL by summed HIP-event time (names as rocprofv3 lists them)
+            dom = timed.get(dom_name) if dom_name else None
+            roof = None
+            if dom:
+                traffic, traffic_src = None, None
+                try:        # fabric bytes per launch of that kernel from the newest committed rocprofv3 PMC passes (scripts/collect_profiles.sh)
+                    import glob
+                    src = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_traffic.json")))[-1]
+                    with open(src) as f:
+                        pk = {k.replace(" ", ""): v for k, v in json.load(f)["per_kernel"].items()}
+                    v = pk.get(dom["name"].replace(" ", ""))
+                    traffic = None if v is None else round((v["fetch_MB_per_launch"] + v["write_MB_per_launch"]) * 1e6)
+                    traffic_src = "profiles/" + os.path.basename(src) + " (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, not measured in this run)"
+                except Exception:
+                    traffic = None
+                # a bf16x3 kernel issues SIX bf16 MFMAs per logical fp32 multiply-add step: its executed matrix FLOP are 6x the logical
+                x3_kernel = "bf16x3" in dom["name"] or ("igemm_x3" in dom["name"] and ",3," in dom["name"])
+                mfma_mult = 6.0 if x3_kernel else 1.0
+                ach = mfma_mult * dom["exec_flop"] / (dom["ms"] * 1e-3) / 1e12
+                # bf16 matrix-core kernels: the fp32-tensor family of csrc/igemm_bf16.hip and the bf16-stored family of csrc/igemm_bf16s.hip
+                on_bf16 = "bf16" in dom["name"] or any(t in dom["name"] for t in ("igemm_kcs_kernel", "igemm_mcs_kernel", "igemm_mcs_tr_kernel", "igemm_halos_kernel",
+                                                                                 "igemm_x3h_kernel", "igemm_x3w_kernel"))
+                peak = PEAK_BF16_MFMA_TFLOPS if on_bf16 else PEAK_FP32_MFMA_TFLOPS
+                worst = sorted((v for k, v in timed_shapes.items() if k.startswith(dom["name"])), key=lambda v: -v["ms"])
+                roof = {"bound": "mfma", "kernel": dom["name"], "achieved": round(ach, 2), "peak": peak, "unit": "TFLOP/s",
+                        "frac": round(ach / peak, 4), "traffic": traffic, "traffic_from": traffic_src,
+                        "algorithmic_bytes_per_launch": round(dom["bytes"] / dom["n"]),
+                        "flop_per_launch_executed": round(mfma_mult * dom["exec_flop"] / dom["n"]),
+                        "logical_fp32_tflops": round(dom["exec_flop"] / (dom["ms"] * 1e-3) / 1e12, 2),
+                        "reference_algorithmic_tflops": round(dom["flop"] / (dom["ms"] * 1e-3) / 1e12, 2),
+                        "note": "achieved = FLOP the kernel executes / its summed HIP-event time" + (
+                                    " — a three-piece (x3) kernel issues SIX bf16 MFMAs per logical fp32 multiply-add step, so its executed matrix FLOP are "
+                                    "6x logical_fp32_tflops and the peak is the dense bf16 MFMA rate" if x3_kernel else "") +
+                                "; reference_algorithmic_tflops charges the UpsampleConv layers at the reference's 4x redundant channel count and "
+                                "is NOT a roofline fraction",
+                        "launches_per_step": dom["n"] / a.steps, "avg_launch_ms": round(dom["ms"] / dom["n"], 4),
+                        "share_of_step": round(dom["ms"] / (dt_eager * 1e3), 3),
+                        "measured_in": "HIP events around this kernel's launches over the %d eagerly launched timed steps (%.3f ms/step)%s" % (
+                            a.steps, dt_eager / a.steps * 1e3,
+                            "; the headline region replays the same launches from a HIP graph, where events cannot be placed" if launch_mode.startswith("hip_graph") else ""),
+                        "launch_shapes": {v["name"][len(dom["name"]) + 1:]: {"n_per_step": v["n"] / a.steps, "avg_ms": round(v["ms"] / v["n"], 4),
+                                                                             "tflops": round(v["exec_flop"] / (v["ms"] * 1e-3) / 1e12, 1)}
+                                          for v in worst[:8]}}
+            # the HBM group (SURVEY.md §8d): clip_accum_noise over the materialised per-sample gradients / slabs, from the instrumented steps
+            roof_hbm = None
+            ck = kernels.get("clip_accum_noise_kernel<float>")
+            if ck and ck["ms"] > 0:
+                gbs = ck["bytes"] / (ck["ms"] * 1e-3) / 1e9
+                roof_hbm = {"bound": "hbm", "kernel": "clip_accum_noise_kernel<float>", "achieved": round(gbs, 1), "peak": PEAK_HBM_GBPS, "unit": "GB/s",
+                            "frac": round(gbs / PEAK_HBM_GBPS, 4), "launches_per_step": ck["n"] / n_pr, "MB_per_step": round(ck["bytes"] / n_pr / 1e6, 1),
+                            "avg_launch_us": round(ck["ms"] / ck["n"] * 1e3, 2),
+                            "note": "algorithmic bytes of each launch (rows x row length read once + one output row) / HIP-event time, instrumented "
+                                    "warm-up steps; SURVEY §8d's materialised-path figure is 34.5 MB/img/clipped pass — ghost clipping materialises only "
+                                    "conv1 + conv2 (5 %% of the parameters), so the kernel moves %.1f MB per step instead of 4.4 GB and is launch-latency "
+                                    "sized" % (ck["bytes"] / n_pr / 1e6)}
+            exec_flop_step = sum(v["exec_flop"] for v in kernels.values()) / n_pr
+            if a.dump_shapes:
+                with open(a.dump_shapes, "w") as f:
+                    f.write("# HIP-event times of the launch-by-launch instrumented steps (eager, one stream, %d step(s)).  An event pair brackets the launch\n"
+                            "# CALL: for a few short launches at the head of the generator (its first linear layer, the first 1x1 / 5x5 convs after a\n"
+                            "# normalisation) the pair reads 0.2-0.6 ms where rocprofv3 --kernel-trace of the same command shows 10-250 us\n"
+                            "# (profiles/*kernel_stats*.csv, authoritative for kernel durations; the headline region replays a HIP graph).\n" % n_pr)
+                    for k, v in sorted(shapes.items(), key=lambda kv: -kv[1]["ms"]):
+                        f.write("%-78s n/step %5.1f  avg_ms %8.4f  ms/step %7.3f  %s\n" % (
+                            k, v["n"] / n_pr, v["ms"] / v["n"], v["ms"] / n_pr,
+                            ("%6.1f TF" % (v["exec_flop"] / (v["ms"] * 1e-3) / 1e12)) if v["exec_flop"] else ("%7.1f GB/s" % (v["bytes"] / (v["ms"] * 1e-3) / 1e9))))
+            step_peak = PEAK_BF16_MFMA_TFLOPS if bf16 else PEAK_FP32_MFMA_TFLOPS
+            # mixed arithmetic (fp32_auto / bf16x3): a launch on a three-piece kernel executes 6 bf16 MFMA FLOP per logical fp32 FLOP and is
+            # priced against the dense bf16 peak, every other launch against the fp32 MFMA peak; the sum is the step's matrix-pipe floor
+            is_x3 = lambda k: "bf16x3" in k or ("igemm_x3" in k and ",3," in k)
+            x3_flop = sum(v["exec_flop"] for k, v in kernels.items() if is_x3(k)) / n_pr
+            mfma_floor_s = 6.0 * x3_flop / (PEAK_BF16_MFMA_TFLOPS * 1e12) + (exec_flop_step - x3_flop) / (step_peak * 1e12)
+            fig = {
+                "step_gflop_executed_per_image": round(exec_flop_step / B / 1e9, 3),
+                "step_tflops_executed": round(exec_flop_step / (dt / a.steps) / 1e12, 2),
+                ("step_frac_of_bf16_mfma_peak" if bf16 else "step_frac_of_fp32_mfma_peak"): round(exec_flop_step / (dt / a.steps) / 1e12 / step_peak, 4),
+                "step_share_of_flop_on_x3_kernels": round(x3_flop / max(exec_flop_step, 1.0), 4),
+                "step_mfma_floor_ms": round(mfma_floor_s * 1e3, 3),
+                "step_frac_of_mfma_roofline": round(mfma_floor_s / (dt / a.steps), 4),
+            }
+            tables = {
+                "tables_from": "%d launch-by-launch instrumented warm-up step(s) run on ONE stream (isolated kernel times); roofline from the "
+                               "eagerly launched timed region; both timed regions run the step's two streams" % n_pr,
+                "entries_ms_per_step": {k: round(v["ms"] / n_pr, 3) for k, v in sorted(entries.items(), key=lambda kv: -kv[1]["ms"])},
+                "kernels_ms_per_step": {k: {"ms": round(v["ms"] / n_pr, 3), "n": v["n"] / n_pr,
+                                            "tflops": round(v["exec_flop"] / (v["ms"] * 1e-3) / 1e12, 1) if v["exec_flop"] else None,
+                                            "GBps": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1) if not v["exec_flop"] else None}
+                                        for k, v in sorted(kernels.items(), key=lambda kv: -kv[1]["ms"])},
+            }
         mode = ("dp_mode=gc -gcm %s" % opt.grad_clip_mode) if opt.dp_mode == "gc" else ("dp_mode=is -ispp %s" % bool(opt.imm_sens_per_param))
         line = {
             # the BASELINE.json metric for the default command; with --opt the line names what was actually run
@@ -342,26 +415,13 @@ def main():
                        "step": ("train_D (adaptive pass + G fwd + 2 D passes + per-sample grads + clip + GP + noise + Adam)" if opt.dp_mode == "gc" else
                                 "train_D (G fwd + D passes + create_graph gradients + one double-backward sweep per sensitivity + GP + noise + Adam)")},
             "per_gpu": round(ips / world, 2),
-            "step_gflop_executed_per_image": round(exec_flop_step / B / 1e9, 3),
-            "step_tflops_executed": round(exec_flop_step / (dt / a.steps) / 1e12, 2),
-            ("step_frac_of_bf16_mfma_peak" if bf16 else "step_frac_of_fp32_mfma_peak"): round(exec_flop_step / (dt / a.steps) / 1e12 / step_peak, 4),
-            "step_share_of_flop_on_x3_kernels": round(x3_flop / max(exec_flop_step, 1.0), 4),
-            "step_mfma_floor_ms": round(mfma_floor_s * 1e3, 3),
-            "step_frac_of_mfma_roofline": round(mfma_floor_s / (dt / a.steps), 4),
+            **fig,
             "step_tflops_reference_algorithmic": None if a.opt else round(FLOP_PER_IMG_STEP * ips / world / 1e12, 2),
-            "roofline": roof,
-            "roofline_hbm": roof_hbm,
-            "secondary": loop,
-            "variants": variant,
-            "graph_error": graph_err,
-            "tables_from": "%d launch-by-launch instrumented warm-up step(s) run on ONE stream (isolated kernel times); roofline from the "
-                           "eagerly launched timed region; both timed regions run the step's two streams" % n_pr,
-            "entries_ms_per_step": {k: round(v["ms"] / n_pr, 3) for k, v in sorted(entries.items(), key=lambda kv: -kv[1]["ms"])},
-            "kernels_ms_per_step": {k: {"ms": round(v["ms"] / n_pr, 3), "n": v["n"] / n_pr,
-                                        "tflops": round(v["exec_flop"] / (v["ms"] * 1e-3) / 1e12, 1) if v["exec_flop"] else None,
-                                        "GBps": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1) if not v["exec_flop"] else None}
-                                    for k, v in sorted(kernels.items(), key=lambda kv: -kv[1]["ms"])},
         }
+        if a.full:
+            line.update(roofline=roof, roofline_hbm=roof_hbm, secondary=loop, variants=variant)
+        line["graph_error"] = graph_err
+        line.update(tables)
         if world == 1 and not a.no_cpu_baseline and with_cpu:
             line["cpu_baseline"] = cpu_baseline()
             line["gpu_over_cpu"] = round(ips / line["cpu_baseline"]["value"], 1)
@@ -383,9 +443,12 @@ def main():
 
         def _bail():
             try:
-                finish(dt_eager, "eager", "the HIP-graph region did not finish within %.0f s on %d ranks; the eager region is reported" % (limit, world),
-                       None, None, with_cpu=False)
-                sys.stdout.flush()
+                if dt_eager is not None:        # --full: the eager region A has been measured
+                    finish(dt_eager, "eager", "the HIP-graph region did not finish within %.0f s on %d ranks; the eager region is reported" % (limit, world),
+                           None, None, with_cpu=False)
+                    sys.stdout.flush()
+                else:
+                    print("error: the HIP-graph region did not finish within %.0f s on %d ranks" % (limit, world), file=sys.stderr, flush=True)
             finally:
                 os._exit(3)
         bail = threading.Timer(limit, _bail)
@@ -393,7 +456,9 @@ def main():
         bail.start()
     if gs is not None:              # N > 1: every rank records the same step, RCCL all-reduce included (trainer.setup_privacy_engine)
         try:
-            for _ in range(gs.warmup + 2):
+            # a plain run warms up here, on the headline step itself: its first gs.warmup calls run eagerly, the next one records
+            # the graph and replays it, the rest replay it (at least one replay before the timed steps)
+            for _ in range(gs.warmup + 2 if a.full else max(a.warmup, gs.warmup + 2)):
                 gs(img, None)
             if gs.graph is not None:
                 # N > 1 by default: "hip_graph_segments" — the step replays as graphs that end at each collective, the collectives
@@ -405,8 +470,18 @@ def main():
             graph_err = repr(e)[:200]
     if bail is not None:
         bail.cancel()
+    if dt is None:                  # plain run without a replayable graph: the step launched eagerly, as --full's region A times it
+        if gs is not None:
+            gs.release()            # back to plain eager stepping (the step draws its own mean-sample batches)
+        for _ in range(1 if gs is not None else a.warmup):
+            step()
+        dt = time_region(step, a.steps)
+    if a.dump_outputs and rank == 0:
+        # what the timed step computed in its last step (before --full's variants step the trainer further)
+        torch.cuda.synchronize()
+        dump_outputs(step_outputs(tr), a.dump_outputs)
     variant = None
-    if not a.opt and world == 1 and not a.no_variants:
+    if a.full and not a.opt and world == 1 and not a.no_variants:
         variant = {}
         if launch_mode == "hip_graph":
             variant["eager"] = {"value": round(world * B * a.steps / dt_eager, 2), "unit": "images/sec", "ms_per_step": round(dt_eager / a.steps * 1e3, 3),
@@ -469,7 +544,7 @@ def main():
                 "value": round(world * B * n16 / d16, 2), "unit": "images/sec", "ms_per_step": round(d16 / n16 * 1e3, 3), "dtype": "bf16", "launch": mode16,
                 "what": "BASELINE configs[4]: the same D-step at 3x128x128, bs=%d per GPU, --compute_dtype bf16 --storage_dtype bf16 (bfloat16 "
                         "activations / activation gradients / filter copies in HBM, fp32 accumulate, fp32 weight gradients, norms, clip, noise, Adam); "
-                        "per-kernel figures: python bench.py --opt \"--compute_dtype bf16 --storage_dtype bf16 --im_size 128\"" % B}
+                        "per-kernel figures: python bench.py --full --opt \"--compute_dtype bf16 --storage_dtype bf16 --im_size 128\"" % B}
             del tr16, img16, g16
         except Exception as e:      # the variant must not cost the headline line
             variant["bf16_storage_128x128"] = {"error": repr(e)[:200]}
@@ -480,7 +555,7 @@ def main():
             torch.cuda.empty_cache()
     # secondary metric: the full train() loop, a G step forced on every n_d_steps-th iteration
     loop = None
-    if a.loop_steps > 0:
+    if a.full and a.loop_steps > 0:
         opt.train_d_until_threshold = float("inf")
         lbl = torch.zeros(B, dtype=torch.long)
         for i in range(opt.n_d_steps):
@@ -489,7 +564,7 @@ def main():
         loop = {"metric": "full train() loop, G step every %d iterations" % opt.n_d_steps, "value": round(world * B * a.loop_steps / dl, 2),
                 "unit": "images/sec", "iterations": a.loop_steps, "ms_per_iteration": round(dl / a.loop_steps * 1e3, 3)}
 
-    finish(dt, launch_mode, graph_err, variant, loop)
+    finish(dt, launch_mode, graph_err, variant, loop, with_cpu=a.full)
 
 
 if __name__ == "__main__":

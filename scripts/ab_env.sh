@@ -4,7 +4,7 @@
 VAR=${1:-CSLGAN_GP_STREAM}
 for rep in 1 2; do
   for v in 0 1; do
-    env $VAR=$v python bench.py --steps 30 --warmup 5 --no-cpu-baseline --loop-steps 0 2>/dev/null | python -c "
+    env $VAR=$v python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --loop-steps 0 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$VAR=$v %s %.3f ms  eager %s ms' % (d['config']['launch'], d['ms_per_step'], (d['variants'].get('eager') or {}).get('ms_per_step')))"

@@ -5,7 +5,7 @@ TAG=$1; shift
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 timeout -k 10 500 python -m pytest tests/test_bf16s_gpu.py -q > $OUT/test.log 2>&1
 grep -E "^(FAILED|ERROR)|passed|failed" $OUT/test.log | head -20
-B="python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --loop-steps 0 --no-variants"
+B="python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --loop-steps 0 --no-variants"
 O="--compute_dtype bf16 --storage_dtype bf16 --im_size 128"
 run() {  # $1 = label, $2 = env assignment or ""
   env $2 timeout -k 10 200 $B --dump-shapes $OUT/shapes_$1.txt --opt "$O" > $OUT/bench_$1.json 2> $OUT/err_$1.txt

@@ -5,9 +5,9 @@ set -e
 R=$(pwd); OUT=$R/gpurun_out/$1; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 if [ -n "$2" ]; then
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-variants --loop-steps 0 --opt "$2" > $OUT/bench.json 2> $OUT/err.txt
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- python3 $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-variants --loop-steps 0 --opt "$2" > $OUT/bench.json 2> $OUT/err.txt
 else
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-variants --loop-steps 0 > $OUT/bench.json 2> $OUT/err.txt
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- python3 $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-variants --loop-steps 0 > $OUT/bench.json 2> $OUT/err.txt
 fi
 cd $R
 cp $(ls $OUT/stats/*kernel_stats.csv | head -1) $OUT/kernel_stats.csv

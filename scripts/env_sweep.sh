@@ -6,7 +6,7 @@ mkdir -p $OUT
 i=0
 for e in "BASE=1" "$@" "BASE=2"; do
   i=$((i+1))
-  env $e timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --loop-steps 0 --dump-shapes $OUT/shapes_$i.txt > $OUT/bench_$i.json 2>/dev/null
+  env $e timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --loop-steps 0 --dump-shapes $OUT/shapes_$i.txt > $OUT/bench_$i.json 2>/dev/null
   python - "$e" $OUT/bench_$i.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().split("\n")[-1])

@@ -83,3 +83,44 @@ def test_storage_dtype_needs_bf16_compute(tmp_path):
     from csl_gan_amd import options
     with pytest.raises(Exception, match="needs --compute_dtype bf16"):
         options.parse(["CelebA", "-dpm", "gc", "-nms", "1", "-bs", "4", "-gd", "cuda:0", "-dd", "cuda:0", "-o", str(tmp_path), "--storage_dtype", "bf16"])
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_step(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`, a plain run: one JSON line with the headline fields and none of
+    --full's, its figures from exactly K replayed steps; DIR holds what the last timed step computed as float32 .npy files within
+    64 MB, and a second run with the same arguments computes the same numbers from the same inputs.
+
+    "The same" to the step's own reproducibility: the generated images depend on the seeded draws alone and come out bitwise equal;
+    the critic's reductions (per-sample norms, split-K sums) add with floating-point atomics, so its scores, losses and clip
+    statistics agree to rounding (measured <= 8e-5 of each array's scale), and Adam's per-coordinate normalisation magnifies such
+    differences in its parameters step by step (measured <= 6.2e-4 after the 7 critic steps of this run, 2 eager + recording +
+    4 replays)."""
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines, dumps = [], []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        ls = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(ls) == 1, r.stdout[-2000:]
+        lines.append(json.loads(ls[0]))
+        dumps.append(d)
+    line = lines[0]
+    assert (line["steps"], line["warmup"], line["n_gpus"], line["unit"], line["dtype"]) == (3, 2, 1, "images/sec", "f32"), line
+    assert line["higher_is_better"] is True and line["config"]["launch"] == "hip_graph" and line["graph_error"] is None, line
+    assert abs(line["value"] - 128 * 1e3 / line["ms_per_step"]) <= 1e-3 * line["value"], line
+    for k in ("cpu_baseline", "variants", "secondary", "roofline", "kernels_ms_per_step"):
+        assert k not in line, k
+    files = sorted(os.listdir(dumps[0]))
+    assert files == sorted(os.listdir(dumps[1])) and {"last.fake_img.npy", "last.d_real_loss.npy"} <= set(files), files
+    assert any(f.startswith("D.") for f in files) and sum(os.path.getsize(dumps[0] / f) for f in files) <= 64 << 20
+    assert np.load(dumps[0] / "last.fake_img.npy").shape == (128, 3, 64, 64)
+    for f in files:
+        x, y = np.load(dumps[0] / f), np.load(dumps[1] / f)
+        assert x.dtype == np.float32 and x.shape == y.shape and np.isfinite(x).all(), f
+        tol = 1e-6 if f == "last.fake_img.npy" else 1e-2 if f.startswith("D.") else 1e-3
+        assert np.abs(x.astype(np.float64) - y).max() <= tol * max(float(np.abs(x).max()), 1e-6), f

@@ -245,7 +245,7 @@ def test_bench_two_ranks_reports_the_eager_step_by_default(tmp_path, segments):
     env = dict(os.environ, CSLGAN_DIST_BACKEND="gloo", CSLGAN_FORCE_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0",
                CSLGAN_GRAPH_SEGMENTS="1" if segments else "0")
     env.pop("CSLGAN_GRAPH_DIST", None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
                         "--loop-steps", "0", "--no-variants"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -364,3 +364,41 @@ def test_bench_launches_its_own_ranks(tmp_path):
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1"], env=env1, capture_output=True,
                        text=True, timeout=300)
     assert r.returncode == 2 and "process group has 1 rank" in r.stderr
+
+
+def test_bench_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
+    """bench.py --dump-outputs: every output is written as <name>.npy in float32 (float64 kept), and above the size limit each array
+    keeps a fixed, seeded sample — the same elements on every run — so that the files stay within the limit."""
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    outs = {"last.fake_img": torch.randn(8, 3, 16, 16, generator=g).to(memory_format=torch.channels_last),
+            "last.d_real_loss": torch.tensor(0.25), "last.stat64": torch.randn(5, generator=g, dtype=torch.float64),
+            "D.w_bf16": torch.randn(40, 7, generator=g).to(torch.bfloat16), "last.count": torch.arange(6)}
+    shapes = bench.dump_outputs(outs, str(tmp_path / "all"))
+    assert sorted(os.listdir(tmp_path / "all")) == sorted(k + ".npy" for k in outs)
+    for k, t in outs.items():
+        x = np.load(tmp_path / "all" / (k + ".npy"))
+        assert x.dtype == (np.float64 if t.dtype == torch.float64 else np.float32) and x.shape == tuple(t.shape) == shapes[k]
+        assert np.array_equal(x, t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).numpy())
+    limit = 4096
+    for run in ("a", "b"):
+        bench.dump_outputs(outs, str(tmp_path / run), limit=limit)
+        assert sum(os.path.getsize(tmp_path / run / f) for f in os.listdir(tmp_path / run)) <= limit
+    img = outs["last.fake_img"].float().numpy().reshape(-1)
+    a, b = np.load(tmp_path / "a" / "last.fake_img.npy"), np.load(tmp_path / "b" / "last.fake_img.npy")
+    assert 0 < a.size < img.size and np.array_equal(a, b) and np.isin(a, img).all()
+    assert np.load(tmp_path / "a" / "last.d_real_loss.npy") == np.float32(0.25)
+
+
+def test_bench_options():
+    """--full and --dump-outputs exist; --dump-shapes (a table of the --full instrumented steps) is refused without --full."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout, r.stderr[-2000:]
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--dump-shapes", "x.txt"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--dump-shapes needs --full" in r.stderr

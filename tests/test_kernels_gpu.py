@@ -1288,12 +1288,12 @@ def test_groupnorm_statistics_from_the_conv_epilogue(case, mode):
     assert _err64(fused.permute(0, 3, 1, 2), ref) <= (2e-5 if mode == "bf16x3" else 1e-5)
 
 
-def test_generator_forward_with_epilogue_statistics_matches_the_two_launch_form(monkeypatch):
+def test_generator_forward_with_epilogue_statistics_matches_the_two_launch_form(monkeypatch, tmp_path):
     """The frozen DCResNet generator forward (what a D-step runs): every GroupNorm reads the statistics its producing conv left
     (eight statistics launches less per step) — same images as with CSLGAN_GN_FUSE off, to 5e-6 of their range."""
     from csl_gan_amd import init_util, options
     ops = _ops()
-    opt = options.parse(["CelebA", "-dpm", "gc", "-nms", "4", "-bs", "4", "-gd", "cuda:0", "-dd", "cuda:0", "-o", "/tmp/cslgan_gnf", "--manual_seed", "3", "--synthetic"])
+    opt = options.parse(["CelebA", "-dpm", "gc", "-nms", "4", "-bs", "4", "-gd", "cuda:0", "-dd", "cuda:0", "-o", str(tmp_path) + "/", "--manual_seed", "3", "--synthetic"])
     G, _ = init_util.init_models(opt)
     z = torch.randn(4, opt.g_latent_dim, device="cuda:0")
     outs = {}
