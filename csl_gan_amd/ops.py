@@ -1289,14 +1289,24 @@ def sum_rows(slabs, out):
     return out
 
 
+PHILOX_MAX_TENSORS = 64            # include/cslgan.h "Device random streams": first_index < 64
+
+
 def clip_accum_noise(mats, outs, factors=None, noise_std=None, noises=None, seed=0, offset=0, scale=1.0, beta=0.0, call_counter=None,
                      ragged=False):
     """outs[i] = beta*outs[i] + scale*(sum_r f_r * mats[i][r] + noise_std[i]*z_i).  mats may mix fp32 and bf16
     segments (one launch per element type, fp32 accumulation either way).  call_counter: device int64 [1] whose value is
     added to `offset` inside the kernel (graph-captured steps: the counter lives in HBM, not in the launch arguments).
-    ragged: the segments may have different row counts (plain column sums: no factors)."""
+    ragged: the segments may have different row counts (plain column sums: no factors).
+    Philox noise (noise_std without noises): tensor i draws the stream of (seed, offset + *call_counter, i) — include/cslgan.h
+    "Device random streams"; at most 64 tensors per call, and the caller never repeats (seed, offset + *call_counter)."""
     if ragged and factors is not None:
         raise RuntimeError("clip_accum_noise: ragged segments take no clip factors")
+    if noise_std is not None and noises is None and len(mats) > PHILOX_MAX_TENSORS:
+        # a launch's stream offset is 64 * (offset + call counter) + the position of its first tensor: position 64 of this call
+        # would draw exactly the normals of position 0 of the next one
+        raise RuntimeError("clip_accum_noise: Philox noise for at most %d tensors per call, got %d (a tensor's position takes the low "
+                           "6 bits of the stream offset; beyond that it repeats the next call's noise)" % (PHILOX_MAX_TENSORS, len(mats)))
     L = _lib.lib()
     if factors is not None:
         _chk(factors, "factors")

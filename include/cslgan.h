@@ -91,7 +91,24 @@ int cslgan_clip_factors_f32(const float* sq, int n_seg, int64_t n_rows, const fl
 /* out[s][j] = beta*out[s][j] + scale * ( sum_r f(s,r) * in[s][r][j] + noise_std[s] * z[s][j] )
  *   factors: device [n_rows] (factors_per_seg==0) or [n_seg,n_rows] (factors_per_seg!=0), NULL -> 1
  *   noise_std: DEVICE [n_seg] or NULL (no noise); z from segs->noise[s] when given, else
- *   Philox4x32-10 + Box-Muller keyed by (seed, offset, s, j).
+ *   Philox4x32-10 + Box-Muller keyed by (seed, offset, s, j):
+ *
+ * Device random streams (restated on the host by oracle/noise_streams.py; tests/test_noise_streams*.py hold both to it).
+ *   Philox4x32-10 as in Random123 (Salmon et al., SC'11): counter (c0, c1, c2, c3), key (k0, k1), four 32-bit words out.
+ *   Box-Muller on a word pair (a, b): u1 = (a >> 8) 2^-24 + 2^-25, u2 = (b >> 8) 2^-24, r = sqrt(-2 ln u1),
+ *   (r cos 2 pi u2, r sin 2 pi u2), in fp32 with the fast log / sincos.  u1 lies on a 2^-24 grid inside (0, 1), so
+ *   |z| <= sqrt(-2 ln 2^-25) = 5.89; the fp32 sum rounds u1 to even above 1/2 (at most 2.5e-4 on z, reached where u1 -> 1).
+ *   Column j of segment s:  q = j >> 2;  off64 = offset + 64 * *call_counter (mod 2^64);
+ *       counter = (q lo, q hi, (s + (off64 << 8)) mod 2^32, off64 >> 24),  key = (seed lo, seed hi);
+ *       words 0, 1 -> columns 4q, 4q+1; words 2, 3 -> columns 4q+2, 4q+3.
+ *   Every (off64, s, q) has a counter of its own for s < 256 (a launch has s < 16), off64 < 2^56, len < 2^34 (above, q hi != 0
+ *   still separates).  The CALLER keeps off64 unique per launch: csl_gan_amd.ops.clip_accum_noise passes
+ *   offset = 64 * (its own offset argument) + first_index, first_index = the position in its tensor list of the launch's first
+ *   tensor, so one call may hold at most 64 tensors (it refuses more: position 64 would be position 0 of the next call); the
+ *   engines pass offset 0 and count their steps in *call_counter, which their checkpoints carry.
+ *   The mean sampler (cslgan_mean_sample_f32 below) draws from the same generator with counters that can coincide with
+ *   these: the two are kept apart by their SEEDS alone (engine: manual_seed + 7919 * rank; sampler: the process seed xor
+ *   0x6D65616E73616D70), as are ranks.
  * Replaces privacy_engine.clip() + accum_grads_across_passes() (train.py:399-402) and, with
  * noise/scale, the engine-wrapped d_optimizer.step() noise + 1/B (train.py:484). */
 int cslgan_clip_accum_noise_f32(const cslgan_segs_t* segs, int64_t n_rows, const float* factors,
@@ -110,7 +127,15 @@ int cslgan_l2_clip_rows_f32(const float* in, float* out, int64_t n_rows, int64_t
 /* MeanSampler.sample (mean_sampler.py:75-84; called from train.py:200-202, 214-216) on device-resident mean samples:
  *   out[i][:] = mean_samples[labels[i]][perms[i]][:] + noise_mean_std * z_i + noise_std * z_{i,:}
  * mean_samples [n_classes][num_samples][len], labels (nullable when n_classes == 1) and perms [n] int64, out [n][len];
- * z ~ N(0,1) from Philox4x32-10 keyed (seed, offset): the caller advances offset per call.
+ * z ~ N(0,1) from Philox4x32-10 keyed (seed, offset): the caller advances offset per call (MeanSampler: 1, 2, ... per draw,
+ * checkpointed).  Key = (seed lo, seed hi) and, with off lo / off hi the 32-bit halves of offset, the counters of image i are
+ *     permutation keys  (j, i / num_samples, off lo, 0x7065726D ^ off hi)   word 0 for j < num_samples; the image takes the j whose
+ *                                                                           key has rank i mod num_samples (equal keys: lower j first)
+ *     label             (i, 0x6C61626C, off lo, off hi)                      (word 0 * n_classes) >> 32
+ *     jitter z_i        (i, 0xFFFFFFFF, off lo, off hi)                      first Box-Muller output of words 0, 1
+ *     pixels 4q .. 4q+3 (q, i, off lo, off hi)                               Box-Muller of words 0, 1 and of words 2, 3
+ * (Box-Muller as under cslgan_clip_accum_noise_f32 "Device random streams").  No two of them coincide for n <= 65535 (below
+ * both tags), offset < 2^60 (then 0x7065726D ^ off hi >= 2^28 is no off hi in use) and len < 2^34.
  * perms == NULL (num_samples <= 1024): the kernel draws them — image i takes entry i mod num_samples of the (i / num_samples)-th
  * uniform random permutation (torch.cat of randperms, mean_sampler.py:76).  labels == NULL with n_classes > 1: uniform labels
  * are drawn (mean_sampler.py:77).  labels_out (nullable, [n] int64) receives the labels used. */
