@@ -100,8 +100,7 @@ __global__ __launch_bounds__(256, C == 32 ? 3 : (C == 64 ? 2 : 1)) void conv1x1_
 }
 
 bool conv1x1_eligible(const cslgan_conv_t* c, const float* x, const float* w, const float* residual) {
-    static const int env = [] { const char* e = getenv("CSLGAN_CONV1X1"); return e ? atoi(e) : 1; }();
-    return env && !residual && c->compute == CSLGAN_COMPUTE_F32 && c->R == 1 && c->S == 1 && c->stride == 1 && c->pad == 0 &&
+    return !residual && c->compute == CSLGAN_COMPUTE_F32 && c->R == 1 && c->S == 1 && c->stride == 1 && c->pad == 0 &&
            // measured at 128 images: 82 -> 60 us (C = 32, 64x64), 60 -> 49 us (C = 64, 32x32); 128 channels on <= 16x16 grids have too
            // few row tiles to stream (42 -> 48 us, 26 -> 82 us) and stay on the generic kernel
            (c->C == 32 || c->C == 64) && (c->K & 63) == 0 && c->K >= 64 && (long long)c->N * c->H * c->W >= 65536 &&

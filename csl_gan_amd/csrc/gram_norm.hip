@@ -14,6 +14,7 @@
 // their partial Gram matrices are added in LDS.  32 < PQ <= 64: four 32x32 tiles, one per wavefront.
 #include "common.h"
 #include "igemm.h"
+#include "conv_classes.h"
 
 namespace cslgan {
 
@@ -409,8 +410,7 @@ int cslgan_conv2d_wgrad_sqnorm_gram_f32(const cslgan_conv_t* c, const float* gy,
             max_pix = pix > max_pix ? pix : max_pix;
         }
         const bool small = cls_ok && P * Q <= 16 && max_pix <= 16 && c->K % 64 == 0 && c->C % 16 == 0;
-        static const int cls64_env = [] { const char* e = getenv("CSLGAN_GRAM_CLS64"); return e ? atoi(e) : 1; }();
-        const bool cls64 = cls_ok && !small && cls64_env && c->K % 4 == 0 && c->C % 4 == 0;
+        const bool cls64 = cls_ok && !small && c->K % 4 == 0 && c->C % 4 == 0;
         if (small || cls64) {
             auto fl = [](int v, int d) { return v >= 0 ? v / d : -((-v + d - 1) / d); };
             sp.gy = gy; sp.x = x; sp.N = c->N; sp.H = c->H; sp.W = c->W; sp.C = c->C; sp.K = c->K; sp.PQ = P * Q; sp.Q = Q;
@@ -435,9 +435,7 @@ int cslgan_conv2d_wgrad_sqnorm_gram_f32(const cslgan_conv_t* c, const float* gy,
     GramParams p{};
     p.gy = gy; p.x = x; p.N = c->N; p.H = c->H; p.W = c->W; p.C = c->C; p.K = c->K; p.PQ = P * Q; p.Q = Q; p.T = c->R * c->S;
     p.stride = c->stride; p.n1 = c->K / 32; p.n2 = p.T * (c->C / 32); p.alpha2 = alpha * alpha; p.sq = sq;
-    for (int t = 0; t < IG_MAX_TAPS; ++t) { p.ty[t] = 0; p.tx[t] = 0; }
-    for (int kh = 0; kh < c->R; ++kh)
-        for (int kw = 0; kw < c->S; ++kw) { p.ty[kh * c->S + kw] = (signed char)(kh - c->pad); p.tx[kh * c->S + kw] = (signed char)(kw - c->pad); }
+    fill_forward_taps(p.ty, p.tx, c->R, c->S, c->pad);
     const dim3 grid((unsigned)c->N), block(256);
     note_kernel("gram_sqnorm_kernel<%d>", p.PQ <= 32 ? 1 : 4);
     if (p.PQ <= 32) hipLaunchKernelGGL((gram_sqnorm_kernel<1>), grid, block, 0, (hipStream_t)stream, p);

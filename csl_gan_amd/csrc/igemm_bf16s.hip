@@ -9,9 +9,8 @@
 //   igemm_kcs_kernel   forward conv / linear and data gradient: a 16-byte global load is 8 consecutive k of one row = exactly
 //                      one operand of v_mfma_f32_32x32x16_bf16, stored to LDS as it is (no conversion, half the bytes of the
 //                      fp32 loader, K tile 64); the epilogue (bias, residual, activation, LeakyReLU mask) writes bf16 or fp32.
-//   igemm_mcs_kernel   grouped / per-sample weight gradient: the reduction index (pixel) is the slow one of both operands, so a
-//                      thread loads the same 8 channels of 8 consecutive pixels (8 x 16 bytes, a pixel row's 256 bytes
-//                      coalesced across 16 lanes) and transposes the 8x8 block in registers into 8 LDS operands.
+//   igemm_mcs_tr_kernel  grouped / per-sample weight gradient: the reduction index (pixel) is the slow one of both operands; the
+//                      [pixel][channel] tiles go to LDS as loaded and come back through gfx950's transposing LDS read.
 //   round / repack     the fp32 master filter rounded once per parameter version (plain KRSC order for the forward conv,
 //                      per-parity-class [C][taps][K] matrices for the data gradient), cached by the caller.
 //   casts, activation backward, bias gradient on bf16 tensors.
@@ -22,9 +21,9 @@
 //
 // Replaces (reference file:line): nn.Conv2d / nn.Linear forward and autograd data gradients (DCResNet_models.py:131-132,145),
 // the Opacus-fork per-sample weight gradients (train.py:373,387), F.leaky_relu's backward, bias gradients.
-#include <stdlib.h>
 #include "common.h"
 #include "igemm.h"
+#include "conv_classes.h"
 
 namespace cslgan {
 
@@ -543,8 +542,7 @@ __global__ __launch_bounds__(256) void conv1x1s_kernel(const unsigned short* __r
 }
 
 static bool conv1x1s_eligible(const cslgan_conv_t* c, const void* residual) {
-    static const int env = [] { const char* e = getenv("CSLGAN_CONV1X1S"); return e ? atoi(e) : 1; }();
-    return env && !residual && c->R == 1 && c->S == 1 && c->stride == 1 && c->pad == 0 && (c->C == 16 || c->C == 32 || c->C == 64) &&
+    return !residual && c->R == 1 && c->S == 1 && c->stride == 1 && c->pad == 0 && (c->C == 16 || c->C == 32 || c->C == 64) &&
            c->K % 32 == 0 && c->K >= 32 && c->K <= 128 && (long long)c->N * c->H * c->W >= 65536;
 }
 
@@ -576,16 +574,12 @@ int split_filter_x3(const float* w, int Nn, int T, int C, void* w3, hipStream_t 
 // stride-1 classes (one for a forward conv; the output-parity classes of a strided data gradient), each on an 8x8-patchable grid of at
 // least 16x16, channels a multiple of 16, 2..25 taps within a 12x12 halo, >= 64 filters
 static bool halos_eligible(const KsParams& p) {
-    static const int env = [] { const char* e = getenv("CSLGAN_HALOS"); return e ? atoi(e) : 1; }();
-    if (!env || p.n_cls < 1 || p.sy != 1 || p.sx != 1 || (p.AC & 15) || p.Nn < 64 || !aligned16(p.a)) return false;
+    if (p.n_cls < 1 || p.sy != 1 || p.sx != 1 || (p.AC & 15) || p.Nn < 64 || !aligned16(p.a)) return false;
     for (int c = 0; c < p.n_cls; ++c) {
         const KcClass& k = p.cls[c];
         if (k.T < 2 || (k.M & 63) || (k.OHc & 7) || (k.OWc & 7) || k.OHc < 16 || k.OWc < 16) return false;
-        int ymin = 127, ymax = -128, xmin = 127, xmax = -128;
-        for (int t = 0; t < k.T; ++t) {
-            ymin = k.ty[t] < ymin ? k.ty[t] : ymin; ymax = k.ty[t] > ymax ? k.ty[t] : ymax;
-            xmin = k.tx[t] < xmin ? k.tx[t] : xmin; xmax = k.tx[t] > xmax ? k.tx[t] : xmax;
-        }
+        int ymin, ymax, xmin, xmax;
+        tap_range(k, ymin, ymax, xmin, xmax);
         if (ymax - ymin > 4 || xmax - xmin > 4) return false;
     }
     return true;
@@ -596,11 +590,8 @@ static int launch_halos(KsParams& p, bool out_bf16, hipStream_t st) {
     long long w_el = 0;
     for (int c = 0; c < p.n_cls; ++c) {
         KcClass& k = p.cls[c];
-        int ymin = 127, ymax = -128, xmin = 127, xmax = -128;
-        for (int t = 0; t < k.T; ++t) {
-            ymin = k.ty[t] < ymin ? k.ty[t] : ymin; ymax = k.ty[t] > ymax ? k.ty[t] : ymax;
-            xmin = k.tx[t] < xmin ? k.tx[t] : xmin; xmax = k.tx[t] > xmax ? k.tx[t] : xmax;
-        }
+        int ymin, ymax, xmin, xmax;
+        tap_range(k, ymin, ymax, xmin, xmax);
         k.ty_min = ymin; k.tx_min = xmin; k.halo_h = 8 + ymax - ymin; k.halo_w = 8 + xmax - xmin;
         k.patch = 1; k.tile0 = tm;
         tm += (k.M + 127) / 128;
@@ -704,7 +695,6 @@ static unsigned stream_blocks(long long n_items) {
 // data-gradient classes: wt[off_cls + (c*Tc + t)*K + k] = bf16(w[((k*R + kh)*S + kw)*C + c]) for the (kh, kw) of the class's tap t
 struct DgradRepack {
     int K, R, S, C, n_cls;
-    int step_major;      // 1: igemm_halos' layout [(k/16) * Tc + t][c][k % 16] per class instead of the plain [c][t][k]
     int cls_off[IG_MAX_CLS], cls_T[IG_MAX_CLS];
     signed char kh[IG_MAX_CLS][IG_MAX_TAPS], kw[IG_MAX_CLS][IG_MAX_TAPS];
 };
@@ -717,8 +707,7 @@ __global__ void repack_dgrad_bf16_kernel(const float* __restrict__ w, unsigned s
         const int k = (int)(i % a.K);
         const long long rest = i / a.K;
         const int t = (int)(rest % Tc), c = (int)(rest / Tc);
-        const long long dst = a.step_major ? ((((long long)(k >> 4) * Tc + t) * a.C + c) << 4) + (k & 15) : i;
-        wt[a.cls_off[cls] + dst] = f2bf(w[(((long long)k * a.R + a.kh[cls][t]) * a.S + a.kw[cls][t]) * a.C + c]);
+        wt[a.cls_off[cls] + i] = f2bf(w[(((long long)k * a.R + a.kh[cls][t]) * a.S + a.kw[cls][t]) * a.C + c]);
     }
 }
 
@@ -740,187 +729,14 @@ struct MsParams {
 
 constexpr int MS_BK = 64;        // pixels per LDS tile
 
-// Q8: Q % 8 == 0, so the 8 consecutive pixels a thread gathers lie in one output row of one image (one decode per tile)
-template <bool Q8>
-__global__ __launch_bounds__(256, 2) void igemm_mcs_kernel(const MsParams p) {
-    constexpr int ES = 128 + 1;                              // uint4 units per LDS entry (128 rows x 16 B + 16 B pad)
-    __shared__ __attribute__((aligned(16))) uint4 As[2][8 * ES];
-    __shared__ __attribute__((aligned(16))) uint4 Bs[2][8 * ES];
-    __shared__ float s_red[4];
-
-    const int tid = threadIdx.x;
-    const int per_g = p.tiles_m * p.tiles_n;
-    const int split = p.ksplit > 1 ? blockIdx.x % p.ksplit : 0;
-    const int bid = p.ksplit > 1 ? blockIdx.x / p.ksplit : blockIdx.x;
-    const int g = bid / per_g;
-    const int tl = bid - g * per_g;
-    const int tile_m = tl / p.tiles_n, tile_n = tl - tile_m * p.tiles_n;
-    const int m0 = tile_m * 128, n0 = tile_n * 128;
-    const int PQ = p.P * p.Q;
-    const int Ktot = p.group * PQ;
-    const long long pix_base = (long long)g * p.group * PQ;
-
-    const bool is_a = tid < 128;
-    const int lt = tid & 127;
-    const int c8 = (lt & 15) * 8;        // first of this thread's 8 rows (m or n) within the tile: 16 lanes cover 256 contiguous bytes of a pixel
-    const int kg = lt >> 4;              // its group of 8 pixels within the 64-pixel tile = its LDS entry
-    // X columns are fixed per thread: 8 consecutive n share a tap (C % 8 == 0)
-    const int nb = n0 + c8;
-    const bool b_ok = nb < p.Ndim;
-    const int b_t = b_ok ? nb / p.C : 0;
-    const int b_c = nb - b_t * p.C;
-    const int b_ty = p.ty[b_t], b_tx = p.tx[b_t];
-    const bool a_ok = m0 + c8 < p.Kc;
-    const unsigned short* __restrict__ gyh = reinterpret_cast<const unsigned short*>(p.gy);
-    const unsigned short* __restrict__ xh = reinterpret_cast<const unsigned short*>(p.x);
-
-    uint4 rv[8];
-    auto load_tile = [&](int kt) {
-        const int kk0 = kt * MS_BK + kg * 8;
-        if (is_a) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                uint4 v = make_uint4(0u, 0u, 0u, 0u);
-                if (a_ok && kk0 + j < Ktot) v = *reinterpret_cast<const uint4*>(gyh + (pix_base + kk0 + j) * p.Kc + m0 + c8);
-                rv[j] = v;
-            }
-        } else if (Q8) {
-            const int il = kk0 / PQ;
-            const int pix = kk0 - il * PQ;
-            const int oy = pix / p.Q, ox0 = pix - oy * p.Q;
-            const long long img = (long long)g * p.group + il;
-            const int iy = oy * p.stride + b_ty;
-            const bool row_ok = b_ok && kk0 < Ktot && iy >= 0 && iy < p.H;
-            const unsigned short* src = xh + ((img * p.H + iy) * p.W) * p.C + b_c;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int ix = (ox0 + j) * p.stride + b_tx;
-                uint4 v = make_uint4(0u, 0u, 0u, 0u);
-                if (row_ok && ix >= 0 && ix < p.W) v = *reinterpret_cast<const uint4*>(src + (long long)ix * p.C);
-                rv[j] = v;
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int kk = kk0 + j;
-                uint4 v = make_uint4(0u, 0u, 0u, 0u);
-                if (b_ok && kk < Ktot) {
-                    const int il = kk / PQ;
-                    const int pix = kk - il * PQ;
-                    const int oy = pix / p.Q, ox = pix - oy * p.Q;
-                    const long long img = (long long)g * p.group + il;
-                    const int iy = oy * p.stride + b_ty, ix = ox * p.stride + b_tx;
-                    if (iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) v = *reinterpret_cast<const uint4*>(xh + ((img * p.H + iy) * p.W + ix) * p.C + b_c);
-                }
-                rv[j] = v;
-            }
-        }
-    };
-    // rv[j] = channels c8..c8+7 of pixel j  ->  entry kg, row c8+ch: the 8 pixels of channel ch (an 8x8 transpose of 16-bit values).
-    // Row R of an entry is stored at slot swz(R) = (R & ~7) | ((R + (R >> 3)) & 7): the 8 lanes that write the same channel of 8
-    // consecutive row blocks (128 bytes apart) land on 8 different 16-byte bank groups, and a 32-row fragment read still covers
-    // the same 512 contiguous bytes.  (Rotating the DATA per lane instead made rv[] dynamically indexed -> scratch.)
-    auto store_tile = [&](int buf) {
-        uint4* dst = (is_a ? As[buf] : Bs[buf]) + kg * ES + c8;
-        const int rot = (c8 >> 3) & 7;
-#pragma unroll
-        for (int ch = 0; ch < 8; ++ch) {
-            unsigned w4[4];
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) {
-                const uint4 a = rv[2 * jj], b = rv[2 * jj + 1];
-                const unsigned lo = (ch >> 1) == 0 ? a.x : ((ch >> 1) == 1 ? a.y : ((ch >> 1) == 2 ? a.z : a.w));
-                const unsigned hi = (ch >> 1) == 0 ? b.x : ((ch >> 1) == 1 ? b.y : ((ch >> 1) == 2 ? b.z : b.w));
-                w4[jj] = (ch & 1) ? ((lo >> 16) | (hi & 0xffff0000u)) : ((lo & 0xffffu) | (hi << 16));
-            }
-            dst[(ch + rot) & 7] = make_uint4(w4[0], w4[1], w4[2], w4[3]);
-        }
-    };
-    auto swz = [](int R) { return (R & ~7) | ((R + (R >> 3)) & 7); };
-
-    const int lane = tid & 63, wid = tid >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const int wm = wid >> 1, wn = wid & 1;
-    const int arow[2] = {swz(wm * 64 + r), swz(wm * 64 + r + 32)}, brow[2] = {swz(wn * 64 + r), swz(wn * 64 + r + 32)};
-
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) acc[i][j][v] = 0.f;
-
-    const int nk_all = (Ktot + MS_BK - 1) / MS_BK;
-    int kt0 = 0, nk = nk_all;
-    if (p.ksplit > 1) {
-        const int per = (nk_all + p.ksplit - 1) / p.ksplit;
-        kt0 = split * per;
-        nk = kt0 + per < nk_all ? kt0 + per : nk_all;
-        if (kt0 >= nk) return;      // uniform across the workgroup
-    }
-    load_tile(kt0);
-    store_tile(0);
-    __syncthreads();
-    for (int kt = kt0; kt < nk; ++kt) {
-        const int buf = (kt - kt0) & 1;
-        if (kt + 1 < nk) load_tile(kt + 1);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            bf16x8 af[2], bf[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) af[i] = __builtin_bit_cast(bf16x8, As[buf][(2 * s + h) * ES + arow[i]]);
-#pragma unroll
-            for (int j = 0; j < 2; ++j) bf[j] = __builtin_bit_cast(bf16x8, Bs[buf][(2 * s + h) * ES + brow[j]]);
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bf[j], acc[i][j], 0, 0, 0);
-        }
-        if (kt + 1 < nk) store_tile(buf ^ 1);
-        __syncthreads();
-    }
-
-    // ---- epilogue: scale, store, per-group sum of squares (as igemm_mc) ------------------------
-    float ss = 0.f;
-    float* __restrict__ outg = (p.gw && !p.out_bf16) ? reinterpret_cast<float*>(p.gw) + (long long)g * p.Kc * p.Ndim : nullptr;
-    unsigned short* __restrict__ outh = (p.gw && p.out_bf16) ? reinterpret_cast<unsigned short*>(p.gw) + (long long)g * p.Kc * p.Ndim : nullptr;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int n = n0 + wn * 64 + j * 32 + r;
-        if (n >= p.Ndim) continue;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int m = m0 + wm * 64 + i * 32 + (v & 3) + 8 * (v >> 2) + 4 * h;
-                if (m >= p.Kc) continue;
-                float val = p.alpha * acc[i][j][v];
-                if (p.out_bf16) {      // what is stored is what gets clipped: norm of the rounded value
-                    const unsigned short u = f2bf(val);
-                    if (outh) outh[(long long)m * p.Ndim + n] = u;
-                    val = bf2f(u);
-                }
-                ss = fmaf(val, val, ss);
-                if (outg) {
-                    if (p.ksplit > 1) atomicAdd(&outg[(long long)m * p.Ndim + n], val);
-                    else outg[(long long)m * p.Ndim + n] = val;
-                }
-            }
-        }
-    }
-    if (p.sq && p.ksplit <= 1) {
-        const float tot = block_sum_256(ss, s_red);
-        if (tid == 0) atomicAdd(p.sq + g, tot);
-    }
-}
-
-// Same contraction with NO register transpose: the [pixel][channel] tiles go to LDS as they are loaded (row-major, 256-byte rows,
+// The [pixel][channel] tiles go to LDS as they are loaded (row-major, 256-byte rows,
 // 16-byte chunks XOR-swizzled by the row so that both the row writes and the transposed reads are conflict-free) and the MFMA
 // operands come back through ds_read_b64_tr_b16, gfx950's transposing LDS read: per 16-lane group a block of 4 rows (pixels) x 16
 // columns (channels) is delivered column-major, i.e. each lane receives 4 consecutive k of ITS channel; two such reads are one
-// operand of v_mfma_f32_32x32x16_bf16.  The register transpose above costs ~100 vector instructions per thread and K tile beside
-// 16 MFMAs per wave (measured 176-208 TF); here a K tile is 8 global loads, 8 ds_write_b128 and 32 transposed reads per thread.
+// operand of v_mfma_f32_32x32x16_bf16.  A K tile is 8 global loads, 8 ds_write_b128 and 32 transposed reads per thread (an earlier
+// form that transposed 8x8 blocks in registers cost ~100 vector instructions per thread and K tile beside 16 MFMAs per wave and
+// measured 176-208 TF against 259-339 TF here; DESIGN.md, appendix of retired switches).
+// Q8: Q % 8 == 0, so the 8 consecutive pixels a thread gathers lie in one output row of one image (one decode per tile).
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
 
@@ -1383,9 +1199,7 @@ int cslgan_conv2d_fwd_bf16s(const cslgan_conv_t* c, const void* x, const float* 
     p.n_cls = 1;
     KcClass& k = p.cls[0];
     k.M = c->N * c->P * c->Q; k.OHc = c->P; k.OWc = c->Q; k.T = c->R * c->S; k.Kdim = k.T * c->C; k.w_off = 0; k.oy0 = k.ox0 = 0;
-    for (int t = 0; t < IG_MAX_TAPS; ++t) { k.ty[t] = 0; k.tx[t] = 0; }
-    for (int kh = 0; kh < c->R; ++kh)
-        for (int kw = 0; kw < c->S; ++kw) { k.ty[kh * c->S + kw] = (signed char)(kh - c->pad); k.tx[kh * c->S + kw] = (signed char)(kw - c->pad); }
+    fill_forward_taps(k.ty, k.tx, c->R, c->S, c->pad);
     // the layout of the bf16 filter copy follows the kernel, and the kernel follows the SHAPE alone (a layer always takes the same
     // route, so a cached copy is always in the layout its reader expects): step-major for the LDS-halo form, plain KRSC otherwise
     const bool halo = halos_eligible(p) && aligned16(w) && aligned16(wb_ws) && wn % 4 == 0;
@@ -1424,48 +1238,25 @@ int cslgan_conv2d_dgrad_bf16s(const cslgan_conv_t* c, const void* gy, const floa
     p.w = wt_ws; p.Nn = c->C; p.out = gx; p.OHf = c->H; p.OWf = c->W; p.osy = p.osx = s; p.ldo = c->C;
     p.dense_out = (s == 1) ? 1 : 0;
     p.bias = nullptr; p.res = nullptr; p.mask = mask; p.mask_bf16 = gx_bf16; p.act = CSLGAN_ACT_NONE;
-    int off = 0, ncls = 0;
-    for (int py = 0; py < s; ++py)
-        for (int px = 0; px < s; ++px) {
-            const int OHc = (c->H - py + s - 1) / s, OWc = (c->W - px + s - 1) / s;
-            if (OHc <= 0 || OWc <= 0) continue;
-            const int cls = ncls++;
-            KcClass& k = p.cls[cls];
-            for (int t = 0; t < IG_MAX_TAPS; ++t) { k.ty[t] = 0; k.tx[t] = 0; }
-            int T = 0;
-            for (int kh = 0; kh < c->R; ++kh) {
-                if (((py + c->pad - kh) % s + s) % s != 0) continue;
-                for (int kw = 0; kw < c->S; ++kw) {
-                    if (((px + c->pad - kw) % s + s) % s != 0) continue;
-                    ra.kh[cls][T] = (signed char)kh; ra.kw[cls][T] = (signed char)kw;
-                    k.ty[T] = (signed char)((py + c->pad - kh) / s);
-                    k.tx[T] = (signed char)((px + c->pad - kw) / s);
-                    ++T;
-                }
-            }
-            CSLGAN_REQUIRE(T > 0, "conv2d_dgrad_bf16s: a parity class has no taps (filter smaller than stride)");
-            k.M = c->N * OHc * OWc; k.OHc = OHc; k.OWc = OWc; k.T = T; k.Kdim = T * c->K; k.w_off = off; k.oy0 = py; k.ox0 = px;
-            ra.cls_T[cls] = T; ra.cls_off[cls] = off; off += T * c->K * c->C;
-        }
+    ClassTaps src;
+    const int ncls = build_dgrad_classes(c, p.cls, src);
+    CSLGAN_REQUIRE(ncls > 0, "conv2d_dgrad_bf16s: a parity class has no taps (filter smaller than stride)");
+    for (int cls = 0; cls < ncls; ++cls) {
+        const KcClass& k = p.cls[cls];
+        for (int t = 0; t < k.T; ++t) { ra.kh[cls][t] = src.kh[cls][t]; ra.kw[cls][t] = src.kw[cls][t]; }
+        ra.cls_T[cls] = k.T; ra.cls_off[cls] = k.w_off;
+    }
     p.n_cls = ncls; ra.n_cls = ncls;
-    // the LDS-halo form reads step-major class matrices; like the forward entry, the route (and with it the layout of the cached bf16
-    // copy) follows the SHAPE alone
-    // Measured (128x128, same run, gather vs halo): conv2's data gradient into 64 channels 0.652 vs 0.682 ms at 384 rows (247 / 236 TF),
-    // conv3's into 128 channels 0.386 vs 0.473 ms (417 / 340 TF): with 4-9 taps per class the halo's reuse does not pay for its
-    // one-MFMA-tile-per-wave steps, so the data gradient stays on the gather form (CSLGAN_HALOS_DGRAD=1 routes it to the halo form).
-    static const int halo_dgrad_env = [] { const char* e = getenv("CSLGAN_HALOS_DGRAD"); return e ? atoi(e) : 0; }();
-    const bool halo = halo_dgrad_env && c->K % 16 == 0 && halos_eligible(p) && aligned16(wt_ws);
-    ra.step_major = halo ? 1 : 0;
+    // The data gradient always runs on the gather form, whose class matrices are plain [C][taps][K].  Measured (128x128, same run,
+    // gather vs LDS-halo): conv2's data gradient into 64 channels 0.652 vs 0.682 ms at 384 rows (247 / 236 TF), conv3's into 128
+    // channels 0.386 vs 0.473 ms (417 / 340 TF): with 4-9 taps per class the halo's reuse does not pay for its one-MFMA-tile-per-wave
+    // steps.
     if (repack) {
         unsigned gxn = (unsigned)(((long long)c->K * c->C * c->R * c->S / (s * s) + 255) / 256);
         gxn = gxn > 1024 ? 1024 : (gxn < 1 ? 1 : gxn);
         hipLaunchKernelGGL(repack_dgrad_bf16_kernel, dim3(gxn, (unsigned)ncls), dim3(256), 0, st, w, reinterpret_cast<unsigned short*>(wt_ws), ra);
         rc = check_launch("repack_dgrad_bf16_kernel");
         if (rc) return rc;
-    }
-    if (halo) {
-        p.w3 = wt_ws;
-        return launch_halos(p, gx_bf16 != 0, st);
     }
     return launch_kcs(p, gx_bf16 != 0, st);
 }
@@ -1486,9 +1277,7 @@ int cslgan_conv2d_wgrad_grouped_bf16s(const cslgan_conv_t* c, const void* gy, co
     p.gy = gy; p.x = x; p.N = c->N; p.H = c->H; p.W = c->W; p.C = c->C; p.P = c->P; p.Q = c->Q; p.Kc = c->K;
     p.T = c->R * c->S; p.Ndim = p.T * c->C; p.stride = c->stride; p.group = group; p.n_groups = c->N / group;
     p.alpha = alpha; p.gw = gw; p.sq = sq; p.out_bf16 = gw_bf16;
-    for (int t = 0; t < IG_MAX_TAPS; ++t) { p.ty[t] = 0; p.tx[t] = 0; }
-    for (int kh = 0; kh < c->R; ++kh)
-        for (int kw = 0; kw < c->S; ++kw) { p.ty[kh * c->S + kw] = (signed char)(kh - c->pad); p.tx[kh * c->S + kw] = (signed char)(kw - c->pad); }
+    fill_forward_taps(p.ty, p.tx, c->R, c->S, c->pad);
     p.tiles_m = (p.Kc + 127) / 128;
     p.tiles_n = (p.Ndim + 127) / 128;
     p.ksplit = 1;
@@ -1507,17 +1296,10 @@ int cslgan_conv2d_wgrad_grouped_bf16s(const cslgan_conv_t* c, const void* gy, co
     }
     const long long nb = (long long)p.n_groups * p.tiles_m * p.tiles_n * p.ksplit;
     CSLGAN_REQUIRE(nb <= 0x7fffffffll, "conv2d_wgrad_bf16s: grid too large");
-    static const int tr_env = [] { const char* e = getenv("CSLGAN_MCS_TR"); return e ? atoi(e) : 1; }();
-    if (tr_env) {
-        note_kernel("igemm_mcs_tr_kernel<128,128>");
-        if (c->Q % 8 == 0) hipLaunchKernelGGL(igemm_mcs_tr_kernel<true>, dim3((unsigned)nb), dim3(256), 0, st, p);
-        else hipLaunchKernelGGL(igemm_mcs_tr_kernel<false>, dim3((unsigned)nb), dim3(256), 0, st, p);
-    } else {
-        note_kernel("igemm_mcs_kernel<128,128>");
-        if (c->Q % 8 == 0) hipLaunchKernelGGL(igemm_mcs_kernel<true>, dim3((unsigned)nb), dim3(256), 0, st, p);
-        else hipLaunchKernelGGL(igemm_mcs_kernel<false>, dim3((unsigned)nb), dim3(256), 0, st, p);
-    }
-    rc = check_launch("igemm_mcs_kernel");
+    note_kernel("igemm_mcs_tr_kernel<128,128>");
+    if (c->Q % 8 == 0) hipLaunchKernelGGL(igemm_mcs_tr_kernel<true>, dim3((unsigned)nb), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(igemm_mcs_tr_kernel<false>, dim3((unsigned)nb), dim3(256), 0, st, p);
+    rc = check_launch("igemm_mcs_tr_kernel");
     if (rc) return rc;
     if (p.ksplit > 1 && p.sq) rc = sqnorm_rows_accumulate(reinterpret_cast<float*>(p.gw), p.n_groups, (long long)p.Kc * p.Ndim, p.sq, st);
     return rc;
@@ -1540,9 +1322,7 @@ int cslgan_conv2d_wgrad_scaled_bf16s(const cslgan_conv_t* c, const void* gy, con
     p.gy = gy; p.x = x; p.N = c->N; p.H = c->H; p.W = c->W; p.C = c->C; p.P = c->P; p.Q = c->Q; p.Kc = c->K;
     p.T = c->R * c->S; p.Ndim = p.T * c->C; p.stride = c->stride; p.group = group; p.n_groups = c->N / group;
     p.alpha = alpha; p.gw = gw; p.sq = nullptr; p.out_bf16 = 0; p.row_scale = row_scale; p.ksplit = 1;
-    for (int t = 0; t < IG_MAX_TAPS; ++t) { p.ty[t] = 0; p.tx[t] = 0; }
-    for (int kh = 0; kh < c->R; ++kh)
-        for (int kw = 0; kw < c->S; ++kw) { p.ty[kh * c->S + kw] = (signed char)(kh - c->pad); p.tx[kh * c->S + kw] = (signed char)(kw - c->pad); }
+    fill_forward_taps(p.ty, p.tx, c->R, c->S, c->pad);
     p.tiles_m = (p.Kc + 127) / 128;
     p.tiles_n = (p.Ndim + 127) / 128;
     const long long nb = (long long)p.n_groups * p.tiles_m * p.tiles_n;

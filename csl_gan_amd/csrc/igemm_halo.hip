@@ -13,6 +13,7 @@
 // Same MFMA schedule as igemm_kc (v_mfma_f32_32x32x2_f32, half-wave h owns k = 8g+4h+e), same epilogue.
 #include "common.h"
 #include "igemm.h"
+#include "conv_classes.h"
 
 namespace cslgan {
 
@@ -265,11 +266,8 @@ bool halo_eligible(const KcParams& p) {
         if (k.T < 2 || (k.M & 63)) return false;
         if (quad && k.M < 4096) return false;       // too few four-image patches to fill the chip: igemm_kc's small tiles win
         if (!quad && ((k.OHc & 7) || (k.OWc & 7))) return false;
-        int ymin = 127, ymax = -128, xmin = 127, xmax = -128;
-        for (int t = 0; t < k.T; ++t) {
-            ymin = k.ty[t] < ymin ? k.ty[t] : ymin; ymax = k.ty[t] > ymax ? k.ty[t] : ymax;
-            xmin = k.tx[t] < xmin ? k.tx[t] : xmin; xmax = k.tx[t] > xmax ? k.tx[t] : xmax;
-        }
+        int ymin, ymax, xmin, xmax;
+        tap_range(k, ymin, ymax, xmin, xmax);
         const int lim = quad ? 2 : 4;       // four 6x6 halos fill the 144-pixel LDS image
         if (ymax - ymin > lim || xmax - xmin > lim) return false;
     }
@@ -280,11 +278,8 @@ int launch_halo(KcParams& p, hipStream_t st) {
     int tm = 0;
     for (int c = 0; c < p.n_cls; ++c) {
         KcClass& k = p.cls[c];
-        int ymin = 127, ymax = -128, xmin = 127, xmax = -128;
-        for (int t = 0; t < k.T; ++t) {
-            ymin = k.ty[t] < ymin ? k.ty[t] : ymin; ymax = k.ty[t] > ymax ? k.ty[t] : ymax;
-            xmin = k.tx[t] < xmin ? k.tx[t] : xmin; xmax = k.tx[t] > xmax ? k.tx[t] : xmax;
-        }
+        int ymin, ymax, xmin, xmax;
+        tap_range(k, ymin, ymax, xmin, xmax);
         const bool quad = k.OHc == 4 && k.OWc == 4;
         const int side = quad ? 4 : 8;
         k.ty_min = ymin; k.tx_min = xmin; k.halo_h = side + ymax - ymin; k.halo_w = side + xmax - xmin;
@@ -298,31 +293,16 @@ int launch_halo(KcParams& p, hipStream_t st) {
     // gradient): 64-wide tiles, and the heaviest class is paired with the lightest in ONE workgroup so every workgroup
     // carries the same number of K steps — when the halved grid still fills the chip.  Measured on the critic's data
     // gradients at 128 / 384 rows (scripts/dgrad_sweep.py): 63 -> 81, 68 -> 75, 76 -> 96, 83 -> 98, 65 -> 79 TF.
-    bool same_m = true, same_t = true;
-    for (int c = 1; c < p.n_cls; ++c) { same_m = same_m && p.cls[c].M == p.cls[0].M; same_t = same_t && p.cls[c].T == p.cls[0].T; }
-    static const int wide_min = [] { const char* e = getenv("CSLGAN_HALO_WIDE_MIN"); return e ? atoi(e) : 0; }();
-    bool wide = p.Nn > 64 && same_t && (long long)tm * ((p.Nn + 127) / 128) >= wide_min;
-    p.pair_mode = 0;
+    constexpr int HALO_PAIR_MIN = 256;         // smallest paired grid that still fills the chip
+    constexpr int HALO_ACC_WIDE_MIN = 256;     // acc_classes: 128-wide N tiles from this many 128x128 tiles on
+    bool same_t = true;
+    for (int c = 1; c < p.n_cls; ++c) same_t = same_t && p.cls[c].T == p.cls[0].T;
+    bool wide = p.Nn > 64 && same_t;
     if (p.acc_classes) {        // all classes in every workgroup: one class's tiles, balanced by construction
         p.tiles_m = (p.cls[0].M + 127) / 128;
-        wide = p.Nn > 64 && (long long)p.tiles_m * ((p.Nn + 127) / 128) >= 256;
+        wide = p.Nn > 64 && (long long)p.tiles_m * ((p.Nn + 127) / 128) >= HALO_ACC_WIDE_MIN;
     }
-    static const int pair_min = [] { const char* e = getenv("CSLGAN_HALO_PAIR_MIN"); return e ? atoi(e) : 256; }();
-    if (!p.acc_classes && p.n_cls == 4 && same_m && !same_t) {
-        const int tpc = (p.cls[0].M + 127) / 128;
-        const long long paired = 2ll * tpc * (wide ? (p.Nn + 127) / 128 : (p.Nn + 63) / 64);
-        if (paired >= pair_min) {
-            int o[4] = {0, 1, 2, 3};
-            for (int i = 0; i < 4; ++i)
-                for (int j = i + 1; j < 4; ++j)
-                    if (p.cls[o[j]].T > p.cls[o[i]].T) { const int t = o[i]; o[i] = o[j]; o[j] = t; }
-            p.pair_mode = 1;
-            p.pair_cls[0][0] = o[0]; p.pair_cls[0][1] = o[3];
-            p.pair_cls[1][0] = o[1]; p.pair_cls[1][1] = o[2];
-            p.tiles_per_cls = tpc;
-            p.tiles_m = 2 * tpc;
-        }
-    }
+    pair_unequal_classes(p, wide, HALO_PAIR_MIN);
     p.tiles_n = wide ? (p.Nn + 127) / 128 : (p.Nn + 63) / 64;
     const dim3 grid((unsigned)(p.tiles_m * p.tiles_n)), block(256);
     bool gen = p.pair_mode != 0 || p.acc_classes != 0;

@@ -18,9 +18,9 @@
 //
 // Replaces (reference file:line): torch.nn.Conv2d / nn.Linear forward DCResNet_models.py:131-132,
 // 145, 16 (the conv of UpsampleConv, on the depth-to-space tensor), 60-70, 95-104; MNIST_models.py:17-23, 41-46; and the autograd data-gradient of those.
-#include <stdlib.h>
 #include "common.h"
 #include "igemm.h"
+#include "conv_classes.h"
 
 namespace cslgan {
 
@@ -443,8 +443,7 @@ int launch_kc(KcParams& p, hipStream_t st, long long out_elems) {
         }
     }
     // 1..4 output channels: vector-ALU kernel, fp32 in every compute mode (a 32-wide MFMA tile would be 29/32 padding)
-    static const int skinny_env = [] { const char* e = getenv("CSLGAN_KC_SKINNY"); return e ? atoi(e) : 1; }();
-    if (skinny_env && !p.acc_classes && skinny_eligible(p)) {
+    if (!p.acc_classes && skinny_eligible(p)) {
         if (p.gn_part) { set_error("conv2d_fwd: gn_part is not produced by the 1..4-output-channel kernel"); return CSLGAN_ERR_INVALID_ARG; }
         return launch_skinny(p, st);
     }
@@ -454,12 +453,10 @@ int launch_kc(KcParams& p, hipStream_t st, long long out_elems) {
     }
     if (p.w3 && x3h_eligible(p)) return launch_x3h(p, st);          // exact fp32 on the round-4 halo kernel (step-major fp32 filter copy in p.w3)
     if (p.gn_part || p.in_scale) { set_error("conv2d_fwd: gn_part / in_scale given but the shape does not run on the LDS-halo kernel"); return CSLGAN_ERR_INVALID_ARG; }
-    static const int halo_env = [] { const char* e = getenv("CSLGAN_KC_HALO"); return e ? atoi(e) : 1; }();
-    if (halo_env && halo_eligible(p)) return launch_halo(p, st);
-    static const int patch_env = [] { const char* e = getenv("CSLGAN_KC_PATCH"); return e ? atoi(e) : 1; }();
+    if (halo_eligible(p)) return launch_halo(p, st);
     for (int c = 0; c < p.n_cls; ++c) {
         KcClass& k = p.cls[c];
-        k.patch = (patch_env && k.T > 1 && k.OHc % 8 == 0 && k.OWc % 8 == 0) ? 1 : 0;
+        k.patch = (k.T > 1 && k.OHc % 8 == 0 && k.OWc % 8 == 0) ? 1 : 0;
     }
     bool kd4 = true;
     for (int c = 0; c < p.n_cls; ++c) kd4 = kd4 && (p.cls[c].Kdim % 4 == 0) && (p.cls[c].w_off % 4 == 0);
@@ -470,12 +467,12 @@ int launch_kc(KcParams& p, hipStream_t st, long long out_elems) {
         if (tiles_for(p, 128, 64) >= 192) return launch_kc_tile<128, 64, 2, 2>(p, vecA, vecB, st, out_elems);
         return launch_kc_tile<64, 64, 2, 2>(p, vecA, vecB, st, out_elems);
     }
-    static const int t128 = [] { const char* e = getenv("CSLGAN_KC_T128"); return e ? atoi(e) : 300; }();
+    constexpr int KC_T128 = 300;       // 128x128 tiles from which the large tile is used
     // classes of one launch have different K (9/6/6/4 taps for a 5x5 stride-2 data gradient): with about one
     // workgroup per CU the launch lasts as long as its heaviest class, so multi-class launches want more, smaller tiles
-    static const int tmc = [] { const char* e = getenv("CSLGAN_KC_TMC"); return e ? atoi(e) : 520; }();
-    const int t64 = p.n_cls > 1 ? tmc : 192;
-    if (tiles_for(p, 128, 128) >= t128) return launch_kc_tile<128, 128, 2, 2>(p, vecA, vecB, st, out_elems);
+    constexpr int KC_TMC = 520;
+    const int t64 = p.n_cls > 1 ? KC_TMC : 192;
+    if (tiles_for(p, 128, 128) >= KC_T128) return launch_kc_tile<128, 128, 2, 2>(p, vecA, vecB, st, out_elems);
     if (tiles_for(p, 64, 128) >= t64) return launch_kc_tile<64, 128, 1, 4>(p, vecA, vecB, st, out_elems);
     return launch_kc_tile<64, 64, 2, 2>(p, vecA, vecB, st, out_elems);
 }
@@ -491,10 +488,6 @@ static int check_conv(const cslgan_conv_t* c, const char* who) {
     CSLGAN_REQUIRE((long long)c->N * c->P * c->Q * c->K < (1ll << 31) && (long long)c->N * VH * VW * c->C < (1ll << 31) &&
                    (long long)c->K * c->R * c->S * c->C < (1ll << 31), "%s: tensor too large for 32-bit offsets", who);
     return CSLGAN_OK;
-}
-
-static void clear_taps(KcClass& k) {
-    for (int t = 0; t < IG_MAX_TAPS; ++t) { k.ty[t] = 0; k.tx[t] = 0; }
 }
 
 }  // namespace cslgan
@@ -541,7 +534,6 @@ static int conv2d_fwd_impl(const cslgan_conv_t* c, const float* x, const float* 
     int rc = check_conv(c, "conv2d_fwd");
     if (rc) return rc;
     CSLGAN_REQUIRE(act >= 0 && act <= 3, "conv2d_fwd: unknown activation %d", act);
-    static const int c3_env = [] { const char* e = getenv("CSLGAN_C3"); return e ? atoi(e) : 1; }();
     if (c->in_scale) {      // the input affine map is applied by the halo kernel's and the 1..4-output kernel's staging only
         CSLGAN_REQUIRE(c->in_shift && !x_bf16 && c->stride == 1 && c->R * c->S > 1 && aligned16(c->in_scale) && aligned16(c->in_shift),
                        "conv2d_fwd: in_scale needs in_shift, stride 1, a filter larger than 1x1 and 16-byte aligned tables");
@@ -555,7 +547,7 @@ static int conv2d_fwd_impl(const cslgan_conv_t* c, const float* x, const float* 
     if (x_bf16) {
         CSLGAN_REQUIRE(c->K <= 4 && c->C == 64 && c->stride == 1 && !residual, "conv2d_fwd_skinny_bf16in: needs 1..4 output channels, 64 input channels, stride 1");
     } else
-    if (c3_env && c3_fwd_eligible(c, residual))          // the critic's RGB first layer (conv_c3.hip), exact fp32 in every compute mode
+    if (c3_fwd_eligible(c, residual))          // the critic's RGB first layer (conv_c3.hip), exact fp32 in every compute mode
         return launch_c3_fwd(c, x, w, bias, act, y, (hipStream_t)stream);
     if (conv1x1_eligible(c, x, w, residual))                     // the generator's shortcut convs (conv1x1.hip)
         return launch_conv1x1(c, x, w, bias, act, y, (hipStream_t)stream);
@@ -574,9 +566,7 @@ static int conv2d_fwd_impl(const cslgan_conv_t* c, const float* x, const float* 
     p.n_cls = 1;
     KcClass& k = p.cls[0];
     k.M = c->N * c->P * c->Q; k.OHc = c->P; k.OWc = c->Q; k.T = c->R * c->S; k.Kdim = k.T * c->C; k.w_off = 0; k.oy0 = k.ox0 = 0;
-    clear_taps(k);
-    for (int kh = 0; kh < c->R; ++kh)
-        for (int kw = 0; kw < c->S; ++kw) { k.ty[kh * c->S + kw] = (signed char)(kh - c->pad); k.tx[kh * c->S + kw] = (signed char)(kw - c->pad); }
+    fill_forward_taps(k.ty, k.tx, c->R, c->S, c->pad);
     return launch_kc(p, (hipStream_t)stream, (long long)c->N * c->P * c->Q * c->K);
 }
 
@@ -624,7 +614,6 @@ static int conv2d_s2_fwd_impl(const cslgan_conv_t* c, const float* x, const floa
     for (int a = 0; ok && a < 2; ++a)
         for (int b = 0; ok && b < 2; ++b) {
             KcClass& k = p.cls[n];
-            clear_taps(k);
             int T = 0;
             for (int kh = 0; kh < R; ++kh)
                 for (int kw = 0; kw < R; ++kw) {
@@ -642,11 +631,9 @@ static int conv2d_s2_fwd_impl(const cslgan_conv_t* c, const float* x, const floa
             ++n;
         }
     p.n_cls = n; ra.n_class = n;
-    static const int halo_env = [] { const char* e = getenv("CSLGAN_KC_HALO"); return e ? atoi(e) : 1; }();
-    static const int s2_env = [] { const char* e = getenv("CSLGAN_S2_HALO"); return e ? atoi(e) : 1; }();
     // Measured on the critic (B=128 and the fused 384 rows, scripts/shape_times.py): 92 -> 109 TF on the 768-tile conv2
     // launch, no gain or a loss below ~500 tiles (four halo stagings per chunk for 2-9 taps each) -> igemm_kc keeps those.
-    static const int s2_min_tiles = [] { const char* e = getenv("CSLGAN_S2_MIN_TILES"); return e ? atoi(e) : 512; }();
+    constexpr int S2_MIN_TILES = 512;
     const long long wide_tiles = ((long long)c->N * c->P * c->Q + 127) / 128 * ((c->K + 127) / 128);
     if (w3_ws) {        // the round-4 LDS-halo kernel: three-piece, plain bf16 or exact fp32 operands, any tile count
         p.bf16 = c->compute == CSLGAN_COMPUTE_BF16X3 ? 3 : (c->compute == CSLGAN_COMPUTE_BF16 ? 1 : 0);
@@ -670,7 +657,7 @@ static int conv2d_s2_fwd_impl(const cslgan_conv_t* c, const float* x, const floa
     if (w3_ws) {
         if (!ok || n == 0 || !x3h_eligible(p))
             return cslgan_conv2d_fwd_f32(c, x, w, bias, nullptr, act, y, stream);
-    } else if (!ok || n == 0 || !halo_env || !s2_env || wide_tiles < s2_min_tiles || c->compute != CSLGAN_COMPUTE_F32 || !halo_eligible(p))
+    } else if (!ok || n == 0 || wide_tiles < S2_MIN_TILES || c->compute != CSLGAN_COMPUTE_F32 || !halo_eligible(p))
         return cslgan_conv2d_fwd_f32(c, x, w, bias, nullptr, act, y, stream);
     return launch_kc(p, st, 0);
 }
@@ -720,30 +707,17 @@ static int conv2d_dgrad_impl(const cslgan_conv_t* c, const float* gy, const floa
     p.a_bf16 = gy_bf16;
     p.w3 = (w3_ws && c->K % 16 == 0 && aligned16(w3_ws)) ? w3_ws : nullptr;
     p.part = reinterpret_cast<float*>(c->split_ws); p.part_floats = c->split_ws_floats; p.out_floats = (long long)c->N * c->H * c->W * c->C;
-    int off = 0, ncls = 0;
-    for (int py = 0; py < s; ++py)
-        for (int px = 0; px < s; ++px) {
-            const int OHc = (c->H - py + s - 1) / s, OWc = (c->W - px + s - 1) / s;
-            if (OHc <= 0 || OWc <= 0) continue;
-            const int cls = ncls++;
-            KcClass& k = p.cls[cls];
-            clear_taps(k);
-            int T = 0;
-            for (int kh = 0; kh < c->R; ++kh) {
-                if (((py + c->pad - kh) % s + s) % s != 0) continue;
-                for (int kw = 0; kw < c->S; ++kw) {
-                    if (((px + c->pad - kw) % s + s) % s != 0) continue;
-                    ra.kh_lo[cls][T] = (signed char)kh; ra.kh_hi[cls][T] = (signed char)(kh + 1);
-                    ra.kw_lo[cls][T] = (signed char)kw; ra.kw_hi[cls][T] = (signed char)(kw + 1);
-                    k.ty[T] = (signed char)((py + c->pad - kh) / s);
-                    k.tx[T] = (signed char)((px + c->pad - kw) / s);
-                    ++T;
-                }
-            }
-            CSLGAN_REQUIRE(T > 0, "conv2d_dgrad: a parity class has no taps (filter smaller than stride)");
-            k.M = c->N * OHc * OWc; k.OHc = OHc; k.OWc = OWc; k.T = T; k.Kdim = T * c->K; k.w_off = off; k.oy0 = py; k.ox0 = px;
-            ra.cls_T[cls] = T; ra.cls_off[cls] = off; off += T * c->K * c->C;
+    ClassTaps src;
+    const int ncls = build_dgrad_classes(c, p.cls, src);
+    CSLGAN_REQUIRE(ncls > 0, "conv2d_dgrad: a parity class has no taps (filter smaller than stride)");
+    for (int cls = 0; cls < ncls; ++cls) {
+        const KcClass& k = p.cls[cls];
+        for (int t = 0; t < k.T; ++t) {
+            ra.kh_lo[cls][t] = src.kh[cls][t]; ra.kh_hi[cls][t] = (signed char)(src.kh[cls][t] + 1);
+            ra.kw_lo[cls][t] = src.kw[cls][t]; ra.kw_hi[cls][t] = (signed char)(src.kw[cls][t] + 1);
         }
+        ra.cls_T[cls] = k.T; ra.cls_off[cls] = k.w_off;
+    }
     p.n_cls = ncls; ra.n_class = ncls;
     if (repack) {
         unsigned gxn = (unsigned)(((long long)c->K * c->C * c->R * c->S / (s * s) + 255) / 256);

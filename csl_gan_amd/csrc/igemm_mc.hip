@@ -13,6 +13,7 @@
 // conflict-free).  v_mfma_f32_32x32x2_f32, exact fp32.
 #include "common.h"
 #include "igemm.h"
+#include "conv_classes.h"
 
 namespace cslgan {
 
@@ -349,27 +350,22 @@ static int wgrad_grouped_impl(const cslgan_conv_t* c, const float* gy, const flo
     CSLGAN_REQUIRE(c->compute >= CSLGAN_COMPUTE_F32 && c->compute <= CSLGAN_COMPUTE_BF16X3, "conv2d_wgrad: unknown cslgan_conv_t.compute %d", c->compute);
     const int P = (c->H + 2 * c->pad - c->R) / c->stride + 1, Q = (c->W + 2 * c->pad - c->S) / c->stride + 1;
     CSLGAN_REQUIRE(P == c->P && Q == c->Q, "conv2d_wgrad: output %dx%d does not match P,Q=%d,%d", P, Q, c->P, c->Q);
-    static const int c3_env = [] { const char* e = getenv("CSLGAN_C3"); return e ? atoi(e) : 1; }();
-    if (c3_env && !row_scale && c3_wgrad_eligible(c, group, out_bf16, gy))     // the critic's RGB first layer (conv_c3.hip)
+    if (!row_scale && c3_wgrad_eligible(c, group, out_bf16, gy))     // the critic's RGB first layer (conv_c3.hip)
         return launch_c3_wgrad(c, gy, x, alpha, gw, sq, (hipStream_t)stream);
-    static const int wgh_env = [] { const char* e = getenv("CSLGAN_WGH"); return e ? atoi(e) : 1; }();
-    if (wgh_env && ((c->compute == CSLGAN_COMPUTE_F32 && wgh_eligible(c, out_bf16, gy, x)) ||
-                    (c->compute == CSLGAN_COMPUTE_BF16X3 && (x3w_eligible(c, out_bf16, gy, x) || x3w_quad_eligible(c, group, out_bf16, gy, x)))))
+    if ((c->compute == CSLGAN_COMPUTE_F32 && wgh_eligible(c, out_bf16, gy, x)) ||
+        (c->compute == CSLGAN_COMPUTE_BF16X3 && (x3w_eligible(c, out_bf16, gy, x) || x3w_quad_eligible(c, group, out_bf16, gy, x))))
         return launch_wgh(c, gy, x, group, alpha, gw, sq, (hipStream_t)stream, row_scale);
     McParams p{};
     p.gy = gy; p.x = x; p.N = c->N; p.H = c->H; p.W = c->W; p.C = c->C; p.P = c->P; p.Q = c->Q; p.Kc = c->K;
     p.T = c->R * c->S; p.Ndim = p.T * c->C; p.stride = c->stride; p.group = group; p.n_groups = c->N / group;
     p.alpha = alpha; p.gw = gw; p.sq = sq; p.out_bf16 = out_bf16; p.row_scale = row_scale;
-    for (int t = 0; t < IG_MAX_TAPS; ++t) { p.ty[t] = 0; p.tx[t] = 0; }
-    for (int kh = 0; kh < c->R; ++kh)
-        for (int kw = 0; kw < c->S; ++kw) { p.ty[kh * c->S + kw] = (signed char)(kh - c->pad); p.tx[kh * c->S + kw] = (signed char)(kw - c->pad); }
+    fill_forward_taps(p.ty, p.tx, c->R, c->S, c->pad);
     const bool vecA = (c->K % 4 == 0) && aligned16(gy);
     const bool vecB = (c->C % 4 == 0) && aligned16(x);
     if (c->compute != CSLGAN_COMPUTE_F32) return launch_mc_bf16(p, vecA, vecB, (hipStream_t)stream, c->compute == CSLGAN_COMPUTE_BF16X3 ? 3 : 1);
     if (c->K > 64) return launch_mc_tile<128, 128, 2, 2>(p, vecA, vecB, (hipStream_t)stream);
     // 64 output channels: a 64x256 tile reads 20 KB per K tile for the MACs a 64x128 tile does with 12 KB twice
-    static const int wide64 = [] { const char* e = getenv("CSLGAN_MC_WIDE64"); return e ? atoi(e) : 1; }();
-    if (wide64 && c->K > 32 && p.Ndim >= 1024 && (long long)p.n_groups * ((p.Ndim + 255) / 256) >= 256)
+    if (c->K > 32 && p.Ndim >= 1024 && (long long)p.n_groups * ((p.Ndim + 255) / 256) >= 256)
         return launch_mc_tile<64, 256, 1, 4>(p, vecA, vecB, (hipStream_t)stream);
     return launch_mc_tile<64, 128, 1, 4>(p, vecA, vecB, (hipStream_t)stream);
 }

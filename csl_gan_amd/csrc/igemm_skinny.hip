@@ -9,6 +9,7 @@
 // 16 partial sums meet in a 4-step butterfly.  Same KcParams classes / epilogue contract as igemm_kc.
 #include "common.h"
 #include "igemm.h"
+#include "conv_classes.h"
 
 namespace cslgan {
 
@@ -183,11 +184,8 @@ bool skinny_eligible(const KcParams& p) {
     for (int c = 0; c < p.n_cls; ++c) {
         const KcClass& k = p.cls[c];
         if (k.T < 1 || k.T > SK_MAXT || (k.OHc & 7) || (k.OWc & 7) || (k.M & 63) || (k.w_off & 3)) return false;
-        int ymin = 127, ymax = -128, xmin = 127, xmax = -128;
-        for (int t = 0; t < k.T; ++t) {
-            ymin = k.ty[t] < ymin ? k.ty[t] : ymin; ymax = k.ty[t] > ymax ? k.ty[t] : ymax;
-            xmin = k.tx[t] < xmin ? k.tx[t] : xmin; xmax = k.tx[t] > xmax ? k.tx[t] : xmax;
-        }
+        int ymin, ymax, xmin, xmax;
+        tap_range(k, ymin, ymax, xmin, xmax);
         if (ymax - ymin > 4 || xmax - xmin > 4) return false;
     }
     return true;
@@ -197,11 +195,8 @@ int launch_skinny(KcParams& p, hipStream_t st) {
     int tm = 0;
     for (int c = 0; c < p.n_cls; ++c) {
         KcClass& k = p.cls[c];
-        int ymin = 127, ymax = -128, xmin = 127, xmax = -128;
-        for (int t = 0; t < k.T; ++t) {
-            ymin = k.ty[t] < ymin ? k.ty[t] : ymin; ymax = k.ty[t] > ymax ? k.ty[t] : ymax;
-            xmin = k.tx[t] < xmin ? k.tx[t] : xmin; xmax = k.tx[t] > xmax ? k.tx[t] : xmax;
-        }
+        int ymin, ymax, xmin, xmax;
+        tap_range(k, ymin, ymax, xmin, xmax);
         k.ty_min = ymin; k.tx_min = xmin; k.halo_h = 8 + ymax - ymin; k.halo_w = 8 + xmax - xmin;
         k.patch = 1;
         k.tile0 = tm;                  // in 8x8 patches
@@ -217,8 +212,7 @@ int launch_skinny(KcParams& p, hipStream_t st) {
         uy0 = k.ty_min < uy0 ? k.ty_min : uy0; ux0 = k.tx_min < ux0 ? k.tx_min : ux0;
         uy1 = k.ty_min + k.halo_h > uy1 ? k.ty_min + k.halo_h : uy1; ux1 = k.tx_min + k.halo_w > ux1 ? k.tx_min + k.halo_w : ux1;
     }
-    static const int all_env = [] { const char* e = getenv("CSLGAN_SKINNY_ALL"); return e ? atoi(e) : 1; }();
-    all = all && all_env && (uy1 - uy0) * (ux1 - ux0) <= SK_HALO;
+    all = all && (uy1 - uy0) * (ux1 - ux0) <= SK_HALO;
     if (all) {
         for (int c = 0; c < p.n_cls; ++c) {
             KcClass& k = p.cls[c];
@@ -373,8 +367,7 @@ int cslgan_conv2d_wgrad_skinny_f32(const cslgan_conv_t* c, const float* gy, cons
     p.n_patches = c->N * (c->P >> 3) * (c->Q >> 3);
     p.x_bytes = (unsigned)(4ll * c->N * c->H * c->W * SK_C);
     p.alpha = alpha; p.partial = partial;
-    for (int kh = 0; kh < c->R; ++kh)
-        for (int kw = 0; kw < c->S; ++kw) { p.ty[kh * c->S + kw] = (signed char)(kh - c->pad); p.tx[kh * c->S + kw] = (signed char)(kw - c->pad); }
+    fill_forward_taps(p.ty, p.tx, c->R, c->S, c->pad);
     p.ty_min = -c->pad; p.tx_min = -c->pad; p.halo_h = 8 + c->R - 1; p.halo_w = 8 + c->S - 1;
     const dim3 grid((unsigned)n_blocks), block(256);
     note_kernel("skinny_wgrad_kernel<%d>", c->K);

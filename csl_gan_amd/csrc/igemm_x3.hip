@@ -32,9 +32,9 @@
 //
 // Replaces (reference file:line): nn.Conv2d forward and its autograd data gradient, DCResNet_models.py:16,60-70,95-104,
 // 131-132; gradient_penalty.py:48-54 (the double backward runs the same two ops).
-#include <stdlib.h>
 #include "common.h"
 #include "igemm.h"
+#include "conv_classes.h"
 
 namespace cslgan {
 
@@ -623,14 +623,6 @@ int split_filter_x3(const float* w, int Nn, int T, int C, void* w3, hipStream_t 
     return check_launch("split_filter_x3_kernel");
 }
 
-static void tap_range(const KcClass& k, int& ymin, int& ymax, int& xmin, int& xmax) {
-    ymin = 127; ymax = -128; xmin = 127; xmax = -128;
-    for (int t = 0; t < k.T; ++t) {
-        ymin = k.ty[t] < ymin ? k.ty[t] : ymin; ymax = k.ty[t] > ymax ? k.ty[t] : ymax;
-        xmin = k.tx[t] < xmin ? k.tx[t] : xmin; xmax = k.tx[t] > xmax ? k.tx[t] : xmax;
-    }
-}
-
 // Row-major affine tap grid: returns taps per row (nkw), 0 if the table is not one.
 static int affine_taps(const KcClass& k) {
     int nkw = 1;
@@ -647,18 +639,15 @@ static int affine_taps(const KcClass& k) {
 // Shapes the x3 halo form takes: stride-1 classes on 8x8-patchable (or 4x4) grids, channels a multiple of 16, 2..25 affine taps
 // within a 12x12 (6x6) halo, >= 64 output channels, and the pre-split filter (p.w3).
 bool x3h_eligible(const KcParams& p) {
-    static const int env = [] { const char* e = getenv("CSLGAN_X3_HALO"); return e ? atoi(e) : 1; }();
-    static const int env32 = [] { const char* e = getenv("CSLGAN_F32_HALO"); return e ? atoi(e) : 1; }();
-    if (!p.bf16 && !env32) return false;          // exact fp32 on this kernel (NP = 0) is an A/B switch of its own
-    if (!env || !p.w3 || p.sy != 1 || p.sx != 1 || (p.AC & 15) || p.Nn < 64 || p.ksplit > 1 || !aligned16(p.a) || !aligned16(p.w3)) return false;
+    if (!p.w3 || p.sy != 1 || p.sx != 1 || (p.AC & 15) || p.Nn < 64 || p.ksplit > 1 || !aligned16(p.a) || !aligned16(p.w3)) return false;
     // 4-element epilogue vectors: channel counts and the output row pitch multiples of 4, every epilogue operand 16-byte aligned
     if ((p.Nn & 3) || (p.ldo & 3) || !aligned16(p.out) || (p.bias && !aligned16(p.bias)) || (p.res && !aligned16(p.res)) || (p.mask && !aligned16(p.mask))) return false;
-    static const int quad_min = [] { const char* e = getenv("CSLGAN_X3_QUAD_MIN"); return e ? atoi(e) : 2048; }();
+    constexpr int X3_QUAD_MIN = 2048;      // rows of a 4x4-grid class below which the four-image patches leave the chip idle
     for (int c = 0; c < p.n_cls; ++c) {
         const KcClass& k = p.cls[c];
         const bool quad = k.OHc == 4 && k.OWc == 4;
         if (k.T < 2 || (k.M & 63) || (k.Kdim & 3) || (k.w_off & 7)) return false;
-        if (quad && (k.M < quad_min || !p.bf16)) return false;   // exact fp32 keeps its round-3 kernels on 4x4 grids (measured: 52-73 vs 74-84 TF)
+        if (quad && (k.M < X3_QUAD_MIN || !p.bf16)) return false;   // exact fp32 keeps its round-3 kernels on 4x4 grids (measured: 52-73 vs 74-84 TF)
         if (!quad && ((k.OHc & 7) || (k.OWc & 7))) return false;
         if (!affine_taps(k)) return false;
         int ymin, ymax, xmin, xmax;
@@ -693,44 +682,27 @@ int launch_x3h(KcParams& p, hipStream_t st) {
     }
     p.tiles_m = tm;
     p.ksplit = 1;
-    p.pair_mode = 0;
-    bool same_m = true, same_t = true;
-    for (int c = 1; c < p.n_cls; ++c) { same_m = same_m && p.cls[c].M == p.cls[0].M; same_t = same_t && p.cls[c].T == p.cls[0].T; }
     bool wide = p.Nn > 64;
     if (p.acc_classes) p.tiles_m = (p.cls[0].M + 127) / 128;       // all classes in every workgroup
     // unequal classes (9/6/6/4 taps): the heaviest runs with the lightest in ONE workgroup (9+4, 6+6 K steps) while the halved grid
     // still fills the chip — the rule of igemm_halo.hip
-    static const int pair_min = [] { const char* e = getenv("CSLGAN_X3_PAIR_MIN"); return e ? atoi(e) : 256; }();
-    if (!p.acc_classes && p.n_cls == 4 && same_m && !same_t) {
-        const int tpc = (p.cls[0].M + 127) / 128;
-        const long long paired = 2ll * tpc * (wide ? (p.Nn + 127) / 128 : (p.Nn + 63) / 64);
-        if (paired >= pair_min) {
-            int o[4] = {0, 1, 2, 3};
-            for (int i = 0; i < 4; ++i)
-                for (int j = i + 1; j < 4; ++j)
-                    if (p.cls[o[j]].T > p.cls[o[i]].T) { const int t = o[i]; o[i] = o[j]; o[j] = t; }
-            p.pair_mode = 1;
-            p.pair_cls[0][0] = o[0]; p.pair_cls[0][1] = o[3];
-            p.pair_cls[1][0] = o[1]; p.pair_cls[1][1] = o[2];
-            p.tiles_per_cls = tpc;
-            p.tiles_m = 2 * tpc;
-        }
-    }
+    constexpr int X3_PAIR_MIN = 256;
+    pair_unequal_classes(p, wide, X3_PAIR_MIN);
     // 64-wide N tiles when the 128-wide grid would leave CUs idle (128-row launches of the critic's last layers)
-    static const int wide_min = [] { const char* e = getenv("CSLGAN_X3_WIDE_MIN"); return e ? atoi(e) : 192; }();
-    if (wide && (long long)p.tiles_m * ((p.Nn + 127) / 128) < wide_min) wide = false;
+    constexpr int X3_WIDE_MIN = 192;
+    if (wide && (long long)p.tiles_m * ((p.Nn + 127) / 128) < X3_WIDE_MIN) wide = false;
     p.tiles_n = wide ? (p.Nn + 127) / 128 : (p.Nn + 63) / 64;
     // Channel split: a launch of fewer than 512 workgroups (two per CU) leaves CUs idle or with one wave per SIMD — the critic's
     // third and fourth convs run 64..384 tiles.  With scratch from the caller the 16-channel chunks are divided over `csplit`
     // workgroups per tile; cost model = rounds of 256 CUs x work per workgroup, ceil(tiles * s / 256) / s, smallest s on ties,
     // at least two chunks per workgroup (prologue + epilogue stay a small share).
     p.csplit = 1;
-    static const int split_env = [] { const char* e = getenv("CSLGAN_X3_SPLIT"); return e ? atoi(e) : 8; }();       // max split, 0/1 = off
+    constexpr int X3_MAX_SPLIT = 8;        // largest split; the caller opts in by handing scratch (p.part)
     const long long tiles = (long long)p.tiles_m * p.tiles_n;
-    if (split_env > 1 && p.part && !p.res && p.ldo == p.Nn && p.out_floats > 0 && (p.out_floats & 3) == 0 && aligned16(p.part) && tiles < 512) {
+    if (p.part && !p.res && p.ldo == p.Nn && p.out_floats > 0 && (p.out_floats & 3) == 0 && aligned16(p.part) && tiles < 512) {
         const int n_cc = p.AC >> 4;
         double best = (double)((tiles + 255) / 256);
-        for (int s = 2; s <= split_env && n_cc / s >= 2 && (long long)s * p.out_floats <= p.part_floats; ++s) {
+        for (int s = 2; s <= X3_MAX_SPLIT && n_cc / s >= 2 && (long long)s * p.out_floats <= p.part_floats; ++s) {
             const double cost = (double)((tiles * s + 255) / 256) / s + 0.02 * s;      // + the partial stores / the reduce pass
             if (cost < best - 1e-9) { best = cost; p.csplit = s; }
         }

@@ -44,8 +44,7 @@ __global__ __launch_bounds__(256) void linear_k1_dgrad_kernel(const float* __res
 
 // a linear layer with one output and a long input: H = W = P = Q = R = S = 1, K = 1, C % 4 == 0
 bool linear_k1_shape(const cslgan_conv_t* c) {
-    static const int env = [] { const char* e = getenv("CSLGAN_LINEAR_K1"); return e ? atoi(e) : 1; }();
-    return env && c->K == 1 && c->H == 1 && c->W == 1 && c->R == 1 && c->S == 1 && c->P == 1 && c->Q == 1 && c->stride == 1 && c->pad == 0 &&
+    return c->K == 1 && c->H == 1 && c->W == 1 && c->R == 1 && c->S == 1 && c->P == 1 && c->Q == 1 && c->stride == 1 && c->pad == 0 &&
            (c->C & 3) == 0 && c->C >= 256 && c->N <= 65535;
 }
 

@@ -514,9 +514,8 @@ static int launch_norm_apply(const TX* x, const float* gamma, const float* beta,
                              int cpg, int n_groups, float eps, int relu, float* stats, TY* y, int d2s_H, int d2s_W,
                              TY* xs, bool vec, hipStream_t st, const float* part = nullptr, int n_part = 0, int chan = 0) {
     const long long total = R * C;
-    static const int rows_env = [] { const char* e = getenv("CSLGAN_NORM_ROWS"); return e ? atoi(e) : 1; }();
     const long long n_rg = R / rows_per_stat;
-    if (vec && rows_env && rows_per_stat * C < (1ll << 32) && n_rg <= 65535) {
+    if (vec && rows_per_stat * C < (1ll << 32) && n_rg <= 65535) {
         long long bx = (rows_per_stat * C / 4 + 255) / 256;
         const long long cap = (4096 + n_rg - 1) / n_rg;                 // about 4096 workgroups in all
         bx = bx > cap ? cap : (bx < 1 ? 1 : bx);
@@ -559,9 +558,7 @@ static int launch_norm(const TX* x, const float* gamma, const float* beta, long 
     // Two-launch form: per-workgroup partial statistics into `scratch` (2 * n_stats * grid.x floats, grid.x <= CSLGAN_NORM_PARTIAL_BLOCKS),
     // summed by the apply kernel's prologue — no zeroed accumulator, no global atomics, no finalize launch (round 3: four launches per
     // normalisation, 36 per D-step; its ticket-fused attempt needed a device-scope fence per workgroup and lost).
-    static const int part_env = [] { const char* e = getenv("CSLGAN_NORM_PARTIALS"); return e ? atoi(e) : 1; }();
-    static const int rows_env2 = [] { const char* e = getenv("CSLGAN_NORM_ROWS"); return e ? atoi(e) : 1; }();
-    if (part_env && scratch && vec && rows_env2 && grid.x <= CSLGAN_NORM_PARTIAL_BLOCKS && rows_per_stat * C < (1ll << 32) && n_row_groups <= 65535 &&
+    if (scratch && vec && grid.x <= CSLGAN_NORM_PARTIAL_BLOCKS && rows_per_stat * C < (1ll << 32) && n_row_groups <= 65535 &&
         2 * (size_t)n_groups * sizeof(float) <= 32768) {
         hipLaunchKernelGGL((norm_stats_kernel<true, true, TX>), grid, block, 2 * lds, st, x, rows_per_stat, C, cpg, n_groups, (int)rpb, stats, scratch, n_stats);
         const int rc1 = check_launch("norm_stats_kernel");
@@ -727,8 +724,7 @@ int cslgan_groupnorm_apply_parts_f32(const float* x, const float* gamma, const f
     int H = 0;
     int rc = check_d2s(HW, C, d2s_W, x_shuffled, &H);
     if (rc) return rc;
-    static const int rows_env = [] { const char* e = getenv("CSLGAN_NORM_ROWS"); return e ? atoi(e) : 1; }();
-    CSLGAN_REQUIRE(norm_vec_ok(x, y, x_shuffled, C, C / groups) && rows_env && (long long)HW * C < (1ll << 32) && 2 * (size_t)groups * sizeof(float) <= 32768,
+    CSLGAN_REQUIRE(norm_vec_ok(x, y, x_shuffled, C, C / groups) && (long long)HW * C < (1ll << 32) && 2 * (size_t)groups * sizeof(float) <= 32768,
                    "groupnorm_apply_parts: shape not taken by the row-walking apply kernel");
     return launch_norm_apply(x, gamma, beta, (long long)N * HW, HW, C, C / groups, groups, eps, relu, stats_ws, y, H, d2s_W, x_shuffled, true,
                              (hipStream_t)stream, part, n_part, 1);

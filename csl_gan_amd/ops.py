@@ -7,7 +7,6 @@ are [K,R,S,C].  Device tensors only — there is no CPU path in this module.
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import List, Optional, Sequence
 
 import torch
@@ -53,14 +52,14 @@ def _kc_compute(rows, n_out, kdim):
     return _compute
 
 
-_F32_HALO = os.environ.get("CSLGAN_F32_HALO", "1") == "1"        # A/B: exact-fp32 launches the round-4 LDS-halo kernel takes run on it (igemm_x3h<., 0, .>)
+_F32_HALO = True        # exact-fp32 launches the round-4 LDS-halo kernel takes run on it (igemm_x3h<., 0, .>); set_f32_halo switches it
 
 
 # Largest channel split of a low-fill halo launch (<= 1: never split).  OFF by default: measured alone the critic's last convs gain
 # (conv4 forward, 384 rows: 167 -> 200 TF; 128 rows: 86 -> 140 TF), but inside the two-stream recorded step the other branch
 # already fills the idle CUs and the step does not move (6.797 ms split, 6.731 ms unsplit, 6.723 ms split + 128-wide tiles: noise)
-# while every split launch adds a reduce launch.  CSLGAN_X3_SPLIT=8 switches it on (single-stream / eager runs).
-_X3_SPLIT = int(os.environ.get("CSLGAN_X3_SPLIT", "0"))
+# while every split launch adds a reduce launch.  8 switches it on (single-stream / eager runs; the kernel side caps the split at 8).
+_X3_SPLIT = 0
 
 
 def _split_scratch(d, rows, cols, red_channels, out):
@@ -75,7 +74,7 @@ def _split_scratch(d, rows, cols, red_channels, out):
     return ws
 
 
-_GN_FUSE = os.environ.get("CSLGAN_GN_FUSE", "1") == "1"            # A/B: GroupNorm statistics from the producing conv's epilogue
+_GN_FUSE = True            # GroupNorm statistics from the producing conv's epilogue (tests switch it off to compare)
 
 
 class gn_partials:
@@ -116,13 +115,11 @@ def set_f32_halo(on):
     return prev
 
 
-_X3_WGRAD = os.environ.get("CSLGAN_X3_WGRAD", "1") == "1"      # A/B: fp32_auto sends eligible weight gradients to the three-piece kernel
-_AUTO_WG_MIN_FLOP = float(os.environ.get("CSLGAN_AUTO_WG_MIN_GFLOP", "0.5")) * 1e9
-_X3_S2 = os.environ.get("CSLGAN_X3_S2", "1") == "1"            # A/B: the LDS-halo form of the bf16 paths for stride-2 forward convs
-_X3_DGRAD = os.environ.get("CSLGAN_X3_DGRAD", "1") == "1"      # ... and for data gradients (0: the gather kernels, as in round 3)
-# fp32_auto thresholds (A/B switches; scripts/compute_modes.py): 128x128 tiles of the launch, reduction length
-_AUTO_MIN_TILES = int(os.environ.get("CSLGAN_AUTO_MIN_TILES", "32"))
-_AUTO_MIN_K = int(os.environ.get("CSLGAN_AUTO_MIN_K", "512"))
+# fp32_auto thresholds (scripts/compute_modes.py): 128x128 tiles of a forward / data-gradient launch, its reduction length, and the
+# FLOP from which an eligible weight gradient goes to the three-piece kernel
+_AUTO_MIN_TILES = 32
+_AUTO_MIN_K = 512
+_AUTO_WG_MIN_FLOP = 0.5e9
 
 
 class compute_dtype:
@@ -426,7 +423,7 @@ def _conv_desc(N, H, W, Cc, K, R, S, stride, pad, kind="wgrad", group=None):
         comp = _kc_compute(N * P * Q, K, R * S * Cc)
     elif kind == "dgrad":
         comp = _kc_compute(N * H * W, Cc, (R * S * K) // (stride * stride))
-    elif (kind == "wgrad" and _auto and _X3_WGRAD and S == 5 and stride in (1, 2) and K % 64 == 0 and Cc % 64 == 0 and 2.0 * N * P * Q * K * R * S * Cc >= _AUTO_WG_MIN_FLOP
+    elif (kind == "wgrad" and _auto and S == 5 and stride in (1, 2) and K % 64 == 0 and Cc % 64 == 0 and 2.0 * N * P * Q * K * R * S * Cc >= _AUTO_WG_MIN_FLOP
           and ((P % 8 == 0 and Q % 8 == 0) or
                ((P, Q, H, W, stride, pad) == (4, 4, 8, 8, 2, 2) and group is not None and group % 2 == 0))):
         comp = COMPUTE_BF16X3          # weight gradient on the LDS-resident three-piece kernel (csrc/igemm_wgh.hip: igemm_x3w_kernel)
@@ -437,29 +434,58 @@ def _conv_desc(N, H, W, Cc, K, R, S, stride, pad, kind="wgrad", group=None):
     return ConvT(N, H, W, Cc, K, R, S, stride, pad, comp, P, Q), P, Q
 
 
-def _conv2d_fwd_stored(x, w, bias, stride, pad, residual, act, out, wkey, alg_scale, wversion, out_dtype):
-    """conv2d_fwd with bf16-stored activations (x and / or y bfloat16): the bf16-stored kernel when x is bf16 with C % 8 == 0,
-    otherwise the fp32 kernels between casts."""
+# Per compute mode of an LDS-halo launch (csrc/igemm_x3.hip): suffix of the stride-2 / data-gradient repack-cache keys and timer tags,
+# cache key of the stride-1 forward filter copy, bfloat16 pieces of that copy (0: a step-major fp32 copy).
+_HALO_KIND = {COMPUTE_BF16X3: ("x3", "x3w", 3), COMPUTE_BF16: ("b16", "bf16w", 1), COMPUTE_F32: ("f32h", "f32w", 0)}
+
+
+def _halo_arith(comp):
+    """Arithmetic the LDS-halo kernel of csrc/igemm_x3.hip runs in: both bf16 forms, and exact fp32 unless set_f32_halo(False)."""
+    return comp in (COMPUTE_BF16X3, COMPUTE_BF16) or (comp == COMPUTE_F32 and _F32_HALO)
+
+
+def _fwd_halo_s1(comp, Cc, K, R, S, stride, P, Q):
+    """This fp32-tensor forward call takes the stride-1 LDS-halo kernel (cslgan_conv2d_fwd_x3_f32): the one rule for conv2d_fwd's
+    route and for in_affine_ok's promise about it."""
+    return _halo_arith(comp) and stride == 1 and R * S > 1 and Cc % 16 == 0 and K >= 64 and K % 4 == 0 and P % 8 == 0 and Q % 8 == 0
+
+
+def _fwd_geometry(x, w, stride, pad):
+    """The checked operands of a forward conv: (N, H, W, C, K, R, S, P, Q)."""
     _chk(x, "x", allow_bf16=True); _chk(w, "w")
     N, H, W, Cc = x.shape
     K, R, S, C2 = w.shape
     if C2 != Cc:
         raise RuntimeError("conv2d_fwd: channel mismatch x C=%d, w C=%d" % (Cc, C2))
-    P, Q = conv_out_size(H, R, stride, pad), conv_out_size(W, S, stride, pad)
+    return N, H, W, Cc, K, R, S, conv_out_size(H, R, stride, pad), conv_out_size(W, S, stride, pad)
+
+
+def _chk_bias_residual(bias, residual, y_shape, allow_bf16=False):
+    if bias is not None:
+        _chk(bias, "bias")
+    if residual is not None:
+        _chk(residual, "residual", allow_bf16=allow_bf16)
+        if tuple(residual.shape) != tuple(y_shape):
+            raise RuntimeError("conv2d_fwd: residual shape %s, expected %s" % (tuple(residual.shape), tuple(y_shape)))
+
+
+def _conv2d_fwd_stored(geom, x, w, bias, stride, pad, residual, act, out, wkey, alg_scale, wversion, out_dtype):
+    """conv2d_fwd with bf16-stored activations (x and / or y bfloat16): the bf16-stored kernel when x is bf16 with C % 8 == 0,
+    otherwise the fp32 kernels between casts."""
+    N, H, W, Cc, K, R, S, P, Q = geom
+
+    def desc(comp):
+        return ConvT(N, H, W, Cc, K, R, S, stride, pad, comp, P, Q)
+
     if out_dtype is None:           # follow the input: conv layers answer bf16 activations in kind; heads and 1..4-channel images stay fp32
         out_dtype = torch.bfloat16 if (x.dtype == torch.bfloat16 and P * Q > 1 and K > 4) else torch.float32
     y_bf16 = out_dtype == torch.bfloat16
     if x.dtype == torch.bfloat16 and Cc % 8 == 0 and (K > 4 or P * Q == 1):      # 1..4 output channels of an image: the fp32 vector-ALU kernel below
-        d = ConvT(N, H, W, Cc, K, R, S, stride, pad, COMPUTE_BF16, P, Q)
+        d = desc(COMPUTE_BF16)
         y = out if out is not None else torch.empty((N, P, Q, K), device=x.device, dtype=out_dtype)
         if y.dtype != out_dtype:
             raise RuntimeError("conv2d_fwd: out has dtype %s, expected %s" % (y.dtype, out_dtype))
-        if bias is not None:
-            _chk(bias, "bias")
-        if residual is not None:
-            _chk(residual, "residual", allow_bf16=True)
-            if tuple(residual.shape) != (N, P, Q, K):
-                raise RuntimeError("conv2d_fwd: residual shape %s, expected %s" % (tuple(residual.shape), (N, P, Q, K)))
+        _chk_bias_residual(bias, residual, (N, P, Q, K), allow_bf16=True)
         ws, repack = repack_cache.get("bf16s_fwd", w, (w.numel() + 1) // 2, wkey, version=wversion)
         flop = 2.0 * N * P * Q * K * R * S * Cc * alg_scale
         nbytes = 2.0 * (N * H * W * Cc + K * R * S * Cc) + y.element_size() * float(N * P * Q * K)
@@ -472,10 +498,9 @@ def _conv2d_fwd_stored(x, w, bias, stride, pad, residual, act, out, wkey, alg_sc
     if (x.dtype == torch.bfloat16 and not y_bf16 and K <= 4 and Cc == 64 and stride == 1 and R * S <= 9 and P % 8 == 0 and Q % 8 == 0
             and residual is None and out is None):
         # the generator's output conv (64 -> 3 channels): the vector-ALU kernel reads the bf16-stored input as it is
-        d = ConvT(N, H, W, Cc, K, R, S, stride, pad, COMPUTE_F32, P, Q)
+        d = desc(COMPUTE_F32)
         y = torch.empty((N, P, Q, K), device=x.device, dtype=torch.float32)
-        if bias is not None:
-            _chk(bias, "bias")
+        _chk_bias_residual(bias, None, y.shape)
         _timed("conv2d_fwd", 2.0 * N * P * Q * K * R * S * Cc, 2.0 * N * H * W * Cc + 4.0 * N * P * Q * K, lambda: check(
             _lib.lib().cslgan_conv2d_fwd_skinny_bf16in(C.byref(d), _p(x), _p(w), _p(bias), act, _p(y), _stream()), "conv2d_fwd_skinny_bf16in"),
             tag=lambda: "N%d %dx%d C%d K%d R%d s%d bf16in" % (N, H, W, Cc, K, R, stride))
@@ -483,10 +508,9 @@ def _conv2d_fwd_stored(x, w, bias, stride, pad, residual, act, out, wkey, alg_sc
     if (x.dtype == torch.float32 and y_bf16 and residual is None and out is None
             and Cc == 3 and _c3_layer(H, W, K, R, S, stride, pad, H % 16 == 0 and W % 32 == 0)):
         # the RGB first layer: fp32 image in, bf16-stored activations out of the same kernel (no cast pass)
-        d = ConvT(N, H, W, Cc, K, R, S, stride, pad, COMPUTE_F32, P, Q)
+        d = desc(COMPUTE_F32)
         y = torch.empty((N, P, Q, K), device=x.device, dtype=torch.bfloat16)
-        if bias is not None:
-            _chk(bias, "bias")
+        _chk_bias_residual(bias, None, y.shape)
         _timed("conv2d_fwd", 2.0 * N * P * Q * K * R * S * Cc, 4.0 * N * H * W * Cc + 2.0 * N * P * Q * K, lambda: check(
             _lib.lib().cslgan_conv2d_c3_fwd_bf16out(C.byref(d), _p(x), _p(w), _p(bias), act, _p(y), _stream()), "conv2d_c3_fwd_bf16out"),
             tag=lambda: "N%d %dx%d C%d K%d R%d s%d bf16out" % (N, H, W, Cc, K, R, stride))
@@ -508,12 +532,10 @@ def in_affine_ok(x, w, stride, pad):
     N, H, W, Cc = x.shape
     K, R, S, _ = w.shape
     P, Q = conv_out_size(H, R, stride, pad), conv_out_size(W, S, stride, pad)
-    if R * S == 1 or P % 8 or Q % 8:
-        return False
     if K <= 4:
-        return Cc == 64 and R * S <= 9
+        return Cc == 64 and 1 < R * S <= 9 and P % 8 == 0 and Q % 8 == 0
     comp = _kc_compute(N * P * Q, K, R * S * Cc)
-    return (comp == COMPUTE_BF16X3 or (comp == COMPUTE_F32 and _F32_HALO)) and Cc % 16 == 0 and K >= 64 and K % 4 == 0
+    return comp != COMPUTE_BF16 and _fwd_halo_s1(comp, Cc, K, R, S, stride, P, Q)
 
 
 def groupnorm_affine(part, gamma, beta, groups, eps, N, HW, Cc):
@@ -537,26 +559,18 @@ def conv2d_fwd(x, w, bias=None, stride=1, pad=0, residual=None, act=ACT_NONE, ou
     alg_scale: FLOP the reference spends on this layer / FLOP of this call (4 for an UpsampleConv's conv, which the
     reference runs over four identical channel groups) — bench accounting only.
     out_dtype: torch.bfloat16 stores the output as bfloat16 (set_storage_dtype); None follows the input's element type."""
+    geom = _fwd_geometry(x, w, stride, pad)
     if x.dtype == torch.bfloat16 or out_dtype == torch.bfloat16 or _is_bf16(residual):
-        return _conv2d_fwd_stored(x, w, bias, stride, pad, residual, act, out, wkey, alg_scale, wversion, out_dtype)
-    _chk(x, "x"); _chk(w, "w")
-    N, H, W, Cc = x.shape
-    K, R, S, C2 = w.shape
-    if C2 != Cc:
-        raise RuntimeError("conv2d_fwd: channel mismatch x C=%d, w C=%d" % (Cc, C2))
+        return _conv2d_fwd_stored(geom, x, w, bias, stride, pad, residual, act, out, wkey, alg_scale, wversion, out_dtype)
+    N, H, W, Cc, K, R, S, P, Q = geom
+    c_alg = Cc                    # channels the reference convolves (FLOP accounting)
     if Cc == 3 and R * S > 1 and not _c3_layer(H, W, K, R, S, stride, pad, residual is None and H % 16 == 0 and W % 32 == 0):
         # RGB input on a shape the first-layer kernel (csrc/conv_c3.hip) does not take: a zero 4th channel makes every tap one
         # aligned 16-byte load (scalar gathers ran at 22-32 TF); the zero channel adds nothing to the sums
         x, w, Cc, wkey = _pad_c4(x), _pad_c4(w), 4, None
-    c_alg = C2                    # channels the reference convolves (FLOP accounting)
-    d, P, Q = _conv_desc(N, H, W, Cc, K, R, S, stride, pad, kind="fwd")
+    d, _, _ = _conv_desc(N, H, W, Cc, K, R, S, stride, pad, kind="fwd")
     y = out if out is not None else torch.empty((N, P, Q, K), device=x.device, dtype=torch.float32)
-    if bias is not None:
-        _chk(bias, "bias")
-    if residual is not None:
-        _chk(residual, "residual")
-        if tuple(residual.shape) != (N, P, Q, K):
-            raise RuntimeError("conv2d_fwd: residual shape %s, expected %s" % (tuple(residual.shape), (N, P, Q, K)))
+    _chk_bias_residual(bias, residual, (N, P, Q, K))
     if in_affine is not None:
         a_sc, a_sh, a_relu = in_affine
         _chk(a_sc, "in_affine scale"); _chk(a_sh, "in_affine shift")
@@ -566,10 +580,9 @@ def conv2d_fwd(x, w, bias=None, stride=1, pad=0, residual=None, act=ACT_NONE, ou
     flop = 2.0 * N * P * Q * K * R * S * c_alg * alg_scale    # the dense conv the reference executes
     nbytes = 4.0 * (N * H * W * c_alg + K * R * S * c_alg + N * P * Q * K)
     xflop = 2.0 * N * P * Q * K * R * S * Cc
-    halo_arith = d.compute in (COMPUTE_BF16X3, COMPUTE_BF16) or (d.compute == COMPUTE_F32 and _F32_HALO)
-    kind_sfx = {COMPUTE_BF16X3: "x3", COMPUTE_BF16: "b16", COMPUTE_F32: "f32h"}[d.compute]
-    if (halo_arith and stride == 2 and R == S and R % 2 == 1 and R > 1 and Cc % 16 == 0 and K >= 64
-            and residual is None and w.numel() % 8 == 0 and _X3_S2):
+    kind_sfx, s1_key, s1_pieces = _HALO_KIND[d.compute]
+    if (_halo_arith(d.compute) and stride == 2 and R == S and R % 2 == 1 and R > 1 and Cc % 16 == 0 and K >= 64
+            and residual is None and w.numel() % 8 == 0):
         # parity sub-images through the LDS-halo kernel of the bf16 matrix cores (csrc/igemm_x3.hip): one workspace holds the fp32
         # class matrices and, behind them, their bfloat16 pieces in step-major order
         nw = w.numel()
@@ -590,10 +603,10 @@ def conv2d_fwd(x, w, bias=None, stride=1, pad=0, residual=None, act=ACT_NONE, ou
             "conv2d_s2_fwd"), exec_flop=xflop, tag=lambda: "N%d %dx%d C%d K%d R%d s2 halo" % (N, H, W, Cc, K, R))
         repack_cache.packed()
         return y
-    if halo_arith and stride == 1 and R * S > 1 and Cc % 16 == 0 and K >= 64 and P % 8 == 0 and Q % 8 == 0 and K % 4 == 0:
+    if _fwd_halo_s1(d.compute, Cc, K, R, S, stride, P, Q):
         # the round-4 LDS-halo kernel reads the filter in step-major order: pre-split into bfloat16 pieces / pre-rounded / as an fp32 copy
         # (cached per parameter version)
-        ws, repack = repack_cache.get({COMPUTE_BF16X3: "x3w", COMPUTE_BF16: "bf16w", COMPUTE_F32: "f32w"}[d.compute], w, (3 * w.numel() + 1) // 2, wkey, version=wversion)
+        ws, repack = repack_cache.get(s1_key, w, (3 * w.numel() + 1) // 2, wkey, version=wversion)
         req, gpart = gn_partials._req, None
         if req is not None:
             gn_partials._req = None         # one conv per request
@@ -606,8 +619,7 @@ def conv2d_fwd(x, w, bias=None, stride=1, pad=0, residual=None, act=ACT_NONE, ou
             _lib.lib().cslgan_conv2d_fwd_x3_f32(C.byref(d), _p(x), _p(w), _p(ws), repack, _p(bias), _p(residual), act, _p(y), _stream()),
             "conv2d_fwd_x3"), exec_flop=xflop, tag=lambda: "N%d %dx%d C%d K%d R%d s%d" % (N, H, W, Cc, K, R, stride))
         if repack:
-            pieces = {COMPUTE_BF16X3: 3, COMPUTE_BF16: 1, COMPUTE_F32: 0}[d.compute]
-            repack_cache.set_rebuild(lambda: check(_lib.lib().cslgan_split_filter_x3_f32(_p(w), K, R * S, Cc, _p(ws), pieces, _stream()), "split_filter_x3"))
+            repack_cache.set_rebuild(lambda: check(_lib.lib().cslgan_split_filter_x3_f32(_p(w), K, R * S, Cc, _p(ws), s1_pieces, _stream()), "split_filter_x3"))
         repack_cache.packed()
         return y
     _timed("conv2d_fwd", flop, nbytes, lambda: check(
@@ -674,13 +686,28 @@ def _pad_c4(t):
     return out
 
 
-def _conv2d_dgrad_stored(gy, w, in_hw, stride, pad, mask, wkey, out_dtype):
-    """conv2d_dgrad with bf16-stored activation gradients: the bf16-stored kernel when gy is bf16 with K % 8 == 0, otherwise the
-    fp32 kernels between casts."""
+def _dgrad_geometry(gy, w, in_hw, stride, pad):
+    """The checked operands of a data gradient: (N, H, W, C, K, R, S, P, Q)."""
     _chk(gy, "gy", allow_bf16=True); _chk(w, "w")
     N, P, Q, K = gy.shape
     K2, R, S, Cc = w.shape
     H, W = in_hw
+    if K2 != K or (conv_out_size(H, R, stride, pad), conv_out_size(W, S, stride, pad)) != (P, Q):
+        raise RuntimeError("conv2d_dgrad: gy shape %s inconsistent with input %dx%d" % (tuple(gy.shape), H, W))
+    return N, H, W, Cc, K, R, S, P, Q
+
+
+def _chk_mask(mask, gx, allow_bf16=False):
+    if mask is not None:
+        _chk(mask, "mask", allow_bf16=allow_bf16)
+        if tuple(mask.shape) != tuple(gx.shape):
+            raise RuntimeError("conv2d_dgrad: mask shape mismatch")
+
+
+def _conv2d_dgrad_stored(geom, gy, w, in_hw, stride, pad, mask, wkey, out_dtype):
+    """conv2d_dgrad with bf16-stored activation gradients: the bf16-stored kernel when gy is bf16 with K % 8 == 0, otherwise the
+    fp32 kernels between casts."""
+    N, H, W, Cc, K, R, S, P, Q = geom
     if out_dtype is None:
         out_dtype = torch.bfloat16 if (gy.dtype == torch.bfloat16 and Cc > 4) else torch.float32
     if mask is not None and mask.dtype != out_dtype:
@@ -689,22 +716,15 @@ def _conv2d_dgrad_stored(gy, w, in_hw, stride, pad, mask, wkey, out_dtype):
             and N <= 65535 and stride == 1 and pad == 0):
         # the critic's head: fp32 loss cotangent, bf16 features
         gx = torch.empty((N, 1, 1, Cc), device=gy.device, dtype=torch.bfloat16)
-        if mask is not None:
-            _chk(mask, "mask", allow_bf16=True)
+        _chk_mask(mask, gx, allow_bf16=True)
         _timed("conv2d_dgrad", 2.0 * N * Cc, 2.0 * N * Cc * (2 if mask is not None else 1) + 4.0 * Cc, lambda: check(
             _lib.lib().cslgan_linear_k1_dgrad_bf16s(_p(gy), _p(w), _p(mask), N, Cc, _p(gx), _stream()), "linear_k1_dgrad_bf16s"),
             tag=lambda: "N%d 1x1 C%d K1 R1 s1 bf16s" % (N, Cc))
         return gx
     if gy.dtype == torch.bfloat16 and K % 8 == 0 and stride in (1, 2) and Cc > 4:
-        P2, Q2 = conv_out_size(H, R, stride, pad), conv_out_size(W, S, stride, pad)
-        if K2 != K or (P2, Q2) != (P, Q):
-            raise RuntimeError("conv2d_dgrad: gy shape %s inconsistent with input %dx%d" % (tuple(gy.shape), H, W))
         d = ConvT(N, H, W, Cc, K, R, S, stride, pad, COMPUTE_BF16, P, Q)
         gx = torch.empty((N, H, W, Cc), device=gy.device, dtype=out_dtype)
-        if mask is not None:
-            _chk(mask, "mask", allow_bf16=True)
-            if tuple(mask.shape) != tuple(gx.shape):
-                raise RuntimeError("conv2d_dgrad: mask shape mismatch")
+        _chk_mask(mask, gx, allow_bf16=True)
         ws, repack = repack_cache.get("bf16s_dgrad%d" % stride, w, (w.numel() + 1) // 2, wkey)
         flop = 2.0 * N * P * Q * K * R * S * Cc
         nbytes = 2.0 * (K * R * S * Cc + N * P * Q * K) + gx.element_size() * float(N * H * W * Cc)
@@ -731,29 +751,21 @@ def _conv2d_dgrad_stored(gy, w, in_hw, stride, pad, mask, wkey, out_dtype):
 
 def conv2d_dgrad(gy, w, in_hw, stride=1, pad=0, mask=None, wkey=None, out_dtype=None):
     """gx[N,H,W,C] = conv_transpose(gy[N,P,Q,K], w[K,R,S,C]) (* lrelu'(mask)).  out_dtype as for conv2d_fwd."""
+    geom = _dgrad_geometry(gy, w, in_hw, stride, pad)
     if gy.dtype == torch.bfloat16 or out_dtype == torch.bfloat16 or _is_bf16(mask):
-        return _conv2d_dgrad_stored(gy, w, in_hw, stride, pad, mask, wkey, out_dtype)
-    _chk(gy, "gy"); _chk(w, "w")
-    N, P, Q, K = gy.shape
-    K2, R, S, Cc = w.shape
-    H, W = in_hw
-    d, P2, Q2 = _conv_desc(N, H, W, Cc, K, R, S, stride, pad, kind="dgrad")
-    if K2 != K or (P2, Q2) != (P, Q):
-        raise RuntimeError("conv2d_dgrad: gy shape %s inconsistent with input %dx%d" % (tuple(gy.shape), H, W))
+        return _conv2d_dgrad_stored(geom, gy, w, in_hw, stride, pad, mask, wkey, out_dtype)
+    N, H, W, Cc, K, R, S, P, Q = geom
+    d, _, _ = _conv_desc(N, H, W, Cc, K, R, S, stride, pad, kind="dgrad")
     gx = torch.empty((N, H, W, Cc), device=gy.device, dtype=torch.float32)
-    if mask is not None:
-        _chk(mask, "mask")
-        if tuple(mask.shape) != tuple(gx.shape):
-            raise RuntimeError("conv2d_dgrad: mask shape mismatch")
+    _chk_mask(mask, gx)
     flop = 2.0 * N * P * Q * K * R * S * Cc
     nbytes = 4.0 * (N * H * W * Cc + K * R * S * Cc + N * P * Q * K)
-    if ((d.compute in (COMPUTE_BF16X3, COMPUTE_BF16) or (d.compute == COMPUTE_F32 and _F32_HALO)) and K % 16 == 0 and Cc >= 64 and Cc % 4 == 0
-            and R * S > 1 and w.numel() % 8 == 0
-            and (H // stride) % 4 == 0 and (W // stride) % 4 == 0 and H % stride == 0 and W % stride == 0 and _X3_DGRAD):
+    if (_halo_arith(d.compute) and K % 16 == 0 and Cc >= 64 and Cc % 4 == 0 and R * S > 1 and w.numel() % 8 == 0
+            and (H // stride) % 4 == 0 and (W // stride) % 4 == 0 and H % stride == 0 and W % stride == 0):
         # LDS-halo kernel of the bf16 matrix cores (csrc/igemm_x3.hip): the repacked class matrices and, behind them, their bfloat16
         # pieces in step-major order share one cached workspace
         nw = w.numel()
-        sfx = {COMPUTE_BF16X3: "x3", COMPUTE_BF16: "b16", COMPUTE_F32: "f32h"}[d.compute]
+        sfx = _HALO_KIND[d.compute][0]
         ws, repack = repack_cache.get("dgrad%d_%s" % (stride, sfx), w, nw + (3 * nw + 1) // 2, wkey)
         part = _split_scratch(d, N * H * W, Cc, K, gx)
         _timed("conv2d_dgrad", flop, nbytes, lambda: check(
@@ -834,7 +846,7 @@ def gram_norms_preferred(gy_shape, x_shape, stride):
     return ((H + stride - 1) // stride) * ((W + stride - 1) // stride) <= _GRAM_MAX_PIX
 
 
-_GRAM_MAX_PIX = int(os.environ.get("CSLGAN_GHOST_MAX_PIX", "64"))     # 16 restores the round-1 rule (ghost clipping for conv4 + linear only)
+_GRAM_MAX_PIX = 64     # (16 was the round-1 rule: ghost clipping for conv4 + linear only)
 
 
 def conv2d_wgrad_sqnorm_gram(gy, x, R, S, stride=1, pad=0, alpha=1.0, sq=None):
@@ -1428,16 +1440,13 @@ def _d2s_out(x, d2s, want_raw, dtype=torch.float32):
 _norm_scratch = {}
 
 
-_NORM_PARTIALS = os.environ.get("CSLGAN_NORM_PARTIALS", "1") == "1"
 NORM_PARTIAL_BLOCKS = 64            # include/cslgan.h CSLGAN_NORM_PARTIAL_BLOCKS
 
 
 def _scratch(dev, n_stats_floats):
     """Workspace for the per-workgroup partial statistics of the two-launch normalisation (cslgan_groupnorm_act_f32's `scratch`):
     n_stats_floats (= 2 * statistics) x NORM_PARTIAL_BLOCKS floats, persistent per (device, stream) — launches on one stream are
-    ordered, and nothing in it outlives the apply launch that follows.  None with CSLGAN_NORM_PARTIALS=0 (A/B: the four-launch form)."""
-    if not _NORM_PARTIALS:
-        return None
+    ordered, and nothing in it outlives the apply launch that follows."""
     need = int(n_stats_floats) * NORM_PARTIAL_BLOCKS
     key = (dev, torch.cuda.current_stream().cuda_stream)
     t = _norm_scratch.get(key)

@@ -458,7 +458,7 @@ class Trainer:
         if adaptive:
             with torch.no_grad():
                 r = None
-                if self.world_size == 1 and os.environ.get("CSLGAN_FUSED_ADAPTIVE_CLIP", "1") == "1":
+                if self.world_size == 1:
                     # one launch: the statistic, the clip norms, and the clip factors clip() is about to ask for
                     r = pe.adaptive_clip_fused(o.adaptive_stat, o.adaptive_scalar, bool(o.use_grad_clip_per_layer))
                 if r is None:
@@ -1047,8 +1047,7 @@ class GraphedDStep:
             # warm-up steps) are PINNED instead — the recording hits them, no replay re-makes them, and refresh_pinned() rebuilds
             # them in place before a replay when a train_G step has changed the weights (round 4; 8 launches per step gone).
             torch.cuda.synchronize()
-            if os.environ.get("CSLGAN_PIN_G_FILTERS", "1") == "1":
-                self._pinned = ops.repack_cache.pin({m._wtoken for m in tr.G.modules() if hasattr(m, "_wtoken")})
+            self._pinned = ops.repack_cache.pin({m._wtoken for m in tr.G.modules() if hasattr(m, "_wtoken")})
             ops.repack_cache.clear()
             torch.cuda.synchronize()
             steps0, calls0 = pe.steps, pe._noise_calls

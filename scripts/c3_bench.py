@@ -1,6 +1,5 @@
 #!/usr/bin/env python3
-"""First-layer (3 -> 64, 5x5, stride 2) forward and per-sample weight gradient: time per launch at the step's shapes.
-CSLGAN_C3=0 in the environment selects the previous path (zero-padded 4th channel on the generic kernels)."""
+"""First-layer (3 -> 64, 5x5, stride 2) forward and per-sample weight gradient: time per launch at the step's shapes."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -30,5 +29,5 @@ for N, HW in ((128, 64), (384, 64), (128, 128)):
     t_w = run(lambda: ops.conv2d_wgrad_grouped(gy, x, 5, 5, stride=2, pad=2, group=1, alpha=float(N), sq=sq))
     t_n = run(lambda: ops.conv2d_wgrad_grouped(gy, x, 5, 5, stride=2, pad=2, group=1, alpha=float(N), want_gw=False, sq=sq))
     t_d = run(lambda: ops.conv2d_wgrad_dense(gy, x, 5, 5, stride=2, pad=2, alpha=1.0))
-    print("C3=%s N%d %dx%d: fwd %.1f us (%.0f GB/s out)  wgrad per-sample %.1f us  norms-only %.1f us  dense %.1f us" % (
-        os.environ.get("CSLGAN_C3", "1"), N, HW, HW, t_f, gy.numel() * 4 / t_f / 1e3, t_w, t_n, t_d))
+    print("N%d %dx%d: fwd %.1f us (%.0f GB/s out)  wgrad per-sample %.1f us  norms-only %.1f us  dense %.1f us" % (
+        N, HW, HW, t_f, gy.numel() * 4 / t_f / 1e3, t_w, t_n, t_d))

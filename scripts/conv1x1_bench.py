@@ -19,4 +19,4 @@ for (HW, C, K) in ((64, 32, 64), (32, 64, 128), (16, 128, 256), (8, 128, 512)):
     torch.cuda.synchronize(); ops.set_launch_timer(None)
     for k, v in t.summary(by_kernel=True).items():
         us = v["ms"] / v["n"] * 1e3
-        print("CONV1X1=%s %dx%d C%d K%d %s: %.1f us  %.0f GB/s" % (os.environ.get("CSLGAN_CONV1X1", "1"), HW, HW, C, K, k, us, 4e-3 * (x.numel() + 128 * HW * HW * K) / us))
+        print("%dx%d C%d K%d %s: %.1f us  %.0f GB/s" % (HW, HW, C, K, k, us, 4e-3 * (x.numel() + 128 * HW * HW * K) / us))

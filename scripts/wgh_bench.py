@@ -19,4 +19,4 @@ for (N, HW, C, K) in ((128, 32, 64, 128), (128, 16, 128, 256)):
         f()
     torch.cuda.synchronize(); ops.set_launch_timer(None)
     for k, v in t.summary(by_kernel=True).items():
-        print("HALF=%s N%d %dx%d C%d K%d %s: %.1f us  %.1f TF" % (os.environ.get("CSLGAN_WGH_HALF", "0"), N, HW, HW, C, K, k, v["ms"] / v["n"] * 1e3, v["flop"] / v["ms"] / 1e9))
+        print("N%d %dx%d C%d K%d %s: %.1f us  %.1f TF" % (N, HW, HW, C, K, k, v["ms"] / v["n"] * 1e3, v["flop"] / v["ms"] / 1e9))
