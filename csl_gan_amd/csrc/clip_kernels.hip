@@ -12,6 +12,7 @@
 //   backprop_clip.py:18-22 l2_clip                -> l2_clip_rows
 //   gradient_penalty.py:52-53 gradients.norm(2, dim=1) -> row_l2norm (+ backward)
 #include "common.h"
+#include "device_prims.h"
 
 namespace cslgan {
 
@@ -42,10 +43,9 @@ template <> struct Elem<float> {
 template <> struct Elem<unsigned short> {
     static __device__ __forceinline__ float4 load4(const unsigned short* p) {
         const uint2 r = *reinterpret_cast<const uint2*>(p);
-        return make_float4(__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u), __uint_as_float(r.y << 16),
-                           __uint_as_float(r.y & 0xffff0000u));
+        return make_float4(bf_lo(r.x), bf_hi(r.x), bf_lo(r.y), bf_hi(r.y));
     }
-    static __device__ __forceinline__ float load1(const unsigned short* p) { return __uint_as_float((unsigned)(*p) << 16); }
+    static __device__ __forceinline__ float load1(const unsigned short* p) { return bf2f(*p); }
     static constexpr int align = 8;
 };
 

@@ -5,11 +5,11 @@
 // channels at a time, each wavefront owns 32 rows x 64 outputs (two 32x32 fp32 MFMA tiles, k = 8g + 4h + e on both operands so a
 // fragment is one ds_read_b128), bias / activation in the epilogue, 128-byte contiguous stores.  gfx950 only.
 #include "common.h"
+#include "device_prims.h"
 #include "igemm.h"
 
 namespace cslgan {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct C1Params {
     const float* x;      // [M][C]
@@ -89,9 +89,7 @@ __global__ __launch_bounds__(256, C == 32 ? 3 : (C == 64 ? 2 : 1)) void conv1x1_
                     const int ro = (v & 3) + 8 * (v >> 2);
                     if (ro >= rows_left) continue;
                     float val = acc[j][v] + bv;
-                    if (p.act == CSLGAN_ACT_LRELU02) val = val > 0.f ? val : 0.2f * val;
-                    else if (p.act == CSLGAN_ACT_RELU) val = val > 0.f ? val : 0.f;
-                    else if (p.act == CSLGAN_ACT_TANH) val = tanhf(val);
+                    val = apply_act(val, p.act);
                     yj[ro * p.K] = val;
                 }
             }

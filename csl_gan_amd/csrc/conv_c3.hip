@@ -16,11 +16,11 @@
 //                     the MFMAs), eight wavefronts split the strip's 64 k steps, partial sums meet in LDS; the epilogue scales,
 //                     stores gw[img][k][5][5][3] and adds the squared norm into sq[img].
 #include "common.h"
+#include "device_prims.h"
 #include "igemm.h"
 
 namespace cslgan {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int C3_K = 64, C3_R = 5, C3_KD = 75, C3_KSTEPS = 38;
 constexpr int C3F_PH = 19, C3F_ROW = 35 * 3, C3F_PITCH = C3F_ROW + 1;       // forward window: 19 rows x 35 pixels
@@ -119,14 +119,10 @@ __global__ __launch_bounds__(256) void c3_fwd_kernel(const C3Params p) {
                 const int m = (v & 3) + 8 * (v >> 2) + 4 * h;
                 const int oy = oy0 + 2 * wid + (m >> 4), ox = ox0 + (m & 15);
                 float val = acc[j][v] + bv;
-                if (p.act == CSLGAN_ACT_LRELU02) val = val > 0.f ? val : 0.2f * val;
-                else if (p.act == CSLGAN_ACT_RELU) val = val > 0.f ? val : 0.f;
-                else if (p.act == CSLGAN_ACT_TANH) val = tanhf(val);
+                val = apply_act(val, p.act);
                 const long long o = (((long long)img * p.P + oy) * p.Q + ox) * C3_K + n;
                 if (p.y_bf16) {
-                    unsigned u = __float_as_uint(val);
-                    u += 0x7FFFu + ((u >> 16) & 1u);
-                    reinterpret_cast<unsigned short*>(p.y)[o] = (unsigned short)(u >> 16);
+                    reinterpret_cast<unsigned short*>(p.y)[o] = (unsigned short)rne_bf16(val);
                 } else {
                     p.y[o] = val;
                 }
@@ -148,8 +144,8 @@ __device__ __forceinline__ void c3w_fetch(const C3Params& p, C3wStage& st, int s
         const unsigned short* gh = reinterpret_cast<const unsigned short*>(p.gy);
         const uint2 a = *reinterpret_cast<const uint2*>(gh + g0 + (long long)(tid >> 3) * C3_K + (tid & 7) * 4);
         const uint2 b = *reinterpret_cast<const uint2*>(gh + g0 + (long long)((tid + 512) >> 3) * C3_K + (tid & 7) * 4);
-        st.g0 = make_float4(__uint_as_float(a.x << 16), __uint_as_float(a.x & 0xffff0000u), __uint_as_float(a.y << 16), __uint_as_float(a.y & 0xffff0000u));
-        st.g1 = make_float4(__uint_as_float(b.x << 16), __uint_as_float(b.x & 0xffff0000u), __uint_as_float(b.y << 16), __uint_as_float(b.y & 0xffff0000u));
+        st.g0 = make_float4(bf_lo(a.x), bf_hi(a.x), bf_lo(a.y), bf_hi(a.y));
+        st.g1 = make_float4(bf_lo(b.x), bf_hi(b.x), bf_lo(b.y), bf_hi(b.y));
     } else {
         st.g0 = *reinterpret_cast<const float4*>(p.gy + g0 + (long long)(tid >> 3) * C3_K + (tid & 7) * 4);
         st.g1 = *reinterpret_cast<const float4*>(p.gy + g0 + (long long)((tid + 512) >> 3) * C3_K + (tid & 7) * 4);

@@ -13,12 +13,12 @@
 // One workgroup per sample.  PQ <= 32: one 32x32 tile, the four wavefronts take every fourth 32-deep K chunk and
 // their partial Gram matrices are added in LDS.  32 < PQ <= 64: four 32x32 tiles, one per wavefront.
 #include "common.h"
+#include "device_prims.h"
 #include "igemm.h"
 #include "conv_classes.h"
 
 namespace cslgan {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct GramParams {
     const float* gy;     // [N][P][Q][K]
@@ -173,7 +173,6 @@ __global__ __launch_bounds__(256) void gram_sqnorm_kernel(const GramParams p) {
 // needs 3.5, the product 105).  One wavefront per parity class on v_mfma_f32_16x16x4_f32 with the operands loaded
 // straight into fragment registers (A and B of X X^T are the same registers); K of GY GY^T is split over the four
 // wavefronts.  ~100 KB read per sample: the kernel is a stream over gy and x.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct GramSmallParams {
     const float* gy;     // [N][PQ][K]

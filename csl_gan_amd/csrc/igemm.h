@@ -160,4 +160,26 @@ int launch_linear_k1_dgrad(const cslgan_conv_t* c, const float* gy, const float*
 bool conv1x1_eligible(const cslgan_conv_t* c, const float* x, const float* w, const float* residual);
 int launch_conv1x1(const cslgan_conv_t* c, const float* x, const float* w, const float* bias, int act, float* y, hipStream_t st);
 
+// igemm_kc.hip routes a K-contiguous launch to one of these (each: eligibility test, then the launch)
+bool skinny_eligible(const KcParams& p);        // igemm_skinny.hip: 1..4 output channels on the vector ALU
+int launch_skinny(KcParams& p, hipStream_t st);
+bool halo_eligible(const KcParams& p);          // igemm_halo.hip: fp32 MFMA over an LDS-resident halo
+int launch_halo(KcParams& p, hipStream_t st);
+bool x3h_eligible(const KcParams& p);           // igemm_x3.hip: the LDS-halo form (stride-1 tap classes, pre-split filter in p.w3)
+int launch_x3h(KcParams& p, hipStream_t st);
+int launch_kc_bf16(KcParams& p, hipStream_t st, long long out_elems);     // igemm_bf16.hip: called by launch_kc when KcParams::bf16 is set
+int split_filter_x3(const float* w, int Nn, int T, int C, void* w3, hipStream_t st, int pieces);      // igemm_x3.hip
+
+// igemm_mc.hip routes a weight gradient to one of these
+bool wgh_eligible(const cslgan_conv_t* c, int out_bf16, const void* gy, const void* x);      // igemm_wgh.hip
+bool x3w_eligible(const cslgan_conv_t* c, int out_bf16, const void* gy, const void* x);      // ... the three-piece (bf16x3) form
+bool x3w_quad_eligible(const cslgan_conv_t* c, int group, int out_bf16, const void* gy, const void* x);     // ... on 4x4 output grids
+int launch_wgh(const cslgan_conv_t* c, const float* gy, const float* x, int group, float alpha, float* gw, float* sq, hipStream_t st,
+               const float* row_scale, int n_seg = 0, const int* seg_first = nullptr, float* const* seg_gw = nullptr,
+               float* const* seg_sq = nullptr);
+int launch_mc_bf16(McParams& p, bool vecA, bool vecB, hipStream_t st, int nsplit);        // igemm_bf16.hip
+
+// clip_kernels.hip: sq_accum[row] += sum of squares of the row (the norms of split-K weight gradients)
+int sqnorm_rows_accumulate(const float* in, long long n_rows, long long len, float* sq_accum, hipStream_t st);
+
 }  // namespace cslgan

@@ -25,48 +25,9 @@
 #include <stdlib.h>
 #include "common.h"
 #include "igemm.h"
+#include "kc_frame.h"
 
 namespace cslgan {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {      // v_cvt_pk_bf16_f32: RNE, lo in bits 0..15
-    const f32x2 v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ uint2 pack4_bf16(const float4& v) { return make_uint2(pack_bf16(v.x, v.y), pack_bf16(v.z, v.w)); }
-
-constexpr unsigned OOB16 = 0xFFFFFFF0u;
-__device__ __forceinline__ float4 bload4(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, 0, 0);
-    return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-}
-__device__ __forceinline__ float bload1(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
-    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, (int)byte_off, 0, 0));
-}
-
-// ---- fp32 from three bfloat16 pieces ---------------------------------------------------------------------------------------
-// x = hi + mid + lo with hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid): three 8-bit mantissas cover fp32's 24 bits
-// (|x - hi - mid - lo| <= 2^-24 |x|).  A product a*b is then the sum of 9 piece products, each EXACT in fp32 (8 x 8 bits);
-// dropping the three smallest (mid*lo, lo*mid, lo*lo: <= 2^-23 |a||b| together) leaves SIX bf16 MFMAs per fp32 MFMA step:
-//     a*b ~= hi*hi + (hi*mid + mid*hi) + (hi*lo + lo*hi + mid*mid)
-// at 16x the fp32 MFMA rate each — 2.67x the fp32 matrix rate for a per-product error of about one fp32 ulp
-// (CSLGAN_COMPUTE_BF16X3; the same construction vendor BLAS libraries ship as "fp32 emulation").  Small terms are added first.
-struct bf16x3_t { uint2 hi, mid, lo; };
-__device__ __forceinline__ float bf_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bf_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
-__device__ __forceinline__ bf16x3_t split4_bf16(const float4& v) {
-    bf16x3_t r;
-    r.hi = make_uint2(pack_bf16(v.x, v.y), pack_bf16(v.z, v.w));
-    const float r0 = v.x - bf_lo(r.hi.x), r1 = v.y - bf_hi(r.hi.x), r2 = v.z - bf_lo(r.hi.y), r3 = v.w - bf_hi(r.hi.y);   // exact
-    r.mid = make_uint2(pack_bf16(r0, r1), pack_bf16(r2, r3));
-    r.lo = make_uint2(pack_bf16(r0 - bf_lo(r.mid.x), r1 - bf_hi(r.mid.x)), pack_bf16(r2 - bf_lo(r.mid.y), r3 - bf_hi(r.mid.y)));
-    return r;
-}
 
 // ---- K-contiguous: Out[m][n] = epilogue( sum_k A(m,k) * Wm[n][k] ) ------------------------------------------------------
 // K tile = 32 (two 16-k MFMA steps); LDS entry e = k/8 in the tile (4 entries), each [rows][8 bf16] + 16 B pad.
@@ -86,50 +47,25 @@ __global__ __launch_bounds__(256, 2) void igemm_kc_bf16_kernel(const KcParams p)
     __shared__ int s_roff[BM];
 
     const int tid = threadIdx.x;
-    const int nwg = p.tiles_m * p.tiles_n;
-    const int split = blockIdx.x / nwg;
-    const int wg = xcd_remap(blockIdx.x - split * nwg, nwg);
-    const int tile_mg = wg / p.tiles_n, tile_n = wg - tile_mg * p.tiles_n;
-    int ci = 0;
-#pragma unroll 1
-    while (ci + 1 < p.n_cls && tile_mg >= p.cls[ci + 1].tile0) ++ci;
-    const KcClass& kc = p.cls[ci];
+    int split, m0, n0;
+    int a_img[A_PASS], a_iy[A_PASS], a_ix[A_PASS];
+    unsigned b_off[B_PASS];
+    const KcClass& kc = kc_locate<BM, BN>(p, s_tap, split, m0, n0, a_img, a_iy, a_ix, b_off);
     const int M = kc.M, OHc = kc.OHc, OWc = kc.OWc, Kdim = kc.Kdim;
-    const int m0 = (tile_mg - kc.tile0) * BM, n0 = tile_n * BN;
-    const float* __restrict__ wbase = p.w + kc.w_off;
-
-    if (tid < IG_MAX_TAPS) s_tap[tid] = ((int)kc.ty[tid] << 16) | ((int)kc.tx[tid] & 0xffff);
-
     const int lrow = tid >> 3;   // 0..31
     const int q = tid & 7;       // 4-k chunk within the 32-k tile; chunks 2e, 2e+1 form LDS entry e
-    const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.a), 0, p.a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wbase), 0, p.w_bytes - 4u * (unsigned)kc.w_off, 0x00020000);
-    int a_img[A_PASS], a_iy[A_PASS], a_ix[A_PASS];
-#pragma unroll
-    for (int i = 0; i < A_PASS; ++i) {
-        const int m = m0 + lrow + 32 * i;
-        const bool ok = m < M;
-        const RowCoord rc = kc_decode_row(ok ? m : 0, OHc, OWc, kc.patch);
-        a_img[i] = rc.img * p.AH * p.AW * p.AC;
-        a_iy[i] = ok ? rc.oy * p.sy : -(1 << 20);
-        a_ix[i] = rc.ox * p.sx;
-    }
-    unsigned b_off[B_PASS];
-#pragma unroll
-    for (int i = 0; i < B_PASS; ++i) {
-        const int n = n0 + lrow + 32 * i;
-        b_off[i] = n < p.Nn ? 4u * (unsigned)n * (unsigned)Kdim : OOB16;
-    }
-    __syncthreads();
+    const __amdgpu_buffer_rsrc_t a_rsrc = make_rsrc(p.a, p.a_bytes);
+    const __amdgpu_buffer_rsrc_t w_rsrc = make_rsrc(p.w + kc.w_off, p.w_bytes - 4u * (unsigned)kc.w_off);
+    __syncthreads();  // s_tap visible
 
     float4 ra[A_PASS], rb[B_PASS];
     int k_end = Kdim;
     auto a_offset = [&](int i, int ty, int tx, int c, bool kin) -> unsigned {
         const int iy = a_iy[i] + ty, ix = a_ix[i] + tx;
         const bool ok = kin && (unsigned)iy < (unsigned)p.VH && (unsigned)ix < (unsigned)p.VW;
-        // branch-free: an invalid element ORs 0xFFFFFFF0 into its (always computed) offset -> the descriptor's range check returns zeros;
-        // as `ok ? offset : OOB16` every load sat in its own exec-masked block (found in csrc/igemm_bf16s.hip: +7-10 % there)
-        return (4u * (unsigned)(a_img[i] + (iy * p.AW + ix) * p.AC + c)) | (ok ? 0u : OOB16);
+        // branch-free: an invalid element ORs BUF_OOB into its (always computed) offset -> the descriptor's range check returns zeros;
+        // as `ok ? offset : BUF_OOB` every load sat in its own exec-masked block (found in csrc/igemm_bf16s.hip: +7-10 % there)
+        return (4u * (unsigned)(a_img[i] + (iy * p.AW + ix) * p.AC + c)) | (ok ? 0u : BUF_OOB);
     };
     auto load_tile = [&](int kt) {
         const int kb = kt * IG_BK + q * 4;
@@ -140,7 +76,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kc_bf16_kernel(const KcParams p)
             const int tap = s_tap[t];
             const int ty = tap >> 16, tx = (int)(short)(tap & 0xffff);
 #pragma unroll
-            for (int i = 0; i < A_PASS; ++i) ra[i] = bload4(a_rsrc, a_offset(i, ty, tx, c, kin));
+            for (int i = 0; i < A_PASS; ++i) ra[i] = buf_load4(a_rsrc, a_offset(i, ty, tx, c, kin));
         } else {
             float t4[A_PASS][4];
 #pragma unroll
@@ -152,21 +88,21 @@ __global__ __launch_bounds__(256, 2) void igemm_kc_bf16_kernel(const KcParams p)
                 const int tap = s_tap[t];
                 const int ty = tap >> 16, tx = (int)(short)(tap & 0xffff);
 #pragma unroll
-                for (int i = 0; i < A_PASS; ++i) t4[i][e] = bload1(a_rsrc, a_offset(i, ty, tx, c, kin));
+                for (int i = 0; i < A_PASS; ++i) t4[i][e] = buf_load1(a_rsrc, a_offset(i, ty, tx, c, kin));
             }
 #pragma unroll
             for (int i = 0; i < A_PASS; ++i) ra[i] = make_float4(t4[i][0], t4[i][1], t4[i][2], t4[i][3]);
         }
         if (VEC_B) {
-            const unsigned kofs = kb < k_end ? 4u * (unsigned)kb : OOB16;
+            const unsigned kofs = kb < k_end ? 4u * (unsigned)kb : BUF_OOB;
 #pragma unroll
-            for (int i = 0; i < B_PASS; ++i) rb[i] = bload4(w_rsrc, (b_off[i] + 4u * (unsigned)kb) | ((b_off[i] == OOB16 || kofs == OOB16) ? OOB16 : 0u));
+            for (int i = 0; i < B_PASS; ++i) rb[i] = buf_load4(w_rsrc, (b_off[i] + 4u * (unsigned)kb) | ((b_off[i] == BUF_OOB || kofs == BUF_OOB) ? BUF_OOB : 0u));
         } else {
 #pragma unroll
             for (int i = 0; i < B_PASS; ++i) {
                 float t4[4];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) t4[e] = bload1(w_rsrc, (b_off[i] != OOB16 && (kb + e) < k_end) ? b_off[i] + 4u * (unsigned)(kb + e) : OOB16);
+                for (int e = 0; e < 4; ++e) t4[e] = buf_load1(w_rsrc, (b_off[i] != BUF_OOB && (kb + e) < k_end) ? b_off[i] + 4u * (unsigned)(kb + e) : BUF_OOB);
                 rb[i] = make_float4(t4[0], t4[1], t4[2], t4[3]);
             }
         }
@@ -270,23 +206,10 @@ __global__ __launch_bounds__(256, 2) void igemm_kc_bf16_kernel(const KcParams p)
         }
     }
 
-    // ---- epilogue (as igemm_kc) ---------------------------------------------------------------
-    if (tid < BM) {
-        const int m = m0 + tid;
-        int off = -1, roff = 0;
-        if (m < M) {
-            if (p.dense_out && !p.res && !kc.patch) {
-                off = m * p.ldo;
-            } else {
-                const RowCoord rc = kc_decode_row(m, OHc, OWc, kc.patch);
-                off = kc_out_offset(p, kc, rc);
-                if (p.res) roff = kc_res_offset(p, kc, rc);
-            }
-        }
-        s_off[tid] = off;
-        s_roff[tid] = roff;
-    }
+    // ---- epilogue --------------------------------------------------------------------------------
+    kc_stage_row_offsets<BM>(p, kc, M, OHc, OWc, m0, kc.patch, p.dense_out && !p.res && !kc.patch, s_off, s_roff);
     __syncthreads();
+    // kc_store_tile<TM, TN, true> in place (kc_frame.h says why this kernel does not call it): keep the two in step
     const bool atomic_out = p.ksplit > 1;
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
@@ -306,10 +229,8 @@ __global__ __launch_bounds__(256, 2) void igemm_kc_bf16_kernel(const KcParams p)
                     continue;
                 }
                 if (p.res) val += p.res[s_roff[row] + n];
-                if (p.act == CSLGAN_ACT_LRELU02) val = val > 0.f ? val : 0.2f * val;
-                else if (p.act == CSLGAN_ACT_RELU) val = val > 0.f ? val : 0.f;
-                else if (p.act == CSLGAN_ACT_TANH) val = tanhf(val);
-                if (p.mask) val *= (p.mask[off + n] > 0.f ? 1.f : 0.2f);
+                val = apply_act(val, p.act);
+                if (p.mask) val = lrelu_mask(val, p.mask[off + n]);
                 p.out[off + n] = val;
             }
         }
@@ -318,29 +239,8 @@ __global__ __launch_bounds__(256, 2) void igemm_kc_bf16_kernel(const KcParams p)
 
 template <int BM, int BN, int WM, int WN, int NSPLIT>
 static int launch_kc_bf16_tile(KcParams& p, bool vecA, bool vecB, hipStream_t st, long long out_elems) {
-    int tm = 0;
-    for (int c = 0; c < p.n_cls; ++c) {
-        p.cls[c].tile0 = tm;
-        tm += (p.cls[c].M + BM - 1) / BM;
-    }
-    p.tiles_m = tm;
-    p.tiles_n = (p.Nn + BN - 1) / BN;
-    const int tiles = p.tiles_m * p.tiles_n;
-    p.ksplit = 1;
-    int nk_max = 0;
-    for (int c = 0; c < p.n_cls; ++c) {
-        const int nk = (p.cls[c].Kdim + IG_BK - 1) / IG_BK;
-        nk_max = nk > nk_max ? nk : nk_max;
-    }
-    if (tiles < 96 && nk_max >= 16 && p.act == CSLGAN_ACT_NONE && !p.res && !p.mask && out_elems > 0) {
-        const int want = (256 + tiles - 1) / tiles, cap = nk_max / 4;
-        p.ksplit = want < cap ? want : cap;
-        if (p.ksplit < 1) p.ksplit = 1;
-    }
-    if (p.ksplit > 1) {
-        if (int rc = zero_floats(p.out, (size_t)out_elems, st)) return rc;
-    }
-    const dim3 grid((unsigned)(tiles * p.ksplit)), block(256);
+    if (int rc = kc_plan_tiles(p, BM, BN, out_elems, st)) return rc;
+    const dim3 grid((unsigned)(p.tiles_m * p.tiles_n * p.ksplit)), block(256);
     note_kernel(NSPLIT == 1 ? "igemm_kc_bf16_kernel<%d,%d>" : "igemm_kc_bf16x3_kernel<%d,%d>", BM, BN);
     if (vecA && vecB) hipLaunchKernelGGL((igemm_kc_bf16_kernel<BM, BN, WM, WN, true, true, NSPLIT>), grid, block, 0, st, p);
     else if (vecA) hipLaunchKernelGGL((igemm_kc_bf16_kernel<BM, BN, WM, WN, true, false, NSPLIT>), grid, block, 0, st, p);
@@ -350,30 +250,20 @@ static int launch_kc_bf16_tile(KcParams& p, bool vecA, bool vecB, hipStream_t st
 }
 
 // Called by launch_kc (igemm_kc.hip) after the operand-size checks, when KcParams::bf16 is set.
-bool x3h_eligible(const KcParams& p);          // igemm_x3.hip: the LDS-halo form (stride-1 tap classes, pre-split filter)
-int launch_x3h(KcParams& p, hipStream_t st);
-
 int launch_kc_bf16(KcParams& p, hipStream_t st, long long out_elems) {
     if (x3h_eligible(p)) return launch_x3h(p, st);      // needs the pre-split / pre-rounded filter (p.w3)
     if (p.gn_part || p.in_scale) { set_error("conv2d_fwd: gn_part / in_scale given but the shape does not run on the LDS-halo kernel"); return CSLGAN_ERR_INVALID_ARG; }
     if (p.acc_classes) { set_error("igemm_kc_bf16: accumulated classes only run on the LDS-halo form"); return CSLGAN_ERR_INVALID_ARG; }
-    for (int c = 0; c < p.n_cls; ++c) {
-        KcClass& k = p.cls[c];
-        k.patch = (k.T > 1 && k.OHc % 8 == 0 && k.OWc % 8 == 0) ? 1 : 0;
-    }
-    bool kd4 = true;
-    for (int c = 0; c < p.n_cls; ++c) kd4 = kd4 && (p.cls[c].Kdim % 4 == 0) && (p.cls[c].w_off % 4 == 0);
-    const bool vecA = (p.AC % 4 == 0) && aligned16(p.a);
-    const bool vecB = kd4 && aligned16(p.w);
-    long long rows = 0;
-    for (int c = 0; c < p.n_cls; ++c) rows += (p.cls[c].M + 127) / 128;
+    bool vecA, vecB;
+    kc_mark_patches_and_vec(p, vecA, vecB);
+    const bool big = kc_tiles_for(p, 128, 128) >= 256;
     if (p.bf16 == 3) {
         if (p.Nn <= 64) return launch_kc_bf16_tile<128, 64, 2, 2, 3>(p, vecA, vecB, st, out_elems);
-        if (rows * ((p.Nn + 127) / 128) >= 256) return launch_kc_bf16_tile<128, 128, 2, 2, 3>(p, vecA, vecB, st, out_elems);
+        if (big) return launch_kc_bf16_tile<128, 128, 2, 2, 3>(p, vecA, vecB, st, out_elems);
         return launch_kc_bf16_tile<64, 128, 1, 4, 3>(p, vecA, vecB, st, out_elems);
     }
     if (p.Nn <= 64) return launch_kc_bf16_tile<128, 64, 2, 2, 1>(p, vecA, vecB, st, out_elems);
-    if (rows * ((p.Nn + 127) / 128) >= 256) return launch_kc_bf16_tile<128, 128, 2, 2, 1>(p, vecA, vecB, st, out_elems);
+    if (big) return launch_kc_bf16_tile<128, 128, 2, 2, 1>(p, vecA, vecB, st, out_elems);
     return launch_kc_bf16_tile<64, 128, 1, 4, 1>(p, vecA, vecB, st, out_elems);
 }
 
@@ -587,10 +477,9 @@ __global__ __launch_bounds__(256, 2) void igemm_mc_bf16_kernel(const McParams p)
                 if (m >= p.Kc) continue;
                 float val = p.alpha * acc[i][j][v];
                 if (p.out_bf16) {      // what is stored is what gets clipped: norm of the rounded value
-                    unsigned u = __float_as_uint(val);
-                    u += 0x7FFFu + ((u >> 16) & 1u);
+                    const unsigned u = rne_bf16_bits(val);
                     if (outh) outh[(long long)m * p.Ndim + n] = (unsigned short)(u >> 16);
-                    val = __uint_as_float(u & 0xffff0000u);
+                    val = bf_hi(u);
                 }
                 ss = fmaf(val, val, ss);
                 if (outg) {
@@ -605,8 +494,6 @@ __global__ __launch_bounds__(256, 2) void igemm_mc_bf16_kernel(const McParams p)
         if (tid == 0) atomicAdd(p.sq + g, tot);
     }
 }
-
-int sqnorm_rows_accumulate(const float* in, long long n_rows, long long len, float* sq_accum, hipStream_t st);   // clip_kernels.hip
 
 // Called by the wgrad entries (igemm_mc.hip) when cslgan_conv_t.compute == CSLGAN_COMPUTE_BF16.
 int launch_mc_bf16(McParams& p, bool vecA, bool vecB, hipStream_t st, int nsplit) {

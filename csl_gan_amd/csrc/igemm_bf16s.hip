@@ -22,28 +22,11 @@
 // Replaces (reference file:line): nn.Conv2d / nn.Linear forward and autograd data gradients (DCResNet_models.py:131-132,145),
 // the Opacus-fork per-sample weight gradients (train.py:373,387), F.leaky_relu's backward, bias gradients.
 #include "common.h"
+#include "device_prims.h"
 #include "igemm.h"
 #include "conv_classes.h"
 
 namespace cslgan {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr unsigned S_OOB16 = 0xFFFFFFF0u;
-
-__device__ __forceinline__ unsigned short f2bf(float v) {      // round to nearest even (v_cvt_pk_bf16_f32 semantics)
-    const f32x2 t = {v, 0.f};
-    return (unsigned short)(__builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2)) & 0xffffu);
-}
-__device__ __forceinline__ unsigned f2bf_pk(float lo, float hi) {
-    const f32x2 t = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));
-}
-__device__ __forceinline__ float bf2f(unsigned short u) { return __uint_as_float((unsigned)u << 16); }
 
 // ---- K-contiguous form on bf16 tensors -------------------------------------------------------------------------------------
 struct KsParams {
@@ -102,33 +85,29 @@ __device__ __forceinline__ void ks_epilogue(const f32x16 (&acc)[TM][TN], const K
                     if (p.res) {
                         if (p.res_bf16) {
                             const uint2 u = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(p.res) + off + n);
-                            val[0] += __uint_as_float(u.x << 16); val[1] += __uint_as_float(u.x & 0xffff0000u);
-                            val[2] += __uint_as_float(u.y << 16); val[3] += __uint_as_float(u.y & 0xffff0000u);
+                            val[0] += bf_lo(u.x); val[1] += bf_hi(u.x);
+                            val[2] += bf_lo(u.y); val[3] += bf_hi(u.y);
                         } else {
                             const float4 u = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p.res) + off + n);
                             val[0] += u.x; val[1] += u.y; val[2] += u.z; val[3] += u.w;
                         }
                     }
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        if (p.act == CSLGAN_ACT_LRELU02) val[e] = val[e] > 0.f ? val[e] : 0.2f * val[e];
-                        else if (p.act == CSLGAN_ACT_RELU) val[e] = val[e] > 0.f ? val[e] : 0.f;
-                        else if (p.act == CSLGAN_ACT_TANH) val[e] = tanhf(val[e]);
-                    }
+                    for (int e = 0; e < 4; ++e) val[e] = apply_act(val[e], p.act);
                     if (p.mask) {
                         float mv[4];
                         if (p.mask_bf16) {
                             const uint2 u = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(p.mask) + off + n);
-                            mv[0] = __uint_as_float(u.x << 16); mv[1] = __uint_as_float(u.x & 0xffff0000u);
-                            mv[2] = __uint_as_float(u.y << 16); mv[3] = __uint_as_float(u.y & 0xffff0000u);
+                            mv[0] = bf_lo(u.x); mv[1] = bf_hi(u.x);
+                            mv[2] = bf_lo(u.y); mv[3] = bf_hi(u.y);
                         } else {
                             const float4 u = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p.mask) + off + n);
                             mv[0] = u.x; mv[1] = u.y; mv[2] = u.z; mv[3] = u.w;
                         }
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) val[e] *= (mv[e] > 0.f ? 1.f : 0.2f);
+                        for (int e = 0; e < 4; ++e) val[e] = lrelu_mask(val[e], mv[e]);
                     }
-                    if (OUT_BF16) *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(p.out) + off + n) = make_uint2(f2bf_pk(val[0], val[1]), f2bf_pk(val[2], val[3]));
+                    if (OUT_BF16) *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(p.out) + off + n) = make_uint2(pack_bf16(val[0], val[1]), pack_bf16(val[2], val[3]));
                     else *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.out) + off + n) = make_float4(val[0], val[1], val[2], val[3]);
                 } else {
 #pragma unroll
@@ -136,14 +115,12 @@ __device__ __forceinline__ void ks_epilogue(const f32x16 (&acc)[TM][TN], const K
                         if (n + e >= p.Nn) continue;
                         float x = val[e] + (p.bias ? p.bias[n + e] : 0.f);
                         if (p.res) x += p.res_bf16 ? bf2f(reinterpret_cast<const unsigned short*>(p.res)[off + n + e]) : reinterpret_cast<const float*>(p.res)[off + n + e];
-                        if (p.act == CSLGAN_ACT_LRELU02) x = x > 0.f ? x : 0.2f * x;
-                        else if (p.act == CSLGAN_ACT_RELU) x = x > 0.f ? x : 0.f;
-                        else if (p.act == CSLGAN_ACT_TANH) x = tanhf(x);
+                        x = apply_act(x, p.act);
                         if (p.mask) {
                             const float mv = p.mask_bf16 ? bf2f(reinterpret_cast<const unsigned short*>(p.mask)[off + n + e]) : reinterpret_cast<const float*>(p.mask)[off + n + e];
-                            x *= (mv > 0.f ? 1.f : 0.2f);
+                            x = lrelu_mask(x, mv);
                         }
-                        if (OUT_BF16) reinterpret_cast<unsigned short*>(p.out)[off + n + e] = f2bf(x);
+                        if (OUT_BF16) reinterpret_cast<unsigned short*>(p.out)[off + n + e] = bf16_rne(x);
                         else reinterpret_cast<float*>(p.out)[off + n + e] = x;
                     }
                 }
@@ -178,9 +155,8 @@ __global__ __launch_bounds__(256, 2) void igemm_kcs_kernel(const KsParams p) {
 
     const int lrow = tid >> 3;   // 0..31
     const int e = tid & 7;       // LDS entry (8 consecutive k) within the 64-k tile: 8 lanes read 128 contiguous bytes of a row
-    const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.a), 0, p.a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<unsigned short*>(reinterpret_cast<const unsigned short*>(p.w) + kc.w_off), 0, p.w_bytes - 2u * (unsigned)kc.w_off, 0x00020000);
+    const __amdgpu_buffer_rsrc_t a_rsrc = make_rsrc(p.a, p.a_bytes);
+    const __amdgpu_buffer_rsrc_t w_rsrc = make_rsrc(reinterpret_cast<const unsigned short*>(p.w) + kc.w_off, p.w_bytes - 2u * (unsigned)kc.w_off);
     int a_img[A_PASS], a_iy[A_PASS], a_ix[A_PASS];
 #pragma unroll
     for (int i = 0; i < A_PASS; ++i) {
@@ -195,7 +171,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kcs_kernel(const KsParams p) {
 #pragma unroll
     for (int i = 0; i < B_PASS; ++i) {
         const int n = n0 + lrow + 32 * i;
-        b_off[i] = n < p.Nn ? 2u * (unsigned)n * (unsigned)Kdim : S_OOB16;
+        b_off[i] = n < p.Nn ? 2u * (unsigned)n * (unsigned)Kdim : BUF_OOB;
     }
     __syncthreads();
 
@@ -204,7 +180,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kcs_kernel(const KsParams p) {
     // set (loads one tile ahead) the kernel waited on its loads every iteration: 390-500 TF.
     u32x4 ra0[A_PASS], rb0[B_PASS], ra1[A_PASS], rb1[B_PASS];
     auto load_tile = [&](int kt, u32x4 (&ra)[A_PASS], u32x4 (&rb)[B_PASS]) {
-        // Branch-free offsets: an invalid element ORs 0xFFFFFFF0 into its (always computed) offset, which the buffer descriptor's range
+        // Branch-free offsets: an invalid element ORs BUF_OOB into its (always computed) offset, which the buffer descriptor's range
         // check turns into a zero load.  Written as `ok ? offset : OOB` the compiler put every load into its own exec-masked block
         // (nine s_and_saveexec per half iteration), which also kept it from issuing the eight loads back to back.
         const int kb = kt * KS_BK + e * 8;
@@ -213,16 +189,16 @@ __global__ __launch_bounds__(256, 2) void igemm_kcs_kernel(const KsParams p) {
         const int c = (kin ? kb : 0) - t * p.AC;
         const int tap = s_tap[t];
         const int ty = tap >> 16, tx = (int)(short)(tap & 0xffff);
-        const unsigned kbad = kin ? 0u : S_OOB16;
+        const unsigned kbad = kin ? 0u : BUF_OOB;
 #pragma unroll
         for (int i = 0; i < A_PASS; ++i) {
             const int iy = a_iy[i] + ty, ix = a_ix[i] + tx;
-            const unsigned bad = ((unsigned)iy < (unsigned)p.VH && (unsigned)ix < (unsigned)p.VW) ? kbad : S_OOB16;
-            ra[i] = __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, (int)((2u * (unsigned)(a_img[i] + (iy * p.AW + ix) * p.AC + c)) | bad), 0, 0);
+            const unsigned bad = ((unsigned)iy < (unsigned)p.VH && (unsigned)ix < (unsigned)p.VW) ? kbad : BUF_OOB;
+            ra[i] = buf_load4_raw(a_rsrc, (2u * (unsigned)(a_img[i] + (iy * p.AW + ix) * p.AC + c)) | bad);
         }
 #pragma unroll
         for (int i = 0; i < B_PASS; ++i)
-            rb[i] = __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, (int)((b_off[i] + 2u * (unsigned)kb) | kbad | (b_off[i] == S_OOB16 ? S_OOB16 : 0u)), 0, 0);
+            rb[i] = buf_load4_raw(w_rsrc, ((b_off[i] + 2u * (unsigned)kb) | kbad | (b_off[i] == BUF_OOB ? BUF_OOB : 0u)));
     };
     auto store_tile = [&](int buf, const u32x4 (&ra)[A_PASS], const u32x4 (&rb)[B_PASS]) {
 #pragma unroll
@@ -329,7 +305,7 @@ __global__ __launch_bounds__(256, 2) void igemm_halos_kernel(const KsParams p) {
     // tap offset in uint2 units; bit 0 = parity of the tap's halo-row offset (selects the swizzled base)
     if (tid < IG_MAX_TAPS) s_tapoff[tid] = ((((int)kc.ty[tid] - kc.ty_min) * HW_ + ((int)kc.tx[tid] - kc.tx_min)) * 4) | (((int)kc.ty[tid] - kc.ty_min) & 1);
 
-    const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.a), 0, p.a_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t a_rsrc = make_rsrc(p.a, p.a_bytes);
     int p_img[PATCHES], p_y0[PATCHES], p_x0[PATCHES];
     bool p_ok[PATCHES];
 #pragma unroll
@@ -345,14 +321,13 @@ __global__ __launch_bounds__(256, 2) void igemm_halos_kernel(const KsParams p) {
     const int r = lane & 31, h = lane >> 5;
     const int wm = wid / WN, wn = wid - wm * WN;             // wm = patch index
     // filter: lane (r, h), tile j reads 8 consecutive k of filter row n0 + wn*TN*32 + j*32 + r of one step = one 16-byte load
-    const __amdgpu_buffer_rsrc_t w3_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<unsigned short*>(reinterpret_cast<const unsigned short*>(p.w3) + p.w3_off[ci]), 0, 2u * (unsigned)p.Nn * (unsigned)kc.Kdim, 0x00020000);
+    const __amdgpu_buffer_rsrc_t w3_rsrc = make_rsrc(reinterpret_cast<const unsigned short*>(p.w3) + p.w3_off[ci], 2u * (unsigned)p.Nn * (unsigned)kc.Kdim);
     const unsigned step_bytes = 32u * (unsigned)p.Nn;
     unsigned b_off[TN];
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         const int n = n0 + wn * TN * 32 + j * 32 + r;
-        b_off[j] = n < p.Nn ? 32u * (unsigned)n + 16u * (unsigned)h : S_OOB16;
+        b_off[j] = n < p.Nn ? 32u * (unsigned)n + 16u * (unsigned)h : BUF_OOB;
     }
     u32x4 rb[RING][TN];
     const int n_steps = (p.AC >> 4) * T;
@@ -360,7 +335,7 @@ __global__ __launch_bounds__(256, 2) void igemm_halos_kernel(const KsParams p) {
         const unsigned kb = (unsigned)step * step_bytes;
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-            rb[slot][j] = __builtin_amdgcn_raw_buffer_load_b128(w3_rsrc, (int)((b_off[j] + kb) | ((step >= n_steps || b_off[j] == S_OOB16) ? S_OOB16 : 0u)), 0, 0);
+            rb[slot][j] = buf_load4_raw(w3_rsrc, ((b_off[j] + kb) | ((step >= n_steps || b_off[j] == BUF_OOB) ? BUF_OOB : 0u)));
         }
     };
     // halo staging: PATCHES x hpix pixels x 2 halves of 8 channels; <= PATCHES*144*2/256 = 2.25 / 4.5 16-byte loads per thread
@@ -384,7 +359,7 @@ __global__ __launch_bounds__(256, 2) void igemm_halos_kernel(const KsParams p) {
             }
             const int iy = sy0 + hy, ix = sx0 + hx;
             const bool ok = idx < h_total && sok && (unsigned)iy < (unsigned)p.VH && (unsigned)ix < (unsigned)p.VW;
-            rh[j] = __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, (int)((2u * (unsigned)(simg + (iy * p.AW + ix) * p.AC + cc * 16 + half * 8)) | (ok ? 0u : S_OOB16)), 0, 0);
+            rh[j] = buf_load4_raw(a_rsrc, (2u * (unsigned)(simg + (iy * p.AW + ix) * p.AC + cc * 16 + half * 8)) | (ok ? 0u : BUF_OOB));
         }
     };
     auto commit_halo = [&]() {
@@ -531,10 +506,8 @@ __global__ __launch_bounds__(256) void conv1x1s_kernel(const unsigned short* __r
                 const long long row = 32 * t + (v & 3) + 8 * (v >> 2) + 4 * h;
                 if (row >= M) continue;
                 float val = acc[j][v] + bv[j];
-                if (act == CSLGAN_ACT_LRELU02) val = val > 0.f ? val : 0.2f * val;
-                else if (act == CSLGAN_ACT_RELU) val = val > 0.f ? val : 0.f;
-                else if (act == CSLGAN_ACT_TANH) val = tanhf(val);
-                if (OUT_BF16) reinterpret_cast<unsigned short*>(y)[row * K + n] = f2bf(val);
+                val = apply_act(val, act);
+                if (OUT_BF16) reinterpret_cast<unsigned short*>(y)[row * K + n] = bf16_rne(val);
                 else reinterpret_cast<float*>(y)[row * K + n] = val;
             }
         }
@@ -569,7 +542,6 @@ static int launch_conv1x1s_ck(const cslgan_conv_t* c, const void* x, const void*
     return check_launch("conv1x1s_kernel");
 }
 
-int split_filter_x3(const float* w, int Nn, int T, int C, void* w3, hipStream_t st, int pieces);      // igemm_bf16.hip
 
 // stride-1 classes (one for a forward conv; the output-parity classes of a strided data gradient), each on an 8x8-patchable grid of at
 // least 16x16, channels a multiple of 16, 2..25 taps within a 12x12 halo, >= 64 filters
@@ -601,7 +573,7 @@ static int launch_halos(KsParams& p, bool out_bf16, hipStream_t st) {
     const KcClass& k0 = p.cls[0];
     const long long n_img = k0.M / ((long long)k0.OHc * k0.OWc);
     const long long a_b = 2ll * n_img * p.AH * p.AW * p.AC;
-    CSLGAN_REQUIRE(a_b < 0xFFFFFFF0ll && 2ll * w_el < 0xFFFFFFF0ll, "igemm_halos: operand larger than 4 GB");
+    CSLGAN_REQUIRE(a_b < (long long)BUF_OOB && 2ll * w_el < (long long)BUF_OOB, "igemm_halos: operand larger than 4 GB");
     p.a_bytes = (unsigned)a_b;
     const bool wide = p.Nn > 64;
     // (A four-patch form for the 64-filter layers — one patch per wave, each wave all 64 filters, four MFMAs per step instead of two —
@@ -653,7 +625,7 @@ static int launch_kcs(KsParams& p, bool out_bf16, hipStream_t st) {
         CSLGAN_REQUIRE(p.cls[c].Kdim % 8 == 0 && p.cls[c].w_off % 8 == 0, "igemm_kcs: reduction length must be a multiple of 8");
     }
     CSLGAN_REQUIRE(p.AC % 8 == 0 && aligned16(p.a) && aligned16(p.w), "igemm_kcs: channels must be a multiple of 8 and operands 16-byte aligned");
-    CSLGAN_REQUIRE(a_b < 0xFFFFFFF0ll && 2 * w_end < 0xFFFFFFF0ll, "igemm_kcs: operand larger than 4 GB");
+    CSLGAN_REQUIRE(a_b < (long long)BUF_OOB && 2 * w_end < (long long)BUF_OOB, "igemm_kcs: operand larger than 4 GB");
     CSLGAN_REQUIRE((kmax + KS_BK) * (long long)p.AC < (1ll << 32), "igemm_kcs: K too large for reciprocal division");
     p.a_bytes = (unsigned)a_b;
     p.w_bytes = (unsigned)(2 * w_end);
@@ -672,17 +644,16 @@ __global__ void round_bf16_kernel(const float* __restrict__ in, unsigned short* 
     const long long n4 = n >> 2;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
         const float4 v = reinterpret_cast<const float4*>(in)[i];
-        reinterpret_cast<uint2*>(out)[i] = make_uint2(f2bf_pk(v.x, v.y), f2bf_pk(v.z, v.w));
+        reinterpret_cast<uint2*>(out)[i] = make_uint2(pack_bf16(v.x, v.y), pack_bf16(v.z, v.w));
     }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) out[(n4 << 2) + threadIdx.x] = f2bf(in[(n4 << 2) + threadIdx.x]);
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) out[(n4 << 2) + threadIdx.x] = bf16_rne(in[(n4 << 2) + threadIdx.x]);
 }
 
 __global__ void widen_bf16_kernel(const unsigned short* __restrict__ in, float* __restrict__ out, long long n) {
     const long long n4 = n >> 2;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
         const uint2 v = reinterpret_cast<const uint2*>(in)[i];
-        reinterpret_cast<float4*>(out)[i] = make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u),
-                                                        __uint_as_float(v.y << 16), __uint_as_float(v.y & 0xffff0000u));
+        reinterpret_cast<float4*>(out)[i] = make_float4(bf_lo(v.x), bf_hi(v.x), bf_lo(v.y), bf_hi(v.y));
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) out[(n4 << 2) + threadIdx.x] = bf2f(in[(n4 << 2) + threadIdx.x]);
 }
@@ -707,7 +678,7 @@ __global__ void repack_dgrad_bf16_kernel(const float* __restrict__ w, unsigned s
         const int k = (int)(i % a.K);
         const long long rest = i / a.K;
         const int t = (int)(rest % Tc), c = (int)(rest / Tc);
-        wt[a.cls_off[cls] + i] = f2bf(w[(((long long)k * a.R + a.kh[cls][t]) * a.S + a.kw[cls][t]) * a.C + c]);
+        wt[a.cls_off[cls] + i] = bf16_rne(w[(((long long)k * a.R + a.kh[cls][t]) * a.S + a.kw[cls][t]) * a.C + c]);
     }
 }
 
@@ -737,8 +708,6 @@ constexpr int MS_BK = 64;        // pixels per LDS tile
 // form that transposed 8x8 blocks in registers cost ~100 vector instructions per thread and K tile beside 16 MFMAs per wave and
 // measured 176-208 TF against 259-339 TF here; DESIGN.md, appendix of retired switches).
 // Q8: Q % 8 == 0, so the 8 consecutive pixels a thread gathers lie in one output row of one image (one decode per tile).
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
 
 // SCALED (clip-weighted sums for ghost clipping): P*Q is a multiple of the 64-pixel K tile, so every K tile lies
 // in ONE sample; when a sample's last tile has been multiplied its accumulated product is folded into a second accumulator with the
@@ -774,12 +743,12 @@ __global__ __launch_bounds__(256, 2) void igemm_mcs_tr_kernel(const MsParams p) 
     const int b_c = nb - b_t * p.C;
     const int b_ty = p.ty[b_t], b_tx = p.tx[b_t];
     const bool a_ok = m0 + c8 < p.Kc;
-    // buffer loads with branch-free offsets (an invalid element ORs 0xFFFFFFF0 into its offset -> the range check returns zeros): see
+    // buffer loads with branch-free offsets (an invalid element ORs BUF_OOB into its offset -> the range check returns zeros): see
     // igemm_kcs_kernel — as `if (valid) v = *ptr` every load sat in its own exec-masked block
-    const __amdgpu_buffer_rsrc_t gy_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.gy), 0, (unsigned)(2ll * p.N * PQ * p.Kc), 0x00020000);
-    const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.x), 0, (unsigned)(2ll * p.N * p.H * p.W * p.C), 0x00020000);
+    const __amdgpu_buffer_rsrc_t gy_rsrc = make_rsrc(p.gy, (unsigned)(2ll * p.N * PQ * p.Kc));
+    const __amdgpu_buffer_rsrc_t x_rsrc = make_rsrc(p.x, (unsigned)(2ll * p.N * p.H * p.W * p.C));
     auto bld = [](__amdgpu_buffer_rsrc_t r, unsigned off) {
-        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
+        const u32x4 v = buf_load4_raw(r, off);
         return make_uint4(v[0], v[1], v[2], v[3]);
     };
 
@@ -791,19 +760,19 @@ __global__ __launch_bounds__(256, 2) void igemm_mcs_tr_kernel(const MsParams p) 
         if (is_a) {
 #pragma unroll
             for (int j = 0; j < 8; ++j)
-                rv[j] = bld(gy_rsrc, (2u * (((unsigned)pix_base + (unsigned)(kk0 + j)) * (unsigned)p.Kc + (unsigned)(m0 + c8))) | ((a_ok && kk0 + j < k_lim) ? 0u : S_OOB16));
+                rv[j] = bld(gy_rsrc, (2u * (((unsigned)pix_base + (unsigned)(kk0 + j)) * (unsigned)p.Kc + (unsigned)(m0 + c8))) | ((a_ok && kk0 + j < k_lim) ? 0u : BUF_OOB));
         } else if (Q8) {
             const int il = kk0 / PQ;
             const int pix = kk0 - il * PQ;
             const int oy = pix / p.Q, ox0 = pix - oy * p.Q;
             const int img = g * p.group + il;           // (32-bit: the entry checks that both operands are below 4 GB)
             const int iy = oy * p.stride + b_ty;
-            const unsigned row_bad = (b_ok && kk0 < k_lim && iy >= 0 && iy < p.H) ? 0u : S_OOB16;
+            const unsigned row_bad = (b_ok && kk0 < k_lim && iy >= 0 && iy < p.H) ? 0u : BUF_OOB;
             const unsigned src = 2u * (unsigned)(((img * p.H + iy) * p.W) * p.C + b_c);
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int ix = (ox0 + j) * p.stride + b_tx;
-                rv[j] = bld(x_rsrc, (src + 2u * (unsigned)(ix * p.C)) | row_bad | ((unsigned)ix < (unsigned)p.W ? 0u : S_OOB16));
+                rv[j] = bld(x_rsrc, (src + 2u * (unsigned)(ix * p.C)) | row_bad | ((unsigned)ix < (unsigned)p.W ? 0u : BUF_OOB));
             }
         } else {
 #pragma unroll
@@ -816,7 +785,7 @@ __global__ __launch_bounds__(256, 2) void igemm_mcs_tr_kernel(const MsParams p) 
                 const int img = g * p.group + il;
                 const int iy = oy * p.stride + b_ty, ix = ox * p.stride + b_tx;
                 const bool ok = b_ok && kk < k_lim && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
-                rv[j] = bld(x_rsrc, (2u * (unsigned)(((img * p.H + iy) * p.W + ix) * p.C + b_c)) | (ok ? 0u : S_OOB16));
+                rv[j] = bld(x_rsrc, (2u * (unsigned)(((img * p.H + iy) * p.W + ix) * p.C + b_c)) | (ok ? 0u : BUF_OOB));
             }
         }
     };
@@ -960,7 +929,7 @@ __global__ __launch_bounds__(256, 2) void igemm_mcs_tr_kernel(const MsParams p) 
                 if (m >= p.Kc) continue;
                 float val = p.alpha * acc[i][j][v];
                 if (p.out_bf16) {
-                    const unsigned short u = f2bf(val);
+                    const unsigned short u = bf16_rne(val);
                     if (outh) outh[(long long)m * p.Ndim + n] = u;
                     val = bf2f(u);
                 }
@@ -978,7 +947,6 @@ __global__ __launch_bounds__(256, 2) void igemm_mcs_tr_kernel(const MsParams p) 
     }
 }
 
-int sqnorm_rows_accumulate(const float* in, long long n_rows, long long len, float* sq_accum, hipStream_t st);   // clip_kernels.hip
 
 // ---- pointwise kernels on bf16 tensors -----------------------------------------------------------------------------------------
 // out = g * (y > 0 ? 1 : slope): LeakyReLU / ReLU backward from the OUTPUT's sign, 8 values per lane
@@ -990,9 +958,9 @@ __global__ __launch_bounds__(256) void act_bwd_bf16_kernel(const uint4* __restri
         unsigned o[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const float g0 = __uint_as_float(gs[q] << 16), g1 = __uint_as_float(gs[q] & 0xffff0000u);
-            const float y0 = __uint_as_float(ys[q] << 16), y1 = __uint_as_float(ys[q] & 0xffff0000u);
-            o[q] = f2bf_pk(y0 > 0.f ? g0 : slope * g0, y1 > 0.f ? g1 : slope * g1);
+            const float g0 = bf_lo(gs[q]), g1 = bf_hi(gs[q]);
+            const float y0 = bf_lo(ys[q]), y1 = bf_hi(ys[q]);
+            o[q] = pack_bf16(y0 > 0.f ? g0 : slope * g0, y1 > 0.f ? g1 : slope * g1);
         }
         out[i] = make_uint4(o[0], o[1], o[2], o[3]);
     }
@@ -1022,14 +990,14 @@ __global__ __launch_bounds__(256) void bias_grad_bf16_kernel(const unsigned shor
         for (int u = 0; u < 4; ++u) {
             const unsigned d[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
 #pragma unroll
-            for (int q = 0; q < 4; ++q) { acc[2 * q] += __uint_as_float(d[q] << 16); acc[2 * q + 1] += __uint_as_float(d[q] & 0xffff0000u); }
+            for (int q = 0; q < 4; ++q) { acc[2 * q] += bf_lo(d[q]); acc[2 * q + 1] += bf_hi(d[q]); }
         }
     }
     for (; px < npix; px += nsl) {
         const uint4 v = *reinterpret_cast<const uint4*>(base + px * K);
         const unsigned d[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-        for (int q = 0; q < 4; ++q) { acc[2 * q] += __uint_as_float(d[q] << 16); acc[2 * q + 1] += __uint_as_float(d[q] & 0xffff0000u); }
+        for (int q = 0; q < 4; ++q) { acc[2 * q] += bf_lo(d[q]); acc[2 * q + 1] += bf_hi(d[q]); }
     }
 #pragma unroll
     for (int q = 0; q < 8; ++q) atomicAdd(&s_part[8 * c8 + q], acc[q]);
@@ -1057,17 +1025,15 @@ __global__ __launch_bounds__(256) void linear_k1s_fwd_kernel(const unsigned shor
     for (long long i = threadIdx.x; i < (C >> 3); i += 256) {
         const uint4 a = xr[i];
         const float4 b0 = reinterpret_cast<const float4*>(w)[2 * i], b1 = reinterpret_cast<const float4*>(w)[2 * i + 1];
-        acc = fmaf(__uint_as_float(a.x << 16), bf2f(f2bf(b0.x)), acc); acc = fmaf(__uint_as_float(a.x & 0xffff0000u), bf2f(f2bf(b0.y)), acc);
-        acc = fmaf(__uint_as_float(a.y << 16), bf2f(f2bf(b0.z)), acc); acc = fmaf(__uint_as_float(a.y & 0xffff0000u), bf2f(f2bf(b0.w)), acc);
-        acc = fmaf(__uint_as_float(a.z << 16), bf2f(f2bf(b1.x)), acc); acc = fmaf(__uint_as_float(a.z & 0xffff0000u), bf2f(f2bf(b1.y)), acc);
-        acc = fmaf(__uint_as_float(a.w << 16), bf2f(f2bf(b1.z)), acc); acc = fmaf(__uint_as_float(a.w & 0xffff0000u), bf2f(f2bf(b1.w)), acc);
+        acc = fmaf(bf_lo(a.x), bf2f(bf16_rne(b0.x)), acc); acc = fmaf(bf_hi(a.x), bf2f(bf16_rne(b0.y)), acc);
+        acc = fmaf(bf_lo(a.y), bf2f(bf16_rne(b0.z)), acc); acc = fmaf(bf_hi(a.y), bf2f(bf16_rne(b0.w)), acc);
+        acc = fmaf(bf_lo(a.z), bf2f(bf16_rne(b1.x)), acc); acc = fmaf(bf_hi(a.z), bf2f(bf16_rne(b1.y)), acc);
+        acc = fmaf(bf_lo(a.w), bf2f(bf16_rne(b1.z)), acc); acc = fmaf(bf_hi(a.w), bf2f(bf16_rne(b1.w)), acc);
     }
     const float tot = block_sum_256(acc, s_red);
     if (threadIdx.x == 0) {
         float val = tot + (bias ? bias[0] : 0.f);
-        if (act == CSLGAN_ACT_LRELU02) val = val > 0.f ? val : 0.2f * val;
-        else if (act == CSLGAN_ACT_RELU) val = val > 0.f ? val : 0.f;
-        else if (act == CSLGAN_ACT_TANH) val = tanhf(val);
+        val = apply_act(val, act);
         y[n] = val;
     }
 }
@@ -1080,18 +1046,18 @@ __global__ __launch_bounds__(256) void linear_k1s_dgrad_kernel(const float* __re
     if (i >= C8) return;
     const float g = gy[n];
     const float4 b0 = reinterpret_cast<const float4*>(w)[2 * i], b1 = reinterpret_cast<const float4*>(w)[2 * i + 1];
-    float o[8] = {g * bf2f(f2bf(b0.x)), g * bf2f(f2bf(b0.y)), g * bf2f(f2bf(b0.z)), g * bf2f(f2bf(b0.w)),
-                  g * bf2f(f2bf(b1.x)), g * bf2f(f2bf(b1.y)), g * bf2f(f2bf(b1.z)), g * bf2f(f2bf(b1.w))};
+    float o[8] = {g * bf2f(bf16_rne(b0.x)), g * bf2f(bf16_rne(b0.y)), g * bf2f(bf16_rne(b0.z)), g * bf2f(bf16_rne(b0.w)),
+                  g * bf2f(bf16_rne(b1.x)), g * bf2f(bf16_rne(b1.y)), g * bf2f(bf16_rne(b1.z)), g * bf2f(bf16_rne(b1.w))};
     if (mask) {
         const uint4 m = reinterpret_cast<const uint4*>(mask + n * C8 * 8)[i];
         const unsigned md[4] = {m.x, m.y, m.z, m.w};
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            o[2 * q] *= __uint_as_float(md[q] << 16) > 0.f ? 1.f : 0.2f;
-            o[2 * q + 1] *= __uint_as_float(md[q] & 0xffff0000u) > 0.f ? 1.f : 0.2f;
+            o[2 * q] = lrelu_mask(o[2 * q], bf_lo(md[q]));
+            o[2 * q + 1] = lrelu_mask(o[2 * q + 1], bf_hi(md[q]));
         }
     }
-    reinterpret_cast<uint4*>(gx + n * C8 * 8)[i] = make_uint4(f2bf_pk(o[0], o[1]), f2bf_pk(o[2], o[3]), f2bf_pk(o[4], o[5]), f2bf_pk(o[6], o[7]));
+    reinterpret_cast<uint4*>(gx + n * C8 * 8)[i] = make_uint4(pack_bf16(o[0], o[1]), pack_bf16(o[2], o[3]), pack_bf16(o[4], o[5]), pack_bf16(o[6], o[7]));
 }
 
 // gw[g,:] = alpha * sum_{n in group g} gy[n] * x[n,:] (fp32), sq[g] += ||gw[g,:]||^2: the head's per-sample / grouped weight gradient
@@ -1112,8 +1078,8 @@ __global__ __launch_bounds__(256) void linear_k1s_wgrad_kernel(const float* __re
             const unsigned d[4] = {a.x, a.y, a.z, a.w};
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                acc[2 * q] = fmaf(s, __uint_as_float(d[q] << 16), acc[2 * q]);
-                acc[2 * q + 1] = fmaf(s, __uint_as_float(d[q] & 0xffff0000u), acc[2 * q + 1]);
+                acc[2 * q] = fmaf(s, bf_lo(d[q]), acc[2 * q]);
+                acc[2 * q + 1] = fmaf(s, bf_hi(d[q]), acc[2 * q + 1]);
             }
         }
     }
@@ -1271,7 +1237,7 @@ int cslgan_conv2d_wgrad_grouped_bf16s(const cslgan_conv_t* c, const void* gy, co
     if (rc) return rc;
     CSLGAN_REQUIRE(group >= 1 && c->N % group == 0, "conv2d_wgrad_bf16s: N=%d not divisible by group=%d", c->N, group);
     CSLGAN_REQUIRE(c->K % 8 == 0 && c->C % 8 == 0 && aligned16(gy) && aligned16(x), "conv2d_wgrad_bf16s: K and C must be multiples of 8, operands 16-byte aligned");
-    CSLGAN_REQUIRE(2ll * c->N * c->P * c->Q * c->K < 0xFFFFFFF0ll && 2ll * c->N * c->H * c->W * c->C < 0xFFFFFFF0ll, "conv2d_wgrad_bf16s: operand larger than 4 GB");
+    CSLGAN_REQUIRE(2ll * c->N * c->P * c->Q * c->K < (long long)BUF_OOB && 2ll * c->N * c->H * c->W * c->C < (long long)BUF_OOB, "conv2d_wgrad_bf16s: operand larger than 4 GB");
     hipStream_t st = (hipStream_t)stream;
     MsParams p{};
     p.gy = gy; p.x = x; p.N = c->N; p.H = c->H; p.W = c->W; p.C = c->C; p.P = c->P; p.Q = c->Q; p.Kc = c->K;
@@ -1315,7 +1281,7 @@ int cslgan_conv2d_wgrad_scaled_bf16s(const cslgan_conv_t* c, const void* gy, con
     if (rc) return rc;
     CSLGAN_REQUIRE(group >= 1 && c->N % group == 0, "conv2d_wgrad_scaled_bf16s: N=%d not divisible by group=%d", c->N, group);
     CSLGAN_REQUIRE(c->K % 8 == 0 && c->C % 8 == 0 && aligned16(gy) && aligned16(x), "conv2d_wgrad_scaled_bf16s: K and C must be multiples of 8, operands 16-byte aligned");
-    CSLGAN_REQUIRE(2ll * c->N * c->P * c->Q * c->K < 0xFFFFFFF0ll && 2ll * c->N * c->H * c->W * c->C < 0xFFFFFFF0ll, "conv2d_wgrad_scaled_bf16s: operand larger than 4 GB");
+    CSLGAN_REQUIRE(2ll * c->N * c->P * c->Q * c->K < (long long)BUF_OOB && 2ll * c->N * c->H * c->W * c->C < (long long)BUF_OOB, "conv2d_wgrad_scaled_bf16s: operand larger than 4 GB");
     CSLGAN_REQUIRE((c->P * c->Q) % MS_BK == 0, "conv2d_wgrad_scaled_bf16s: P*Q=%d is not a multiple of %d (a K tile must lie in one sample)", c->P * c->Q, MS_BK);
     hipStream_t st = (hipStream_t)stream;
     MsParams p{};

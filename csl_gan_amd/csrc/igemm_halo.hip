@@ -13,21 +13,13 @@
 // Same MFMA schedule as igemm_kc (v_mfma_f32_32x32x2_f32, half-wave h owns k = 8g+4h+e), same epilogue.
 #include "common.h"
 #include "igemm.h"
+#include "kc_frame.h"
 #include "conv_classes.h"
 
 namespace cslgan {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr unsigned HOOB = 0xFFFFFFF0u;
 constexpr int PIX = 36;                // floats per halo pixel in LDS (32 channels + 4 pad)
 constexpr int HALO_MAX = 12 * 12;      // pixels per patch halo (8+4 squared: up to 5x5 taps)
-
-__device__ __forceinline__ float4 hbuf_load4(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, 0, 0);
-    return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-}
 
 // GEN = false: the lean instantiation for single-class / equal-class launches on 8x8 patches (the generator's convs);
 // GEN = true adds class pairs and four-image patches (their index arithmetic costs the big convs 1-4 % when compiled in).
@@ -76,9 +68,8 @@ __global__ __launch_bounds__(256, 2) void igemm_halo_kernel(const KcParams p) {
 
     if (tid < IG_MAX_TAPS) s_tapoff[tid] = (((int)kc.ty[tid] - kc.ty_min) * HW_ + ((int)kc.tx[tid] - kc.tx_min)) * PIX;
 
-    const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.a), 0, p.a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w + kc.w_off), 0,
-                                                                             p.w_bytes - 4u * (unsigned)kc.w_off, 0x00020000);
+    const __amdgpu_buffer_rsrc_t a_rsrc = make_rsrc(p.a, p.a_bytes);
+    const __amdgpu_buffer_rsrc_t w_rsrc = make_rsrc(p.w + kc.w_off, p.w_bytes - 4u * (unsigned)kc.w_off);
     // ---- the two patches of this tile: image and origin of their halos ----------------------------------
     int p_img[2], p_y0[2], p_x0[2];
     bool p_ok[2];
@@ -97,13 +88,13 @@ __global__ __launch_bounds__(256, 2) void igemm_halo_kernel(const KcParams p) {
 #pragma unroll
     for (int i = 0; i < B_PASS; ++i) {
         const int n = n0 + lrow + 32 * i;
-        b_off[i] = n < p.Nn ? 4u * ((unsigned)n * (unsigned)kc.Kdim + (unsigned)(q * 4)) : HOOB;
+        b_off[i] = n < p.Nn ? 4u * ((unsigned)n * (unsigned)kc.Kdim + (unsigned)(q * 4)) : BUF_OOB;
     }
     float4 rb[B_PASS];
     auto load_b = [&](int kbase) {       // kbase = t*AC + cc*32, or -1 past the end
 #pragma unroll
         for (int i = 0; i < B_PASS; ++i)
-            rb[i] = hbuf_load4(w_rsrc, (kbase < 0 || b_off[i] == HOOB) ? HOOB : b_off[i] + 4u * (unsigned)kbase);
+            rb[i] = buf_load4(w_rsrc, (kbase < 0 || b_off[i] == BUF_OOB) ? BUF_OOB : b_off[i] + 4u * (unsigned)kbase);
     };
     auto store_b = [&](int buf) {
 #pragma unroll
@@ -127,8 +118,8 @@ __global__ __launch_bounds__(256, 2) void igemm_halo_kernel(const KcParams p) {
             const int hy = rem / HW_, hx = rem - hy * HW_;
             const int iy = (p_y0[pp] + hy) * ay_mul + ay_off, ix = (p_x0[pp] + hx) * ax_mul + ax_off;
             const bool ok = idx < h_total && p_ok[pp] && (unsigned)iy < (unsigned)p.VH && (unsigned)ix < (unsigned)p.VW;
-            const unsigned off = ok ? 4u * (unsigned)(p_img[pp] + si * img_stride + (iy * p.AW + ix) * p.AC + cc * 32 + ch * 4) : HOOB;
-            rh[j] = hbuf_load4(a_rsrc, off);
+            const unsigned off = ok ? 4u * (unsigned)(p_img[pp] + si * img_stride + (iy * p.AW + ix) * p.AC + cc * 32 + ch * 4) : BUF_OOB;
+            rh[j] = buf_load4(a_rsrc, off);
         }
     };
     auto commit_halo = [&]() {
@@ -216,42 +207,11 @@ __global__ __launch_bounds__(256, 2) void igemm_halo_kernel(const KcParams p) {
         cc = ccn;
     }
 
-    // ---- epilogue (as igemm_kc) ---------------------------------------------------------------------------
+    // ---- epilogue ----------------------------------------------------------------------------------------
     if (accumulate && sub + 1 < n_sub) { __syncthreads(); continue; }
-    if (tid < BM) {
-        const int m = m0 + tid;
-        int off = -1, roff = 0;
-        if (m < M) {
-            const RowCoord rc = kc_decode_row(m, OHc, OWc, quad ? 0 : 1);
-            off = kc_out_offset(p, kc, rc);
-            if (p.res) roff = kc_res_offset(p, kc, rc);
-        }
-        s_off[tid] = off;
-        s_roff[tid] = roff;
-    }
+    kc_stage_row_offsets<BM>(p, kc, M, OHc, OWc, m0, quad ? 0 : 1, false, s_off, s_roff);
     __syncthreads();
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int n = n0 + wn * TN * 32 + j * 32 + r;
-        if (n >= p.Nn) continue;
-        const float bv = p.bias ? p.bias[n] : 0.f;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int row = wm * 64 + i * 32 + (v & 3) + 8 * (v >> 2) + 4 * h;
-                const int off = s_off[row];
-                if (off < 0) continue;
-                float val = acc[i][j][v] + bv;
-                if (p.res) val += p.res[s_roff[row] + n];
-                if (p.act == CSLGAN_ACT_LRELU02) val = val > 0.f ? val : 0.2f * val;
-                else if (p.act == CSLGAN_ACT_RELU) val = val > 0.f ? val : 0.f;
-                else if (p.act == CSLGAN_ACT_TANH) val = tanhf(val);
-                if (p.mask) val *= (p.mask[off + n] > 0.f ? 1.f : 0.2f);
-                p.out[off + n] = val;
-            }
-        }
-    }
+    kc_store_tile<TM, TN, false>(acc, p, s_off, s_roff, wm * TM * 32, n0 + wn * TN * 32, r, h);
     __syncthreads();          // the next class of a pair reuses every LDS array
     }   // sub
 }

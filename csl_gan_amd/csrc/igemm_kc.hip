@@ -20,24 +20,10 @@
 // 145, 16 (the conv of UpsampleConv, on the depth-to-space tensor), 60-70, 95-104; MNIST_models.py:17-23, 41-46; and the autograd data-gradient of those.
 #include "common.h"
 #include "igemm.h"
+#include "kc_frame.h"
 #include "conv_classes.h"
 
 namespace cslgan {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-// Range-checked buffer loads: an offset at or beyond the descriptor's byte count returns 0, so padding taps,
-// ragged rows and the K tail need neither a branch nor a select — the loader is straight-line code that the
-// scheduler can interleave with MFMAs.  32-bit byte offsets (tensors are < 4 GB; checked on the host).
-constexpr unsigned OOB = 0xFFFFFFF0u;
-__device__ __forceinline__ float4 buf_load4(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, 0, 0);
-    return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-}
-__device__ __forceinline__ float buf_load1(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
-    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, (int)byte_off, 0, 0));
-}
 
 // NBUF = 2: LDS double buffer, one barrier per K tile (2 workgroups/CU for the 128x128 tile).
 // NBUF = 1: single LDS buffer, two barriers per K tile, half the LDS -> twice the resident wavefronts,
@@ -55,41 +41,15 @@ __global__ __launch_bounds__(256, (NBUF == 1 ? 4 : 2)) void igemm_kc_kernel(cons
     __shared__ int s_roff[BM];
 
     const int tid = threadIdx.x;
-    const int nwg = p.tiles_m * p.tiles_n;
-    const int split = blockIdx.x / nwg;
-    const int wg = xcd_remap(blockIdx.x - split * nwg, nwg);
-    const int tile_mg = wg / p.tiles_n, tile_n = wg - tile_mg * p.tiles_n;
-    int ci = 0;
-#pragma unroll 1
-    while (ci + 1 < p.n_cls && tile_mg >= p.cls[ci + 1].tile0) ++ci;
-    const KcClass& kc = p.cls[ci];
+    int split, m0, n0;
+    int a_img[A_PASS], a_iy[A_PASS], a_ix[A_PASS];
+    unsigned b_off[B_PASS];
+    const KcClass& kc = kc_locate<BM, BN>(p, s_tap, split, m0, n0, a_img, a_iy, a_ix, b_off);
     const int M = kc.M, OHc = kc.OHc, OWc = kc.OWc, Kdim = kc.Kdim;
-    const int m0 = (tile_mg - kc.tile0) * BM, n0 = tile_n * BN;
-    const float* __restrict__ wbase = p.w + kc.w_off;
-
-    if (tid < IG_MAX_TAPS) s_tap[tid] = ((int)kc.ty[tid] << 16) | ((int)kc.tx[tid] & 0xffff);
-
-    // ---- per-thread loader coordinates -----------------------------------------------------
     const int lrow = tid >> 3;   // 0..31
     const int q = tid & 7;       // k-chunk within the tile
-    const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.a), 0, p.a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wbase), 0, p.w_bytes - 4u * (unsigned)kc.w_off, 0x00020000);
-    int a_img[A_PASS], a_iy[A_PASS], a_ix[A_PASS];   // a_img: image base in elements; a_iy = -2^20 marks a row past M
-#pragma unroll
-    for (int i = 0; i < A_PASS; ++i) {
-        const int m = m0 + lrow + 32 * i;
-        const bool ok = m < M;
-        const RowCoord rc = kc_decode_row(ok ? m : 0, OHc, OWc, kc.patch);
-        a_img[i] = rc.img * p.AH * p.AW * p.AC;
-        a_iy[i] = ok ? rc.oy * p.sy : -(1 << 20);
-        a_ix[i] = rc.ox * p.sx;
-    }
-    unsigned b_off[B_PASS];      // byte offset of row n in this class's filter matrix, OOB when n >= Nn
-#pragma unroll
-    for (int i = 0; i < B_PASS; ++i) {
-        const int n = n0 + lrow + 32 * i;
-        b_off[i] = n < p.Nn ? 4u * (unsigned)n * (unsigned)Kdim : OOB;
-    }
+    const __amdgpu_buffer_rsrc_t a_rsrc = make_rsrc(p.a, p.a_bytes);
+    const __amdgpu_buffer_rsrc_t w_rsrc = make_rsrc(p.w + kc.w_off, p.w_bytes - 4u * (unsigned)kc.w_off);
     __syncthreads();  // s_tap visible
 
     float4 ra[A_PASS], rb[B_PASS];
@@ -98,7 +58,7 @@ __global__ __launch_bounds__(256, (NBUF == 1 ? 4 : 2)) void igemm_kc_kernel(cons
         const int iy = a_iy[i] + ty, ix = a_ix[i] + tx;
         const bool ok = kin && (unsigned)iy < (unsigned)p.VH && (unsigned)ix < (unsigned)p.VW;
         const unsigned e = (unsigned)(a_img[i] + (iy * p.AW + ix) * p.AC + c);
-        return ok ? 4u * e : OOB;
+        return ok ? 4u * e : BUF_OOB;   // (igemm_kc_bf16_kernel ORs BUF_OOB into the offset instead: a separate, measured change here)
     };
 
     int k_end = Kdim;            // exclusive K bound of this workgroup's slice (split-K), set below
@@ -109,7 +69,7 @@ __global__ __launch_bounds__(256, (NBUF == 1 ? 4 : 2)) void igemm_kc_kernel(cons
     // part: 0 = everything, 1 = A rows [0, A_PASS/2), 2 = A rows [A_PASS/2, A_PASS), 3 = B rows
     auto calc_offsets = [&](int kt, int part = 0) {
         const int kb = kt * IG_BK + q * 4;
-        const int Kdim = k_end;  // shadows the class's Kdim: beyond this workgroup's K slice everything is OOB
+        const int Kdim = k_end;  // shadows the class's Kdim: beyond this workgroup's K slice everything is BUF_OOB
         const int a_lo = part == 2 ? A_PASS / 2 : 0, a_hi = part == 1 ? A_PASS / 2 : (part == 3 ? 0 : A_PASS);
         if (VEC_A) {
             const bool kin = kb < Kdim;
@@ -136,14 +96,14 @@ __global__ __launch_bounds__(256, (NBUF == 1 ? 4 : 2)) void igemm_kc_kernel(cons
         }
         if (part == 1 || part == 2) return;
         if (VEC_B) {
-            const unsigned kofs = kb < Kdim ? 4u * (unsigned)kb : OOB;
+            const unsigned kofs = kb < Kdim ? 4u * (unsigned)kb : BUF_OOB;
 #pragma unroll
-            for (int i = 0; i < B_PASS; ++i) ob[i] = (b_off[i] == OOB || kofs == OOB) ? OOB : b_off[i] + kofs;
+            for (int i = 0; i < B_PASS; ++i) ob[i] = (b_off[i] == BUF_OOB || kofs == BUF_OOB) ? BUF_OOB : b_off[i] + kofs;
         } else {
 #pragma unroll
             for (int i = 0; i < B_PASS; ++i)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) ob[i * 4 + e] = (b_off[i] != OOB && (kb + e) < Kdim) ? b_off[i] + 4u * (unsigned)(kb + e) : OOB;
+                for (int e = 0; e < 4; ++e) ob[i * 4 + e] = (b_off[i] != BUF_OOB && (kb + e) < Kdim) ? b_off[i] + 4u * (unsigned)(kb + e) : BUF_OOB;
         }
     };
     auto issue_loads = [&]() {
@@ -210,7 +170,7 @@ __global__ __launch_bounds__(256, (NBUF == 1 ? 4 : 2)) void igemm_kc_kernel(cons
 #pragma unroll
             for (int j = 0; j < TN; ++j) bf[slot][j] = *reinterpret_cast<const float4*>(&Bs[buf][ch * B_CH + (brow0 + j * 32) * 4]);
         };
-        issue_loads();       // tile kt+1 (offsets ready since the previous iteration; past the last tile all are OOB -> 0)
+        issue_loads();       // tile kt+1 (offsets ready since the previous iteration; past the last tile all are BUF_OOB -> 0)
         load_frags(0, 0);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -246,62 +206,14 @@ __global__ __launch_bounds__(256, (NBUF == 1 ? 4 : 2)) void igemm_kc_kernel(cons
     }
 
     // ---- epilogue --------------------------------------------------------------------------
-    if (tid < BM) {
-        const int m = m0 + tid;
-        int off = -1, roff = 0;
-        if (m < M) {
-            if (p.dense_out && !p.res && !kc.patch) {
-                off = m * p.ldo;
-            } else {
-                const RowCoord rc = kc_decode_row(m, OHc, OWc, kc.patch);
-                off = kc_out_offset(p, kc, rc);
-                if (p.res) roff = kc_res_offset(p, kc, rc);
-            }
-        }
-        s_off[tid] = off;
-        s_roff[tid] = roff;
-    }
+    kc_stage_row_offsets<BM>(p, kc, M, OHc, OWc, m0, kc.patch, p.dense_out && !p.res && !kc.patch, s_off, s_roff);
     __syncthreads();
-
-    const bool atomic_out = p.ksplit > 1;
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int n = n0 + wn * TN * 32 + j * 32 + r;
-        if (n >= p.Nn) continue;
-        const float bv = (p.bias && split == 0) ? p.bias[n] : 0.f;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int row = wm * TM * 32 + i * 32 + (v & 3) + 8 * (v >> 2) + 4 * h;
-                const int off = s_off[row];
-                if (off < 0) continue;
-                float val = acc[i][j][v] + bv;
-                if (atomic_out) {
-                    atomicAdd(p.out + off + n, val);
-                    continue;
-                }
-                if (p.res) val += p.res[s_roff[row] + n];
-                if (p.act == CSLGAN_ACT_LRELU02) val = val > 0.f ? val : 0.2f * val;
-                else if (p.act == CSLGAN_ACT_RELU) val = val > 0.f ? val : 0.f;
-                else if (p.act == CSLGAN_ACT_TANH) val = tanhf(val);
-                if (p.mask) val *= (p.mask[off + n] > 0.f ? 1.f : 0.2f);
-                p.out[off + n] = val;
-            }
-        }
-    }
+    kc_store_tile<TM, TN, true>(acc, p, s_off, s_roff, wm * TM * 32, n0 + wn * TN * 32, r, h, split);
 }
 
 // Repack KRSC filters into per-class [Nout][taps][Cred] matrices.
 //   transposed == 1 (data gradient): wt[off + (c*Tc + t)*K + k]      = w[((k*R + kh_t)*S + kw_t)*C + c]
 //   transposed == 0 (stride-2 forward parity classes): wt[off + (k*Tc + t)*C + c] = the (kh,kw) of tap t
-__device__ __forceinline__ unsigned short f32_to_bf16_rne(float x) {      // the rounding v_cvt_pk_bf16_f32 performs (finite inputs)
-    typedef float f2_t __attribute__((ext_vector_type(2)));
-    typedef __bf16 b2_t __attribute__((ext_vector_type(2)));
-    const f2_t v = {x, 0.f};
-    return (unsigned short)(__builtin_bit_cast(unsigned, __builtin_convertvector(v, b2_t)) & 0xffffu);
-}
-
 struct RepackArgs {
     int K, R, S, C;
     int n_class;
@@ -348,14 +260,14 @@ __global__ void repack_filters_kernel(const float* __restrict__ w, float* __rest
         } else if (a.pieces) {
             const int rows = a.transposed ? a.C : a.K, row = a.transposed ? c : k, red = a.transposed ? k : c;
             unsigned short* dst = a.w3 + (long long)a.pieces * a.cls_off[cls] + ((((long long)(red >> 4) * Tc + t) * rows + row) << 4) + (red & 15);
-            const unsigned short hi = f32_to_bf16_rne(sum);
+            const unsigned short hi = bf16_rne(sum);
             dst[0] = hi;
             if (a.pieces == 3) {
-                const float r1 = sum - __uint_as_float((unsigned)hi << 16);
-                const unsigned short mid = f32_to_bf16_rne(r1);
+                const float r1 = sum - bf2f(hi);
+                const unsigned short mid = bf16_rne(r1);
                 const long long plane = total;
                 dst[plane] = mid;
-                dst[2 * plane] = f32_to_bf16_rne(r1 - __uint_as_float((unsigned)mid << 16));
+                dst[2 * plane] = bf16_rne(r1 - bf2f(mid));
             }
         }
     }
@@ -363,31 +275,8 @@ __global__ void repack_filters_kernel(const float* __restrict__ w, float* __rest
 
 template <int BM, int BN, int WM, int WN>
 static int launch_kc_tile(KcParams& p, bool vecA, bool vecB, hipStream_t st, long long out_elems) {
-    int tm = 0;
-    for (int c = 0; c < p.n_cls; ++c) {
-        p.cls[c].tile0 = tm;
-        tm += (p.cls[c].M + BM - 1) / BM;
-    }
-    p.tiles_m = tm;
-    p.tiles_n = (p.Nn + BN - 1) / BN;
-    const int tiles = p.tiles_m * p.tiles_n;
-    // split K only for purely linear epilogues and launches that would leave most CUs idle
-    p.ksplit = 1;
-    int nk_max = 0;
-    for (int c = 0; c < p.n_cls; ++c) {
-        const int nk = (p.cls[c].Kdim + IG_BK - 1) / IG_BK;
-        nk_max = nk > nk_max ? nk : nk_max;
-    }
-    if (tiles < 96 && nk_max >= 16 && p.act == CSLGAN_ACT_NONE && !p.res && !p.mask && out_elems > 0) {
-        int want = (256 + tiles - 1) / tiles;
-        const int cap = nk_max / 4;
-        p.ksplit = want < cap ? want : cap;
-        if (p.ksplit < 1) p.ksplit = 1;
-    }
-    if (p.ksplit > 1) {
-        if (int rc = zero_floats(p.out, (size_t)out_elems, st)) return rc;
-    }
-    const dim3 grid((unsigned)(tiles * p.ksplit)), block(256);
+    if (int rc = kc_plan_tiles(p, BM, BN, out_elems, st)) return rc;
+    const dim3 grid((unsigned)(p.tiles_m * p.tiles_n * p.ksplit)), block(256);
     // NBUF = 1 (single LDS buffer, 4 workgroups/CU) was measured slower on every shape of the D-step
     // (G b1: 59 vs 102 TF; G b4: 107 vs 105 TF), so only the double-buffered form is instantiated.
     note_kernel("igemm_kc_kernel<%d,%d>", BM, BN);
@@ -397,21 +286,6 @@ static int launch_kc_tile(KcParams& p, bool vecA, bool vecB, hipStream_t st, lon
     else hipLaunchKernelGGL((igemm_kc_kernel<BM, BN, WM, WN, false, false, 2>), grid, block, 0, st, p);
     return check_launch("igemm_kc_kernel");
 }
-
-static long long tiles_for(const KcParams& p, int BM, int BN) {
-    long long tm = 0;
-    for (int c = 0; c < p.n_cls; ++c) tm += (p.cls[c].M + BM - 1) / BM;
-    return tm * ((p.Nn + BN - 1) / BN);
-}
-
-int launch_kc_bf16(KcParams& p, hipStream_t st, long long out_elems);     // igemm_bf16.hip
-int split_filter_x3(const float* w, int Nn, int T, int C, void* w3, hipStream_t st, int pieces);      // igemm_x3.hip
-bool x3h_eligible(const KcParams& p);
-int launch_x3h(KcParams& p, hipStream_t st);
-bool halo_eligible(const KcParams& p);          // igemm_halo.hip
-int launch_halo(KcParams& p, hipStream_t st);
-bool skinny_eligible(const KcParams& p);        // igemm_skinny.hip
-int launch_skinny(KcParams& p, hipStream_t st);
 
 // out_elems: total floats of the output tensor (needed to zero it when K is split), or 0 to forbid splitting
 int launch_kc(KcParams& p, hipStream_t st, long long out_elems) {
@@ -426,7 +300,7 @@ int launch_kc(KcParams& p, hipStream_t st, long long out_elems) {
             const long long e = (long long)p.cls[c].w_off + (long long)p.Nn * p.cls[c].Kdim;
             w_end = e > w_end ? e : w_end;
         }
-        if (a_b >= 0xFFFFFFF0ll || 4 * w_end >= 0xFFFFFFF0ll) {
+        if (a_b >= (long long)BUF_OOB || 4 * w_end >= (long long)BUF_OOB) {
             set_error("igemm_kc: operand larger than 4 GB");
             return CSLGAN_ERR_INVALID_ARG;
         }
@@ -454,17 +328,11 @@ int launch_kc(KcParams& p, hipStream_t st, long long out_elems) {
     if (p.w3 && x3h_eligible(p)) return launch_x3h(p, st);          // exact fp32 on the round-4 halo kernel (step-major fp32 filter copy in p.w3)
     if (p.gn_part || p.in_scale) { set_error("conv2d_fwd: gn_part / in_scale given but the shape does not run on the LDS-halo kernel"); return CSLGAN_ERR_INVALID_ARG; }
     if (halo_eligible(p)) return launch_halo(p, st);
-    for (int c = 0; c < p.n_cls; ++c) {
-        KcClass& k = p.cls[c];
-        k.patch = (k.T > 1 && k.OHc % 8 == 0 && k.OWc % 8 == 0) ? 1 : 0;
-    }
-    bool kd4 = true;
-    for (int c = 0; c < p.n_cls; ++c) kd4 = kd4 && (p.cls[c].Kdim % 4 == 0) && (p.cls[c].w_off % 4 == 0);
-    const bool vecA = (p.AC % 4 == 0) && aligned16(p.a);
-    const bool vecB = kd4 && aligned16(p.w);
+    bool vecA, vecB;
+    kc_mark_patches_and_vec(p, vecA, vecB);
     if (p.Nn <= 32) return launch_kc_tile<128, 32, 4, 1>(p, vecA, vecB, st, out_elems);
     if (p.Nn <= 64) {
-        if (tiles_for(p, 128, 64) >= 192) return launch_kc_tile<128, 64, 2, 2>(p, vecA, vecB, st, out_elems);
+        if (kc_tiles_for(p, 128, 64) >= 192) return launch_kc_tile<128, 64, 2, 2>(p, vecA, vecB, st, out_elems);
         return launch_kc_tile<64, 64, 2, 2>(p, vecA, vecB, st, out_elems);
     }
     constexpr int KC_T128 = 300;       // 128x128 tiles from which the large tile is used
@@ -472,8 +340,8 @@ int launch_kc(KcParams& p, hipStream_t st, long long out_elems) {
     // workgroup per CU the launch lasts as long as its heaviest class, so multi-class launches want more, smaller tiles
     constexpr int KC_TMC = 520;
     const int t64 = p.n_cls > 1 ? KC_TMC : 192;
-    if (tiles_for(p, 128, 128) >= KC_T128) return launch_kc_tile<128, 128, 2, 2>(p, vecA, vecB, st, out_elems);
-    if (tiles_for(p, 64, 128) >= t64) return launch_kc_tile<64, 128, 1, 4>(p, vecA, vecB, st, out_elems);
+    if (kc_tiles_for(p, 128, 128) >= KC_T128) return launch_kc_tile<128, 128, 2, 2>(p, vecA, vecB, st, out_elems);
+    if (kc_tiles_for(p, 64, 128) >= t64) return launch_kc_tile<64, 128, 1, 4>(p, vecA, vecB, st, out_elems);
     return launch_kc_tile<64, 64, 2, 2>(p, vecA, vecB, st, out_elems);
 }
 
@@ -522,7 +390,7 @@ int cslgan_conv2d_fwd_x3_f32(const cslgan_conv_t* c, const float* x, const float
     CSLGAN_REQUIRE(aligned16(w) && aligned16(w3_ws) && ((long long)c->K * c->R * c->S * c->C) % 4 == 0, "conv2d_fwd_x3: filter must be 16-byte aligned with a multiple of 4 elements");
     if (repack) {       // CSLGAN_COMPUTE_F32: a step-major fp32 copy (the exact-fp32 form of the LDS-halo kernel, K*R*S*C floats)
         int rc = split_filter_x3(w, c->K, c->R * c->S, c->C, w3_ws, (hipStream_t)stream,
-                                 c->compute == CSLGAN_COMPUTE_BF16X3 ? 3 : (c->compute == CSLGAN_COMPUTE_BF16 ? 1 : 0));
+                                 kc_pieces(c->compute));
         if (rc) return rc;
     }
     return conv2d_fwd_impl(c, x, w, w3_ws, bias, residual, act, y, stream);
@@ -558,7 +426,7 @@ static int conv2d_fwd_impl(const cslgan_conv_t* c, const float* x, const float* 
     p.VH = c->H; p.VW = c->W;
     p.sy = p.sx = c->stride;
     p.w = w; p.w3 = w3; p.Nn = c->K; p.out = y; p.OHf = c->P; p.OWf = c->Q; p.osy = p.osx = 1; p.ldo = c->K; p.dense_out = 1;
-    p.bias = bias; p.res = residual; p.mask = nullptr; p.act = act; p.bf16 = c->compute == CSLGAN_COMPUTE_BF16 ? 1 : (c->compute == CSLGAN_COMPUTE_BF16X3 ? 3 : 0);
+    p.bias = bias; p.res = residual; p.mask = nullptr; p.act = act; p.bf16 = kc_pieces(c->compute);
     p.a_bf16 = x_bf16;
     p.part = reinterpret_cast<float*>(c->split_ws); p.part_floats = c->split_ws_floats; p.out_floats = (long long)c->N * c->P * c->Q * c->K;
     if (c->gn_part) { p.gn_part = c->gn_part; p.gn_cpg = c->K / c->gn_groups; p.gn_slots = c->P * c->Q / 64; p.part = nullptr; }
@@ -636,7 +504,7 @@ static int conv2d_s2_fwd_impl(const cslgan_conv_t* c, const float* x, const floa
     constexpr int S2_MIN_TILES = 512;
     const long long wide_tiles = ((long long)c->N * c->P * c->Q + 127) / 128 * ((c->K + 127) / 128);
     if (w3_ws) {        // the round-4 LDS-halo kernel: three-piece, plain bf16 or exact fp32 operands, any tile count
-        p.bf16 = c->compute == CSLGAN_COMPUTE_BF16X3 ? 3 : (c->compute == CSLGAN_COMPUTE_BF16 ? 1 : 0);
+        p.bf16 = kc_pieces(c->compute);
         p.w3 = w3_ws;
         p.a_bytes = 0; p.w_bytes = 0;      // (launch_kc sets the operand sizes)
     }
@@ -703,7 +571,7 @@ static int conv2d_dgrad_impl(const cslgan_conv_t* c, const float* gy, const floa
     p.a = gy; p.AH = c->P; p.AW = c->Q; p.AC = c->K; p.VH = c->P; p.VW = c->Q; p.sy = p.sx = 1;
     p.w = wt_ws; p.Nn = c->C; p.out = gx; p.OHf = c->H; p.OWf = c->W; p.osy = p.osx = s; p.ldo = c->C;
     p.dense_out = (s == 1) ? 1 : 0;
-    p.bias = nullptr; p.res = nullptr; p.mask = mask; p.act = CSLGAN_ACT_NONE; p.bf16 = c->compute == CSLGAN_COMPUTE_BF16 ? 1 : (c->compute == CSLGAN_COMPUTE_BF16X3 ? 3 : 0);
+    p.bias = nullptr; p.res = nullptr; p.mask = mask; p.act = CSLGAN_ACT_NONE; p.bf16 = kc_pieces(c->compute);
     p.a_bf16 = gy_bf16;
     p.w3 = (w3_ws && c->K % 16 == 0 && aligned16(w3_ws)) ? w3_ws : nullptr;
     p.part = reinterpret_cast<float*>(c->split_ws); p.part_floats = c->split_ws_floats; p.out_floats = (long long)c->N * c->H * c->W * c->C;

@@ -12,12 +12,12 @@
 // goes to a [k][m] LDS image; MFMA operands are ds_read_b32 (32 consecutive floats per half-wave:
 // conflict-free).  v_mfma_f32_32x32x2_f32, exact fp32.
 #include "common.h"
+#include "device_prims.h"
 #include "igemm.h"
 #include "conv_classes.h"
 
 namespace cslgan {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int MC_BK = 16;
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool VEC_A, bool VEC_B>
@@ -197,10 +197,9 @@ __global__ __launch_bounds__(256) void igemm_mc_kernel(const McParams p) {
                 if (m >= p.Kc) continue;
                 float val = p.alpha * acc[i][j][v];
                 if (p.out_bf16) {      // what is stored is what gets clipped: norm of the rounded value
-                    unsigned u = __float_as_uint(val);
-                    u += 0x7FFFu + ((u >> 16) & 1u);
+                    const unsigned u = rne_bf16_bits(val);
                     if (outh) outh[(long long)m * p.Ndim + n] = (unsigned short)(u >> 16);
-                    val = __uint_as_float(u & 0xffff0000u);
+                    val = bf_hi(u);
                 }
                 ss = fmaf(val, val, ss);
                 if (outg) {
@@ -286,17 +285,6 @@ __global__ __launch_bounds__(256) void bias_grad_grouped_vec_kernel(const float*
         if (tid == 0) atomicAdd(sq + g, tot);
     }
 }
-
-int sqnorm_rows_accumulate(const float* in, long long n_rows, long long len, float* sq_accum, hipStream_t st);   // clip_kernels.hip
-
-bool wgh_eligible(const cslgan_conv_t* c, int out_bf16, const void* gy, const void* x);      // igemm_wgh.hip
-bool x3w_eligible(const cslgan_conv_t* c, int out_bf16, const void* gy, const void* x);      // igemm_wgh.hip: the three-piece (bf16x3) form
-bool x3w_quad_eligible(const cslgan_conv_t* c, int group, int out_bf16, const void* gy, const void* x);     // ... on 4x4 output grids
-int launch_wgh(const cslgan_conv_t* c, const float* gy, const float* x, int group, float alpha, float* gw, float* sq, hipStream_t st,
-               const float* row_scale, int n_seg = 0, const int* seg_first = nullptr, float* const* seg_gw = nullptr,
-               float* const* seg_sq = nullptr);      // igemm_wgh.hip
-
-int launch_mc_bf16(McParams& p, bool vecA, bool vecB, hipStream_t st, int nsplit);        // igemm_bf16.hip
 
 template <int BM, int BN, int WM, int WN>
 static int launch_mc_tile(McParams& p, bool vecA, bool vecB, hipStream_t st) {

@@ -8,22 +8,15 @@
 // (4 channels per lane, one ds_read_b128 per tap) with that lane's T x NJ filter float4s held in registers; the
 // 16 partial sums meet in a 4-step butterfly.  Same KcParams classes / epilogue contract as igemm_kc.
 #include "common.h"
+#include "device_prims.h"
 #include "igemm.h"
 #include "conv_classes.h"
 
 namespace cslgan {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr unsigned SOOB = 0xFFFFFFF0u;
 constexpr int SK_MAXT = 9;             // taps per class held in registers
 constexpr int SK_C = 64;               // input channels (16 lanes x float4)
 constexpr int SK_HALO = 12 * 12;
-
-__device__ __forceinline__ float4 sbuf_load4(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, 0, 0);
-    return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-}
 
 // ALL: the classes of the launch (the four parity classes of a stride-2 data gradient) have the same grid and read the same
 // input patch: one workgroup stages the union halo once and runs the classes one after the other (a quarter of the halo traffic;
@@ -45,7 +38,7 @@ __global__ __launch_bounds__(256) void igemm_skinny_kernel(const KcParams p) {
     const int y0 = rc0.oy + kc.ty_min, x0 = rc0.ox + kc.tx_min;
     const int img_base = rc0.img * p.AH * p.AW * SK_C;
 
-    const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.a), 0, p.a_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t a_rsrc = make_rsrc(p.a, p.a_bytes);
     // ---- halo: hpix pixels x 16 float4 ------------------------------------------------------------------
     const int cl = tid & 15;
     if (p.a_bf16) {
@@ -61,7 +54,7 @@ __global__ __launch_bounds__(256) void igemm_skinny_kernel(const KcParams p) {
             const int hy = pix / HW_, hx = pix - hy * HW_;
             const int iy = y0 + hy, ix = x0 + hx;
             const bool ok = pix < hpix && (unsigned)iy < (unsigned)p.VH && (unsigned)ix < (unsigned)p.VW;
-            const auto v = __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, (int)(ok ? 2u * (unsigned)(img_base + (iy * p.AW + ix) * SK_C + c8 * 8) : SOOB), 0, 0);
+            const auto v = buf_load4_raw(a_rsrc, (ok ? 2u * (unsigned)(img_base + (iy * p.AW + ix) * SK_C + c8 * 8) : BUF_OOB));
             r8[j] = make_uint4(v[0], v[1], v[2], v[3]);
         }
 #pragma unroll
@@ -69,8 +62,8 @@ __global__ __launch_bounds__(256) void igemm_skinny_kernel(const KcParams p) {
             const int idx = tid + 256 * j;
             if ((idx >> 3) < hpix) {
                 const uint4 v = r8[j];
-                Hs[2 * idx] = make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u), __uint_as_float(v.y << 16), __uint_as_float(v.y & 0xffff0000u));
-                Hs[2 * idx + 1] = make_float4(__uint_as_float(v.z << 16), __uint_as_float(v.z & 0xffff0000u), __uint_as_float(v.w << 16), __uint_as_float(v.w & 0xffff0000u));
+                Hs[2 * idx] = make_float4(bf_lo(v.x), bf_hi(v.x), bf_lo(v.y), bf_hi(v.y));
+                Hs[2 * idx + 1] = make_float4(bf_lo(v.z), bf_hi(v.z), bf_lo(v.w), bf_hi(v.w));
             }
         }
     } else {
@@ -93,7 +86,7 @@ __global__ __launch_bounds__(256) void igemm_skinny_kernel(const KcParams p) {
             const int iy = y0 + hy, ix = x0 + hx;
             const bool ok = pix < hpix && (unsigned)iy < (unsigned)p.VH && (unsigned)ix < (unsigned)p.VW;
             okm |= (ok ? 1u : 0u) << j;
-            rh[j] = sbuf_load4(a_rsrc, ok ? 4u * (unsigned)(img_base + (iy * p.AW + ix) * SK_C + c4 * 4) : SOOB);
+            rh[j] = buf_load4(a_rsrc, ok ? 4u * (unsigned)(img_base + (iy * p.AW + ix) * SK_C + c4 * 4) : BUF_OOB);
         }
 #pragma unroll
         for (int j = 0; j < HREG; ++j) {
@@ -118,8 +111,7 @@ __global__ __launch_bounds__(256) void igemm_skinny_kernel(const KcParams p) {
     for (int cc = ALL ? 0 : ci; cc < (ALL ? p.n_cls : ci + 1); ++cc) {
     const KcClass& kk = p.cls[cc];
     const int Tc = kk.T;
-    const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w + kk.w_off), 0,
-                                                                             p.w_bytes - 4u * (unsigned)kk.w_off, 0x00020000);
+    const __amdgpu_buffer_rsrc_t w_rsrc = make_rsrc(p.w + kk.w_off, p.w_bytes - 4u * (unsigned)kk.w_off);
     // ---- this lane's filter values: 4 channels x T taps x NJ outputs ------------------------------------
     float4 wr[SK_MAXT][NJ];
     int toff[SK_MAXT];
@@ -128,7 +120,7 @@ __global__ __launch_bounds__(256) void igemm_skinny_kernel(const KcParams p) {
         toff[t] = t < Tc ? (((int)kk.ty[t] - kk.ty_min) * HW_ + ((int)kk.tx[t] - kk.tx_min)) * 16 : 0;
 #pragma unroll
         for (int j = 0; j < NJ; ++j)
-            wr[t][j] = sbuf_load4(w_rsrc, (t < Tc && j < p.Nn) ? 4u * (unsigned)(j * kk.Kdim + t * SK_C + cl * 4) : SOOB);
+            wr[t][j] = buf_load4(w_rsrc, (t < Tc && j < p.Nn) ? 4u * (unsigned)(j * kk.Kdim + t * SK_C + cl * 4) : BUF_OOB);
     }
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
@@ -166,10 +158,8 @@ __global__ __launch_bounds__(256) void igemm_skinny_kernel(const KcParams p) {
             const RowCoord rc = {rc0.img, rc0.oy + qy, rc0.ox + qx};
             const int off = kc_out_offset(p, kk, rc);
             if (p.res) val += p.res[kc_res_offset(p, kk, rc) + cl];
-            if (p.act == CSLGAN_ACT_LRELU02) val = val > 0.f ? val : 0.2f * val;
-            else if (p.act == CSLGAN_ACT_RELU) val = val > 0.f ? val : 0.f;
-            else if (p.act == CSLGAN_ACT_TANH) val = tanhf(val);
-            if (p.mask) val *= (p.mask[off + cl] > 0.f ? 1.f : 0.2f);
+            val = apply_act(val, p.act);
+            if (p.mask) val = lrelu_mask(val, p.mask[off + cl]);
             p.out[off + cl] = val;
         }
     }
@@ -264,7 +254,7 @@ __global__ __launch_bounds__(256) void skinny_wgrad_kernel(const SkinnyWgradPara
     const int tid = threadIdx.x;
     const int T = p.T, HW_ = p.halo_w, hpix = p.halo_h * p.halo_w;
     const int cl = tid & 15, wid = tid >> 6, pg = (tid & 63) >> 4;
-    const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, p.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t x_rsrc = make_rsrc(p.x, p.x_bytes);
     int toff[SK_MAXT];
 #pragma unroll
     for (int t = 0; t < SK_MAXT; ++t) toff[t] = t < T ? (((int)p.ty[t] - p.ty_min) * HW_ + ((int)p.tx[t] - p.tx_min)) * 16 : 0;
@@ -288,7 +278,7 @@ __global__ __launch_bounds__(256) void skinny_wgrad_kernel(const SkinnyWgradPara
             const int hy = pix / HW_, hx = pix - hy * HW_;
             const int iy = oy0 + p.ty_min + hy, ix = ox0 + p.tx_min + hx;
             const bool ok = pix < hpix && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
-            rh[j] = sbuf_load4(x_rsrc, ok ? 4u * (unsigned)(((img * p.H + iy) * p.W + ix) * SK_C + c4 * 4) : SOOB);
+            rh[j] = buf_load4(x_rsrc, ok ? 4u * (unsigned)(((img * p.H + iy) * p.W + ix) * SK_C + c4 * 4) : BUF_OOB);
         }
         float gv = 0.f;
         if (tid < 64 * NJ) {
@@ -361,7 +351,7 @@ int cslgan_conv2d_wgrad_skinny_f32(const cslgan_conv_t* c, const float* gy, cons
     CSLGAN_REQUIRE(c->N > 0 && c->P == c->H + 2 * c->pad - c->R + 1 && c->Q == c->W + 2 * c->pad - c->S + 1, "conv2d_wgrad_skinny: inconsistent output size");
     CSLGAN_REQUIRE((c->P & 7) == 0 && (c->Q & 7) == 0, "conv2d_wgrad_skinny: output grid must be a multiple of 8x8");
     CSLGAN_REQUIRE(n_blocks >= 1 && aligned16(x), "conv2d_wgrad_skinny: bad workspace / alignment");
-    CSLGAN_REQUIRE(4ll * c->N * c->H * c->W * SK_C < 0xFFFFFFF0ll, "conv2d_wgrad_skinny: input larger than 4 GB");
+    CSLGAN_REQUIRE(4ll * c->N * c->H * c->W * SK_C < (long long)BUF_OOB, "conv2d_wgrad_skinny: input larger than 4 GB");
     SkinnyWgradParams p{};
     p.gy = gy; p.x = x; p.N = c->N; p.H = c->H; p.W = c->W; p.P = c->P; p.Q = c->Q; p.T = c->R * c->S;
     p.n_patches = c->N * (c->P >> 3) * (c->Q >> 3);

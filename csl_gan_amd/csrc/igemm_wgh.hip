@@ -10,11 +10,11 @@
 // Both operands have the pixel (the reduction index) as the slow dimension, so fragments are ds_read_b32 of 32
 // consecutive channels: conflict-free, no transposes.  v_mfma_f32_32x32x2_f32, exact fp32; 4 wavefronts = 2 (m) x 2 (c).
 #include "common.h"
+#include "device_prims.h"
 #include "igemm.h"
 
 namespace cslgan {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int WG_BM = 128, WG_BC = 64, WG_MAXS = 5;
 constexpr int WG_LDX = WG_BC + 4;      // floats per pixel of the input slab in LDS
@@ -176,8 +176,6 @@ __global__ __launch_bounds__(256, 2) void igemm_wgh_kernel(const WghParams p) {
     }
 }
 
-bool wgh_eligible(const cslgan_conv_t* c, int out_bf16, const void* gy, const void* x);
-
 // ---- the same contraction with fp32 emulated from three bfloat16 pieces on the bf16 matrix cores (round 4) ----------------------------
 // cslgan_conv_t.compute == CSLGAN_COMPUTE_BF16X3 (csrc/igemm_bf16.hip states the arithmetic: x = hi + mid + lo in bfloat16, six exact
 // piece products per multiply-add, smallest first, fp32 accumulate — fp32-accurate at 2.67x the fp32 matrix rate).
@@ -196,35 +194,12 @@ bool wgh_eligible(const cslgan_conv_t* c, int out_bf16, const void* gy, const vo
 //   * the next stage's global loads are issued before the MFMA phase and held in registers across it (7 float4), so a stage is
 //     barrier - split/store - barrier - MFMAs, and with two workgroups per CU one multiplies while the other splits.
 // Per wavefront and 16-k step: 6 + 30 transposing reads (8 B per lane) for 30 MFMAs.
-typedef float x3w_f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 x3w_bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 x3w_bf16x8 __attribute__((ext_vector_type(8)));
-typedef short x3w_s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) x3w_s16x4* x3w_lds_ptr;
-typedef unsigned int x3w_u32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
-__device__ __forceinline__ unsigned w_pack(float lo, float hi) {
-    const x3w_f32x2 v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, x3w_bf16x2));
-}
-__device__ __forceinline__ float w_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float w_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
-__device__ __forceinline__ void w_split4(const float4& v, uint2& hi, uint2& mid, uint2& lo) {
-    hi = make_uint2(w_pack(v.x, v.y), w_pack(v.z, v.w));
-    const float r0 = v.x - w_lo(hi.x), r1 = v.y - w_hi(hi.x), r2 = v.z - w_lo(hi.y), r3 = v.w - w_hi(hi.y);   // exact
-    mid = make_uint2(w_pack(r0, r1), w_pack(r2, r3));
-    lo = make_uint2(w_pack(r0 - w_lo(mid.x), r1 - w_hi(mid.x)), w_pack(r2 - w_lo(mid.y), r3 - w_hi(mid.y)));
-}
-__device__ __forceinline__ float4 w_bld(__amdgpu_buffer_rsrc_t r, unsigned off) {
-    const x3w_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
-    return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-}
-__device__ __forceinline__ x3w_bf16x8 w_tr_pair(const unsigned char* lo_addr, const unsigned char* hi_addr) {
-    const x3w_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((x3w_lds_ptr)lo_addr);
-    const x3w_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((x3w_lds_ptr)hi_addr);
+__device__ __forceinline__ bf16x8 w_tr_pair(const unsigned char* lo_addr, const unsigned char* hi_addr) {
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)lo_addr);
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)hi_addr);
     const uint4 w = make_uint4(__builtin_bit_cast(uint2, lo).x, __builtin_bit_cast(uint2, lo).y, __builtin_bit_cast(uint2, hi).x, __builtin_bit_cast(uint2, hi).y);
-    return __builtin_bit_cast(x3w_bf16x8, w);
+    return __builtin_bit_cast(bf16x8, w);
 }
 }  // namespace
 
@@ -234,7 +209,6 @@ __device__ __forceinline__ x3w_bf16x8 w_tr_pair(const unsigned char* lo_addr, co
 template <int STRIDE, bool QUAD = false>
 __global__ __launch_bounds__(256, 2) void igemm_x3w_kernel(const WghParams p) {
     constexpr int S = 5;
-    constexpr unsigned OOB = 0xFFFFFFF0u;
     constexpr int XW = QUAD ? 3 * STRIDE + S : 7 * STRIDE + S;      // staged columns of the slab (of one sample for QUAD)
     constexpr int XPITCH = STRIDE == 1 ? 64 : 96;      // bytes per slab pixel in a 32-channel plane (see the bank note above)
     constexpr int XPIX = QUAD ? 2 * 4 * XW : 4 * XW;   // slab pixels per stage (4 input rows; two samples for QUAD)
@@ -265,8 +239,8 @@ __global__ __launch_bounds__(256, 2) void igemm_x3w_kernel(const WghParams p) {
     const int wm = wid >> 1, wn = wid & 1;
     const int gq = (lane >> 2) & 3, gp = lane & 3, ghalf = (lane >> 4) & 1;
 
-    const __amdgpu_buffer_rsrc_t gy_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.gy), 0, (unsigned)(4ll * p.N * p.P * p.Q * p.K), 0x00020000);
-    const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, (unsigned)(4ll * p.N * p.H * p.W * p.C), 0x00020000);
+    const __amdgpu_buffer_rsrc_t gy_rsrc = make_rsrc(p.gy, (unsigned)(4ll * p.N * p.P * p.Q * p.K));
+    const __amdgpu_buffer_rsrc_t x_rsrc = make_rsrc(p.x, (unsigned)(4ll * p.N * p.H * p.W * p.C));
 
     f32x16 acc[S];
 #pragma unroll
@@ -292,7 +266,7 @@ __global__ __launch_bounds__(256, 2) void igemm_x3w_kernel(const WghParams p) {
             rs_next2 = p.row_scale ? p.row_scale[img0 + 1] : 1.f;
 #pragma unroll
             for (int j = 0; j < 2; ++j)
-                rg[j] = w_bld(gy_rsrc, 4u * ((unsigned)(img0 * 16 + a_pix[j]) * (unsigned)p.K + (unsigned)(m0 + a_m4[j] * 4)));
+                rg[j] = buf_load4(gy_rsrc, 4u * ((unsigned)(img0 * 16 + a_pix[j]) * (unsigned)p.K + (unsigned)(m0 + a_m4[j] * 4)));
 #pragma unroll
             for (int j = 0; j < NX; ++j) {
                 const int idx = tid + 256 * j;
@@ -301,7 +275,7 @@ __global__ __launch_bounds__(256, 2) void igemm_x3w_kernel(const WghParams p) {
                 const int row = pr2 / XW, col = pr2 - row * XW;
                 const int iy = row * STRIDE + r - p.pad, ix = col - p.pad;
                 const bool ok = pc < XPIX && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
-                rx[j] = w_bld(x_rsrc, (4u * (unsigned)((((img0 + smp) * p.H + iy) * p.W + ix) * p.C + c0 + c4 * 4)) | (ok ? 0u : OOB));
+                rx[j] = buf_load4(x_rsrc, (4u * (unsigned)((((img0 + smp) * p.H + iy) * p.W + ix) * p.C + c0 + c4 * 4)) | (ok ? 0u : BUF_OOB));
             }
             return;
         }
@@ -312,7 +286,7 @@ __global__ __launch_bounds__(256, 2) void igemm_x3w_kernel(const WghParams p) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const unsigned gpix = (unsigned)((img * p.P + py0 + (a_pix[j] >> 3)) * p.Q + px0 + (a_pix[j] & 7));
-            rg[j] = w_bld(gy_rsrc, 4u * (gpix * (unsigned)p.K + (unsigned)(m0 + a_m4[j] * 4)));
+            rg[j] = buf_load4(gy_rsrc, 4u * (gpix * (unsigned)p.K + (unsigned)(m0 + a_m4[j] * 4)));
         }
 #pragma unroll
         for (int j = 0; j < NX; ++j) {
@@ -321,7 +295,7 @@ __global__ __launch_bounds__(256, 2) void igemm_x3w_kernel(const WghParams p) {
             const int row = pc / XW, col = pc - row * XW;
             const int iy = (py0 + row) * STRIDE + r - p.pad, ix = px0 * STRIDE - p.pad + col;
             const bool ok = pc < XPIX && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
-            rx[j] = w_bld(x_rsrc, (4u * (unsigned)(((img * p.H + iy) * p.W + ix) * p.C + c0 + c4 * 4)) | (ok ? 0u : OOB));
+            rx[j] = buf_load4(x_rsrc, (4u * (unsigned)(((img * p.H + iy) * p.W + ix) * p.C + c0 + c4 * 4)) | (ok ? 0u : BUF_OOB));
         }
     };
     auto store_stage = [&](float rs, float rs2) {
@@ -330,24 +304,22 @@ __global__ __launch_bounds__(256, 2) void igemm_x3w_kernel(const WghParams p) {
             float4 v = rg[j];
             if (QUAD && a_pix[j] >= 16) rs = rs2;      // (j = 1 for every thread: pixels 16..31 are the second sample's)
             v.x *= rs; v.y *= rs; v.z *= rs; v.w *= rs;
-            uint2 hi, mid, lo;
-            w_split4(v, hi, mid, lo);
+            const bf16x3_t t = split4_bf16(v);
             const int at = a_pix[j] * 64 + (a_m4[j] & 7) * 8, pl = a_m4[j] >> 3;
-            *reinterpret_cast<uint2*>(&As[0][pl][at]) = hi;
-            *reinterpret_cast<uint2*>(&As[1][pl][at]) = mid;
-            *reinterpret_cast<uint2*>(&As[2][pl][at]) = lo;
+            *reinterpret_cast<uint2*>(&As[0][pl][at]) = t.hi;
+            *reinterpret_cast<uint2*>(&As[1][pl][at]) = t.mid;
+            *reinterpret_cast<uint2*>(&As[2][pl][at]) = t.lo;
         }
 #pragma unroll
         for (int j = 0; j < NX; ++j) {
             const int idx = tid + 256 * j;
             const int c4 = idx & 15, pc = idx >> 4;
             if (pc < XPIX) {
-                uint2 hi, mid, lo;
-                w_split4(rx[j], hi, mid, lo);
+                const bf16x3_t t = split4_bf16(rx[j]);
                 const int at = pc * XPITCH + (c4 & 7) * 8, pl = c4 >> 3;
-                *reinterpret_cast<uint2*>(&Xs[0][pl][at]) = hi;
-                *reinterpret_cast<uint2*>(&Xs[1][pl][at]) = mid;
-                *reinterpret_cast<uint2*>(&Xs[2][pl][at]) = lo;
+                *reinterpret_cast<uint2*>(&Xs[0][pl][at]) = t.hi;
+                *reinterpret_cast<uint2*>(&Xs[1][pl][at]) = t.mid;
+                *reinterpret_cast<uint2*>(&Xs[2][pl][at]) = t.lo;
             }
         }
     };
@@ -365,25 +337,25 @@ __global__ __launch_bounds__(256, 2) void igemm_x3w_kernel(const WghParams p) {
     // 41-44 % matrix-pipe busy).  Software-pipelined by hand as in igemm_x3h: the NEXT unit's fragments are read right after this
     // unit's first MFMA is issued and pinned there (sched_barrier), so five MFMAs (160 cycles) cover their latency; the second
     // k-step's gy fragments ride along with the first unit.
-    auto read_a = [&](int ks, x3w_bf16x8 (&a)[3]) {
+    auto read_a = [&](int ks, bf16x8 (&a)[3]) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) a[c] = w_tr_pair(&As[c][wm][a_tr[0] + ks * 16 * 64], &As[c][wm][a_tr[1] + ks * 16 * 64]);
     };
-    auto read_b = [&](int ks, int s, x3w_bf16x8 (&b)[3]) {
+    auto read_b = [&](int ks, int s, bf16x8 (&b)[3]) {
 #pragma unroll
         for (int c = 0; c < 3; ++c)
             b[c] = w_tr_pair(&Xs[c][wn][b_tr[0] + ks * KS_STEP + s * XPITCH], &Xs[c][wn][b_tr[1] + ks * KS_STEP + s * XPITCH]);
     };
     auto mma_stage = [&]() {
-        x3w_bf16x8 a0[3], a1[3], b0[3], b1[3];
+        bf16x8 a0[3], a1[3], b0[3], b1[3];
         read_a(0, a0);
         read_b(0, 0, b0);
 #pragma unroll
         for (int i = 0; i < 2 * S; ++i) {
             const int ks = i / S, s = i - ks * S;
-            x3w_bf16x8 (&a)[3] = ks ? a1 : a0;
-            x3w_bf16x8 (&b)[3] = (i & 1) ? b1 : b0;
-            x3w_bf16x8 (&bn)[3] = (i & 1) ? b0 : b1;
+            bf16x8 (&a)[3] = ks ? a1 : a0;
+            bf16x8 (&b)[3] = (i & 1) ? b1 : b0;
+            bf16x8 (&bn)[3] = (i & 1) ? b0 : b1;
             f32x16 t = acc[s];                       // smallest terms first
             t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], t, 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
@@ -452,8 +424,8 @@ __global__ __launch_bounds__(256, 2) void igemm_x3w_kernel(const WghParams p) {
 
 // Shapes the three-piece form takes: what igemm_wgh takes with 5 filter columns, both tensors below 4 GB (32-bit buffer offsets).
 bool x3w_eligible(const cslgan_conv_t* c, int out_bf16, const void* gy, const void* x) {
-    return wgh_eligible(c, out_bf16, gy, x) && c->S == 5 && 4ll * c->N * c->P * c->Q * c->K < 0xFFFFFFF0ll &&
-           4ll * c->N * c->H * c->W * c->C < 0xFFFFFFF0ll;
+    return wgh_eligible(c, out_bf16, gy, x) && c->S == 5 && 4ll * c->N * c->P * c->Q * c->K < (long long)BUF_OOB &&
+           4ll * c->N * c->H * c->W * c->C < (long long)BUF_OOB;
 }
 
 // The 4x4-output form (the critic's last conv): stride 2, 5 filter columns, pad 2, 8x8 input, channel counts multiples of 64, an even
@@ -461,10 +433,9 @@ bool x3w_eligible(const cslgan_conv_t* c, int out_bf16, const void* gy, const vo
 bool x3w_quad_eligible(const cslgan_conv_t* c, int group, int out_bf16, const void* gy, const void* x) {
     return !out_bf16 && c->stride == 2 && c->S == 5 && c->R <= 5 && c->P == 4 && c->Q == 4 && c->H == 8 && c->W == 8 && c->pad == 2 &&
            c->K % 64 == 0 && c->C % WG_BC == 0 && group % 2 == 0 && aligned16(gy) && aligned16(x) &&
-           4ll * c->N * 16 * c->K < 0xFFFFFFF0ll && 4ll * c->N * 64 * c->C < 0xFFFFFFF0ll;
+           4ll * c->N * 16 * c->K < (long long)BUF_OOB && 4ll * c->N * 64 * c->C < (long long)BUF_OOB;
 }
 
-int sqnorm_rows_accumulate(const float* in, long long n_rows, long long len, float* sq_accum, hipStream_t st);   // clip_kernels.hip
 
 // Shapes this kernel takes (the rest stays on igemm_mc).
 bool wgh_eligible(const cslgan_conv_t* c, int out_bf16, const void* gy, const void* x) {

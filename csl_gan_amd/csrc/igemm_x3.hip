@@ -33,20 +33,14 @@
 // Replaces (reference file:line): nn.Conv2d forward and its autograd data gradient, DCResNet_models.py:16,60-70,95-104,
 // 131-132; gradient_penalty.py:48-54 (the double backward runs the same two ops).
 #include "common.h"
+#include "device_prims.h"
 #include "igemm.h"
 #include "conv_classes.h"
 
 namespace cslgan {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
-constexpr unsigned XOOB = 0xFFFFFFF0u;
 constexpr unsigned XFAR = 0xFFFF0000u;  // an out-of-range byte offset that STAYS out of range when a chunk / step offset (< 64 KB) is added to it
 constexpr int XH_MAX = 160;            // pixels of a patch's LDS image: 12 rows x 12 (8+4 squared: up to 5x5 taps), or four 6x6 halos at a
                                        // pitch of 40 (quad patches)
@@ -55,26 +49,6 @@ constexpr int XH_MAX = 160;            // pixels of a patch's LDS image: 12 rows
 // apart) keep their 16-byte reads on distinct banks.  A 3x3-tap class (halo 10 wide) indexed with ITS width ran 2-way conflicted on
 // half the reads (rocprofv3: SQ_LDS_BANK_CONFLICT = 45 % of SQ_LDS_IDX_ACTIVE on the critic's launches, 0 on the generator's 12-wide halos).
 constexpr int XROW = 12, XQROW = 6, XQIMG = 40;
-
-__device__ __forceinline__ unsigned xpack(float lo, float hi) {      // v_cvt_pk_bf16_f32: RNE, lo in bits 0..15
-    const f32x2 v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ float xlo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float xhi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
-struct x3_t { uint2 hi, mid, lo; };
-__device__ __forceinline__ x3_t xsplit4(const float4& v) {
-    x3_t r;
-    r.hi = make_uint2(xpack(v.x, v.y), xpack(v.z, v.w));
-    const float r0 = v.x - xlo(r.hi.x), r1 = v.y - xhi(r.hi.x), r2 = v.z - xlo(r.hi.y), r3 = v.w - xhi(r.hi.y);   // exact
-    r.mid = make_uint2(xpack(r0, r1), xpack(r2, r3));
-    r.lo = make_uint2(xpack(r0 - xlo(r.mid.x), r1 - xhi(r.mid.x)), xpack(r2 - xlo(r.mid.y), r3 - xhi(r.mid.y)));
-    return r;
-}
-__device__ __forceinline__ float4 xload4(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, 0, 0);
-    return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-}
 
 }  // namespace
 
@@ -113,7 +87,7 @@ __global__ __launch_bounds__(256, 2) void igemm_x3h_kernel(const KcParams p) {
     const int r = lane & 31, h = lane >> 5;
     const int wm = wid >> 1, wn = wid & 1;                     // wm = patch index
     const int n0 = tile_n * BN;
-    const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.a), 0, p.a_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t a_rsrc = make_rsrc(p.a, p.a_bytes);
 
     f32x16 acc[TM][TN];
 #pragma unroll 1
@@ -202,15 +176,15 @@ __global__ __launch_bounds__(256, 2) void igemm_x3h_kernel(const KcParams p) {
         float4 sc0, sc1, sh0, sh1;
         // buffer descriptors made once: with plain pointers the compiler re-read p.in_scale / p.in_shift from the kernel arguments
         // inside the loop (s_load: lgkmcnt) and every such read drained the LDS fragment reads in flight (+10 % kernel time)
-        const __amdgpu_buffer_rsrc_t sc_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(AFF ? p.in_scale : p.a), 0, 0xFFFFFFF0u, 0x00020000);
-        const __amdgpu_buffer_rsrc_t sh_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(AFF ? p.in_shift : p.a), 0, 0xFFFFFFF0u, 0x00020000);
+        const __amdgpu_buffer_rsrc_t sc_rsrc = make_rsrc(AFF ? p.in_scale : p.a, BUF_OOB);
+        const __amdgpu_buffer_rsrc_t sh_rsrc = make_rsrc(AFF ? p.in_shift : p.a, BUF_OOB);
         auto fetch_halo = [&](int cc) {
             const unsigned co = 64u * (unsigned)(cc + cc_lo);  // 16 channels x 4 B per chunk
 #pragma unroll
-            for (int j = 0; j < HREG; ++j) rh[j] = xload4(a_rsrc, h_goff[j] + co);      // an invalid element sits at XFAR: + co (< 64 KB) stays out of range
+            for (int j = 0; j < HREG; ++j) rh[j] = buf_load4(a_rsrc, h_goff[j] + co);      // an invalid element sits at XFAR: + co (< 64 KB) stays out of range
             if (AFF) {
-                sc0 = xload4(sc_rsrc, 4u * (unsigned)aff_off[0] + co); sh0 = xload4(sh_rsrc, 4u * (unsigned)aff_off[0] + co);
-                sc1 = xload4(sc_rsrc, 4u * (unsigned)aff_off[1] + co); sh1 = xload4(sh_rsrc, 4u * (unsigned)aff_off[1] + co);
+                sc0 = buf_load4(sc_rsrc, 4u * (unsigned)aff_off[0] + co); sh0 = buf_load4(sh_rsrc, 4u * (unsigned)aff_off[0] + co);
+                sc1 = buf_load4(sc_rsrc, 4u * (unsigned)aff_off[1] + co); sh1 = buf_load4(sh_rsrc, 4u * (unsigned)aff_off[1] + co);
             }
         };
         auto commit_halo = [&](int buf) {
@@ -231,9 +205,9 @@ __global__ __launch_bounds__(256, 2) void igemm_x3h_kernel(const KcParams p) {
                     if (F32) {
                         Hs[buf][0][h_lds[j]] = make_uint4(__float_as_uint(rh[j].x), __float_as_uint(rh[j].y), __float_as_uint(rh[j].z), __float_as_uint(rh[j].w));
                     } else if (NP == 1) {
-                        img0[h_lds[j]] = make_uint2(xpack(rh[j].x, rh[j].y), xpack(rh[j].z, rh[j].w));
+                        img0[h_lds[j]] = make_uint2(pack_bf16(rh[j].x, rh[j].y), pack_bf16(rh[j].z, rh[j].w));
                     } else {
-                        const x3_t t3 = xsplit4(rh[j]);
+                        const bf16x3_t t3 = split4_bf16(rh[j]);
                         img0[h_lds[j]] = t3.hi;
                         reinterpret_cast<uint2*>(&Hs[buf][NI > 1 ? 1 : 0][0])[h_lds[j]] = t3.mid;
                         reinterpret_cast<uint2*>(&Hs[buf][NI > 2 ? 2 : 0][0])[h_lds[j]] = t3.lo;
@@ -248,29 +222,28 @@ __global__ __launch_bounds__(256, 2) void igemm_x3h_kernel(const KcParams p) {
         // wave-load touches are 1 KB contiguous.
         // fp32 (NP = 0): ONE step-major fp32 copy [step][n][16 floats]; operand e of lane (r, h) = channels 8e + 4h .. + 3 of filter row n.
         const unsigned piece_bytes = F32 ? 32u : 2u * (unsigned)p.Nn * (unsigned)kc.Kdim;     // distance between a tile's operand registers
-        const __amdgpu_buffer_rsrc_t w3_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<char*>(reinterpret_cast<const char*>(p.w3) + (F32 ? 4ll : 2ll * NP) * kc.w_off), 0,
-            F32 ? 4u * (unsigned)p.Nn * (unsigned)kc.Kdim : NP * piece_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t w3_rsrc = make_rsrc(reinterpret_cast<const char*>(p.w3) + (F32 ? 4ll : 2ll * NP) * kc.w_off,
+                                                           F32 ? 4u * (unsigned)p.Nn * (unsigned)kc.Kdim : NP * piece_bytes);
         const unsigned n_bytes = F32 ? 64u : 32u;                 // bytes of one filter row in a step's slice
         const unsigned step_bytes = n_bytes * (unsigned)p.Nn;
         unsigned b_off[TN];
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             const int n = n0 + wn * TN * 32 + j * 32 + r;
-            b_off[j] = n < p.Nn ? n_bytes * (unsigned)n + 16u * (unsigned)h : XOOB;       // tested again in load_b
+            b_off[j] = n < p.Nn ? n_bytes * (unsigned)n + 16u * (unsigned)h : BUF_OOB;       // tested again in load_b
         }
         const int n_steps = n_cc * T;
         const unsigned step0_bytes = (unsigned)(cc_lo * T) * step_bytes;
         u32x4 B0[NO][TN], B1[NO][TN];                          // two-slot ring of filter slices: slot s % 2 is refilled with step s + 2
         auto load_b = [&](int step, u32x4 (&dst)[NO][TN]) {    // right after the MFMAs of step s have read it (no third slot, no copies)
             const unsigned kb = (unsigned)step * step_bytes + step0_bytes;
-            const unsigned past = step >= n_steps ? XOOB : 0u;
+            const unsigned past = step >= n_steps ? BUF_OOB : 0u;
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
-                const unsigned bad = past | (b_off[j] == XOOB ? XOOB : 0u);
+                const unsigned bad = past | (b_off[j] == BUF_OOB ? BUF_OOB : 0u);
 #pragma unroll
                 for (int c = 0; c < NO; ++c)
-                    dst[c][j] = __builtin_amdgcn_raw_buffer_load_b128(w3_rsrc, (int)((b_off[j] + kb + c * piece_bytes) | bad), 0, 0);
+                    dst[c][j] = buf_load4_raw(w3_rsrc, ((b_off[j] + kb + c * piece_bytes) | bad));
             }
         };
 
@@ -460,19 +433,10 @@ __global__ __launch_bounds__(256, 2) void igemm_x3h_kernel(const KcParams p) {
                         g2[j][q].x = fmaf(d.x, d.x, g2[j][q].x); g2[j][q].y = fmaf(d.y, d.y, g2[j][q].y);
                         g2[j][q].z = fmaf(d.z, d.z, g2[j][q].z); g2[j][q].w = fmaf(d.w, d.w, g2[j][q].w);
                     }
-                    if (p.act == CSLGAN_ACT_LRELU02) {
-                        val.x = val.x > 0.f ? val.x : 0.2f * val.x; val.y = val.y > 0.f ? val.y : 0.2f * val.y;
-                        val.z = val.z > 0.f ? val.z : 0.2f * val.z; val.w = val.w > 0.f ? val.w : 0.2f * val.w;
-                    } else if (p.act == CSLGAN_ACT_RELU) {
-                        val.x = val.x > 0.f ? val.x : 0.f; val.y = val.y > 0.f ? val.y : 0.f;
-                        val.z = val.z > 0.f ? val.z : 0.f; val.w = val.w > 0.f ? val.w : 0.f;
-                    } else if (p.act == CSLGAN_ACT_TANH) {
-                        val.x = tanhf(val.x); val.y = tanhf(val.y); val.z = tanhf(val.z); val.w = tanhf(val.w);
-                    }
+                    apply_act4(val, p.act);
                     if (p.mask) {
                         const float4 mv = *reinterpret_cast<const float4*>(p.mask + off + n);
-                        val.x *= mv.x > 0.f ? 1.f : 0.2f; val.y *= mv.y > 0.f ? 1.f : 0.2f;
-                        val.z *= mv.z > 0.f ? 1.f : 0.2f; val.w *= mv.w > 0.f ? 1.f : 0.2f;
+                        val.x = lrelu_mask(val.x, mv.x); val.y = lrelu_mask(val.y, mv.y); val.z = lrelu_mask(val.z, mv.z); val.w = lrelu_mask(val.w, mv.w);
                     }
                     *reinterpret_cast<float4*>(p.out + off + n) = val;
                 }
@@ -571,16 +535,10 @@ __global__ __launch_bounds__(256) void x3h_split_reduce_kernel(const float* __re
             const float4 bv = *reinterpret_cast<const float4*>(bias + (int)((i << 2) % Nn));
             v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
         }
-        if (act == CSLGAN_ACT_LRELU02) {
-            v.x = v.x > 0.f ? v.x : 0.2f * v.x; v.y = v.y > 0.f ? v.y : 0.2f * v.y; v.z = v.z > 0.f ? v.z : 0.2f * v.z; v.w = v.w > 0.f ? v.w : 0.2f * v.w;
-        } else if (act == CSLGAN_ACT_RELU) {
-            v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f; v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
-        } else if (act == CSLGAN_ACT_TANH) {
-            v.x = tanhf(v.x); v.y = tanhf(v.y); v.z = tanhf(v.z); v.w = tanhf(v.w);
-        }
+        apply_act4(v, act);
         if (mask) {
             const float4 mv = reinterpret_cast<const float4*>(mask)[i];
-            v.x *= mv.x > 0.f ? 1.f : 0.2f; v.y *= mv.y > 0.f ? 1.f : 0.2f; v.z *= mv.z > 0.f ? 1.f : 0.2f; v.w *= mv.w > 0.f ? 1.f : 0.2f;
+            v.x = lrelu_mask(v.x, mv.x); v.y = lrelu_mask(v.y, mv.y); v.z = lrelu_mask(v.z, mv.z); v.w = lrelu_mask(v.w, mv.w);
         }
         reinterpret_cast<float4*>(out)[i] = v;
     }
@@ -602,7 +560,7 @@ __global__ void split_filter_x3_kernel(const float* __restrict__ w, int Nn, int 
             *reinterpret_cast<float4*>(reinterpret_cast<float*>(w3) + dst) = reinterpret_cast<const float4*>(w)[i];
             continue;
         }
-        const x3_t s3 = xsplit4(reinterpret_cast<const float4*>(w)[i]);
+        const bf16x3_t s3 = split4_bf16(reinterpret_cast<const float4*>(w)[i]);
         *reinterpret_cast<uint2*>(w3 + dst) = s3.hi;           // = the round-to-nearest-even bfloat16 of w: all the NP = 1 form needs
         if (NP == 3) {
             *reinterpret_cast<uint2*>(w3 + n_el + dst) = s3.mid;

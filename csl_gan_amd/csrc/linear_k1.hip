@@ -2,6 +2,7 @@
 // plain streams.  As an implicit GEMM with N = 1 they ran on a 128x32 MFMA tile that is 31/32 padding (14-29 us per launch for
 // 4-13 MB); here a workgroup takes one row: y[n] = act(<x[n,:], w> + b) and gx[n,:] = gy[n] * w (* lrelu'(mask)).  gfx950 only.
 #include "common.h"
+#include "device_prims.h"
 #include "igemm.h"
 
 namespace cslgan {
@@ -20,9 +21,7 @@ __global__ __launch_bounds__(256) void linear_k1_fwd_kernel(const float* __restr
     const float tot = block_sum_256(acc, s_red);
     if (threadIdx.x == 0) {
         float val = tot + (bias ? bias[0] : 0.f) + (res ? res[n] : 0.f);
-        if (act == CSLGAN_ACT_LRELU02) val = val > 0.f ? val : 0.2f * val;
-        else if (act == CSLGAN_ACT_RELU) val = val > 0.f ? val : 0.f;
-        else if (act == CSLGAN_ACT_TANH) val = tanhf(val);
+        val = apply_act(val, act);
         y[n] = val;
     }
 }
@@ -37,7 +36,7 @@ __global__ __launch_bounds__(256) void linear_k1_dgrad_kernel(const float* __res
     float4 o = make_float4(g * b.x, g * b.y, g * b.z, g * b.w);
     if (mask) {
         const float4 m = reinterpret_cast<const float4*>(mask + n * C4 * 4)[i];
-        o.x *= m.x > 0.f ? 1.f : 0.2f; o.y *= m.y > 0.f ? 1.f : 0.2f; o.z *= m.z > 0.f ? 1.f : 0.2f; o.w *= m.w > 0.f ? 1.f : 0.2f;
+        o.x = lrelu_mask(o.x, m.x); o.y = lrelu_mask(o.y, m.y); o.z = lrelu_mask(o.z, m.z); o.w = lrelu_mask(o.w, m.w);
     }
     reinterpret_cast<float4*>(gx + n * C4 * 4)[i] = o;
 }

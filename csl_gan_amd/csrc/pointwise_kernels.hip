@@ -3,6 +3,7 @@
 // Replaces (reference file:line): F.leaky_relu backward DCResNet_models.py:132 (autograd);
 // nn.GroupNorm + F.relu DCResNet_models.py:55-57,63-67,101-102; torch.optim.Adam.step train.py:76,484.
 #include "common.h"
+#include "device_prims.h"
 
 namespace cslgan {
 
@@ -49,16 +50,11 @@ constexpr int NS_ROWS_MIN = 64;   // rows per block, lower bound (the launch pic
 // statistics and arithmetic are fp32 either way, a bf16 output is rounded to nearest even).
 typedef unsigned short bf16_t;
 __device__ __forceinline__ float ldf(const float* p, long long i) { return p[i]; }
-__device__ __forceinline__ float ldf(const bf16_t* p, long long i) { return __uint_as_float((unsigned)p[i] << 16); }
+__device__ __forceinline__ float ldf(const bf16_t* p, long long i) { return bf2f(p[i]); }
 __device__ __forceinline__ float4 ld4(const float* p, long long i) { return *reinterpret_cast<const float4*>(p + i); }
 __device__ __forceinline__ float4 ld4(const bf16_t* p, long long i) {
     const uint2 v = *reinterpret_cast<const uint2*>(p + i);
-    return make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u), __uint_as_float(v.y << 16), __uint_as_float(v.y & 0xffff0000u));
-}
-__device__ __forceinline__ unsigned rne_bf16(float f) {
-    unsigned u = __float_as_uint(f);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return u >> 16;
+    return make_float4(bf_lo(v.x), bf_hi(v.x), bf_lo(v.y), bf_hi(v.y));
 }
 __device__ __forceinline__ void st1(float* p, long long i, float v) { p[i] = v; }
 __device__ __forceinline__ void st1(bf16_t* p, long long i, float v) { p[i] = (bf16_t)rne_bf16(v); }

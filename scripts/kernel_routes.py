@@ -7,6 +7,8 @@ tests/test_kernel_routes_gpu.py asserts them, so a refactor of the dispatch laye
     python scripts/kernel_routes.py                 # name per case
     python scripts/kernel_routes.py --checksum      # ... and a hash of the output bytes (cases that accumulate with float atomics
                                                     #     differ between two runs of the same build: compare those by name only)
+    python scripts/kernel_routes.py --checksum --epilogue   # the same launches with a bias and an activation (forward) or a mask
+                                                    #     (data gradient), so the hashes cover every routed kernel's epilogue
     python scripts/kernel_routes.py --record tests/kernel_routes.json
 
 Only public entry points are used (ops.conv2d_fwd / conv2d_dgrad / conv2d_wgrad_grouped / conv2d_wgrad_sqnorm_gram, ops.compute_dtype,
@@ -130,8 +132,12 @@ CASES = {
 }
 
 
-def run_case(case, seed=0):
-    """Launch one case; returns (kernel name, output tensor)."""
+def run_case(case, seed=0, epilogue=False, act=None):
+    """Launch one case; returns (kernel name, output tensor).
+
+    epilogue: forward cases also pass a random bias and the activation `act` (main() passes 1 + case index % 3, so the three
+    activations alternate over the cases; default 1 + seed % 3); data-gradient cases pass a random mask.  No residual: it changes routes (and an
+    activation keeps K from being split, so those launches hash reproducibly)."""
     import torch
     from csl_gan_amd import _lib, ops
 
@@ -150,9 +156,11 @@ def run_case(case, seed=0):
             P, Q = ops.conv_out_size(H, R, stride, pad), ops.conv_out_size(W, R, stride, pad)
             w = torch.randn(K, R, R, Cc, generator=g).cuda() * 0.1
             if op == "fwd":
-                out = ops.conv2d_fwd(rnd(N, H, W, Cc), w, stride=stride, pad=pad)
+                extra = dict(bias=torch.randn(K, generator=g).cuda(), act=1 + seed % 3 if act is None else act) if epilogue else {}
+                out = ops.conv2d_fwd(rnd(N, H, W, Cc), w, stride=stride, pad=pad, **extra)
             elif op == "dgrad":
-                out = ops.conv2d_dgrad(rnd(N, P, Q, K), w, (H, W), stride=stride, pad=pad)
+                extra = dict(mask=rnd(N, H, W, Cc)) if epilogue else {}
+                out = ops.conv2d_dgrad(rnd(N, P, Q, K), w, (H, W), stride=stride, pad=pad, **extra)
             elif op == "wgrad":
                 out = ops.conv2d_wgrad_grouped(rnd(N, P, Q, K), rnd(N, H, W, Cc), R, R, stride=stride, pad=pad, group=case["group"])
             elif op == "gram":
@@ -175,11 +183,12 @@ def checksum(t):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--checksum", action="store_true", help="also print a hash of each case's output bytes")
+    ap.add_argument("--epilogue", action="store_true", help="forward cases with a bias and an activation, data-gradient cases with a mask")
     ap.add_argument("--record", metavar="JSON", help="write {case: kernel name} to this file")
     a = ap.parse_args()
     names = {}
     for i, (key, case) in enumerate(CASES.items()):
-        name, out = run_case(case, seed=i)
+        name, out = run_case(case, seed=i, epilogue=a.epilogue, act=1 + i % 3)
         names[key] = name
         print("%-24s %-44s %s" % (key, name, checksum(out) if a.checksum else ""), flush=True)
     if a.record:
