@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CSLGAN_LIB_PATH") or os.path.join(_HERE, "libcslgan_hip.so")      # override: kernel experiments
 MAX_SEGS = 16
-ABI_VERSION = 6          # include/cslgan.h CSLGAN_ABI_VERSION
+ABI_VERSION = 7          # include/cslgan.h CSLGAN_ABI_VERSION
 
 EXPORTS = [
     "cslgan_version", "cslgan_last_error", "cslgan_last_kernel", "cslgan_device_count",
@@ -31,6 +31,7 @@ EXPORTS = [
     "cslgan_act_bwd_bf16", "cslgan_bias_grad_grouped_bf16", "cslgan_linear_k1_dgrad_bf16s", "cslgan_linear_k1_wgrad_bf16s",
     "cslgan_conv2d_c3_fwd_bf16out", "cslgan_conv2d_c3_wgrad_bf16gy", "cslgan_groupnorm_act_bf16s",
     "cslgan_conv2d_fwd_skinny_bf16in", "cslgan_conv2d_dgrad_skinny_bf16in", "cslgan_conv2d_wgrad_scaled_bf16s",
+    "cslgan_latent_normal_f32", "cslgan_f32_to_u8",
 ]
 
 
@@ -145,6 +146,8 @@ def lib():
         "cslgan_groupnorm_act_bf16s": [vp, i32, vp, vp, i32, i32, i32, i32, f32, i32, vp, vp, i32, vp, vp],
         "cslgan_conv2d_fwd_skinny_bf16in": [C.POINTER(ConvT), vp, vp, vp, i32, vp, vp],
         "cslgan_conv2d_dgrad_skinny_bf16in": [C.POINTER(ConvT), vp, vp, vp, i32, vp, vp],
+        "cslgan_latent_normal_f32": [u64, u64, vp, i64, i32, vp, i32, i32, vp, vp],
+        "cslgan_f32_to_u8": [vp, i64, f32, f32, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

@@ -218,6 +218,38 @@ __global__ __launch_bounds__(256) void mean_sample_kernel(const float* __restric
     }
 }
 
+// ---- indexed latent stream (gensamples.py:36: the generator's z, here a function of (seed, sample index) alone) ----------------
+//   row i is sample g = first + *first_dev + i;  counter (q, g lo, g hi, 0x7A6C6174) -> columns 4q .. 4q+3 of the row
+// One thread per counter: the four normals are made the same way whatever the row length or the alignment of z, so a row's bits do
+// not depend on which launch (batch size, index split, chunk) drew it; only the stores differ.  labels (nullable): the fixed
+// label or g mod n_classes, written by the thread of q == 0.
+constexpr uint32_t LATENT_COUNTER_TAG = 0x7A6C6174u;
+__global__ __launch_bounds__(256) void latent_normal_kernel(unsigned long long key, unsigned long long first,
+                                                            const unsigned long long* __restrict__ first_dev, long long n, int dim, int nq,
+                                                            float* __restrict__ z, int vec, int n_classes, int fixed_label,
+                                                            long long* __restrict__ labels) {
+    if (first_dev) first += *first_dev;
+    const long long total = n * nq;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
+        const long long i = t / nq;
+        const int q = (int)(t - i * nq);
+        const unsigned long long g = first + (unsigned long long)i;
+        uint32_t rnd[4];
+        philox4x32_10((uint32_t)q, (uint32_t)g, (uint32_t)(g >> 32), LATENT_COUNTER_TAG, (uint32_t)key, (uint32_t)(key >> 32), rnd);
+        float v[4];
+        box_muller(rnd[0], rnd[1], v[0], v[1]);
+        box_muller(rnd[2], rnd[3], v[2], v[3]);
+        float* __restrict__ o = z + i * dim + 4 * q;
+        if (vec) {                                       // dim % 4 == 0 and z 16-byte aligned: every counter is a whole float4
+            *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+            for (int k = 0; k < 4; ++k)
+                if (4 * q + k < dim) o[k] = v[k];
+        }
+        if (labels && q == 0) labels[i] = fixed_label >= 0 ? (long long)fixed_label : (long long)(g % (unsigned long long)n_classes);
+    }
+}
+
 constexpr int CA_THREADS = 256;
 constexpr int CA_COLS = CA_THREADS * 4;  // columns per block
 
@@ -520,6 +552,23 @@ int cslgan_mean_sample_f32(const float* mean_samples, int n_classes, int num_sam
                        (long long)len, noise_mean_std, noise_std, (unsigned long long)seed, (unsigned long long)offset, out,
                        reinterpret_cast<long long*>(labels_out));
     return check_launch("mean_sample_kernel");
+}
+
+int cslgan_latent_normal_f32(uint64_t seed, uint64_t first_index, const unsigned long long* first_index_dev, int64_t n, int dim, float* z,
+                             int n_classes, int fixed_label, int64_t* labels, void* stream) {
+    CSLGAN_REQUIRE(z, "latent_normal: null argument");
+    CSLGAN_REQUIRE(n > 0 && n <= (1ll << 32), "latent_normal: n=%lld out of range", (long long)n);
+    CSLGAN_REQUIRE(dim > 0 && dim <= (1 << 24), "latent_normal: dim=%d out of range", dim);
+    CSLGAN_REQUIRE(n_classes >= 1, "latent_normal: n_classes=%d must be at least 1", n_classes);
+    CSLGAN_REQUIRE(fixed_label < n_classes, "latent_normal: fixed_label=%d is no class of %d", fixed_label, n_classes);
+    const int nq = (dim + 3) / 4;
+    const long long blocks = ((long long)n * nq + 255) / 256;
+    const int vec = (dim % 4 == 0 && aligned16(z)) ? 1 : 0;
+    note_kernel("latent_normal_kernel");
+    hipLaunchKernelGGL(latent_normal_kernel, dim3((unsigned)(blocks > 65536 ? 65536 : blocks)), dim3(256), 0, (hipStream_t)stream,
+                       (unsigned long long)(seed ^ 0x6C6174656E747A73ull), (unsigned long long)first_index, first_index_dev, (long long)n, dim, nq,
+                       z, vec, n_classes, fixed_label, reinterpret_cast<long long*>(labels));
+    return check_launch("latent_normal_kernel");
 }
 
 int cslgan_row_l2norm_f32(const float* in, int64_t n_rows, int64_t len, float* out_norm, void* stream) {

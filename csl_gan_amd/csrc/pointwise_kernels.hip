@@ -813,6 +813,48 @@ int cslgan_u8_to_f32_nhwc(const void* src_u8, const void* flip_u8, int N, int H,
     return check_launch("u8_to_f32_nhwc_kernel");
 }
 
+// ---- the inverse: fp32 images -> uint8 rows of the cache (util.denorm_celeba + util.save_image's quantisation, elementwise) -----------
+//   t = clamp(src * scale + bias, 0, 1);  dst = (uint8) clamp(t * 255 + 0.5, 0, 255)        truncation; NaN -> 0
+// Bit-identical to the host's fp32 expression: every product and sum is rounded on its own (no contraction into an fma, which
+// would skip the product's rounding and can move a value across a (k + 0.5) / 255 boundary), in the host's order.
+__device__ __forceinline__ unsigned quantise_u8(float x, float scale, float bias) {
+#pragma clang fp contract(off)
+    float t = x * scale;
+    t = t + bias;
+    t = fminf(fmaxf(t, 0.f), 1.f);               // fmaxf(NaN, 0) = 0
+    float u = t * 255.f;
+    u = u + 0.5f;
+    u = fminf(fmaxf(u, 0.f), 255.f);
+    return (unsigned)u;
+}
+
+// vec: src 16-byte and dst 4-byte aligned — one float4 load and one packed 4-byte store per thread and step; the n % 4 tail and
+// misaligned slices go element by element.
+__global__ __launch_bounds__(256) void f32_to_u8_kernel(const float* __restrict__ src, long long n, float scale, float bias,
+                                                        unsigned char* __restrict__ dst, int vec) {
+    const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long long)gridDim.x * blockDim.x;
+    long long done = 0;
+    if (vec) {
+        const long long n4 = n >> 2;
+        for (long long i = tid; i < n4; i += nth) {
+            const float4 v = reinterpret_cast<const float4*>(src)[i];
+            reinterpret_cast<unsigned*>(dst)[i] = quantise_u8(v.x, scale, bias) | (quantise_u8(v.y, scale, bias) << 8) |
+                                                  (quantise_u8(v.z, scale, bias) << 16) | (quantise_u8(v.w, scale, bias) << 24);
+        }
+        done = n4 << 2;
+    }
+    for (long long i = done + tid; i < n; i += nth) dst[i] = (unsigned char)quantise_u8(src[i], scale, bias);
+}
+
+int cslgan_f32_to_u8(const float* src, int64_t n, float scale, float bias, void* dst_u8, void* stream) {
+    CSLGAN_REQUIRE(src && dst_u8, "f32_to_u8: null argument");
+    CSLGAN_REQUIRE(n > 0, "f32_to_u8: n=%lld must be positive", (long long)n);
+    const int vec = (aligned16(src) && (reinterpret_cast<uintptr_t>(dst_u8) & 3u) == 0) ? 1 : 0;
+    hipLaunchKernelGGL(f32_to_u8_kernel, dim3(grid_for(n, vec ? 4 : 1)), dim3(256), 0, (hipStream_t)stream, src, (long long)n, scale, bias,
+                       reinterpret_cast<unsigned char*>(dst_u8), vec);
+    return check_launch("f32_to_u8_kernel");
+}
+
 int cslgan_depth_to_space_f32(const float* x, int N, int H, int W, int C, int inverse, float* y, void* stream) {
     CSLGAN_REQUIRE(x && y, "depth_to_space: null argument");
     CSLGAN_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "depth_to_space: needs C %% 4 == 0 (C=%d)", C);

@@ -46,6 +46,12 @@ def _private_loader(ds, opt, rank, world, **kw):
     return DataLoader(ds, batch_size=opt.batch_size, sampler=sampler, drop_last=True, **kw)
 
 
+def is_image_cache(path):
+    """True when `path` names a finished cache of csl_gan_amd.pipeline (path.u8 / .labels.npy / .json) itself."""
+    from . import pipeline as pl
+    return bool(path) and all(os.path.exists(p) for p in pl.cache_paths(path))
+
+
 def init_cached_data(opt, rank=0, world=1):
     """The real files through the preprocessed-tensor cache and the device prefetcher (csl_gan_amd/pipeline.py; `--data_cache PATH`):
     the cache is built once from the same dataset classes (flip off — the flip is drawn per batch on the host and applied by the
@@ -63,7 +69,16 @@ def init_cached_data(opt, rank=0, world=1):
                 torch.distributed.barrier()
         return pl.CachedImages(path)
 
-    if opt.dataset == "MNIST":
+    if is_image_cache(opt.data_cache):
+        # PATH itself is a finished cache (csl_gan_amd.gensamples --cache PATH: a synthetic dataset): read as it is, no files needed
+        data, pub = pl.CachedImages(opt.data_cache), None
+        want = (28, 28, 1) if opt.dataset == "MNIST" else (opt.im_size, opt.im_size, 3)
+        if (data.H, data.W, data.C) != want:
+            raise RuntimeError("image cache %s holds %dx%dx%d images, the run needs %dx%dx%d" % ((opt.data_cache, data.H, data.W, data.C) + want))
+        if opt.public_set_size > 0:
+            raise RuntimeError("a ready-made image cache has no public partition (--public_set_size 0, or mean samples)")
+        flip = opt.dataset != "MNIST"
+    elif opt.dataset == "MNIST":
         tr = ds.MNISTDataset(opt.data_path, train=True, per_class=opt.train_set_size // 10)
         data = pl.CachedImages.from_arrays((tr.x.squeeze(1).numpy() * 255.0).round().astype("uint8")[..., None], tr.y.numpy(), signed=False)
         pub = None
@@ -110,6 +125,8 @@ def init_data(opt, rank=0, world=1):
     init_util.init_data: same return tuple, shuffle=True loaders (rank-partitioned under --dist, see _private_loader)."""
     if not getattr(opt, "synthetic", False) and opt.data_path and os.path.isdir(opt.data_path):
         return init_real_data(opt, rank, world)
+    if not getattr(opt, "synthetic", False) and is_image_cache(getattr(opt, "data_cache", None)):
+        return init_cached_data(opt, rank, world)           # a ready-made cache needs no --data_path
     n = min(opt.train_set_size, getattr(opt, "synthetic_cap", 4096))
     ds = SyntheticImages(opt.dataset, n, opt.im_size, seed=opt.manual_seed)
     pub = SyntheticImages(opt.dataset, min(opt.public_set_size, 2048), opt.im_size, seed=opt.manual_seed, offset=1) \

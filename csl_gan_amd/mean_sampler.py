@@ -39,7 +39,8 @@ class MeanSampler:
             for c in range(self.n_classes):
                 pick = samples if self.n_classes == 1 else samples[labels == c][: self.mean_size]
                 mean = pick.sum(dim=0) / self.mean_size          # divides by mean_size even if fewer were found
-                per_class[c].append(mean + torch.empty(mean.shape).normal_(0, self.noise_std))
+                # (the noise is drawn on the host either way; a device prefetcher's batches — --data_cache — get it moved over)
+                per_class[c].append(mean + torch.empty(mean.shape).normal_(0, self.noise_std).to(mean.device))
         self.mean_samples = torch.stack([torch.stack(v) for v in per_class]).to(self.device)
         if save_path is not None:
             save_path = util.add_slash(save_path)

@@ -1393,6 +1393,41 @@ def mean_sample(mean_samples, labels, perms, noise_mean_std, noise_std, seed, of
     return out
 
 
+def latent_normal(seed, first_index, n, dim, first_index_dev=None, n_classes=1, fixed_label=-1, want_labels=False, out=None, labels_out=None,
+                  device=None):
+    """The generator's latent rows of samples first_index + *first_index_dev + (0 .. n-1): [n, dim] unit normals of the indexed
+    stream of include/cslgan.h "Device random streams" (sample g is a function of (seed, g) alone).  first_index_dev: device int64
+    [1] added inside the kernel (a recorded graph draws new rows on every replay).  want_labels / labels_out: also the labels,
+    fixed_label when >= 0 else g mod n_classes.  out / labels_out: caller-owned destinations (static buffers of a recorded graph)."""
+    if out is None:
+        out = torch.empty((n, dim), device=device if device is not None else "cuda", dtype=torch.float32)
+    else:
+        _chk(out, "out")
+        if tuple(out.shape) != (n, dim):
+            raise RuntimeError("latent_normal: out is %s, expected %s" % (tuple(out.shape), (n, dim)))
+    if labels_out is None and want_labels:
+        labels_out = torch.empty(n, device=out.device, dtype=torch.int64)
+    if labels_out is not None and (labels_out.dtype != torch.int64 or not labels_out.is_cuda or labels_out.numel() != n or not labels_out.is_contiguous()):
+        raise RuntimeError("latent_normal: labels_out must be a contiguous int64 device tensor of %d entries" % n)
+    if first_index_dev is not None and (first_index_dev.dtype != torch.int64 or not first_index_dev.is_cuda or first_index_dev.numel() != 1):
+        raise RuntimeError("latent_normal: first_index_dev must be a device int64 tensor of one entry")
+    check(_lib.lib().cslgan_latent_normal_f32(int(seed) & (2 ** 64 - 1), int(first_index) & (2 ** 64 - 1), _p(first_index_dev), n, dim, _p(out),
+                                              int(n_classes), int(fixed_label), _p(labels_out), _stream()), "latent_normal")
+    return (out, labels_out) if (want_labels or labels_out is not None) else out
+
+
+def f32_to_u8(src, scale, bias, out=None):
+    """uint8 bytes of a dense fp32 device tensor in its memory order: clamp(src * scale + bias, 0, 1) * 255 + 0.5, truncated —
+    bit-identical to util.denorm_celeba + util.save_image's quantisation on the host ((0.5, 0.5); (1, 0) for [0, 1] images)."""
+    _chk_dense(src, "src")
+    if out is None:
+        out = torch.empty(src.numel(), device=src.device, dtype=torch.uint8)
+    elif out.dtype != torch.uint8 or not out.is_cuda or out.numel() != src.numel() or not out.is_contiguous():
+        raise RuntimeError("f32_to_u8: out must be a contiguous uint8 device tensor of %d entries" % src.numel())
+    check(_lib.lib().cslgan_f32_to_u8(_p(src), src.numel(), float(scale), float(bias), _p(out), _stream()), "f32_to_u8")
+    return out
+
+
 def row_l2norm(t2d):
     _chk(t2d, "t")
     n, L = t2d.shape

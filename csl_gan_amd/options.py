@@ -7,7 +7,9 @@ Additions of this build (all optional, none changes a reference default):
   --synthetic          use the synthetic in-memory dataset (the container has no MNIST/CelebA files)
   --data_cache PATH    real data through the preprocessed-tensor cache and the device prefetcher (csl_gan_amd/pipeline.py): the files
                        under --data_path are decoded / resized / cropped ONCE into PATH.*.u8 (uint8 NHWC memmap) and every batch is
-                       uploaded as bytes on a side stream and normalised + flipped by one kernel
+                       uploaded as bytes on a side stream and normalised + flipped by one kernel.  When PATH itself is a finished
+                       cache (PATH.u8 / PATH.labels.npy / PATH.json, e.g. the synthetic dataset `python -m csl_gan_amd.gensamples
+                       --cache PATH` writes) it is read as it is and no --data_path is needed; give its size as -tss
   --max_iters N        stop after N training iterations (smoke runs)
   --dist               one process per GPU under torch.distributed (RCCL); see csl_gan_amd/distributed.py
   --fuse_passes B      run the adaptive / generated / real discriminator passes as one forward+backward over the

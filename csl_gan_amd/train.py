@@ -78,7 +78,7 @@ def main(argv=None):
             json.dump(opt.__dict__, f)
 
     G, D = init_util.init_models(opt)
-    if not getattr(opt, "synthetic", False) and not os.path.isdir(opt.data_path or ""):
+    if not getattr(opt, "synthetic", False) and not os.path.isdir(opt.data_path or "") and not syn_data.is_image_cache(getattr(opt, "data_cache", None)):
         print("data_path %r not found: using the synthetic dataset (--synthetic)" % opt.data_path)
     dataset, dataloader, public_dataset, public_dataloader = syn_data.init_data(opt, rank, world)
     mean_sampler, mean_cost = build_mean_sampler(opt, dataset, rank, world)

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define CSLGAN_ABI_VERSION 6
+#define CSLGAN_ABI_VERSION 7
 
 typedef enum {
     CSLGAN_OK = 0,
@@ -109,6 +109,10 @@ int cslgan_clip_factors_f32(const float* sq, int n_seg, int64_t n_rows, const fl
  *   The mean sampler (cslgan_mean_sample_f32 below) draws from the same generator with counters that can coincide with
  *   these: the two are kept apart by their SEEDS alone (engine: manual_seed + 7919 * rank; sampler: the process seed xor
  *   0x6D65616E73616D70), as are ranks.
+ *   The indexed latent stream (cslgan_latent_normal_f32 below; ABI v7), sample g = first_index + *first_index_dev + i of row i:
+ *       key = the two halves of (seed xor 0x6C6174656E747A73),  counter = (q, g lo, g hi, 0x7A6C6174) -> columns 4q .. 4q+3 of row i
+ *   (words 0, 1 -> 4q, 4q+1; words 2, 3 -> 4q+2, 4q+3; a row's last counter is partly used when dim % 4 != 0).  It is kept apart from
+ *   the two streams above by its seed tag; inside it every (g, q) has a counter of its own for dim < 2^34.
  * Replaces privacy_engine.clip() + accum_grads_across_passes() (train.py:399-402) and, with
  * noise/scale, the engine-wrapped d_optimizer.step() noise + 1/B (train.py:484). */
 int cslgan_clip_accum_noise_f32(const cslgan_segs_t* segs, int64_t n_rows, const float* factors,
@@ -142,6 +146,16 @@ int cslgan_l2_clip_rows_f32(const float* in, float* out, int64_t n_rows, int64_t
 int cslgan_mean_sample_f32(const float* mean_samples, int n_classes, int num_samples, int64_t len, const int64_t* labels,
                            const int64_t* perms, int64_t n, float noise_mean_std, float noise_std, uint64_t seed, uint64_t offset,
                            float* out, int64_t* labels_out, void* stream);
+
+/* The generator's latent batch (gensamples.py:36, train.py:256: torch normal_ on the process RNG) as an INDEXED stream (ABI v7):
+ * z[i][:] (row-major [n, dim]) holds the dim unit normals of sample g = first_index + *first_index_dev + i, a function of
+ * (seed, g) alone — not of the batch size, of where a run was cut, or of how an index range is split between calls ("Device random
+ * streams" above; csl_gan_amd.generate.latent_normals_host restates it on the host).  first_index_dev (nullable, device): its value
+ * is ADDED to first_index inside the kernel, as call_counter is for the gradient noise — a recorded graph draws new rows on every
+ * replay.  labels (nullable, [n] int64) receives fixed_label when fixed_label >= 0, else g mod n_classes: class-balanced over any
+ * contiguous range, no draw needed.  n_classes >= 1, fixed_label < n_classes; dim need not be a multiple of 4. */
+int cslgan_latent_normal_f32(uint64_t seed, uint64_t first_index, const unsigned long long* first_index_dev, int64_t n, int dim, float* z,
+                             int n_classes, int fixed_label, int64_t* labels, void* stream);
 
 /* Row L2 norms of a [n_rows, len] matrix (gradient_penalty.py:52-53) and the backward of
  * norm: gin[r][j] = gnorm[r] * in[r][j] / norm[r]. */
@@ -515,6 +529,14 @@ int cslgan_lipschitz_term_bwd_f32(const float* t, const float* norm, const float
  * Replaces the per-image ToTensor / RandomHorizontalFlip / Normalize of datasets.py:41-47 (flip: nullable [N] bytes drawn by the host
  * with p = 0.5; scale = 1/127.5, bias = -1 for Normalize(0.5, 0.5)). */
 int cslgan_u8_to_f32_nhwc(const void* src_u8, const void* flip_u8, int N, int H, int W, int C, float scale, float bias, float* out, void* stream);
+
+/* The inverse (ABI v7): n fp32 values in memory order (NHWC images) -> n bytes,
+ *   t = clamp(src * scale + bias, 0, 1);  dst = (uint8) clamp(t * 255 + 0.5, 0, 255)      (truncation; NaN -> 0)
+ * — util.denorm_celeba followed by the quantisation of util.save_image (train.py:303-306, gensamples.py:37-41) for
+ * (scale, bias) = (0.5, 0.5), MNIST's [0, 1] images for (1, 0).  Every product and sum is rounded on its own, in this order: the bytes
+ * equal the host's fp32 expression bit for bit.  16-byte loads / 4-byte stores where src is 16-byte and dst 4-byte aligned, element
+ * by element otherwise. */
+int cslgan_f32_to_u8(const float* src, int64_t n, float scale, float bias, void* dst_u8, void* stream);
 
 #ifdef __cplusplus
 }
