@@ -7,7 +7,7 @@ are [K,R,S,C].  Device tensors only — there is no CPU path in this module.
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import torch
 
@@ -184,7 +184,7 @@ def cast_bf16(t):
     """fp32 -> bfloat16 (round to nearest even), same shape and strides; one pass of cslgan_cast_f32_bf16."""
     if t.dtype == torch.bfloat16:
         return t
-    _chk_dense(t, "t")
+    _chk(t, "t", any_order=True)
     out = torch.empty_like(t, dtype=torch.bfloat16)
     check(_lib.lib().cslgan_cast_f32_bf16(_p(t), _p(out), t.numel(), _stream()), "cast_f32_bf16")
     return out
@@ -194,21 +194,10 @@ def cast_f32(t):
     """bfloat16 -> fp32 (exact), same shape and strides."""
     if t is None or t.dtype == torch.float32:
         return t
-    _chk_dense(t, "t", allow_bf16=True)
+    _chk(t, "t", allow_bf16=True, any_order=True)
     out = torch.empty_like(t, dtype=torch.float32)
     check(_lib.lib().cslgan_cast_bf16_f32(_p(t), _p(out), t.numel(), _stream()), "cast_bf16_f32")
     return out
-
-
-def _chk_dense(t, name, allow_bf16=False):
-    """A device tensor whose memory is one dense block in some dimension order (casts are layout-agnostic)."""
-    if not t.is_cuda:
-        raise RuntimeError("%s must be a device tensor (csl_gan_amd.ops has no CPU path)" % name)
-    if t.dtype != torch.float32 and not (allow_bf16 and t.dtype == torch.bfloat16):
-        raise RuntimeError("%s must be float32%s, got %s" % (name, " or bfloat16" if allow_bf16 else "", t.dtype))
-    if not (t.is_contiguous() or _dense_block(t)):
-        raise RuntimeError("%s must be dense" % name)
-    return t
 
 
 def _dense_block(t):
@@ -401,13 +390,15 @@ def _p(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
-def _chk(t: torch.Tensor, name: str, allow_bf16=False):
+def _chk(t: torch.Tensor, name: str, allow_bf16=False, any_order=False):
+    """A device tensor of fp32 (or bf16) elements, contiguous — any_order (the casts are layout-agnostic): one dense block of memory
+    in some dimension order."""
     if not t.is_cuda:
         raise RuntimeError("%s must be a device tensor (csl_gan_amd.ops has no CPU path)" % name)
     if t.dtype != torch.float32 and not (allow_bf16 and t.dtype == torch.bfloat16):
         raise RuntimeError("%s must be float32%s, got %s" % (name, " or bfloat16" if allow_bf16 else "", t.dtype))
-    if not t.is_contiguous():
-        raise RuntimeError("%s must be contiguous" % name)
+    if not t.is_contiguous() and not (any_order and _dense_block(t)):
+        raise RuntimeError("%s must be %s" % (name, "dense" if any_order else "contiguous"))
     return t
 
 
@@ -415,15 +406,67 @@ def conv_out_size(H, R, stride, pad):
     return (H + 2 * pad - R) // stride + 1
 
 
-def _conv_desc(N, H, W, Cc, K, R, S, stride, pad, kind="wgrad", group=None):
-    """kind: "fwd" / "dgrad" may take the bf16x3 path under fp32_auto; weight gradients never do."""
-    P, Q = conv_out_size(H, R, stride, pad), conv_out_size(W, S, stride, pad)
+# ---- conv dispatch: one geometry per call, each shape rule once, one launch helper ----------------------------------------------------
+
+class _Geom(NamedTuple("_Geom", [(f, int) for f in "N H W C K R S stride pad P Q".split()])):
+    """The shape of one conv call, built and checked once per public op: x[N,H,W,C], w[K,R,S,C], y / gy[N,P,Q,K]."""
+    __slots__ = ()
+
+    def __new__(cls, N, H, W, Cc, K, R, S, stride, pad):
+        return tuple.__new__(cls, (N, H, W, Cc, K, R, S, stride, pad, conv_out_size(H, R, stride, pad), conv_out_size(W, S, stride, pad)))
+
+    flop = property(lambda g: 2.0 * g.N * g.P * g.Q * g.K * g.R * g.S * g.C)
+    wsize = property(lambda g: g.K * g.R * g.S * g.C)         # elements of the filter / of one weight gradient
+
+    def desc(self, comp):
+        return ConvT(*self[:9], comp, self.P, self.Q)
+
+    def tag(self, sfx="", vals=(), stride=True):
+        """Shape tag of a launch-timer record, the one place its format is written: the shape, then the route's words (sfx % vals)."""
+        return ("N%d %dx%d C%d K%d R%d" % (self.N, self.H, self.W, self.C, self.K, self.R) + (" s%d" % self.stride if stride else "")
+                + (" " + sfx % vals if sfx else ""))
+
+
+def _fwd_geom(x, w, stride, pad):
+    _chk(x, "x", allow_bf16=True); _chk(w, "w")
+    N, H, W, Cc = x.shape
+    K, R, S, C2 = w.shape
+    if C2 != Cc:
+        raise RuntimeError("conv2d_fwd: channel mismatch x C=%d, w C=%d" % (Cc, C2))
+    return _Geom(N, H, W, Cc, K, R, S, stride, pad)
+
+
+def _dgrad_geom(gy, w, in_hw, stride, pad):
+    _chk(gy, "gy", allow_bf16=True); _chk(w, "w")
+    N, P, Q, K = gy.shape
+    K2, R, S, Cc = w.shape
+    H, W = in_hw
+    g = _Geom(N, H, W, Cc, K, R, S, stride, pad)
+    if K2 != K or (g.P, g.Q) != (P, Q):
+        raise RuntimeError("conv2d_dgrad: gy shape %s inconsistent with input %dx%d" % (tuple(gy.shape), H, W))
+    return g
+
+
+def _wgrad_geom(op, gy, x, R, S, stride, pad):
+    """Geometry of a weight gradient / Gram call from its operands' shapes (element types are the route's business)."""
+    N, H, W, Cc = x.shape
+    N2, P, Q, K = gy.shape
+    g = _Geom(N, H, W, Cc, K, R, S, stride, pad)
+    if N2 != N or (g.P, g.Q) != (P, Q):
+        raise RuntimeError("%s: gy %s inconsistent with x %s" % (op, tuple(gy.shape), tuple(x.shape)))
+    return g
+
+
+def _auto_desc(g, kind, group=None):
+    """Descriptor in the process's compute mode.  kind: "fwd" / "dgrad" may take the bf16x3 path under fp32_auto; weight gradients
+    only on the LDS-resident three-piece kernel's shapes."""
+    N, H, W, Cc, K, R, S, stride, pad, P, Q = g
     comp = _compute
     if kind == "fwd":
         comp = _kc_compute(N * P * Q, K, R * S * Cc)
     elif kind == "dgrad":
         comp = _kc_compute(N * H * W, Cc, (R * S * K) // (stride * stride))
-    elif (kind == "wgrad" and _auto and S == 5 and stride in (1, 2) and K % 64 == 0 and Cc % 64 == 0 and 2.0 * N * P * Q * K * R * S * Cc >= _AUTO_WG_MIN_FLOP
+    elif (kind == "wgrad" and _auto and S == 5 and stride in (1, 2) and K % 64 == 0 and Cc % 64 == 0 and g.flop >= _AUTO_WG_MIN_FLOP
           and ((P % 8 == 0 and Q % 8 == 0) or
                ((P, Q, H, W, stride, pad) == (4, 4, 8, 8, 2, 2) and group is not None and group % 2 == 0))):
         comp = COMPUTE_BF16X3          # weight gradient on the LDS-resident three-piece kernel (csrc/igemm_wgh.hip: igemm_x3w_kernel)
@@ -431,8 +474,27 @@ def _conv_desc(N, H, W, Cc, K, R, S, stride, pad, kind="wgrad", group=None):
         # small linear layers (the critic's head, the generator's first layer): a few hundred MFLOP on skinny GEMMs where the bf16
         # gather kernels ran at < 1 TF (0.35 ms for 268 MFLOP); the fp32 kernels take 15-30 us and are exact
         comp = COMPUTE_F32
-    return ConvT(N, H, W, Cc, K, R, S, stride, pad, comp, P, Q), P, Q
+    return ConvT(N, H, W, Cc, K, R, S, stride, pad, comp, P, Q)
 
+
+def _conv_desc(N, H, W, Cc, K, R, S, stride, pad, kind="wgrad", group=None):
+    """(descriptor, P, Q) from plain sizes: _auto_desc for callers that hold no geometry (the tests)."""
+    g = _Geom(N, H, W, Cc, K, R, S, stride, pad)
+    return _auto_desc(g, kind, group), g.P, g.Q
+
+
+def _launch(name, entry, args, g, nbytes, sfx="", vals=(), exec_flop=None, flop=None, tag_stride=True):
+    """One C-ABI launch, cslgan_<entry>(*args, stream), timed as `name`.  The timer's figures are callables (or plain numbers), so
+    that like the tag they cost nothing when no timer is installed: nbytes; flop (default g.flop), the op as the reference executes
+    it; exec_flop, what the kernel really issues; sfx % vals, the route's words in the shape tag."""
+    fn = getattr(_lib.lib(), "cslgan_" + entry)
+    if _timer is None:
+        return check(fn(*args, _stream()), entry)
+    flop, nbytes, exec_flop = (v() if callable(v) else v for v in (g.flop if flop is None else flop, nbytes, exec_flop))
+    return _timed(name, flop, nbytes, lambda: check(fn(*args, _stream()), entry), exec_flop=exec_flop, tag=lambda: g.tag(sfx, vals, tag_stride))
+
+
+# -- shape rules: each kernel's "takes this launch", written once (the C side re-checks what it needs)
 
 # Per compute mode of an LDS-halo launch (csrc/igemm_x3.hip): suffix of the stride-2 / data-gradient repack-cache keys and timer tags,
 # cache key of the stride-1 forward filter copy, bfloat16 pieces of that copy (0: a step-major fp32 copy).
@@ -444,20 +506,61 @@ def _halo_arith(comp):
     return comp in (COMPUTE_BF16X3, COMPUTE_BF16) or (comp == COMPUTE_F32 and _F32_HALO)
 
 
-def _fwd_halo_s1(comp, Cc, K, R, S, stride, P, Q):
+def _fwd_halo_s1(comp, g):
     """This fp32-tensor forward call takes the stride-1 LDS-halo kernel (cslgan_conv2d_fwd_x3_f32): the one rule for conv2d_fwd's
     route and for in_affine_ok's promise about it."""
-    return _halo_arith(comp) and stride == 1 and R * S > 1 and Cc % 16 == 0 and K >= 64 and K % 4 == 0 and P % 8 == 0 and Q % 8 == 0
+    return (_halo_arith(comp) and g.stride == 1 and g.R * g.S > 1 and g.C % 16 == 0 and g.K >= 64 and g.K % 4 == 0
+            and g.P % 8 == 0 and g.Q % 8 == 0)
 
 
-def _fwd_geometry(x, w, stride, pad):
-    """The checked operands of a forward conv: (N, H, W, C, K, R, S, P, Q)."""
-    _chk(x, "x", allow_bf16=True); _chk(w, "w")
-    N, H, W, Cc = x.shape
-    K, R, S, C2 = w.shape
-    if C2 != Cc:
-        raise RuntimeError("conv2d_fwd: channel mismatch x C=%d, w C=%d" % (Cc, C2))
-    return N, H, W, Cc, K, R, S, conv_out_size(H, R, stride, pad), conv_out_size(W, S, stride, pad)
+def _fwd_parity_s2(g, c_mult, residual):
+    """A stride-2 forward conv as parity sub-images: odd square filter, channels a multiple of c_mult, no residual."""
+    return g.stride == 2 and g.R == g.S and g.R % 2 == 1 and g.R > 1 and g.C % c_mult == 0 and g.K >= 64 and residual is None
+
+
+def _skinny(g):
+    """The 1..4-output-channel vector-ALU kernels (csrc/igemm_skinny.hip): 64 input channels, stride 1, up to 3x3, 8x8-patchable output."""
+    return g.K <= 4 and g.C == 64 and g.stride == 1 and g.R * g.S <= 9 and g.P % 8 == 0 and g.Q % 8 == 0
+
+
+def _c3_layer(g, grid_ok):
+    """The critic's first conv as csrc/conv_c3.hip takes it (c3_shape there): 3 -> 64 channels, 5x5, stride 2, pad 2, even image."""
+    return g.K == 64 and g.R == 5 and g.S == 5 and g.stride == 2 and g.pad == 2 and g.H % 2 == 0 and g.W % 2 == 0 and grid_ok
+
+
+def _c3_fwd(g):
+    return g.C == 3 and _c3_layer(g, g.H % 16 == 0 and g.W % 32 == 0)
+
+
+def _c3_wgrad(g):
+    """The first-layer kernel's weight gradient: RGB input, an output grid of 16 / 32 / 64 columns in whole 128-pixel row groups."""
+    return g.C == 3 and _c3_layer(g, g.Q in (16, 32, 64) and g.P % (128 // g.Q) == 0)
+
+
+def _head_bf16(g):
+    """The critic's head on bf16 features (csrc/linear_k1.hip): one output, 1x1 input, feature rows of whole 16-byte vectors."""
+    return g.K == 1 and g.R == 1 and g.S == 1 and g.H == 1 and g.W == 1 and g.C % 8 == 0
+
+
+def _f32_or_none(t):
+    return t is None or t.dtype == torch.float32
+
+
+def _wgrad_bf16s_ok(g, gy, x, want_gw, sq, out, row_scale):
+    """The bf16-stored weight-gradient kernels take this call (cslgan_conv2d_wgrad_grouped_bf16s; with row_scale
+    cslgan_conv2d_wgrad_scaled_bf16s: a K tile of 64 pixels must lie inside one sample, fp32 gradient out, no norms)."""
+    return (gy.dtype == x.dtype == torch.bfloat16 and g.K % 8 == 0 and g.C % 8 == 0 and (want_gw or sq is not None)
+            and (row_scale is None or ((g.P * g.Q) % 64 == 0 and sq is None and want_gw and _f32_or_none(out))))
+
+
+def _wgh_shape(S, stride, K, Cc, P, Q):
+    """Launches the LDS-resident weight-gradient kernels take (mirrors wgh_eligible in csrc/igemm_wgh.hip): they exist in exact fp32
+    (2..5 filter columns) and in the three-piece form (5 columns)."""
+    return ((_compute == COMPUTE_F32 or (_compute == COMPUTE_BF16X3 and S == 5)) and stride in (1, 2) and 2 <= S <= 5
+            and K % 64 == 0 and Cc % 64 == 0 and P % 8 == 0 and Q % 8 == 0)
+
+
+_GRAM_MAX_PIX = 64     # (16 was the round-1 rule: ghost clipping for conv4 + linear only)
 
 
 def _chk_bias_residual(bias, residual, y_shape, allow_bf16=False):
@@ -469,53 +572,40 @@ def _chk_bias_residual(bias, residual, y_shape, allow_bf16=False):
             raise RuntimeError("conv2d_fwd: residual shape %s, expected %s" % (tuple(residual.shape), tuple(y_shape)))
 
 
-def _conv2d_fwd_stored(geom, x, w, bias, stride, pad, residual, act, out, wkey, alg_scale, wversion, out_dtype):
+def _conv2d_fwd_stored(g, x, w, bias, residual, act, out, wkey, alg_scale, wversion, out_dtype):
     """conv2d_fwd with bf16-stored activations (x and / or y bfloat16): the bf16-stored kernel when x is bf16 with C % 8 == 0,
     otherwise the fp32 kernels between casts."""
-    N, H, W, Cc, K, R, S, P, Q = geom
-
-    def desc(comp):
-        return ConvT(N, H, W, Cc, K, R, S, stride, pad, comp, P, Q)
-
+    N, P, Q, K = g.N, g.P, g.Q, g.K
+    x_bf16 = x.dtype == torch.bfloat16
     if out_dtype is None:           # follow the input: conv layers answer bf16 activations in kind; heads and 1..4-channel images stay fp32
-        out_dtype = torch.bfloat16 if (x.dtype == torch.bfloat16 and P * Q > 1 and K > 4) else torch.float32
+        out_dtype = torch.bfloat16 if (x_bf16 and P * Q > 1 and K > 4) else torch.float32
     y_bf16 = out_dtype == torch.bfloat16
-    if x.dtype == torch.bfloat16 and Cc % 8 == 0 and (K > 4 or P * Q == 1):      # 1..4 output channels of an image: the fp32 vector-ALU kernel below
-        d = desc(COMPUTE_BF16)
+    if x_bf16 and g.C % 8 == 0 and (K > 4 or P * Q == 1):      # 1..4 output channels of an image: the fp32 vector-ALU kernel below
         y = out if out is not None else torch.empty((N, P, Q, K), device=x.device, dtype=out_dtype)
         if y.dtype != out_dtype:
             raise RuntimeError("conv2d_fwd: out has dtype %s, expected %s" % (y.dtype, out_dtype))
         _chk_bias_residual(bias, residual, (N, P, Q, K), allow_bf16=True)
         ws, repack = repack_cache.get("bf16s_fwd", w, (w.numel() + 1) // 2, wkey, version=wversion)
-        flop = 2.0 * N * P * Q * K * R * S * Cc * alg_scale
-        nbytes = 2.0 * (N * H * W * Cc + K * R * S * Cc) + y.element_size() * float(N * P * Q * K)
-        _timed("conv2d_fwd", flop, nbytes, lambda: check(
-            _lib.lib().cslgan_conv2d_fwd_bf16s(C.byref(d), _p(x), _p(w), _p(ws), repack, _p(bias), _p(residual), 1 if _is_bf16(residual) else 0,
-                                               act, _p(y), 1 if y_bf16 else 0, _stream()), "conv2d_fwd_bf16s"),
-            exec_flop=2.0 * N * P * Q * K * R * S * Cc, tag=lambda: "N%d %dx%d C%d K%d R%d s%d bf16s" % (N, H, W, Cc, K, R, stride))
+        _launch("conv2d_fwd", "conv2d_fwd_bf16s", (C.byref(g.desc(COMPUTE_BF16)), _p(x), _p(w), _p(ws), repack, _p(bias), _p(residual),
+                                                   1 if _is_bf16(residual) else 0, act, _p(y), 1 if y_bf16 else 0),
+                g, lambda: 2.0 * (x.numel() + w.numel()) + y.element_size() * float(N * P * Q * K), "bf16s", flop=lambda: g.flop * alg_scale, exec_flop=lambda: g.flop)
         repack_cache.packed()
         return y
-    if (x.dtype == torch.bfloat16 and not y_bf16 and K <= 4 and Cc == 64 and stride == 1 and R * S <= 9 and P % 8 == 0 and Q % 8 == 0
-            and residual is None and out is None):
+    if x_bf16 and not y_bf16 and _skinny(g) and residual is None and out is None:
         # the generator's output conv (64 -> 3 channels): the vector-ALU kernel reads the bf16-stored input as it is
-        d = desc(COMPUTE_F32)
         y = torch.empty((N, P, Q, K), device=x.device, dtype=torch.float32)
         _chk_bias_residual(bias, None, y.shape)
-        _timed("conv2d_fwd", 2.0 * N * P * Q * K * R * S * Cc, 2.0 * N * H * W * Cc + 4.0 * N * P * Q * K, lambda: check(
-            _lib.lib().cslgan_conv2d_fwd_skinny_bf16in(C.byref(d), _p(x), _p(w), _p(bias), act, _p(y), _stream()), "conv2d_fwd_skinny_bf16in"),
-            tag=lambda: "N%d %dx%d C%d K%d R%d s%d bf16in" % (N, H, W, Cc, K, R, stride))
+        _launch("conv2d_fwd", "conv2d_fwd_skinny_bf16in", (C.byref(g.desc(COMPUTE_F32)), _p(x), _p(w), _p(bias), act, _p(y)),
+                g, lambda: 2.0 * x.numel() + 4.0 * N * P * Q * K, "bf16in")
         return y
-    if (x.dtype == torch.float32 and y_bf16 and residual is None and out is None
-            and Cc == 3 and _c3_layer(H, W, K, R, S, stride, pad, H % 16 == 0 and W % 32 == 0)):
+    if x.dtype == torch.float32 and y_bf16 and residual is None and out is None and _c3_fwd(g):
         # the RGB first layer: fp32 image in, bf16-stored activations out of the same kernel (no cast pass)
-        d = desc(COMPUTE_F32)
         y = torch.empty((N, P, Q, K), device=x.device, dtype=torch.bfloat16)
         _chk_bias_residual(bias, None, y.shape)
-        _timed("conv2d_fwd", 2.0 * N * P * Q * K * R * S * Cc, 4.0 * N * H * W * Cc + 2.0 * N * P * Q * K, lambda: check(
-            _lib.lib().cslgan_conv2d_c3_fwd_bf16out(C.byref(d), _p(x), _p(w), _p(bias), act, _p(y), _stream()), "conv2d_c3_fwd_bf16out"),
-            tag=lambda: "N%d %dx%d C%d K%d R%d s%d bf16out" % (N, H, W, Cc, K, R, stride))
+        _launch("conv2d_fwd", "conv2d_c3_fwd_bf16out", (C.byref(g.desc(COMPUTE_F32)), _p(x), _p(w), _p(bias), act, _p(y)),
+                g, lambda: 4.0 * x.numel() + 2.0 * N * P * Q * K, "bf16out")
         return y
-    yf = conv2d_fwd(cast_f32(x), w, bias, stride=stride, pad=pad, residual=cast_f32(residual), act=act, wkey=wkey, alg_scale=alg_scale,
+    yf = conv2d_fwd(cast_f32(x), w, bias, stride=g.stride, pad=g.pad, residual=cast_f32(residual), act=act, wkey=wkey, alg_scale=alg_scale,
                     wversion=wversion)
     y = cast_bf16(yf) if y_bf16 else yf
     if out is not None:
@@ -531,11 +621,11 @@ def in_affine_ok(x, w, stride, pad):
         return False
     N, H, W, Cc = x.shape
     K, R, S, _ = w.shape
-    P, Q = conv_out_size(H, R, stride, pad), conv_out_size(W, S, stride, pad)
+    g = _Geom(N, H, W, Cc, K, R, S, stride, pad)
     if K <= 4:
-        return Cc == 64 and 1 < R * S <= 9 and P % 8 == 0 and Q % 8 == 0
-    comp = _kc_compute(N * P * Q, K, R * S * Cc)
-    return comp != COMPUTE_BF16 and _fwd_halo_s1(comp, Cc, K, R, S, stride, P, Q)
+        return _skinny(g) and 1 < R * S
+    comp = _kc_compute(N * g.P * g.Q, K, R * S * Cc)
+    return comp != COMPUTE_BF16 and _fwd_halo_s1(comp, g)
 
 
 def groupnorm_affine(part, gamma, beta, groups, eps, N, HW, Cc):
@@ -559,51 +649,46 @@ def conv2d_fwd(x, w, bias=None, stride=1, pad=0, residual=None, act=ACT_NONE, ou
     alg_scale: FLOP the reference spends on this layer / FLOP of this call (4 for an UpsampleConv's conv, which the
     reference runs over four identical channel groups) — bench accounting only.
     out_dtype: torch.bfloat16 stores the output as bfloat16 (set_storage_dtype); None follows the input's element type."""
-    geom = _fwd_geometry(x, w, stride, pad)
+    g = _fwd_geom(x, w, stride, pad)
     if x.dtype == torch.bfloat16 or out_dtype == torch.bfloat16 or _is_bf16(residual):
-        return _conv2d_fwd_stored(geom, x, w, bias, stride, pad, residual, act, out, wkey, alg_scale, wversion, out_dtype)
-    N, H, W, Cc, K, R, S, P, Q = geom
-    c_alg = Cc                    # channels the reference convolves (FLOP accounting)
-    if Cc == 3 and R * S > 1 and not _c3_layer(H, W, K, R, S, stride, pad, residual is None and H % 16 == 0 and W % 32 == 0):
+        return _conv2d_fwd_stored(g, x, w, bias, residual, act, out, wkey, alg_scale, wversion, out_dtype)
+    alg = g                       # the conv the reference executes (FLOP and byte accounting)
+    if g.C == 3 and g.R * g.S > 1 and not (residual is None and _c3_fwd(g)):
         # RGB input on a shape the first-layer kernel (csrc/conv_c3.hip) does not take: a zero 4th channel makes every tap one
         # aligned 16-byte load (scalar gathers ran at 22-32 TF); the zero channel adds nothing to the sums
-        x, w, Cc, wkey = _pad_c4(x), _pad_c4(w), 4, None
-    d, _, _ = _conv_desc(N, H, W, Cc, K, R, S, stride, pad, kind="fwd")
+        x, w, g, wkey = _pad_c4(x), _pad_c4(w), g._replace(C=4), None
+    N, P, Q, K = g.N, g.P, g.Q, g.K
+    d = _auto_desc(g, "fwd")
     y = out if out is not None else torch.empty((N, P, Q, K), device=x.device, dtype=torch.float32)
     _chk_bias_residual(bias, residual, (N, P, Q, K))
     if in_affine is not None:
         a_sc, a_sh, a_relu = in_affine
         _chk(a_sc, "in_affine scale"); _chk(a_sh, "in_affine shift")
-        if tuple(a_sc.shape) != (N, Cc) or tuple(a_sh.shape) != (N, Cc):
-            raise RuntimeError("conv2d_fwd: in_affine tables must be [N, C] = [%d, %d]" % (N, Cc))
+        if tuple(a_sc.shape) != (N, g.C) or tuple(a_sh.shape) != (N, g.C):
+            raise RuntimeError("conv2d_fwd: in_affine tables must be [N, C] = [%d, %d]" % (N, g.C))
         d.in_scale, d.in_shift, d.in_relu = a_sc.data_ptr(), a_sh.data_ptr(), 1 if a_relu else 0
-    flop = 2.0 * N * P * Q * K * R * S * c_alg * alg_scale    # the dense conv the reference executes
-    nbytes = 4.0 * (N * H * W * c_alg + K * R * S * c_alg + N * P * Q * K)
-    xflop = 2.0 * N * P * Q * K * R * S * Cc
+    flop, xflop = (lambda: alg.flop * alg_scale), (lambda: g.flop)   # the dense conv the reference executes / this launch
+    nbytes = lambda: 4.0 * (alg.N * alg.H * alg.W * alg.C + alg.wsize + N * P * Q * K)
     kind_sfx, s1_key, s1_pieces = _HALO_KIND[d.compute]
-    if (_halo_arith(d.compute) and stride == 2 and R == S and R % 2 == 1 and R > 1 and Cc % 16 == 0 and K >= 64
-            and residual is None and w.numel() % 8 == 0):
+    if _halo_arith(d.compute) and _fwd_parity_s2(g, 16, residual) and w.numel() % 8 == 0:
         # parity sub-images through the LDS-halo kernel of the bf16 matrix cores (csrc/igemm_x3.hip): one workspace holds the fp32
         # class matrices and, behind them, their bfloat16 pieces in step-major order
         nw = w.numel()
         ws, repack = repack_cache.get("s2_fwd_" + kind_sfx, w, nw + (3 * nw + 1) // 2, wkey)
-        part = _split_scratch(d, N * P * Q, K, Cc, y)
-        _timed("conv2d_fwd", flop, nbytes, lambda: check(
-            _lib.lib().cslgan_conv2d_s2_fwd_x3_f32(C.byref(d), _p(x), _p(w), _p(ws), C.c_void_p(ws.data_ptr() + 4 * nw), repack, _p(bias), act,
-                                                   _p(y), _stream()),
-            "conv2d_s2_fwd_x3"), exec_flop=xflop, tag=lambda: "N%d %dx%d C%d K%d R%d s2 %s" % (N, H, W, Cc, K, R, kind_sfx))
+        part = _split_scratch(d, N * P * Q, K, g.C, y)
+        _launch("conv2d_fwd", "conv2d_s2_fwd_x3_f32", (C.byref(d), _p(x), _p(w), _p(ws), C.c_void_p(ws.data_ptr() + 4 * nw), repack, _p(bias),
+                                                       act, _p(y)), g, nbytes, kind_sfx, flop=flop, exec_flop=xflop)
         del part
         repack_cache.packed()
         return y
-    if stride == 2 and R == S and R % 2 == 1 and R > 1 and Cc % 32 == 0 and K >= 64 and residual is None:
+    if _fwd_parity_s2(g, 32, residual):
         # parity sub-images through the LDS-halo kernel (the C entry falls back to the generic kernel for other grids)
         ws, repack = repack_cache.get("s2_fwd", w, w.numel(), wkey)
-        _timed("conv2d_fwd", flop, nbytes, lambda: check(
-            _lib.lib().cslgan_conv2d_s2_fwd_f32(C.byref(d), _p(x), _p(w), _p(ws), repack, _p(bias), act, _p(y), _stream()),
-            "conv2d_s2_fwd"), exec_flop=xflop, tag=lambda: "N%d %dx%d C%d K%d R%d s2 halo" % (N, H, W, Cc, K, R))
+        _launch("conv2d_fwd", "conv2d_s2_fwd_f32", (C.byref(d), _p(x), _p(w), _p(ws), repack, _p(bias), act, _p(y)), g, nbytes, "halo",
+                flop=flop, exec_flop=xflop)
         repack_cache.packed()
         return y
-    if _fwd_halo_s1(d.compute, Cc, K, R, S, stride, P, Q):
+    if _fwd_halo_s1(d.compute, g):
         # the round-4 LDS-halo kernel reads the filter in step-major order: pre-split into bfloat16 pieces / pre-rounded / as an fp32 copy
         # (cached per parameter version)
         ws, repack = repack_cache.get(s1_key, w, (3 * w.numel() + 1) // 2, wkey, version=wversion)
@@ -615,16 +700,13 @@ def conv2d_fwd(x, w, bias=None, stride=1, pad=0, residual=None, act=ACT_NONE, ou
                 gpart = torch.empty(N * (P * Q // 64) * req.groups * 2, device=x.device, dtype=torch.float32)
                 d.gn_part, d.gn_groups = gpart.data_ptr(), req.groups
                 req.part = (gpart, P * Q // 64)
-        _timed("conv2d_fwd", flop, nbytes, lambda: check(
-            _lib.lib().cslgan_conv2d_fwd_x3_f32(C.byref(d), _p(x), _p(w), _p(ws), repack, _p(bias), _p(residual), act, _p(y), _stream()),
-            "conv2d_fwd_x3"), exec_flop=xflop, tag=lambda: "N%d %dx%d C%d K%d R%d s%d" % (N, H, W, Cc, K, R, stride))
+        _launch("conv2d_fwd", "conv2d_fwd_x3_f32", (C.byref(d), _p(x), _p(w), _p(ws), repack, _p(bias), _p(residual), act, _p(y)), g, nbytes,
+                flop=flop, exec_flop=xflop)
         if repack:
-            repack_cache.set_rebuild(lambda: check(_lib.lib().cslgan_split_filter_x3_f32(_p(w), K, R * S, Cc, _p(ws), s1_pieces, _stream()), "split_filter_x3"))
+            repack_cache.set_rebuild(lambda: check(_lib.lib().cslgan_split_filter_x3_f32(_p(w), K, g.R * g.S, g.C, _p(ws), s1_pieces, _stream()), "split_filter_x3"))
         repack_cache.packed()
         return y
-    _timed("conv2d_fwd", flop, nbytes, lambda: check(
-        _lib.lib().cslgan_conv2d_fwd_f32(C.byref(d), _p(x), _p(w), _p(bias), _p(residual), act, _p(y), _stream()),
-        "conv2d_fwd"), exec_flop=xflop, tag=lambda: "N%d %dx%d C%d K%d R%d s%d" % (N, H, W, Cc, K, R, stride))
+    _launch("conv2d_fwd", "conv2d_fwd_f32", (C.byref(d), _p(x), _p(w), _p(bias), _p(residual), act, _p(y)), g, nbytes, flop=flop, exec_flop=xflop)
     return y
 
 
@@ -674,27 +756,11 @@ def unfold_channels4(gwf):
     return gw
 
 
-def _c3_layer(H, W, K, R, S, stride, pad, grid_ok):
-    """The critic's first conv as csrc/conv_c3.hip takes it (c3_shape there): 3 -> 64 channels, 5x5, stride 2, pad 2, even image."""
-    return K == 64 and R == 5 and S == 5 and stride == 2 and pad == 2 and H % 2 == 0 and W % 2 == 0 and grid_ok
-
-
 def _pad_c4(t):
     """[..., 3] -> [..., 4] with a zero last channel (one small elementwise pass)."""
     out = torch.zeros(t.shape[:-1] + (4,), device=t.device, dtype=t.dtype)
     out[..., :3] = t
     return out
-
-
-def _dgrad_geometry(gy, w, in_hw, stride, pad):
-    """The checked operands of a data gradient: (N, H, W, C, K, R, S, P, Q)."""
-    _chk(gy, "gy", allow_bf16=True); _chk(w, "w")
-    N, P, Q, K = gy.shape
-    K2, R, S, Cc = w.shape
-    H, W = in_hw
-    if K2 != K or (conv_out_size(H, R, stride, pad), conv_out_size(W, S, stride, pad)) != (P, Q):
-        raise RuntimeError("conv2d_dgrad: gy shape %s inconsistent with input %dx%d" % (tuple(gy.shape), H, W))
-    return N, H, W, Cc, K, R, S, P, Q
 
 
 def _chk_mask(mask, gx, allow_bf16=False):
@@ -704,63 +770,56 @@ def _chk_mask(mask, gx, allow_bf16=False):
             raise RuntimeError("conv2d_dgrad: mask shape mismatch")
 
 
-def _conv2d_dgrad_stored(geom, gy, w, in_hw, stride, pad, mask, wkey, out_dtype):
+def _conv2d_dgrad_stored(g, gy, w, in_hw, mask, wkey, out_dtype):
     """conv2d_dgrad with bf16-stored activation gradients: the bf16-stored kernel when gy is bf16 with K % 8 == 0, otherwise the
     fp32 kernels between casts."""
-    N, H, W, Cc, K, R, S, P, Q = geom
+    N, H, W, Cc, K, stride = g.N, g.H, g.W, g.C, g.K, g.stride
+    gy_bf16 = gy.dtype == torch.bfloat16
     if out_dtype is None:
-        out_dtype = torch.bfloat16 if (gy.dtype == torch.bfloat16 and Cc > 4) else torch.float32
+        out_dtype = torch.bfloat16 if (gy_bf16 and Cc > 4) else torch.float32
     if mask is not None and mask.dtype != out_dtype:
         mask = cast_bf16(mask) if out_dtype == torch.bfloat16 else cast_f32(mask)
-    if (gy.dtype == torch.float32 and out_dtype == torch.bfloat16 and K == 1 and (P, Q, R, S, H, W) == (1, 1, 1, 1, 1, 1) and Cc % 8 == 0
-            and N <= 65535 and stride == 1 and pad == 0):
+    if (gy.dtype == torch.float32 and out_dtype == torch.bfloat16 and _head_bf16(g) and g.P == 1 and g.Q == 1 and N <= 65535
+            and stride == 1 and g.pad == 0):
         # the critic's head: fp32 loss cotangent, bf16 features
         gx = torch.empty((N, 1, 1, Cc), device=gy.device, dtype=torch.bfloat16)
         _chk_mask(mask, gx, allow_bf16=True)
-        _timed("conv2d_dgrad", 2.0 * N * Cc, 2.0 * N * Cc * (2 if mask is not None else 1) + 4.0 * Cc, lambda: check(
-            _lib.lib().cslgan_linear_k1_dgrad_bf16s(_p(gy), _p(w), _p(mask), N, Cc, _p(gx), _stream()), "linear_k1_dgrad_bf16s"),
-            tag=lambda: "N%d 1x1 C%d K1 R1 s1 bf16s" % (N, Cc))
+        _launch("conv2d_dgrad", "linear_k1_dgrad_bf16s", (_p(gy), _p(w), _p(mask), N, Cc, _p(gx)), g,
+                lambda: 2.0 * N * Cc * (2 if mask is not None else 1) + 4.0 * Cc, "bf16s")
         return gx
-    if gy.dtype == torch.bfloat16 and K % 8 == 0 and stride in (1, 2) and Cc > 4:
-        d = ConvT(N, H, W, Cc, K, R, S, stride, pad, COMPUTE_BF16, P, Q)
+    if gy_bf16 and K % 8 == 0 and stride in (1, 2) and Cc > 4:
         gx = torch.empty((N, H, W, Cc), device=gy.device, dtype=out_dtype)
         _chk_mask(mask, gx, allow_bf16=True)
         ws, repack = repack_cache.get("bf16s_dgrad%d" % stride, w, (w.numel() + 1) // 2, wkey)
-        flop = 2.0 * N * P * Q * K * R * S * Cc
-        nbytes = 2.0 * (K * R * S * Cc + N * P * Q * K) + gx.element_size() * float(N * H * W * Cc)
-        _timed("conv2d_dgrad", flop, nbytes, lambda: check(
-            _lib.lib().cslgan_conv2d_dgrad_bf16s(C.byref(d), _p(gy), _p(w), _p(ws), repack, _p(mask), _p(gx),
-                                                 1 if out_dtype == torch.bfloat16 else 0, _stream()), "conv2d_dgrad_bf16s"),
-            tag=lambda: "N%d %dx%d C%d K%d R%d s%d bf16s" % (N, H, W, Cc, K, R, stride))
+        _launch("conv2d_dgrad", "conv2d_dgrad_bf16s", (C.byref(g.desc(COMPUTE_BF16)), _p(gy), _p(w), _p(ws), repack, _p(mask), _p(gx),
+                                                       1 if out_dtype == torch.bfloat16 else 0),
+                g, lambda: 2.0 * (w.numel() + gy.numel()) + gx.element_size() * float(N * H * W * Cc), "bf16s")
         repack_cache.packed()
         return gx
-    if (gy.dtype == torch.bfloat16 and out_dtype == torch.float32 and mask is None and Cc <= 4 and K == 64 and stride in (1, 2) and R * S <= 25
-            and H % stride == 0 and W % stride == 0 and (H // stride) % 8 == 0 and (W // stride) % 8 == 0 and (R <= 3 or stride == 2)):
+    if (gy_bf16 and out_dtype == torch.float32 and mask is None and Cc <= 4 and K == 64 and stride in (1, 2) and g.R * g.S <= 25
+            and H % stride == 0 and W % stride == 0 and (H // stride) % 8 == 0 and (W // stride) % 8 == 0 and (g.R <= 3 or stride == 2)):
         # the critic's first layer: the image gradient from a bf16-stored output gradient on the vector-ALU kernel
-        d = ConvT(N, H, W, Cc, K, R, S, stride, pad, COMPUTE_F32, P, Q)
         gx = torch.empty((N, H, W, Cc), device=gy.device, dtype=torch.float32)
         ws, repack = repack_cache.get("dgrad%d" % stride, w, w.numel(), wkey)
-        _timed("conv2d_dgrad", 2.0 * N * P * Q * K * R * S * Cc, 2.0 * N * P * Q * K + 4.0 * N * H * W * Cc, lambda: check(
-            _lib.lib().cslgan_conv2d_dgrad_skinny_bf16in(C.byref(d), _p(gy), _p(w), _p(ws), repack, _p(gx), _stream()), "conv2d_dgrad_skinny_bf16in"),
-            tag=lambda: "N%d %dx%d C%d K%d R%d s%d bf16in" % (N, H, W, Cc, K, R, stride))
+        _launch("conv2d_dgrad", "conv2d_dgrad_skinny_bf16in", (C.byref(g.desc(COMPUTE_F32)), _p(gy), _p(w), _p(ws), repack, _p(gx)),
+                g, lambda: 2.0 * gy.numel() + 4.0 * N * H * W * Cc, "bf16in")
         repack_cache.packed()
         return gx
-    gx = conv2d_dgrad(cast_f32(gy), w, in_hw, stride=stride, pad=pad, mask=cast_f32(mask), wkey=wkey)
+    gx = conv2d_dgrad(cast_f32(gy), w, in_hw, stride=stride, pad=g.pad, mask=cast_f32(mask), wkey=wkey)
     return cast_bf16(gx) if out_dtype == torch.bfloat16 else gx
 
 
 def conv2d_dgrad(gy, w, in_hw, stride=1, pad=0, mask=None, wkey=None, out_dtype=None):
     """gx[N,H,W,C] = conv_transpose(gy[N,P,Q,K], w[K,R,S,C]) (* lrelu'(mask)).  out_dtype as for conv2d_fwd."""
-    geom = _dgrad_geometry(gy, w, in_hw, stride, pad)
+    g = _dgrad_geom(gy, w, in_hw, stride, pad)
     if gy.dtype == torch.bfloat16 or out_dtype == torch.bfloat16 or _is_bf16(mask):
-        return _conv2d_dgrad_stored(geom, gy, w, in_hw, stride, pad, mask, wkey, out_dtype)
-    N, H, W, Cc, K, R, S, P, Q = geom
-    d, _, _ = _conv_desc(N, H, W, Cc, K, R, S, stride, pad, kind="dgrad")
+        return _conv2d_dgrad_stored(g, gy, w, in_hw, mask, wkey, out_dtype)
+    N, H, W, Cc, K = g.N, g.H, g.W, g.C, g.K
+    d = _auto_desc(g, "dgrad")
     gx = torch.empty((N, H, W, Cc), device=gy.device, dtype=torch.float32)
     _chk_mask(mask, gx)
-    flop = 2.0 * N * P * Q * K * R * S * Cc
-    nbytes = 4.0 * (N * H * W * Cc + K * R * S * Cc + N * P * Q * K)
-    if (_halo_arith(d.compute) and K % 16 == 0 and Cc >= 64 and Cc % 4 == 0 and R * S > 1 and w.numel() % 8 == 0
+    nbytes = lambda: 4.0 * (gx.numel() + w.numel() + gy.numel())
+    if (_halo_arith(d.compute) and K % 16 == 0 and Cc >= 64 and Cc % 4 == 0 and g.R * g.S > 1 and w.numel() % 8 == 0
             and (H // stride) % 4 == 0 and (W // stride) % 4 == 0 and H % stride == 0 and W % stride == 0):
         # LDS-halo kernel of the bf16 matrix cores (csrc/igemm_x3.hip): the repacked class matrices and, behind them, their bfloat16
         # pieces in step-major order share one cached workspace
@@ -768,24 +827,15 @@ def conv2d_dgrad(gy, w, in_hw, stride=1, pad=0, mask=None, wkey=None, out_dtype=
         sfx = _HALO_KIND[d.compute][0]
         ws, repack = repack_cache.get("dgrad%d_%s" % (stride, sfx), w, nw + (3 * nw + 1) // 2, wkey)
         part = _split_scratch(d, N * H * W, Cc, K, gx)
-        _timed("conv2d_dgrad", flop, nbytes, lambda: check(
-            _lib.lib().cslgan_conv2d_dgrad_x3_f32(C.byref(d), _p(gy), _p(w), _p(ws), C.c_void_p(ws.data_ptr() + 4 * nw), repack, _p(mask), _p(gx),
-                                                  _stream()), "conv2d_dgrad_x3"),
-            tag=lambda: "N%d %dx%d C%d K%d R%d s%d %s" % (N, H, W, Cc, K, R, stride, sfx))
+        _launch("conv2d_dgrad", "conv2d_dgrad_x3_f32", (C.byref(d), _p(gy), _p(w), _p(ws), C.c_void_p(ws.data_ptr() + 4 * nw), repack, _p(mask),
+                                                        _p(gx)), g, nbytes, sfx)
         del part
         repack_cache.packed()
         return gx
     ws, repack = repack_cache.get("dgrad%d" % stride, w, w.numel(), wkey)
-    _timed("conv2d_dgrad", flop, nbytes, lambda: check(
-        _lib.lib().cslgan_conv2d_dgrad_f32(C.byref(d), _p(gy), _p(w), _p(ws), repack, _p(mask), _p(gx), _stream()), "conv2d_dgrad"),
-        tag=lambda: "N%d %dx%d C%d K%d R%d s%d" % (N, H, W, Cc, K, R, stride))
+    _launch("conv2d_dgrad", "conv2d_dgrad_f32", (C.byref(d), _p(gy), _p(w), _p(ws), repack, _p(mask), _p(gx)), g, nbytes)
     repack_cache.packed()
     return gx
-
-
-def _wgh_arith(S):
-    """The LDS-resident weight-gradient kernels exist in exact fp32 (2..5 filter columns) and in the three-piece form (5 columns)."""
-    return _compute == COMPUTE_F32 or (_compute == COMPUTE_BF16X3 and S == 5)
 
 
 def dense_wgrad_group(N, K, Cc, R, S, PQ, stride=1, out_hw=None):
@@ -793,8 +843,7 @@ def dense_wgrad_group(N, K, Cc, R, S, PQ, stride=1, out_hw=None):
     time follows how well that count fills 256 CUs x 3 resident workgroups (800 workgroups take two rounds, 3200 take
     4.2: measured 1.45 vs 1.16 ms on the same 55 GFLOP); more slabs cost their write + re-read by the column sum.
     Model: t(g) = FLOP / (100 TF x fill(g)) + 2 x slab bytes / 4 TB/s, minimised over g | N."""
-    if (_wgh_arith(S) and out_hw is not None and stride in (1, 2) and 2 <= S <= 5 and K % 64 == 0 and Cc % 64 == 0
-            and out_hw[0] % 8 == 0 and out_hw[1] % 8 == 0):
+    if out_hw is not None and _wgh_shape(S, stride, K, Cc, out_hw[0], out_hw[1]):
         # igemm_wgh (LDS-resident operands): (K/128)(C/64)R tiles per slab.  Big launches (the generator's convs, >= 40 GFLOP):
         # ONE slab — the kernel splits the patch loop over workgroups itself (atomic adds), no slab traffic.  Small ones:
         # the largest group that keeps >= 1024 workgroups (scripts/wgrad_group_sweep.py).
@@ -846,121 +895,135 @@ def gram_norms_preferred(gy_shape, x_shape, stride):
     return ((H + stride - 1) // stride) * ((W + stride - 1) // stride) <= _GRAM_MAX_PIX
 
 
-_GRAM_MAX_PIX = 64     # (16 was the round-1 rule: ghost clipping for conv4 + linear only)
-
-
 def conv2d_wgrad_sqnorm_gram(gy, x, R, S, stride=1, pad=0, alpha=1.0, sq=None):
     """sq[N] += ||alpha * per-sample weight gradient||^2 from the two PQ x PQ Gram matrices (no gradient formed)."""
     gy, x = cast_f32(gy), cast_f32(x)       # fp32 kernels only (ghost clipping is not combined with bf16 storage)
     _chk(gy, "gy"); _chk(x, "x")
-    N, H, W, Cc = x.shape
-    N2, P, Q, K = gy.shape
-    d, P2, Q2 = _conv_desc(N, H, W, Cc, K, R, S, stride, pad, kind="gram")
-    if N2 != N or (P2, Q2) != (P, Q):
-        raise RuntimeError("conv2d_wgrad_sqnorm_gram: gy %s inconsistent with x %s" % (tuple(gy.shape), tuple(x.shape)))
+    g = _wgrad_geom("conv2d_wgrad_sqnorm_gram", gy, x, R, S, stride, pad)
+    N, PQ = g.N, g.P * g.Q
     if sq is None:
         sq = torch.zeros(N, device=x.device, dtype=torch.float32)
     _chk(sq, "sq")
     if sq.numel() != N:
         raise RuntimeError("conv2d_wgrad_sqnorm_gram: sq needs %d entries" % N)
-    if P * Q == 1 and H * W == 1 and R == 1 and S == 1:
+    if PQ == 1 and g.H * g.W == 1 and R == 1 and S == 1:
         # linear layer: the 1x1 Gram matrices are the two row norms (one pass of the contract norm kernel over gy and x)
-        both = sample_sqnorm([gy.reshape(N, K), x.reshape(N, Cc)])
+        both = sample_sqnorm([gy.reshape(N, g.K), x.reshape(N, g.C)])
         sq.view(-1).addcmul_(both[0], both[1], value=float(alpha) ** 2)
         return sq
-    flop = 2.0 * N * (P * Q) ** 2 * (K + R * S * Cc)          # the tap-by-tap Gram form
-    cls_pix = ((H + stride - 1) // stride) * ((W + stride - 1) // stride)
-    if stride in (1, 2) and P * Q <= 16 and cls_pix <= 16:   # pixel-pair kernels: s^2 class Gram matrices (+ GY GY^T once / per class)
-        xflop = 2.0 * N * ((P * Q) ** 2 * K + stride * stride * cls_pix ** 2 * Cc)
-    elif stride in (1, 2) and P * Q <= 64 and cls_pix <= 64:
-        xflop = 2.0 * N * stride * stride * 64 * 64 * (K + Cc)
-    else:
-        xflop = flop
-    _timed("conv2d_wgrad_gram_norms", flop, 4.0 * (gy.numel() + x.numel()), lambda: check(
-        _lib.lib().cslgan_conv2d_wgrad_sqnorm_gram_f32(C.byref(d), _p(gy), _p(x), float(alpha), _p(sq), _stream()),
-        "conv2d_wgrad_sqnorm_gram"), exec_flop=xflop, tag=lambda: "N%d %dx%d C%d K%d R%d s%d" % (N, H, W, Cc, K, R, stride))
+    flop = lambda: 2.0 * N * PQ ** 2 * (g.K + R * S * g.C)          # the tap-by-tap Gram form
+
+    def xflop():            # pixel-pair kernels: s^2 class Gram matrices (+ GY GY^T once / per class)
+        cls_pix = ((g.H + stride - 1) // stride) * ((g.W + stride - 1) // stride)
+        if stride in (1, 2) and PQ <= 16 and cls_pix <= 16:
+            return 2.0 * N * (PQ ** 2 * g.K + stride * stride * cls_pix ** 2 * g.C)
+        if stride in (1, 2) and PQ <= 64 and cls_pix <= 64:
+            return 2.0 * N * stride * stride * 64 * 64 * (g.K + g.C)
+        return flop()
+
+    _launch("conv2d_wgrad_gram_norms", "conv2d_wgrad_sqnorm_gram_f32", (C.byref(_auto_desc(g, "gram")), _p(gy), _p(x), float(alpha), _p(sq)),
+            g, lambda: 4.0 * (gy.numel() + x.numel()), flop=flop, exec_flop=xflop)
     return sq
+
+
+def _wgrad_outputs(g, group, x, want_gw, sq, out, row_scale=None, bf16_gw=False):
+    """The checked outputs of a weight-gradient route: gw = `out` or a fresh fp32 [N/group,K,R,S,C] (None unless want_gw; a bf16
+    `out` only where the route's kernel writes one), sq and row_scale as the kernels read them."""
+    gw = None
+    if want_gw:
+        gw = out if out is not None else torch.empty((g.N // group, g.K, g.R, g.S, g.C), device=x.device, dtype=torch.float32)
+        _chk(gw, "gw", allow_bf16=bf16_gw)
+    if sq is not None:
+        _chk(sq, "sq")
+    if row_scale is not None:
+        _chk(row_scale, "row_scale")
+        if row_scale.numel() != g.N:
+            raise RuntimeError("conv2d_wgrad: row_scale needs [N] factors")
+    return gw
+
+
+_WGRAD_NAME = {True: "conv2d_wgrad_grouped", False: "conv2d_wgrad_grouped_normonly"}       # launch-timer name by "a gradient is stored"
+
+
+def _wgrad_head(g, gy, x, group, alpha, want_gw, sq, out, row_scale):
+    """The critic's head: fp32 loss cotangent times bf16 feature rows."""
+    N, Cc = g.N, g.C
+    _chk(gy, "gy"); _chk(x, "x", allow_bf16=True)
+    gw = _wgrad_outputs(g, group, x, want_gw, sq, out, row_scale)
+    _launch(_WGRAD_NAME[want_gw], "linear_k1_wgrad_bf16s", (_p(gy), _p(x), _p(row_scale), N, Cc, group, float(alpha), _p(gw), _p(sq)), g,
+            lambda: 2.0 * N * Cc + (4.0 * (N // group) * Cc if want_gw else 0.0), "g%d bf16s scaled" if row_scale is not None else "g%d bf16s", (group,))
+    return gw
+
+
+def _wgrad_c3_bf16gy(g, gy, x, alpha, want_gw, sq, out):
+    """The RGB first layer: bf16-stored output gradient, fp32 image, the first-layer kernel reads gy as stored."""
+    _chk(gy, "gy", allow_bf16=True); _chk(x, "x")
+    gw = _wgrad_outputs(g, 1, x, want_gw, sq, out)
+    _launch(_WGRAD_NAME[want_gw], "conv2d_c3_wgrad_bf16gy", (C.byref(g.desc(COMPUTE_F32)), _p(gy), _p(x), float(alpha), _p(gw), _p(sq)), g,
+            lambda: 4.0 * x.numel() + 2.0 * gy.numel(), "g1 bf16gy")
+    return gw
+
+
+def _wgrad_bf16s(g, gy, x, group, alpha, want_gw, sq, out, row_scale):
+    """bf16 gy and bf16 x (cslgan_conv2d_wgrad_grouped_bf16s): fp32 (or bf16) gw and / or sq.  row_scale [N] (clip-weighted sums):
+    cslgan_conv2d_wgrad_scaled_bf16s — the fp32 weight meets each sample's accumulated product."""
+    _chk(gy, "gy", allow_bf16=True); _chk(x, "x", allow_bf16=True)
+    if g.N % group:
+        raise RuntimeError("conv2d_wgrad: N=%d not divisible by group=%d" % (g.N, group))
+    d = g.desc(COMPUTE_BF16)
+    gw = _wgrad_outputs(g, group, x, want_gw, sq, out, row_scale, bf16_gw=True)
+    nbytes = lambda: 2.0 * (x.numel() + gy.numel()) + (float(gw.element_size()) * ((g.N // group) * g.wsize) if want_gw else 0.0)
+    if row_scale is not None:
+        _launch("conv2d_wgrad_grouped", "conv2d_wgrad_scaled_bf16s", (C.byref(d), _p(gy), _p(x), _p(row_scale), group, float(alpha), _p(gw)),
+                g, nbytes, "g%d bf16s scaled", (group,))
+        return gw
+    _launch(_WGRAD_NAME[want_gw], "conv2d_wgrad_grouped_bf16s", (C.byref(d), _p(gy), _p(x), group, float(alpha), _p(gw), 1 if _is_bf16(gw) else 0,
+                                                                 _p(sq)), g, nbytes, "g%d bf16s", (group,))
+    return gw
+
+
+def _wgrad_rgb_padded(gy, x, R, S, stride, pad, group, alpha, want_gw, sq, out):
+    """RGB input on a shape the first-layer kernel does not take: run on a zero-padded 4th channel (aligned 16-byte gathers), then
+    drop that channel's (zero) gradients."""
+    g4 = conv2d_wgrad_grouped(gy, _pad_c4(x), R, S, stride=stride, pad=pad, group=group, alpha=alpha, want_gw=want_gw, sq=sq)
+    if g4 is None:
+        return None
+    if out is not None:
+        out.view(g4.shape[:-1] + (3,)).copy_(g4[..., :3])
+        return out
+    return g4[..., :3].contiguous()
 
 
 def conv2d_wgrad_grouped(gy, x, R, S, stride=1, pad=0, group=1, alpha=1.0, want_gw=True, sq=None, out=None, row_scale=None):
     """gw[N/group,K,R,S,C] (per-group weight gradients) and/or sq[N/group] += ||alpha*gw_g||^2.
     row_scale [N]: gy of sample n is weighted by row_scale[n] (clip-weighted sums; fp32 output, no sq)."""
+    g = _wgrad_geom("conv2d_wgrad", gy, x, R, S, stride, pad)
+    N, K, Cc, P, Q = g.N, g.K, g.C, g.P, g.Q
     if gy.dtype == torch.bfloat16 or x.dtype == torch.bfloat16:
-        if (gy.dtype == x.dtype and gy.shape[-1] % 8 == 0 and x.shape[-1] % 8 == 0 and (want_gw or sq is not None)
-                and (row_scale is None or _scaled_stored_ok(gy, sq, want_gw, out))):
-            return _conv2d_wgrad_grouped_stored(gy, x, R, S, stride, pad, group, alpha, want_gw, sq, out, row_scale)
-        if (gy.dtype == torch.float32 and x.dtype == torch.bfloat16 and gy.shape[-1] == 1 and R == 1 and S == 1
-                and tuple(x.shape[1:3]) == (1, 1) and x.shape[-1] % 8 == 0 and (out is None or out.dtype == torch.float32)
-                and x.shape[0] % group == 0 and x.shape[0] // group <= 65535 and (row_scale is None or (sq is None and want_gw))):
-            # the critic's head: fp32 loss cotangent times bf16 feature rows
-            N, Cc = x.shape[0], x.shape[-1]
-            _chk(gy, "gy"); _chk(x, "x", allow_bf16=True)
-            gw = None
-            if want_gw:
-                gw = out if out is not None else torch.empty((N // group, 1, 1, 1, Cc), device=x.device, dtype=torch.float32)
-                _chk(gw, "gw")
-            if sq is not None:
-                _chk(sq, "sq")
-            if row_scale is not None:
-                _chk(row_scale, "row_scale")
-                if row_scale.numel() != N:
-                    raise RuntimeError("conv2d_wgrad: row_scale needs [N] factors")
-            _timed("conv2d_wgrad_grouped" + ("" if want_gw else "_normonly"), 2.0 * N * Cc, 2.0 * N * Cc + (4.0 * (N // group) * Cc if want_gw else 0.0),
-                   lambda: check(_lib.lib().cslgan_linear_k1_wgrad_bf16s(_p(gy), _p(x), _p(row_scale), N, Cc, group, float(alpha), _p(gw), _p(sq), _stream()),
-                                 "linear_k1_wgrad_bf16s"), tag=lambda: "N%d 1x1 C%d K1 R1 s1 g%d bf16s%s" % (N, Cc, group, " scaled" if row_scale is not None else ""))
-            return gw
-        if (gy.dtype == torch.bfloat16 and x.dtype == torch.float32 and x.shape[-1] == 3 and group == 1 and row_scale is None
-                and (out is None or out.dtype == torch.float32) and (want_gw or sq is not None)
-                and _c3_layer(x.shape[1], x.shape[2], gy.shape[-1], R, S, stride, pad, gy.shape[2] in (16, 32, 64) and gy.shape[1] % (128 // gy.shape[2]) == 0)):
-            # the RGB first layer: bf16-stored output gradient, fp32 image, the first-layer kernel reads gy as stored
-            N, H, W, Cc = x.shape
-            _, P, Q, K = gy.shape
-            _chk(gy, "gy", allow_bf16=True); _chk(x, "x")
-            d = ConvT(N, H, W, Cc, K, R, S, stride, pad, COMPUTE_F32, P, Q)
-            gw = None
-            if want_gw:
-                gw = out if out is not None else torch.empty((N, K, R, S, Cc), device=x.device, dtype=torch.float32)
-                _chk(gw, "gw")
-            if sq is not None:
-                _chk(sq, "sq")
-            _timed("conv2d_wgrad_grouped" + ("" if want_gw else "_normonly"), 2.0 * N * P * Q * K * R * S * Cc, 4.0 * N * H * W * Cc + 2.0 * N * P * Q * K,
-                   lambda: check(_lib.lib().cslgan_conv2d_c3_wgrad_bf16gy(C.byref(d), _p(gy), _p(x), float(alpha), _p(gw), _p(sq), _stream()),
-                                 "conv2d_c3_wgrad_bf16gy"), tag=lambda: "N%d %dx%d C%d K%d R%d s%d g1 bf16gy" % (N, H, W, Cc, K, R, stride))
-            return gw
+        if _wgrad_bf16s_ok(g, gy, x, want_gw, sq, out, row_scale):
+            return _wgrad_bf16s(g, gy, x, group, alpha, want_gw, sq, out, row_scale)
+        if (gy.dtype == torch.float32 and x.dtype == torch.bfloat16 and _head_bf16(g) and _f32_or_none(out)
+                and N % group == 0 and N // group <= 65535 and (row_scale is None or (sq is None and want_gw))):
+            return _wgrad_head(g, gy, x, group, alpha, want_gw, sq, out, row_scale)
+        if (gy.dtype == torch.bfloat16 and x.dtype == torch.float32 and _c3_wgrad(g) and group == 1 and row_scale is None
+                and _f32_or_none(out) and (want_gw or sq is not None)):
+            return _wgrad_c3_bf16gy(g, gy, x, alpha, want_gw, sq, out)
         gy, x = cast_f32(gy), cast_f32(x)       # mixed element types / shapes the bf16-stored kernel does not take
     _chk(gy, "gy"); _chk(x, "x")
-    N, H, W, Cc = x.shape
-    N2, P, Q, K = gy.shape
-    c3 = (Cc == 3 and group == 1 and row_scale is None and (out is None or out.dtype == torch.float32)
-          and _c3_layer(H, W, K, R, S, stride, pad, Q in (16, 32, 64) and P % (128 // Q) == 0))
-    if Cc == 3 and R * S > 1 and row_scale is None and (out is None or out.dtype == torch.float32) and not c3:
-        # RGB input on a shape the first-layer kernel does not take: run on a zero-padded 4th channel (aligned 16-byte gathers),
-        # then drop that channel's (zero) gradients
-        g4 = conv2d_wgrad_grouped(gy, _pad_c4(x), R, S, stride=stride, pad=pad, group=group, alpha=alpha, want_gw=want_gw, sq=sq)
-        if g4 is None:
-            return None
-        if out is not None:
-            out.view(g4.shape[:-1] + (3,)).copy_(g4[..., :3])
-            return out
-        return g4[..., :3].contiguous()
-    d, P2, Q2 = _conv_desc(N, H, W, Cc, K, R, S, stride, pad, group=group)
-    if N2 != N or (P2, Q2) != (P, Q):
-        raise RuntimeError("conv2d_wgrad: gy %s inconsistent with x %s" % (tuple(gy.shape), tuple(x.shape)))
+    c3 = _c3_wgrad(g) and group == 1 and row_scale is None and _f32_or_none(out)
+    if Cc == 3 and R * S > 1 and row_scale is None and _f32_or_none(out) and not c3:
+        return _wgrad_rgb_padded(gy, x, R, S, stride, pad, group, alpha, want_gw, sq, out)
     if N % group:
         raise RuntimeError("conv2d_wgrad: N=%d not divisible by group=%d" % (N, group))
     G = N // group
+    d = _auto_desc(g, "wgrad", group)
     if row_scale is not None:
-        _chk(row_scale, "row_scale")
-        if row_scale.numel() != N or sq is not None or not want_gw:
+        if sq is not None or not want_gw:
             raise RuntimeError("conv2d_wgrad: row_scale needs [N] factors, a gradient output and no sq")
-        gw = out if out is not None else torch.empty((G, K, R, S, Cc), device=x.device, dtype=torch.float32)
-        _chk(gw, "gw")
-        flop = 2.0 * N * P * Q * K * R * S * Cc
-        _timed("conv2d_wgrad_grouped", flop, 4.0 * (N * H * W * Cc + N * P * Q * K + G * K * R * S * Cc), lambda: check(
-            _lib.lib().cslgan_conv2d_wgrad_scaled_f32(C.byref(d), _p(gy), _p(x), _p(row_scale), group, float(alpha), _p(gw), _stream()),
-            "conv2d_wgrad_scaled"), tag=lambda: "N%d %dx%d C%d K%d R%d s%d g%d scaled" % (N, H, W, Cc, K, R, stride, group))
+        gw = _wgrad_outputs(g, group, x, True, None, out, row_scale)
+        _launch("conv2d_wgrad_grouped", "conv2d_wgrad_scaled_f32", (C.byref(d), _p(gy), _p(x), _p(row_scale), group, float(alpha), _p(gw)),
+                g, lambda: 4.0 * (x.numel() + gy.numel() + G * g.wsize), "g%d scaled", (group,))
         return gw
-    gw = None
     scratch = False
     if not want_gw and sq is not None:
         # norms only, but a layer with a handful of tiles and a long pixel loop (the 3-channel first conv) runs several
@@ -968,79 +1031,27 @@ def conv2d_wgrad_grouped(gy, x, R, S, stride=1, pad=0, group=1, alpha=1.0, want_
         tiles = ((K + 63) // 64) * ((R * S * Cc + 127) // 128) * G
         if not c3 and tiles < 192 and group * P * Q >= 512 and G * K * R * S * Cc <= (1 << 22):
             want_gw, scratch = True, True
-    if want_gw:
-        gw = out if out is not None else torch.empty((G, K, R, S, Cc), device=x.device, dtype=torch.float32)
-        _chk(gw, "gw", allow_bf16=True)
-    if sq is not None:
-        _chk(sq, "sq")
-    flop = 2.0 * N * P * Q * K * R * S * Cc
-    esz = gw.element_size() if want_gw else 0
-    nbytes = 4.0 * (N * H * W * Cc + N * P * Q * K) + float(esz) * (G * K * R * S * Cc)
-    L = _lib.lib()
-    fn = L.cslgan_conv2d_wgrad_grouped_bf16out_f32 if (want_gw and gw.dtype == torch.bfloat16) else L.cslgan_conv2d_wgrad_grouped_f32
-    _timed("conv2d_wgrad_grouped" + ("" if (want_gw and not scratch) else "_normonly"), flop, nbytes, lambda: check(
-        fn(C.byref(d), _p(gy), _p(x), group, float(alpha), _p(gw), _p(sq), _stream()), "conv2d_wgrad_grouped"),
-        tag=lambda: "N%d %dx%d C%d K%d R%d s%d g%d" % (N, H, W, Cc, K, R, stride, group))
+    gw = _wgrad_outputs(g, group, x, want_gw, sq, out, bf16_gw=True)
+    nbytes = lambda: 4.0 * (x.numel() + gy.numel()) + (float(gw.element_size()) * (G * g.wsize) if want_gw else 0.0)
+    _launch(_WGRAD_NAME[want_gw and not scratch], "conv2d_wgrad_grouped_bf16out_f32" if _is_bf16(gw) else "conv2d_wgrad_grouped_f32",
+            (C.byref(d), _p(gy), _p(x), group, float(alpha), _p(gw), _p(sq)), g, nbytes, "g%d", (group,))
     return None if scratch else gw
 
 
-def _scaled_stored_ok(gy, sq, want_gw, out):
-    """Shapes cslgan_conv2d_wgrad_scaled_bf16s takes: a K tile (64 pixels) must lie inside one sample, fp32 gradient out, no norms."""
-    return (gy.shape[1] * gy.shape[2]) % 64 == 0 and sq is None and want_gw and (out is None or out.dtype == torch.float32)
-
-
-def _conv2d_wgrad_grouped_stored(gy, x, R, S, stride, pad, group, alpha, want_gw, sq, out, row_scale=None):
-    """conv2d_wgrad_grouped on bf16 gy and bf16 x (cslgan_conv2d_wgrad_grouped_bf16s): fp32 (or bf16) gw and / or sq.
-    row_scale [N] (clip-weighted sums): cslgan_conv2d_wgrad_scaled_bf16s — the fp32 weight meets each sample's accumulated product."""
-    _chk(gy, "gy", allow_bf16=True); _chk(x, "x", allow_bf16=True)
-    N, H, W, Cc = x.shape
-    N2, P, Q, K = gy.shape
-    P2, Q2 = conv_out_size(H, R, stride, pad), conv_out_size(W, S, stride, pad)
-    if N2 != N or (P2, Q2) != (P, Q):
-        raise RuntimeError("conv2d_wgrad: gy %s inconsistent with x %s" % (tuple(gy.shape), tuple(x.shape)))
-    if N % group:
-        raise RuntimeError("conv2d_wgrad: N=%d not divisible by group=%d" % (N, group))
-    G = N // group
-    d = ConvT(N, H, W, Cc, K, R, S, stride, pad, COMPUTE_BF16, P, Q)
-    gw = None
-    if want_gw:
-        gw = out if out is not None else torch.empty((G, K, R, S, Cc), device=x.device, dtype=torch.float32)
-        _chk(gw, "gw", allow_bf16=True)
-    if sq is not None:
-        _chk(sq, "sq")
-    flop = 2.0 * N * P * Q * K * R * S * Cc
-    nbytes = 2.0 * (N * H * W * Cc + N * P * Q * K) + (float(gw.element_size()) * (G * K * R * S * Cc) if want_gw else 0.0)
-    if row_scale is not None:
-        _chk(row_scale, "row_scale")
-        if row_scale.numel() != N:
-            raise RuntimeError("conv2d_wgrad: row_scale needs [N] factors")
-        _timed("conv2d_wgrad_grouped", flop, nbytes, lambda: check(
-            _lib.lib().cslgan_conv2d_wgrad_scaled_bf16s(C.byref(d), _p(gy), _p(x), _p(row_scale), group, float(alpha), _p(gw), _stream()),
-            "conv2d_wgrad_scaled_bf16s"), tag=lambda: "N%d %dx%d C%d K%d R%d s%d g%d bf16s scaled" % (N, H, W, Cc, K, R, stride, group))
-        return gw
-    _timed("conv2d_wgrad_grouped" + ("" if want_gw else "_normonly"), flop, nbytes, lambda: check(
-        _lib.lib().cslgan_conv2d_wgrad_grouped_bf16s(C.byref(d), _p(gy), _p(x), group, float(alpha), _p(gw),
-                                                     1 if _is_bf16(gw) else 0, _p(sq), _stream()), "conv2d_wgrad_grouped_bf16s"),
-        tag=lambda: "N%d %dx%d C%d K%d R%d s%d g%d bf16s" % (N, H, W, Cc, K, R, stride, group))
-    return gw
-
-
 def wgrad_blocks_eligible(gy_shape, x_shape, R, S, stride):
-    """Shapes cslgan_conv2d_wgrad_blocks_f32 takes (the LDS-resident fp32 kernel): mirrors wgh_eligible in csrc/igemm_wgh.hip."""
+    """Shapes cslgan_conv2d_wgrad_blocks_f32 takes (the LDS-resident fp32 kernel)."""
     _, P, Q, K = gy_shape
-    Cc = x_shape[-1]
-    return (_wgh_arith(S) and stride in (1, 2) and 2 <= S <= 5 and K % 64 == 0 and Cc % 64 == 0 and P % 8 == 0 and Q % 8 == 0)
+    return _wgh_shape(S, stride, K, x_shape[-1], P, Q)
 
 
 def conv2d_wgrad_blocks(gy, x, R, S, stride, pad, alpha, blocks):
     """Per-sample weight gradients of consecutive row blocks in ONE launch.  blocks: [(n_rows, gw_out or None, sq or None)] —
     gw_out [n_rows, K*R*S*C] fp32 (None: nothing stored), sq [n_rows] accumulated (None: no norms)."""
     _chk(gy, "gy"); _chk(x, "x")
-    N, H, W, Cc = x.shape
-    N2, P, Q, K = gy.shape
-    d, P2, Q2 = _conv_desc(N, H, W, Cc, K, R, S, stride, pad)
-    if N2 != N or (P2, Q2) != (P, Q) or sum(b[0] for b in blocks) != N:
-        raise RuntimeError("conv2d_wgrad_blocks: blocks / gy %s inconsistent with x %s" % (tuple(gy.shape), tuple(x.shape)))
+    g = _wgrad_geom("conv2d_wgrad_blocks", gy, x, R, S, stride, pad)
+    if sum(b[0] for b in blocks) != g.N:
+        raise RuntimeError("conv2d_wgrad_blocks: blocks inconsistent with x %s" % (tuple(x.shape),))
+    per_row = g.wsize
     nb = len(blocks)
     first = (C.c_int32 * nb)()
     gws, sqs = (C.c_void_p * nb)(), (C.c_void_p * nb)()
@@ -1050,19 +1061,17 @@ def conv2d_wgrad_blocks(gy, x, R, S, stride, pad, alpha, blocks):
         r0 += n
         if gw is not None:
             _chk(gw, "gw")
-            if gw.numel() != n * K * R * S * Cc:
-                raise RuntimeError("conv2d_wgrad_blocks: gw of block %d has %d elements, expected %d" % (i, gw.numel(), n * K * R * S * Cc))
+            if gw.numel() != n * per_row:
+                raise RuntimeError("conv2d_wgrad_blocks: gw of block %d has %d elements, expected %d" % (i, gw.numel(), n * per_row))
         if sq is not None:
             _chk(sq, "sq")
             if sq.numel() != n:
                 raise RuntimeError("conv2d_wgrad_blocks: sq of block %d needs %d entries" % (i, n))
         gws[i] = None if gw is None else gw.data_ptr()
         sqs[i] = None if sq is None else sq.data_ptr()
-    flop = 2.0 * N * P * Q * K * R * S * Cc
-    nbytes = 4.0 * (x.numel() + gy.numel() + sum(b[1].numel() for b in blocks if b[1] is not None))
-    _timed("conv2d_wgrad_grouped", flop, nbytes, lambda: check(
-        _lib.lib().cslgan_conv2d_wgrad_blocks_f32(C.byref(d), _p(gy), _p(x), float(alpha), nb, first, gws, sqs, _stream()),
-        "conv2d_wgrad_blocks"), tag=lambda: "N%d %dx%d C%d K%d R%d s%d g1 blocks%d" % (N, H, W, Cc, K, R, stride, nb))
+    nbytes = lambda: 4.0 * (x.numel() + gy.numel() + sum(b[1].numel() for b in blocks if b[1] is not None))
+    _launch("conv2d_wgrad_grouped", "conv2d_wgrad_blocks_f32", (C.byref(_auto_desc(g, "wgrad")), _p(gy), _p(x), float(alpha), nb, first, gws, sqs),
+            g, nbytes, "g1 blocks%d", (nb,))
 
 
 def conv2d_wgrad_dense(gy, x, R, S, stride=1, pad=0, alpha=1.0, row_scale=None, out=None, want_rows=False):
@@ -1070,40 +1079,29 @@ def conv2d_wgrad_dense(gy, x, R, S, stride=1, pad=0, alpha=1.0, row_scale=None, 
     vector-ALU kernel for 1..4 output channels.  out (optional, flat fp32 [K*R*S*C]): destination of the sum.
     want_rows: return the UN-SUMMED slabs [n_slabs, K*R*S*C] instead (the caller column-sums them together with other
     contributions in one launch: PrivacyEngine._add_dense_rows)."""
-    if (gy.dtype == torch.float32 and x.dtype == torch.bfloat16 and gy.shape[-1] == 1 and R == 1 and S == 1
-            and tuple(x.shape[1:3]) == (1, 1) and x.shape[-1] % 8 == 0):
+    g = _wgrad_geom("conv2d_wgrad_dense", gy, x, R, S, stride, pad)
+    N, K, Cc, P, Q = g.N, g.K, g.C, g.P, g.Q
+    if gy.dtype == torch.float32 and x.dtype == torch.bfloat16 and _head_bf16(g):
         # the critic's head on bf16 features: weighted sums of feature rows in slabs of 8 samples + a column sum
-        N = x.shape[0]
         slabs = conv2d_wgrad_grouped(gy, x, 1, 1, group=8 if N % 8 == 0 else 1, alpha=alpha, row_scale=row_scale)
-        res = torch.empty(x.shape[-1], device=x.device, dtype=torch.float32) if out is None else out
+        res = torch.empty(Cc, device=x.device, dtype=torch.float32) if out is None else out
         sum_rows(slabs.reshape(slabs.shape[0], -1), res.view(-1))
         return res.view(1, 1, 1, -1)
-    c3_mixed = (gy.dtype == torch.bfloat16 and x.dtype == torch.float32 and x.shape[-1] == 3 and row_scale is None
-                and _c3_layer(x.shape[1], x.shape[2], gy.shape[-1], R, S, stride, pad, gy.shape[2] in (16, 32, 64) and gy.shape[1] % (128 // gy.shape[2]) == 0))
-    if (gy.dtype == torch.bfloat16 or x.dtype == torch.bfloat16) and not c3_mixed and not (
-            gy.dtype == x.dtype and gy.shape[-1] % 8 == 0 and x.shape[-1] % 8 == 0
-            and (row_scale is None or (gy.shape[1] * gy.shape[2]) % 64 == 0)):
+    c3 = row_scale is None and _c3_wgrad(g)         # the grouped call below runs the first-layer kernel (group 1, fp32 slabs)
+    if ((gy.dtype == torch.bfloat16 or x.dtype == torch.bfloat16) and not (c3 and gy.dtype == torch.bfloat16 and x.dtype == torch.float32)
+            and not _wgrad_bf16s_ok(g, gy, x, True, None, None, row_scale)):
         gy, x = cast_f32(gy), cast_f32(x)
-    N, H, W, Cc = x.shape
-    _, P, Q, K = gy.shape
-    if (K <= 4 and Cc == 64 and stride == 1 and R * S <= 9 and P % 8 == 0 and Q % 8 == 0 and row_scale is None):
+    if _skinny(g) and row_scale is None:
         _chk(gy, "gy"); _chk(x, "x")
-        d, P2, Q2 = _conv_desc(N, H, W, Cc, K, R, S, stride, pad)
-        if (P2, Q2) != (P, Q):
-            raise RuntimeError("conv2d_wgrad_dense: gy %s inconsistent with x %s" % (tuple(gy.shape), tuple(x.shape)))
         nb = min(512, N * (P // 8) * (Q // 8))
-        partial = torch.empty((nb, K * R * S * Cc), device=x.device, dtype=torch.float32)
-        flop = 2.0 * N * P * Q * K * R * S * Cc
-        _timed("conv2d_wgrad_grouped", flop, 4.0 * (x.numel() + gy.numel()), lambda: check(
-            _lib.lib().cslgan_conv2d_wgrad_skinny_f32(C.byref(d), _p(gy), _p(x), float(alpha), _p(partial), nb, _stream()),
-            "conv2d_wgrad_skinny"), tag=lambda: "N%d %dx%d C%d K%d R%d skinny" % (N, H, W, Cc, K, R))
-        out = torch.empty(K * R * S * Cc, device=x.device, dtype=torch.float32) if out is None else out
+        partial = torch.empty((nb, g.wsize), device=x.device, dtype=torch.float32)
+        _launch("conv2d_wgrad_grouped", "conv2d_wgrad_skinny_f32", (C.byref(_auto_desc(g, "wgrad")), _p(gy), _p(x), float(alpha), _p(partial), nb),
+                g, lambda: 4.0 * (x.numel() + gy.numel()), "skinny", tag_stride=False)
+        out = torch.empty(g.wsize, device=x.device, dtype=torch.float32) if out is None else out
         sum_rows(partial, out)
         return out.view(K, R, S, Cc)
-    if Cc == 3 and row_scale is None and _c3_layer(H, W, K, R, S, stride, pad, Q in (16, 32, 64) and P % (128 // Q) == 0):
-        group = 1            # first-layer kernel: per-image gradients (19 KB each), summed below
-    else:
-        group = dense_wgrad_group(N, K, Cc, R, S, P * Q, stride=stride, out_hw=(P, Q))
+    # first-layer kernel: per-image gradients (19 KB each), summed below
+    group = 1 if c3 else dense_wgrad_group(N, K, Cc, R, S, P * Q, stride=stride, out_hw=(P, Q))
     slabs = conv2d_wgrad_grouped(gy, x, R, S, stride=stride, pad=pad, group=group, alpha=alpha, row_scale=row_scale)
     if want_rows and out is None:
         return slabs.reshape(slabs.shape[0], -1)
@@ -1419,7 +1417,7 @@ def latent_normal(seed, first_index, n, dim, first_index_dev=None, n_classes=1, 
 def f32_to_u8(src, scale, bias, out=None):
     """uint8 bytes of a dense fp32 device tensor in its memory order: clamp(src * scale + bias, 0, 1) * 255 + 0.5, truncated —
     bit-identical to util.denorm_celeba + util.save_image's quantisation on the host ((0.5, 0.5); (1, 0) for [0, 1] images)."""
-    _chk_dense(src, "src")
+    _chk(src, "src", any_order=True)
     if out is None:
         out = torch.empty(src.numel(), device=src.device, dtype=torch.uint8)
     elif out.dtype != torch.uint8 or not out.is_cuda or out.numel() != src.numel() or not out.is_contiguous():
