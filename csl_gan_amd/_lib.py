@@ -32,6 +32,7 @@ EXPORTS = [
     "cslgan_conv2d_c3_fwd_bf16out", "cslgan_conv2d_c3_wgrad_bf16gy", "cslgan_groupnorm_act_bf16s",
     "cslgan_conv2d_fwd_skinny_bf16in", "cslgan_conv2d_dgrad_skinny_bf16in", "cslgan_conv2d_wgrad_scaled_bf16s",
     "cslgan_latent_normal_f32", "cslgan_f32_to_u8",
+    "cslgan_attack_trials", "cslgan_rank_counts", "cslgan_softmax_max_rows_f32",
 ]
 
 
@@ -148,6 +149,9 @@ def lib():
         "cslgan_conv2d_dgrad_skinny_bf16in": [C.POINTER(ConvT), vp, vp, vp, i32, vp, vp],
         "cslgan_latent_normal_f32": [u64, u64, vp, i64, i32, vp, i32, i32, vp, vp],
         "cslgan_f32_to_u8": [vp, i64, f32, f32, vp, vp],
+        "cslgan_attack_trials": [vp, i64, vp, i64, i32, i32, u64, u64, i64, vp, vp],
+        "cslgan_rank_counts": [vp, i64, vp, i64, vp, vp, vp],
+        "cslgan_softmax_max_rows_f32": [vp, i64, i32, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

@@ -78,6 +78,23 @@ __device__ __forceinline__ bf16x3_t split4_bf16(const float4& v) {
     return r;
 }
 
+// ---- Philox4x32-10 ----------------------------------------------------------------------------------------------------------
+// The counter-based generator of every device random stream (include/cslgan.h "Device random streams"): Random123's
+// philox4x32_R(10, ...), counter (c0..c3), key (k0, k1), four 32-bit words out.
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                                              uint32_t k1, uint32_t out[4]) {
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        const uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
 // ---- epilogue pieces --------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float apply_act(float v, int act) {
     if (act == CSLGAN_ACT_LRELU02) v = v > 0.f ? v : 0.2f * v;

@@ -1426,6 +1426,54 @@ def f32_to_u8(src, scale, bias, out=None):
     return out
 
 
+def attack_trials(vt, vn, n, m, seed, first_trial, trials, out=None):
+    """hits[t], t < trials: train samples among the n best of trial first_trial + t of the membership-inference estimate
+    (mem_inf_attack.py:29-66; sampler and tie rule under include/cslgan.h "Audit sampler") — uint32 stored as an int32 device tensor.
+    vt [N] / vn [M]: the train / non-train scores; n + m <= 4096.  csl_gan_amd.audit.trial_hits is the host model."""
+    _chk(vt, "vt")
+    if vn is not None and vn.numel():
+        _chk(vn, "vn")
+    else:
+        vn = None
+    M = 0 if vn is None else vn.numel()
+    if out is None:
+        out = torch.empty(int(trials), device=vt.device, dtype=torch.int32)
+    elif out.dtype != torch.int32 or not out.is_cuda or out.numel() != int(trials) or not out.is_contiguous():
+        raise RuntimeError("attack_trials: out must be a contiguous int32 device tensor of %d entries" % int(trials))
+    check(_lib.lib().cslgan_attack_trials(_p(vt), vt.numel(), _p(vn), M, int(n), int(m), int(seed) & (2 ** 64 - 1),
+                                          int(first_trial) & (2 ** 64 - 1), int(trials), _p(out), _stream()), "attack_trials")
+    return out
+
+
+def rank_counts(a, b):
+    """(gt, eq), int32 device tensors of a.numel() entries: gt[i] = #{j : a[i] > b[j]}, eq[i] = #{j : a[i] == b[j]} (IEEE compares)."""
+    _chk(a, "a")
+    if b.numel():
+        _chk(b, "b")
+    elif not b.is_cuda:
+        raise RuntimeError("b must be a device tensor (csl_gan_amd.ops has no CPU path)")
+    gt = torch.empty(a.numel(), device=a.device, dtype=torch.int32)
+    eq = torch.empty(a.numel(), device=a.device, dtype=torch.int32)
+    check(_lib.lib().cslgan_rank_counts(_p(a), a.numel(), _p(b) if b.numel() else None, b.numel(), _p(gt), _p(eq), _stream()), "rank_counts")
+    return gt, eq
+
+
+def softmax_max_rows(logits, out=None):
+    """softmax(logits, 1).max(1)[0] of [B, n_classes <= 64] fp32 logits (mem_inf_attack.py:80) in one launch."""
+    _chk(logits, "logits")
+    if logits.dim() != 2:
+        raise RuntimeError("softmax_max_rows: logits must be [B, n_classes], got %s" % (tuple(logits.shape),))
+    B, Cn = logits.shape
+    if out is None:
+        out = torch.empty(B, device=logits.device, dtype=torch.float32)
+    else:
+        _chk(out, "out")
+        if out.numel() != B:
+            raise RuntimeError("softmax_max_rows: out has %d entries, expected %d" % (out.numel(), B))
+    check(_lib.lib().cslgan_softmax_max_rows_f32(_p(logits), B, Cn, _p(out), _stream()), "softmax_max_rows")
+    return out
+
+
 def row_l2norm(t2d):
     _chk(t2d, "t")
     n, L = t2d.shape

@@ -538,6 +538,38 @@ int cslgan_u8_to_f32_nhwc(const void* src_u8, const void* flip_u8, int N, int H,
  * by element otherwise. */
 int cslgan_f32_to_u8(const float* src, int64_t n, float scale, float bias, void* dst_u8, void* stream);
 
+/* ---- membership-inference audit (attack_kernels.hip; backward-compatible additions, ABI stays 7) ---------------------------------
+ * All three validate on the host before any launch, never allocate and never synchronise.
+ *
+ * Audit sampler.  Trial T = first_trial + t (mod 2^64) draws n of the N train scores and m of the M non-train scores without
+ * replacement: element j of a side's subset is v[pi(j)], j < k, with pi a keyed permutation of [0, N) built by the swap-or-not shuffle
+ * (Hoang, Morris, Rogaway, CRYPTO'12) on Philox4x32-10 ("Device random streams" above):
+ *     key     = the two halves of (seed xor 0x6D656D696E666174)
+ *     tag     = 0x7472616E for the train side, 0x6E6F6E74 for the non-train side;  T lo / T hi = the 32-bit halves of T
+ *     rounds  R = 8 * max(1, ceil(log2 N));  round r = 0 .. R-1, on x (starting at x = j):
+ *         K_r = mulhi32(word 0 of Philox(0xFFFFFFFF, r, T lo, T hi ^ tag), N)         (one per round; x < 2^31 is never 0xFFFFFFFF)
+ *         x'  = (K_r + N - x) mod N;   xh = max(x, x');   x <- x' iff word 0 of Philox(xh, r, T lo, T hi ^ tag) is odd
+ * Every round is an involution of [0, N), so pi is a permutation for every N: no cycle walking, no rejection, and pi(j) is computed
+ * by one lane without reference to any other.  csl_gan_amd.audit.subset_indices restates it in numpy.
+ *
+ * cslgan_attack_trials — attack() + _get_random_subset(), mem_inf_attack.py:29-66.  hits[t] (t < trials) = the number of train
+ * elements among the n best of trial first_trial + t.  The pool is the n train values followed by the m non-train values;
+ *     rank(i) = #{j : v[j] > v[i]} + #{j < i : v[j] == v[i]}        (Python's stable sorted(..., reverse=True): ties go to the train
+ *     hits    = #{i < n : rank(i) < n}                               sample, which precedes every non-train sample in the pool)
+ * 1 <= n <= N < 2^31, 0 <= m <= M < 2^31 (vn may be NULL when m == 0), n + m <= 4096 (the pool lives in LDS), trials < 2^31.
+ * One workgroup runs one trial, so a call may be cut into chunks of trials at will. */
+int cslgan_attack_trials(const float* vt, int64_t N, const float* vn, int64_t M, int n, int m, uint64_t seed, uint64_t first_trial,
+                         int64_t trials, uint32_t* hits, void* stream);
+
+/* Exact rank counts (an addition of this build; nothing in the reference): for i < na over b[nb],
+ *     gt[i] = #{j : a[i] > b[j]},   eq[i] = #{j : a[i] == b[j]}         (IEEE comparisons: -0 == +0; a NaN counts nowhere)
+ * from which the host derives AUC = sum(gt + eq / 2) / (na nb) and the TPR at an FPR budget.  na, nb < 2^31. */
+int cslgan_rank_counts(const float* a, int64_t na, const float* b, int64_t nb, uint32_t* gt, uint32_t* eq, void* stream);
+
+/* softmax(logits, 1).max(1)[0], mem_inf_attack.py:80:  out[b] = 1 / sum_j exp(l[b][j] - max_j l[b][j])  for [B, n_classes] fp32
+ * logits, 1 <= n_classes <= 64.  The sum runs in fp64: out is the rounded fp32 of the formula on the fp32 logits. */
+int cslgan_softmax_max_rows_f32(const float* logits, int64_t B, int n_classes, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
