@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import os
 import types
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -187,183 +187,176 @@ class _Clipper:
         return [(n, p.grad_sample) for n, p in self._e.module.named_parameters() if hasattr(p, "grad_sample")]
 
 
+# The filter geometry a layer's backward hands to collect(): one value inside the engine.
+_ConvArgs = NamedTuple("_ConvArgs", [(f, int) for f in "R S stride pad".split()])
+
+# One row block of a layer's backward and what becomes of it.  role: "norms" rows feed only per-sample norms, "dense" rows only their
+# sum, "private" rows are clipped per sample.  (pass_idx, n_pass): the block's slot in the layer's norm / grad_sample buffers.
+# fused: a block of a fused pass (PrivacyEngine.row_roles) — its norms-only norms go to the ("norms", id(p)) buffers instead of the
+# parameter's own, its dense sum is taken as un-reduced rows, and on a ghost layer dense rows wait for the private rows after them.
+_Block = NamedTuple("_Block", [("role", str), ("row0", int), ("n", int), ("scale", float), ("pass_idx", int), ("n_pass", int), ("fused", bool)])
+
+# The never-clipped rows that sit right before a ghost layer's private rows in a fused batch: gz / x span BOTH blocks, and the dense
+# sum of the first n_dense rows rides in the clip-weighted launch (row weight scale_dense instead of f_b * scale).
+_Joint = NamedTuple("_Joint", [("gz", torch.Tensor), ("x", torch.Tensor), ("n_dense", int), ("scale_dense", float)])
+
+# A clipped pass of a ghost layer, kept until clip() knows the factors.
+_GhostRows = NamedTuple("_GhostRows", [("gz", torch.Tensor), ("x", torch.Tensor), ("conv", _ConvArgs), ("scale", float), ("joint", Optional[_Joint])])
+
+# What adaptive_clip_fused computed for the clip() that follows it.  jobs: the (id(p), pass) of the joint launches whose row weights are
+# already written.
+_ClipHandoff = NamedTuple("_ClipHandoff", [("sq", torch.Tensor), ("f", torch.Tensor), ("f_mat", Optional[torch.Tensor]), ("mat_idx", list),
+                                           ("jobs", set), ("per_layer", bool)])
+
+
+class _Backward:
+    """One collect() call: the layer's (gz, x) and what the blocks handled so far leave for the ones after them — held: on a ghost
+    layer, the fused "dense" block waiting for private rows; launch / slabs: the outputs of the one-launch-for-all-blocks route."""
+    __slots__ = ("gz", "x", "conv", "has_bias", "ghost", "held", "launch", "slabs")
+
+    def __init__(self, gz, x, conv, has_bias, ghost, launch):
+        self.gz, self.x, self.conv, self.has_bias, self.ghost, self.held, self.launch, self.slabs = gz, x, conv, has_bias, ghost, None, launch, []
+
+
 class _LayerCollector:
-    """Receives (gz, x) from a layer's backward and launches the per-sample wgrad kernels."""
+    """Receives (gz, x) from a layer's backward and launches the per-sample wgrad kernels: collect() describes the row blocks (one
+    for a separate pass, PrivacyEngine.row_roles for a fused one) and _block() handles each."""
 
     def __init__(self, engine, layer):
         self.e, self.layer = engine, layer
 
     def collect(self, pass_idx, gz, x, R, S, stride, pad, has_bias):
-        e, layer = self.e, self.layer
-        B = x.shape[0]
-        n_pass = e._fwd_count[layer]
-        scale = float(B) if e.loss_reduction == "mean" else 1.0
-        w = layer.weight
-        K, Cc = gz.shape[-1], x.shape[-1]
+        e = self.e
+        mean = e.loss_reduction == "mean"
         if e.row_roles is not None:
-            return self._collect_roles(gz, x, R, S, stride, pad, has_bias)
-        if e.norms_only:
-            # adaptive-clipping pass (train.py:204-245): only the per-sample norms are consumed
-            _, sq = e._buffers(w, n_pass, B, 0)
-            _weight_sqnorms(gz, x, R, S, stride, pad, scale, sq[pass_idx])
-            if has_bias:
-                _, bsq = e._buffers(layer.bias, n_pass, B, 0)
-                ops.bias_grad_grouped(gz, group=1, alpha=scale, want_gb=False, sq=bsq[pass_idx])
-            return
-        n_private = e._n_private(n_pass)
-        if e.lean and pass_idx < n_pass - n_private:
-            # a pass that is never clipped (generated data in split mode): only its SUM is needed
-            e._add_dense(w, _dense_wgrad(gz, x, R, S, stride, pad, scale))
-            if has_bias:
-                e._add_dense_rows(layer.bias, _dense_bgrad(gz, scale))
-            return
-        if e.lean:
-            pass_idx, n_pass = pass_idx - (n_pass - n_private), n_private
-        if e._ghost_layer(gz, x, stride):
-            self._ghost_rows(pass_idx, n_pass, gz, x, R, S, stride, pad, scale, has_bias)
-            return
-        buf, sq = e._buffers(w, n_pass, B, K * R * S * Cc, e._gs_dtype)
-        ops.conv2d_wgrad_grouped(gz, x, R, S, stride=stride, pad=pad, group=1, alpha=scale,
-                                 out=buf[pass_idx].view(B, K, R, S, Cc), sq=sq[pass_idx])
-        if isinstance(layer, nn.Conv2d):
-            view = buf.view(n_pass, B, K, R, S, Cc).permute(0, 1, 2, 5, 3, 4)
+            # one fused forward carried several logical passes as consecutive row blocks (Trainer._fused_passes); each block is its
+            # own mean-reduced loss, hence its own x n scaling
+            blocks, r0 = [], 0
+            for role, n in e.row_roles:
+                blocks.append(_Block(role, r0, n, float(n) if mean else 1.0, 0, 1, True))
+                r0 += n
         else:
-            view = buf.view(n_pass, B, K, Cc)
-        view._cslgan_rows = buf.view(n_pass * B, -1)
-        w.grad_sample = view
-        if has_bias:
-            b = layer.bias
-            bbuf, bsq = e._buffers(b, n_pass, B, K)
-            ops.bias_grad_grouped(gz, group=1, alpha=scale, out=bbuf[pass_idx], sq=bsq[pass_idx])
-            bview = bbuf.view(n_pass, B, K)
-            bview._cslgan_rows = bbuf.view(n_pass * B, K)
-            b.grad_sample = bview
+            B = x.shape[0]
+            n_pass = e._fwd_count[self.layer]
+            shift = n_pass - e._n_private(n_pass)
+            role = "private"
+            if e.norms_only:
+                role = "norms"          # adaptive-clipping pass (train.py:204-245): only the per-sample norms are consumed
+            elif e.lean and pass_idx < shift:
+                role = "dense"          # a pass that is never clipped (generated data in split mode): only its SUM is needed
+            elif e.lean:
+                pass_idx, n_pass = pass_idx - shift, n_pass - shift
+            blocks = [_Block(role, 0, B, float(B) if mean else 1.0, pass_idx, n_pass, False)]
+        conv = _ConvArgs(R, S, stride, pad)
+        ghost = e._ghost_layer(gz, x, stride)
+        # equal row blocks of a layer the LDS-resident kernel takes: ONE launch for all blocks (three launches of 640 workgroups fill
+        # the chip's 512 slots 62 %, one of 1920 fills them 94 %); the blocks' outputs are collected and launched after the loop
+        launch = None
+        if (not ghost and 1 < len(blocks) <= 4 and e._gs_dtype == torch.float32 and isinstance(self.layer, nn.Conv2d)
+                and len({blk.n for blk in blocks}) == 1 and ops.wgrad_blocks_eligible(gz.shape, x.shape, R, S, stride)):
+            launch = []
+        st = _Backward(gz, x, conv, has_bias, ghost, launch)
+        for blk in blocks:
+            self._block(st, blk)
+        if st.held is not None:
+            self._flush_held(st)
+        if launch:
+            ops.conv2d_wgrad_blocks(gz, x, R, S, stride, pad, blocks[0].scale, launch)
+            for slabs in st.slabs:           # a dense block's per-sample slabs: column-summed by the launch that folds the dense sums
+                e._add_dense_rows(self.layer.weight, slabs)
 
+    def _block(self, st, blk):
+        """What "norms", "dense" and "private" rows do, on a materialised layer and on a ghost layer."""
+        e, layer, conv = self.e, self.layer, st.conv
+        w, b = layer.weight, layer.bias
+        role, row0, n, scale, pass_idx, n_pass, fused = blk
+        g_, x_ = (st.gz, st.x) if n == st.x.shape[0] else (st.gz[row0:row0 + n], st.x[row0:row0 + n])
+        if role == "norms":
+            _, sq = e._buffers(("norms", id(w)) if fused else w, n_pass, n, 0)
+            if st.launch is not None:
+                st.launch.append((n, None, sq[pass_idx]))
+            else:
+                _weight_sqnorms(g_, x_, conv, scale, sq[pass_idx])
+            if st.has_bias:
+                _, bsq = e._buffers(("norms", id(b)) if fused else b, n_pass, n, 0)
+                ops.bias_grad_grouped(g_, group=1, alpha=scale, want_gb=False, sq=bsq[pass_idx])
+        elif role == "dense":
+            if st.held is not None:
+                self._flush_held(st)
+            if st.ghost and fused:
+                st.held = blk
+            elif st.launch is not None:
+                st.slabs.append(torch.empty((n, w.numel()), device=g_.device, dtype=torch.float32))
+                st.launch.append((n, st.slabs[-1], None))
+            else:
+                r = _dense_wgrad(g_, x_, conv, scale, rows=fused)
+                (e._add_dense_rows if r.dim() == 2 else e._add_dense)(w, r)
+            if st.has_bias:
+                # per-sample bias gradients [n, K]: their column sum is taken by the launch that folds the dense sums into summed_grad
+                e._add_dense_rows(b, ops.bias_grad_grouped(g_, group=1, alpha=scale))
+        else:
+            K = g_.shape[-1]
+            if st.ghost:
+                # materialize="ghost": only the norms are computed now (Gram kernel); (gz, x) are kept until clip() knows the factors
+                # and forms sum_b f_b g_b with ONE weighted dense wgrad — the per-sample gradient tensor (1.7 GB for the critic's
+                # last conv at B=128) is never written or re-read
+                joint, held = None, st.held
+                if held is not None and held.row0 + held.n == row0:
+                    end = row0 + n
+                    joint, st.held = _Joint(st.gz[held.row0:end], st.x[held.row0:end], held.n, held.scale), None
+                _, sq = e._buffers(w, n_pass, n, 0)
+                ops.conv2d_wgrad_sqnorm_gram(g_, x_, conv.R, conv.S, stride=conv.stride, pad=conv.pad, alpha=scale, sq=sq[pass_idx])
+                e._ghost.setdefault(id(w), {})[pass_idx] = _GhostRows(g_, x_, conv, scale, joint)
+            else:
+                buf, sq = e._buffers(w, n_pass, n, w.numel(), e._gs_dtype)
+                if st.launch is not None:
+                    st.launch.append((n, buf[pass_idx], sq[pass_idx]))
+                else:
+                    ops.conv2d_wgrad_grouped(g_, x_, conv.R, conv.S, stride=conv.stride, pad=conv.pad, group=1, alpha=scale,
+                                             out=buf[pass_idx].view(n, K, conv.R, conv.S, x_.shape[-1]), sq=sq[pass_idx])
+                self._install_weight_rows(buf, K, conv)
+            if st.has_bias:
+                bbuf, bsq = e._buffers(b, n_pass, n, K)
+                ops.bias_grad_grouped(g_, group=1, alpha=scale, out=bbuf[pass_idx], sq=bsq[pass_idx])
+                self._install_bias_rows(bbuf)
 
-def _weight_sqnorms(gz, x, R, S, stride, pad, scale, sq_row):
-    """sq_row[n] += ||scale * per-sample weight gradient||^2 without storing the gradient: from the two pixel-Gram
-    matrices where that is the cheaper form (few output pixels), else from the product kernel's epilogue."""
-    if ops.gram_norms_preferred(gz.shape, x.shape, stride):
-        ops.conv2d_wgrad_sqnorm_gram(gz, x, R, S, stride=stride, pad=pad, alpha=scale, sq=sq_row)
-    else:
-        ops.conv2d_wgrad_grouped(gz, x, R, S, stride=stride, pad=pad, group=1, alpha=scale, want_gw=False, sq=sq_row)
+    def _flush_held(self, st):
+        """Held dense rows that no private block picked up: their plain dense sum."""
+        h, st.held = st.held, None
+        self.e._add_dense(self.layer.weight, _dense_wgrad(st.gz[h.row0:h.row0 + h.n], st.x[h.row0:h.row0 + h.n], st.conv, h.scale))
 
+    def _install_weight_rows(self, buf, K, conv):
+        """w.grad_sample: the [n_pass, n, numel] buffer (filters in KRSC memory order) under the fork's logical shape, and the dense
+        [n_pass * n, numel] rows behind it as _cslgan_rows."""
+        n_pass, n = buf.shape[:2]
+        if isinstance(self.layer, nn.Conv2d):
+            view = buf.view(n_pass, n, K, conv.R, conv.S, -1).permute(0, 1, 2, 5, 3, 4)
+        else:
+            view = buf.view(n_pass, n, K, -1)
+        view._cslgan_rows = buf.view(n_pass * n, -1)
+        self.layer.weight.grad_sample = view
 
-def _ghost_rows(self, pass_idx, n_pass, gz, x, R, S, stride, pad, scale, has_bias, joint=None):
-    """materialize="ghost": a clipped pass of a layer whose norms come from the Gram kernel.  Only the norms are
-    computed now; (gz, x) are kept until clip() knows the factors and forms sum_b f_b g_b with ONE weighted dense
-    wgrad — the per-sample gradient tensor (1.7 GB for the critic's last conv at B=128) is never written or re-read."""
-    e, layer = self.e, self.layer
-    w = layer.weight
-    n = x.shape[0]
-    _, sq = e._buffers(w, n_pass, n, 0)
-    ops.conv2d_wgrad_sqnorm_gram(gz, x, R, S, stride=stride, pad=pad, alpha=scale, sq=sq[pass_idx])
-    # joint = (gz, x, n_dense, scale_dense): the never-clipped rows that sit right before these rows in a fused batch;
-    # their dense sum rides in the same clip-weighted launch (weight scale_dense instead of f_b * scale)
-    e._ghost.setdefault(id(w), {})[pass_idx] = (gz, x, R, S, stride, pad, scale, joint)
-    if has_bias:
-        b = layer.bias
-        K = gz.shape[-1]
-        bbuf, bsq = e._buffers(b, n_pass, n, K)
-        ops.bias_grad_grouped(gz, group=1, alpha=scale, out=bbuf[pass_idx], sq=bsq[pass_idx])
+    def _install_bias_rows(self, bbuf):
+        n_pass, n, K = bbuf.shape
         bview = bbuf.view(n_pass, n, K)
         bview._cslgan_rows = bbuf.view(n_pass * n, K)
-        b.grad_sample = bview
+        self.layer.bias.grad_sample = bview
 
 
-_LayerCollector._ghost_rows = _ghost_rows
+def _weight_sqnorms(gz, x, conv, scale, sq_row):
+    """sq_row[n] += ||scale * per-sample weight gradient||^2 without storing the gradient: from the two pixel-Gram
+    matrices where that is the cheaper form (few output pixels), else from the product kernel's epilogue."""
+    if ops.gram_norms_preferred(gz.shape, x.shape, conv.stride):
+        ops.conv2d_wgrad_sqnorm_gram(gz, x, conv.R, conv.S, stride=conv.stride, pad=conv.pad, alpha=scale, sq=sq_row)
+    else:
+        ops.conv2d_wgrad_grouped(gz, x, conv.R, conv.S, stride=conv.stride, pad=conv.pad, group=1, alpha=scale, want_gw=False, sq=sq_row)
 
 
-def _dense_wgrad(gz, x, R, S, stride, pad, scale, row_scale=None, out=None, rows=False):
+def _dense_wgrad(gz, x, conv, scale, row_scale=None, out=None, rows=False):
     """rows: the un-summed slabs [n, numel] (for PrivacyEngine._add_dense_rows) where the layer's dense gradient is made of slabs."""
-    r = ops.conv2d_wgrad_dense(gz, x, R, S, stride=stride, pad=pad, alpha=scale, row_scale=row_scale, out=out, want_rows=rows)
+    r = ops.conv2d_wgrad_dense(gz, x, conv.R, conv.S, stride=conv.stride, pad=conv.pad, alpha=scale, row_scale=row_scale, out=out,
+                               want_rows=rows)
     return r if (rows and r.dim() == 2 and r.shape[0] > 1) else r.reshape(-1)
-
-
-def _dense_bgrad(gz, scale):
-    """Per-sample bias gradients [N, K] of a never-clipped row block: their column sum is taken by the launch that folds the dense
-    sums into summed_grad (PrivacyEngine._add_dense_rows), not by a launch of its own."""
-    return ops.bias_grad_grouped(gz, group=1, alpha=scale)
-
-
-def _collect_roles(self, gz, x, R, S, stride, pad, has_bias):
-    """One fused forward carried several logical passes as consecutive row blocks (Trainer.train_D_fused):
-    ("norms", n) rows feed only per-sample norms, ("dense", n) rows only their sum, ("private", n) rows are
-    materialised per sample.  Each block is its own mean-reduced loss, hence its own x n scaling."""
-    e, layer = self.e, self.layer
-    w = layer.weight
-    K, Cc = gz.shape[-1], x.shape[-1]
-    r0 = 0
-    ghost = e._ghost_layer(gz, x, stride)
-    held = None                       # ghost layer: ("dense" rows start, count, scale) waiting for the private rows after them
-    # equal row blocks of a layer the LDS-resident kernel takes: ONE launch for all blocks (three launches of 640 workgroups fill
-    # the chip's 512 slots 62 %, one of 1920 fills them 94 %); the blocks' outputs are collected here and launched after the loop
-    blocks = None
-    if (not ghost and len(e.row_roles) > 1 and e._gs_dtype == torch.float32 and isinstance(layer, nn.Conv2d)
-            and len({n for _, n in e.row_roles}) == 1 and len(e.row_roles) <= 4 and ops.wgrad_blocks_eligible(gz.shape, x.shape, R, S, stride)):
-        blocks = []
-    for role, n in e.row_roles:
-        g_, x_ = gz[r0:r0 + n], x[r0:r0 + n]
-        row0 = r0
-        r0 += n
-        scale = float(n) if e.loss_reduction == "mean" else 1.0
-        if role == "norms":
-            _, sq = e._buffers(("norms", id(w)), 1, n, 0)
-            if blocks is not None:
-                blocks.append((n, None, sq[0], None))
-            else:
-                _weight_sqnorms(g_, x_, R, S, stride, pad, scale, sq[0])
-            if has_bias:
-                _, bsq = e._buffers(("norms", id(layer.bias)), 1, n, 0)
-                ops.bias_grad_grouped(g_, group=1, alpha=scale, want_gb=False, sq=bsq[0])
-        elif role == "dense":
-            if held is not None:
-                e._add_dense(w, _dense_wgrad(gz[held[0]:held[0] + held[1]], x[held[0]:held[0] + held[1]], R, S, stride, pad, held[2]))
-                held = None
-            if ghost:
-                held = (row0, n, scale)
-            elif blocks is not None:
-                blocks.append((n, torch.empty((n, K * R * S * Cc), device=gz.device, dtype=torch.float32), None, "dense"))
-            else:
-                r = _dense_wgrad(g_, x_, R, S, stride, pad, scale, rows=True)
-                (e._add_dense_rows if r.dim() == 2 else e._add_dense)(w, r)
-            if has_bias:
-                e._add_dense_rows(layer.bias, _dense_bgrad(g_, scale))
-        elif ghost:
-            joint = None
-            if held is not None and held[0] + held[1] == row0:
-                joint = (gz[held[0]:r0], x[held[0]:r0], held[1], held[2])
-                held = None
-            self._ghost_rows(0, 1, g_, x_, R, S, stride, pad, scale, has_bias, joint=joint)
-        else:
-            buf, sq = e._buffers(w, 1, n, K * R * S * Cc, e._gs_dtype)
-            if blocks is not None:
-                blocks.append((n, buf[0], sq[0], None))
-            else:
-                ops.conv2d_wgrad_grouped(g_, x_, R, S, stride=stride, pad=pad, group=1, alpha=scale,
-                                         out=buf[0].view(n, K, R, S, Cc), sq=sq[0])
-            view = buf.view(1, n, K, R, S, Cc).permute(0, 1, 2, 5, 3, 4) if isinstance(layer, nn.Conv2d) else buf.view(1, n, K, Cc)
-            view._cslgan_rows = buf.view(n, -1)
-            w.grad_sample = view
-            if has_bias:
-                b = layer.bias
-                bbuf, bsq = e._buffers(b, 1, n, K)
-                ops.bias_grad_grouped(g_, group=1, alpha=scale, out=bbuf[0], sq=bsq[0])
-                bview = bbuf.view(1, n, K)
-                bview._cslgan_rows = bbuf.view(n, K)
-                b.grad_sample = bview
-
-    if held is not None:
-        e._add_dense(w, _dense_wgrad(gz[held[0]:held[0] + held[1]], x[held[0]:held[0] + held[1]], R, S, stride, pad, held[2]))
-    if blocks:
-        n = blocks[0][0]
-        ops.conv2d_wgrad_blocks(gz, x, R, S, stride, pad, float(n) if e.loss_reduction == "mean" else 1.0, [(bl[0], bl[1], bl[2]) for bl in blocks])
-        for _, slabs, _, kind in blocks:
-            if kind == "dense":              # the block's sum: its per-sample slabs are column-summed by the launch that folds the dense sums
-                e._add_dense_rows(w, slabs)
-
-
-_LayerCollector._collect_roles = _collect_roles
 
 
 class PrivacyEngine(PerSampleSink):
@@ -392,10 +385,11 @@ class PrivacyEngine(PerSampleSink):
         # (a few KB per sample) stay fp32.
         self._gs_dtype = torch.bfloat16 if grad_sample_dtype == "bf16" else torch.float32
         self.materialize, self.norms_only = materialize, False
-        self.row_roles = None                   # set by Trainer.train_D_fused for one fused forward/backward
+        self.row_roles = None                   # set by Trainer._fused_passes for one fused forward/backward
         self._sq_arena, self._sq_off = None, 0
         self._dense = {}
-        self._ghost = {}                        # id(weight) -> {pass: (gz, x, R, S, stride, pad, scale)} awaiting clip()
+        self._ghost = {}                        # id(weight) -> {pass: _GhostRows} awaiting clip()
+        self._pre = None                        # _ClipHandoff left by adaptive_clip_fused for the next clip()
         self._clip_side = None
         self.module = module
         self.batch_size, self.sample_size = batch_size, sample_size
@@ -475,7 +469,7 @@ class PrivacyEngine(PerSampleSink):
         statistic r of every layer from the "norms" rows, the clip norm(s) r * scalar, the clip factors of the clipped rows, the
         factor rows of the materialised layers and the row weights of the joint clip-weighted launches — what clip() would otherwise
         assemble from a dozen small launches.  Returns r, or None when this step's state does not fit (then the caller runs the
-        separate ops).  clip() picks the results up (self._pre) if nothing invalidated them in between."""
+        separate ops).  clip() picks the results up (self._pre, a _ClipHandoff) if nothing invalidated them in between."""
         ps = self.params
         if not ps or not ps[0].is_cuda or any(("norms", id(p)) not in self._bufs or id(p) not in self._bufs for p in ps):
             return None
@@ -484,18 +478,13 @@ class PrivacyEngine(PerSampleSink):
             return None
         adapt = [self._bufs[("norms", id(p))][1].reshape(-1) for p in ps]
         rows = [self._bufs[id(p)][1].reshape(-1) for p in ps]
-        mat_idx = [i for i, p in enumerate(ps) if id(p) not in self._ghost]
+        mat_idx = self._layer_idx(ghost=False)
         jobs, done = [], set()
         for i, p in enumerate(ps):
-            stash = self._ghost.get(id(p))
-            for k, (gz, x, R, S, stride, pad, sc, joint) in sorted((stash or {}).items()):
-                if joint is not None:
-                    n_d, scale_d = joint[2], joint[3]
-                    key = ("rs", id(p), n_d, float(scale_d), B, str(gz.device))
-                    rs = self._idx_cache.get(key)
-                    if rs is None:
-                        rs = self._idx_cache[key] = torch.full((n_d + B,), float(scale_d), device=gz.device, dtype=torch.float32)
-                    jobs.append((rs[n_d:], i, k * B, float(sc)))
+            for k, g in sorted(self._ghost.get(id(p), {}).items()):
+                if g.joint is not None:
+                    rs = self._joint_row_weights(p, g.joint, B, g.gz.device)
+                    jobs.append((rs[g.joint.n_dense:], i, k * B, float(g.scale)))
                     done.add((id(p), k))
         if len(jobs) > 16:
             return None
@@ -504,7 +493,7 @@ class PrivacyEngine(PerSampleSink):
                                                mat_layers=mat_idx if (per_layer and len(mat_idx) < len(ps)) else (), jobs=jobs)
         self.set_max_grad_norm_device(c)
         self._per_layer = bool(per_layer)
-        self._pre = dict(sq=sq, f=f, f_mat=f_mat, mat_idx=mat_idx, jobs=done, per_layer=bool(per_layer))
+        self._pre = _ClipHandoff(sq, f, f_mat, mat_idx, done, bool(per_layer))
         return r
 
     def norms_rows_sqnorms(self) -> torch.Tensor:
@@ -594,7 +583,7 @@ class PrivacyEngine(PerSampleSink):
         which is what must be used after a caller edited p.grad_sample in place (train.py:447)."""
         stored = [self._bufs[id(p)][1].reshape(-1) for p in self.params]
         if recompute:
-            mat = [i for i, p in enumerate(self.params) if id(p) not in self._ghost]
+            mat = self._layer_idx(ghost=False)
             fresh = ops.sample_sqnorm([_rows(self.params[i].grad_sample) for i in mat])
             for j, i in enumerate(mat):
                 stored[i] = fresh[j]
@@ -604,7 +593,7 @@ class PrivacyEngine(PerSampleSink):
     def clip(self, recompute_norms=False):
         """Per-sample clip factors + clipped sum into p.summed_grad (a SUM over samples)."""
         ps = self.params
-        mat_idx = [i for i, p in enumerate(ps) if id(p) not in self._ghost]
+        mat_idx = self._layer_idx(ghost=False)
         mats = [_rows(ps[i].grad_sample) for i in mat_idx]
         n_pass, B = self._bufs[id(ps[0])][1].shape
         if self.accum_passes and n_pass > 1:
@@ -618,11 +607,12 @@ class PrivacyEngine(PerSampleSink):
             sq = None
         n_private = self._n_private(n_pass)
         per_layer = self._per_layer
-        pre, self._pre = getattr(self, "_pre", None), None
-        if pre is not None and (recompute_norms or pre["mat_idx"] != mat_idx or pre["per_layer"] != per_layer or pre["sq"].shape[1] != n_pass * B):
+        # the hand-off of adaptive_clip_fused holds only if nothing changed what it was computed for
+        pre, self._pre = self._pre, None
+        if pre is not None and (recompute_norms or pre.mat_idx != mat_idx or pre.per_layer != per_layer or pre.sq.shape[1] != n_pass * B):
             pre = None
         if pre is not None:        # adaptive_clip_fused computed them in the launch that made the clip norms
-            sq, f = pre["sq"], pre["f"]
+            sq, f = pre.sq, pre.f
         else:
             if sq is None:
                 sq = self.sample_sqnorms(recompute=recompute_norms)
@@ -636,15 +626,15 @@ class PrivacyEngine(PerSampleSink):
         if len(mat_idx) == len(ps):
             ops.clip_accum_noise(mats, outs, factors=f)
         else:
-            if pre is not None and per_layer and pre["f_mat"] is not None:
-                f_mat = pre["f_mat"]
+            if pre is not None and per_layer and pre.f_mat is not None:
+                f_mat = pre.f_mat
             else:
                 f_mat = f[self._index_tensor(mat_idx, f.device)].contiguous() if per_layer else f
-            self._jobs_done = pre["jobs"] if pre is not None else ()
+            jobs_done = pre.jobs if pre is not None else ()
             ops.clip_accum_noise(mats, [outs[i] for i in mat_idx], factors=f_mat)
             # ghost layers: sum_b f_b g_b as one clip-weighted dense wgrad per pass.  The layers' launches are independent and each
             # under-fills the chip (128 - 640 workgroups): every second one goes to a second stream (CSLGAN_CLIP_STREAM=0: off)
-            ghosts = [i for i, p in enumerate(ps) if self._ghost.get(id(p)) is not None]
+            ghosts = self._layer_idx(ghost=True)
             two = os.environ.get("CSLGAN_CLIP_STREAM", "1") == "1" and len(ghosts) > 1
             cur = torch.cuda.current_stream()
             if two:
@@ -652,10 +642,8 @@ class PrivacyEngine(PerSampleSink):
                     self._clip_side = torch.cuda.Stream(device=ps[0].device)
                 self._clip_side.wait_stream(cur)
             for n_g, i in enumerate(ghosts):
-                p = ps[i]
-                stash = self._ghost.get(id(p))
                 with torch.cuda.stream(self._clip_side if (two and n_g % 2 == 1) else cur):
-                    self._clip_ghost_layer(i, p, stash, f, per_layer, n_pass, B, outs)
+                    self._clip_ghost_layer(ps[i], (f[i] if per_layer else f).reshape(n_pass, B), outs[i], jobs_done)
             if two:
                 cur.wait_stream(self._clip_side)
         if self._dense:       # sums of the never-clipped passes (lean modes)
@@ -664,29 +652,39 @@ class PrivacyEngine(PerSampleSink):
             ops.clip_accum_noise([t if t.dim() == 2 else t.view(1, -1) for t in segs], [outs[i] for i in idx], beta=1.0, ragged=True)
         self._accumulated = False
 
-    def _clip_ghost_layer(self, i, p, stash, f, per_layer, n_pass, B, outs):
-        """One ghost layer of clip(): sum_b f_b g_b as clip-weighted dense weight gradient(s) into outs[i]."""
-        fi = (f[i] if per_layer else f).reshape(n_pass, B)
+    def _clip_ghost_layer(self, p, fi, out, jobs_done):
+        """One ghost layer of clip(): sum_b f_b g_b as clip-weighted dense weight gradient(s) into out.  fi [n_pass, B]: the layer's
+        clip factors; jobs_done: the (id(p), pass) whose joint row weights adaptive_clip_fused wrote already."""
+        stash = self._ghost[id(p)]
         total = None
         single = len(stash) == 1            # one clipped pass: the weighted sum is written straight into summed_grad
-        for k, (gz, x, R, S, stride, pad, scale, joint) in sorted(stash.items()):
-            dst = outs[i] if single else None
-            if joint is None:
-                part = _dense_wgrad(gz, x, R, S, stride, pad, scale, row_scale=fi[k].contiguous(), out=dst)
+        for k, g in sorted(stash.items()):
+            dst = out if single else None
+            if g.joint is None:
+                part = _dense_wgrad(g.gz, g.x, g.conv, g.scale, row_scale=fi[k].contiguous(), out=dst)
             else:
-                gzj, xj, n_d, scale_d = joint
                 # row weights of the joint launch: [scale_d] * n_d (never-clipped rows; a constant prefix kept across
                 # steps) followed by f_b * scale — one launch per step instead of fill + mul + cat
-                key = ("rs", id(p), n_d, float(scale_d), B, str(f.device))
-                rs = self._idx_cache.get(key)
-                if rs is None:
-                    rs = self._idx_cache[key] = torch.full((n_d + B,), float(scale_d), device=f.device, dtype=torch.float32)
-                if (id(p), k) not in getattr(self, "_jobs_done", ()):      # (adaptive_clip_fused wrote the suffix already)
-                    torch.mul(fi[k], float(scale), out=rs[n_d:])
-                part = _dense_wgrad(gzj, xj, R, S, stride, pad, 1.0, row_scale=rs, out=dst)
+                rs = self._joint_row_weights(p, g.joint, fi.shape[1], fi.device)
+                if (id(p), k) not in jobs_done:
+                    torch.mul(fi[k], float(g.scale), out=rs[g.joint.n_dense:])
+                part = _dense_wgrad(g.joint.gz, g.joint.x, g.conv, 1.0, row_scale=rs, out=dst)
             total = part if total is None else total.add_(part)
         if not single:
-            outs[i].copy_(total)
+            out.copy_(total)
+
+    def _joint_row_weights(self, p, joint, B, device):
+        """The cached row-weight vector of a joint launch: [scale_dense] * n_dense, then B entries for f_b * scale that the caller
+        (or the adaptive_clip launch) fills each step."""
+        key = ("rs", id(p), joint.n_dense, float(joint.scale_dense), B, str(device))
+        rs = self._idx_cache.get(key)
+        if rs is None:
+            rs = self._idx_cache[key] = torch.full((joint.n_dense + B,), float(joint.scale_dense), device=device, dtype=torch.float32)
+        return rs
+
+    def _layer_idx(self, ghost):
+        """Positions in self.params of the ghost layers' weights (ghost=True) or of every materialised parameter (False)."""
+        return [i for i, p in enumerate(self.params) if (id(p) in self._ghost) == ghost]
 
     def _index_tensor(self, idx, device):
         """Device copy of a small index list, uploaded once (a host->device copy per step is also not graph-capturable)."""
@@ -819,7 +817,7 @@ class PrivacyEngine(PerSampleSink):
         self._sq_off = 0
         self._dense.clear()
         self._ghost.clear()
-        self._pre, self._jobs_done = None, ()
+        self._pre = None
         self.row_roles = None
         for p in self.params:
             if hasattr(p, "grad_sample"):

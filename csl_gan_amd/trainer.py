@@ -173,13 +173,9 @@ class Trainer:
     def update_adaptive_clipping_params(self):
         o, D, pe = self.opt, self.D, self.privacy_engine
         util.zero_grad(D)
-        if "ms_adapt" in self.explicit:
-            img, labels = self.explicit["ms_adapt"], self.explicit.get("ms_adapt_labels")
-        elif o.public_set_size > 0:
-            img, labels = next(iter(self.public_dataloader))
-            img, labels = img.clone(), (labels.clone() if o.conditional else None)
-        else:
-            img, labels = self.mean_sampler.sample(o.batch_size)
+        img, labels = self._adaptive_batch()
+        if "ms_adapt" not in self.explicit and o.public_set_size > 0:      # the public loader's batch: this pass keeps its own copy
+            img, labels = img.clone(), (None if labels is None else labels.clone())
         img = img.to(o.d_device)
         labels = None if labels is None else labels.to(o.d_device)
         if o.grad_clip_split:
@@ -202,11 +198,24 @@ class Trainer:
                 from .distributed import average_across_ranks
                 r = average_across_ranks(r.contiguous(), use_max=o.adaptive_stat == "max")
             self.last["adaptive_stats"] = r
-            if o.use_grad_clip_per_layer:
-                pe.set_max_grad_norm_device(r * o.adaptive_scalar)
-            else:
-                pe.set_max_grad_norm_device((r.norm(2) * o.adaptive_scalar).reshape(1))
+            pe.set_max_grad_norm_device(self._adaptive_clip_norm(r))
         self.d_optimizer.zero_grad()
+
+    def _adaptive_batch(self):
+        """The batch the adaptive clip norm is estimated on (train.py:206-212): an explicit one, else the public loader's next batch,
+        else mean samples."""
+        o = self.opt
+        if "ms_adapt" in self.explicit:
+            return self.explicit["ms_adapt"], self.explicit.get("ms_adapt_labels")
+        if o.public_set_size > 0:
+            img, labels = next(iter(self.public_dataloader))
+            return img, (labels if o.conditional else None)
+        return self.mean_sampler.sample(o.batch_size)
+
+    def _adaptive_clip_norm(self, r):
+        """train.py:233-243: the statistic r [n_params] times adaptive_scalar per layer, or its 2-norm times adaptive_scalar flat."""
+        o = self.opt
+        return r * o.adaptive_scalar if o.use_grad_clip_per_layer else (r.norm(2) * o.adaptive_scalar).reshape(1)
 
     # ---- train.py:310-329 ---------------------------------------------------------------------
     def update_grad_logging(self):
@@ -395,13 +404,7 @@ class Trainer:
         adaptive = o.grad_clip_mode.startswith("adaptive")
         blocks, roles, lab = [], [], []
         if adaptive:
-            if "ms_adapt" in self.explicit:
-                xa, ya = self.explicit["ms_adapt"], self.explicit.get("ms_adapt_labels")
-            elif o.public_set_size > 0:
-                xa, ya = next(iter(self.public_dataloader))
-                ya = ya if o.conditional else None
-            else:
-                xa, ya = self.mean_sampler.sample(o.batch_size)
+            xa, ya = self._adaptive_batch()
             xa = xa.to(o.d_device)
             blocks.append(xa); roles.append(("norms", xa.size(0))); lab.append(None if ya is None else ya.to(o.d_device))
         yg = None if y is None else y.to(o.g_device)
@@ -468,7 +471,7 @@ class Trainer:
                         from .distributed import average_across_ranks
                         self._join_penalty_stream_at_boundary()
                         r = average_across_ranks(r.contiguous(), use_max=o.adaptive_stat == "max")
-                    pe.set_max_grad_norm_device(r * o.adaptive_scalar if o.use_grad_clip_per_layer else (r.norm(2) * o.adaptive_scalar).reshape(1))
+                    pe.set_max_grad_norm_device(self._adaptive_clip_norm(r))
                 self.last["adaptive_stats"] = r
         pe.row_roles = None
         return d_fake, d_fake_aux, d_fake_loss, d_fake_aux_loss, fake_img.detach(), d_real, d_real_aux, d_real_loss, d_real_aux_loss
@@ -562,12 +565,7 @@ class Trainer:
                 torch.cuda.current_stream().wait_stream(self._gp_stream)
             if use_grad_clip:
                 pe.accumulate_batch()
-            with torch.no_grad():
-                pairs = [(p.summed_grad, g) for p, g in zip(D.parameters(), penalty_grad) if g is not None]
-                if pairs:
-                    torch._foreach_add_([t for t, _ in pairs], [g for _, g in pairs], alpha=o.batch_size)
-                if self.explicit.get("keep"):
-                    self.last["penalty_grads"] = [None if g is None else g.clone() for g in penalty_grad]
+            self._add_penalty_grads(penalty_grad)
         elif len(o.penalty) > 0:
             pen_real, pen_labels = self.get_penalty_data(img, labels)
             alpha = self.explicit.get("alpha")
@@ -581,12 +579,7 @@ class Trainer:
                         pe.accumulate_batch()
                     penalty = calc_penalty(D, o.penalty, pen_real, pen_labels, fake_img, y, **kw)
                     penalty_grad = self._penalty_param_grads(penalty)
-                with torch.no_grad():
-                    pairs = [(p.summed_grad, g) for p, g in zip(D.parameters(), penalty_grad) if g is not None]
-                    if pairs:      # summed_grad is a sum, not a mean (train.py:431); one multi-tensor launch
-                        torch._foreach_add_([t for t, _ in pairs], [g for _, g in pairs], alpha=o.batch_size)
-                    if self.explicit.get("keep"):
-                        self.last["penalty_grads"] = [None if g is None else g.clone() for g in penalty_grad]
+                self._add_penalty_grads(penalty_grad)
             else:
                 penalty = calc_penalty(D, o.penalty, pen_real, pen_labels, fake_img, y, **kw)
                 d_loss = d_loss + penalty
@@ -640,6 +633,16 @@ class Trainer:
             self.last.update(d_real_loss=d_real_loss.detach(), d_fake_loss=d_fake_loss.detach(), penalty=penalty.detach(),
                              d_real=d_real.detach(), d_fake=d_fake.detach(), fake_img=fake_img)
             self._commit_stats()
+
+    def _add_penalty_grads(self, penalty_grad):
+        """train.py:429-431: the penalty's parameter gradients join summed_grad — a sum, not a mean, hence x batch_size; one
+        multi-tensor launch."""
+        with torch.no_grad():
+            pairs = [(p.summed_grad, g) for p, g in zip(self.D.parameters(), penalty_grad) if g is not None]
+            if pairs:
+                torch._foreach_add_([t for t, _ in pairs], [g for _, g in pairs], alpha=self.opt.batch_size)
+            if self.explicit.get("keep"):
+                self.last["penalty_grads"] = [None if g is None else g.clone() for g in penalty_grad]
 
     # ---- train.py:433-450 ---------------------------------------------------------------------
     def _per_sample_penalty(self, pen_real, pen_labels, fake_img, y, kw, use_grad_clip):

@@ -418,6 +418,9 @@ class Harness:
                 return name if addr == lo else "%s+%d" % (name, addr - lo)
         return "new"
 
+    # struct -> {prefix of an array field's name: the field that counts its entries} (anything else: n_seg)
+    _ARRAY_LEN = {"AdaptiveClipT": {"sq": "n_layers", "mat": "n_mat", "job": "n_jobs"}}
+
     def _arg(self, a):
         if a is None or isinstance(a, C.c_void_p):
             return self._where(a.value if a is not None else 0)
@@ -433,8 +436,9 @@ class Harness:
                 continue
             if ctype is C.c_void_p:
                 out[field] = "set" if v else "null"
-            elif isinstance(v, C.Array):            # SegsT: the first n_seg entries
-                out[field] = [self._where(e) if ctype._type_ is C.c_void_p else e for e in list(v)[:obj.n_seg]]
+            elif isinstance(v, C.Array):            # the entries in use: SegsT's first n_seg, AdaptiveClipT's by the field's own count
+                n = getattr(obj, self._ARRAY_LEN.get(type(obj).__name__, {}).get(field.split("_")[0], "n_seg"))
+                out[field] = [self._where(e) if ctype._type_ is C.c_void_p else e for e in list(v)[:n]]
             else:
                 out[field] = v
         return out
