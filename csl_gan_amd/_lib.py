@@ -33,6 +33,7 @@ EXPORTS = [
     "cslgan_conv2d_fwd_skinny_bf16in", "cslgan_conv2d_dgrad_skinny_bf16in", "cslgan_conv2d_wgrad_scaled_bf16s",
     "cslgan_latent_normal_f32", "cslgan_f32_to_u8",
     "cslgan_attack_trials", "cslgan_rank_counts", "cslgan_softmax_max_rows_f32",
+    "cslgan_ovr_logreg_ws_floats", "cslgan_ovr_logreg_eval_f32", "cslgan_ovr_logreg_proba_f32",
 ]
 
 
@@ -152,6 +153,8 @@ def lib():
         "cslgan_attack_trials": [vp, i64, vp, i64, i32, i32, u64, u64, i64, vp, vp],
         "cslgan_rank_counts": [vp, i64, vp, i64, vp, vp, vp],
         "cslgan_softmax_max_rows_f32": [vp, i64, i32, vp, vp],
+        "cslgan_ovr_logreg_eval_f32": [vp, vp, vp, i64, i32, i32, vp, vp, vp, i64, vp],
+        "cslgan_ovr_logreg_proba_f32": [vp, i32, vp, i64, i32, i32, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -159,6 +162,8 @@ def lib():
         fn.restype = C.c_int
     L.cslgan_norm_bwd_ws_floats.argtypes = [i64, i64, i32, i32]
     L.cslgan_norm_bwd_ws_floats.restype = C.c_int64
+    L.cslgan_ovr_logreg_ws_floats.argtypes = [i64, i32]
+    L.cslgan_ovr_logreg_ws_floats.restype = C.c_int64
     if L.cslgan_version() != ABI_VERSION:
         raise HipLibraryMissing("libcslgan_hip.so ABI version mismatch")
     _lib = L

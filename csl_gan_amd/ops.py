@@ -1474,6 +1474,64 @@ def softmax_max_rows(logits, out=None):
     return out
 
 
+def _logreg_shapes(X, U, what):
+    if X.dim() != 2 or U.dim() != 2 or U.shape[0] != X.shape[1] + 1:
+        raise RuntimeError("%s: need X [N, D] and U [D + 1, K], got %s and %s" % (what, tuple(X.shape), tuple(U.shape)))
+    return X.shape[0], X.shape[1], U.shape[1]
+
+
+def ovr_logreg_eval(X, labels, U, out_loss=None, out_grad=None, ws=None):
+    """(loss [K], grad [D + 1, K]) of the K one-vs-rest logistic-regression objectives of include/cslgan.h "downstream classifier" at
+    U [D + 1, K] (last row: the intercepts) on X [N, D] fp32 with int32 labels [N] — one evaluation of downstream.py:87's fit, all
+    classes in one pass over X.  ws: a float32 device tensor of at least ovr_logreg_ws_floats(N, D) entries (an optimiser keeps one
+    across its evaluations); allocated when absent.  csl_gan_amd.classify.objective_host is the host model."""
+    _chk(X, "X"); _chk(U, "U")
+    N, D, K = _logreg_shapes(X, U, "ovr_logreg_eval")
+    if not labels.is_cuda or labels.dtype != torch.int32 or labels.numel() != N or not labels.is_contiguous():
+        raise RuntimeError("ovr_logreg_eval: labels must be a contiguous int32 device tensor of %d entries" % N)
+    if out_loss is None:
+        out_loss = torch.empty(K, device=X.device, dtype=torch.float32)
+    elif _chk(out_loss, "out_loss").numel() != K:
+        raise RuntimeError("ovr_logreg_eval: out_loss has %d entries, expected %d" % (out_loss.numel(), K))
+    if out_grad is None:
+        out_grad = torch.empty((D + 1, K), device=X.device, dtype=torch.float32)
+    elif _chk(out_grad, "out_grad").numel() != (D + 1) * K:
+        raise RuntimeError("ovr_logreg_eval: out_grad has %d entries, expected %d" % (out_grad.numel(), (D + 1) * K))
+    if ws is None:
+        ws = torch.empty(max(ovr_logreg_ws_floats(N, D), 2), device=X.device, dtype=torch.float32)
+    else:
+        _chk(ws, "ws")
+    check(_lib.lib().cslgan_ovr_logreg_eval_f32(_p(X), _p(labels), _p(U), N, D, K, _p(out_loss), _p(out_grad), _p(ws), ws.numel(), _stream()),
+          "ovr_logreg_eval")
+    return out_loss, out_grad
+
+
+def ovr_logreg_ws_floats(N, D):
+    """Workspace of ovr_logreg_eval in floats (0: a shape the kernel does not take)."""
+    return int(_lib.lib().cslgan_ovr_logreg_ws_floats(int(N), int(D)))
+
+
+def ovr_logreg_proba(Xtest, U, out=None):
+    """P [M, K] = sigmoid(z) / sum_k sigmoid(z), z = Xtest U[:D] + U[D] (downstream.py:87 predict_proba).  Xtest [M, D]: float32, or
+    uint8 bytes that are scaled by 1 / 255 in the load (downstream.py:106)."""
+    _chk(U, "U")
+    if Xtest.dtype == torch.uint8:
+        if not Xtest.is_cuda:
+            raise RuntimeError("Xtest must be a device tensor (csl_gan_amd.ops has no CPU path)")
+        if not Xtest.is_contiguous():
+            raise RuntimeError("Xtest must be contiguous")
+    else:
+        _chk(Xtest, "Xtest")
+    M, D, K = _logreg_shapes(Xtest, U, "ovr_logreg_proba")
+    if out is None:
+        out = torch.empty((M, K), device=U.device, dtype=torch.float32)
+    elif _chk(out, "out").numel() != M * K:
+        raise RuntimeError("ovr_logreg_proba: out has %d entries, expected %d" % (out.numel(), M * K))
+    check(_lib.lib().cslgan_ovr_logreg_proba_f32(_p(Xtest), 1 if Xtest.dtype == torch.uint8 else 0, _p(U), M, D, K, _p(out), _stream()),
+          "ovr_logreg_proba")
+    return out
+
+
 def row_l2norm(t2d):
     _chk(t2d, "t")
     n, L = t2d.shape

@@ -570,6 +570,29 @@ int cslgan_rank_counts(const float* a, int64_t na, const float* b, int64_t nb, u
  * logits, 1 <= n_classes <= 64.  The sum runs in fp64: out is the rounded fp32 of the formula on the fp32 logits. */
 int cslgan_softmax_max_rows_f32(const float* logits, int64_t B, int n_classes, float* out, void* stream);
 
+/* ---- downstream classifier (logreg_kernels.hip; backward-compatible additions, ABI stays 7) ---------------------------------------
+ * One-vs-rest logistic regression over K <= 16 classes, as downstream.py:71-72 builds it (OneVsRestClassifier over
+ * LogisticRegression(solver='lbfgs', multi_class='multinomial'), C = 1): handed a binary target, the multinomial form is a two-class
+ * softmax, i.e. a binary logistic regression with C = 2.  With t_ik = [labels[i] == k], s = 2 t - 1 and U [D + 1, K] row-major (row
+ * d < D: the weights of feature d; row D: the intercepts), class k minimises
+ *     f_k(U) = sum_i log(1 + exp(-s_ik z_ik)) + sum_{d < D} U[d][k]^2 / 4,      z_ik = sum_{d < D} X[i][d] U[d][k] + U[D][k]
+ * (no penalty on the intercept).  All entries validate on the host before any launch, never allocate and never synchronise;
+ * 2 <= K <= 16, 1 <= D <= 895 (a 16-row tile of X lives in LDS), 1 <= N, M < 2^31.  D need not be a multiple of 4.
+ *
+ * cslgan_ovr_logreg_eval_f32 — one loss-and-gradient evaluation of all K problems, the inner call of the L-BFGS that replaces
+ * .fit() of downstream.py:87:  loss[k] = f_k(U),  grad[d][k] = d f_k / d U[d][k]  ([D + 1, K] row-major like U).  Both products run
+ * on the exact fp32 matrix instruction; X is read from HBM once; the softplus is the stable form (finite for every finite z);
+ * workgroup partials are added in a fixed order in double, so two calls on the same inputs return the same bits.  labels outside
+ * 0 .. K-1 belong to no class (t = 0 everywhere).  ws: caller workspace of cslgan_ovr_logreg_ws_floats(N, D) floats, 8-byte aligned. */
+int64_t cslgan_ovr_logreg_ws_floats(int64_t N, int D);
+int cslgan_ovr_logreg_eval_f32(const float* X, const int32_t* labels, const float* U, int64_t N, int D, int K, float* loss, float* grad,
+                               float* ws, int64_t ws_floats, void* stream);
+
+/* cslgan_ovr_logreg_proba_f32 — .predict_proba() of downstream.py:87 on the test matrix of :103-106:
+ *     P[i][k] = sigmoid(z_ik) / sum_k' sigmoid(z_ik')          ([M, K] row-major)
+ * Xtest: [M, D] fp32 (is_u8 = 0), or [M, D] bytes (is_u8 = 1) that become floats times 1/255 in the load (:106). */
+int cslgan_ovr_logreg_proba_f32(const void* Xtest, int is_u8, const float* U, int64_t M, int D, int K, float* P, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
