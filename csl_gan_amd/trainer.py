@@ -16,15 +16,25 @@ MI355X-first host changes (results identical):
 """
 from __future__ import annotations
 
+import contextlib
+import gc
+import inspect
 import os
+import warnings
 
 import numpy as np
 import torch
 from torch import autograd
 
+from . import distributed as Dist
 from . import engine as E
+from . import functional as HF
+from . import nn as hnn
+from . import ops
 from . import util
+from .backprop_clip import BackpropClipper
 from .gradient_penalty import calc_penalty
+from .is_engine import ISPrivacyEngine
 from .logger import Logger
 
 
@@ -33,7 +43,6 @@ class Trainer:
                  log_to=None, world_size=1, rank=0, grad_reducer=None):
         self.opt, self.G, self.D = opt, G, D
         if any(p.is_cuda for p in D.parameters()):
-            from . import ops
             ops.set_compute_dtype(getattr(opt, "compute_dtype", "fp32"))     # process-wide: one process drives one run
             ops.set_storage_dtype(getattr(opt, "storage_dtype", "fp32"))
         self.dataset, self.public_dataloader, self.public_dataset = dataset, public_dataloader, public_dataset
@@ -50,6 +59,14 @@ class Trainer:
         self.graphed = None                # GraphedDStep, created by setup_privacy_engine when --hip_graph is set
         self.last = {}                     # observables of the most recent D-step (device tensors), for tests
         self.explicit = {}                 # optional explicit random inputs (alpha / noise / mean-sample batches) for parity tests
+        self._fused_buf = None             # the fused critic batch (_fused_batch)
+        self._g_out_kw = None              # whether G.forward takes out= (_g_takes_out)
+        self._g_flat = None                # the flat bucket of G's gradients (_average_G_grads)
+        self._stat_bufs = {}               # persistent statistic buffers whose rows dev_stats holds (_stat_rows)
+        self._gp_stream = None             # the penalty's side stream (_launch_penalty)
+        self._pending_penalty = None       # (penalty, grads) launched on it and not yet joined
+        self._gp_joined = False            # joined early, at a segment boundary
+        self._warn_ps_pen = True           # the per-sample-penalty warning has not been printed yet
 
     # ---- train.py:75-77 -----------------------------------------------------------------------
     def init_optimizers(self):
@@ -64,7 +81,6 @@ class Trainer:
         o = self.opt
         if not o.backprop_clip:
             return None
-        from .backprop_clip import BackpropClipper
         with torch.no_grad():
             p = ((o.bpc_back_clip_param_pl, o.bpc_forward_clip_param_pl) if o.grad_clip_mode[-3:] == "-pl"
                  else (o.bpc_back_clip_param, o.bpc_forward_clip_param))
@@ -93,7 +109,6 @@ class Trainer:
                                  grad_sample_dtype=getattr(o, "grad_sample_dtype", "fp32"))
             pe.disable_hooks()
         elif o.dp_mode == "is":
-            from .is_engine import ISPrivacyEngine
             pe = ISPrivacyEngine(self.D, **params, per_param=o.imm_sens_per_param,
                                  scaling_vec=None if o.imm_sens_scaling_mode == "standard" else o.imm_sens_scaling_vec)
         else:
@@ -103,17 +118,14 @@ class Trainer:
         pe.attach(self.d_optimizer)
         pe._set_seed(o.manual_seed + 7919 * self.rank)
         self.privacy_engine = pe
-        # gc, and immediate sensitivity (no host read inside the step since round 3).  The IS replays were wrong until the library
-        # stopped using hipMemsetAsync: as a memset node of a captured graph a 128-byte fill (the accumulator of the per-sample
-        # input-gradient norms, B >= 24) replayed with a stale dword per 16 bytes — csrc/common.h zero_floats.
-        # N > 1 ranks over RCCL (round 3): the step's collectives — the flat gradient all-reduce, the 9-float adaptive statistics, the
-        # immediate-sensitivity maxima — are stream-ordered RCCL launches and are RECORDED with the step (every rank records and replays
-        # the same sequence) — OPT-IN with CSLGAN_GRAPH_DIST=1 (round 4: verified on a one-rank RCCL group only, so N > 1 defaults to the
-        # eager step); gloo (CPU rehearsals) stages through the host and keeps the eager step.
-        # Round 4, second half: a multi-rank step whose collectives are not recorded replays as SEGMENTS — the capture ends at each
-        # collective, which is issued eagerly between the replays of the graphs on either side (GraphedDStep._capture_segments).
-        from .distributed import collectives_capturable, segments_enabled
-        if (getattr(o, "hip_graph", False) and (self.world_size == 1 or collectives_capturable() or segments_enabled()) and not o.backprop_clip
+        # Recorded: gc, and immediate sensitivity except moving-avg-pl (its host reads gradient norms inside the step); never with
+        # --backprop_clip.  One rank records the whole step.  N > 1 ranks record it as SEGMENTS — the capture ends at each collective
+        # (the flat gradient all-reduce, the 9-float adaptive statistics, the immediate-sensitivity maxima), which is issued eagerly
+        # between the replays of the graphs on either side (GraphedDStep._capture_segments); with CSLGAN_GRAPH_DIST=1 over RCCL the
+        # collectives are stream-ordered launches and are recorded with the step, whole.  N > 1 with CSLGAN_GRAPH_SEGMENTS=0 and
+        # collectives that are not recorded steps eagerly.
+        # (Replayed fills: the library never uses hipMemsetAsync, whose graph node replays wrongly — csrc/common.h zero_floats.)
+        if (getattr(o, "hip_graph", False) and (self.world_size == 1 or Dist.collectives_capturable() or Dist.segments_enabled()) and not o.backprop_clip
                 and (o.dp_mode == "gc" or (o.dp_mode == "is" and o.imm_sens_scaling_mode != "moving-avg-pl"))):
             self.graphed = GraphedDStep(self)
         return pe
@@ -140,10 +152,7 @@ class Trainer:
         o = self.opt
         yg = None if y is None else y.to(o.g_device)
         frozen = not any(p.requires_grad for p in self.G.parameters())
-        if frozen:
-            with torch.no_grad():
-                img = self.G(z, yg, **g_kwarg)
-        else:
+        with torch.no_grad() if frozen else contextlib.nullcontext():
             img = self.G(z, yg, **g_kwarg)
         img = img.to(o.d_device)
         d_out, d_aux = self.D(img, None if y is None else y.to(o.d_device), **d_kwarg)
@@ -192,13 +201,7 @@ class Trainer:
         with torch.no_grad():
             B = img.size(0)
             # per-layer per-sample norms of pass 0: produced by the wgrad epilogue, never re-read from HBM
-            norms = pe.sample_sqnorms()[:, :B].sqrt()                      # [n_params, B]
-            r = norms.mean(dim=1) if o.adaptive_stat == "mean" else norms.max(dim=1).values
-            if self.world_size > 1:        # every rank must clip and noise with the same C
-                from .distributed import average_across_ranks
-                r = average_across_ranks(r.contiguous(), use_max=o.adaptive_stat == "max")
-            self.last["adaptive_stats"] = r
-            pe.set_max_grad_norm_device(self._adaptive_clip_norm(r))
+            self._set_adaptive_clip_norm(pe.sample_sqnorms()[:, :B].sqrt())
         self.d_optimizer.zero_grad()
 
     def _adaptive_batch(self):
@@ -217,6 +220,18 @@ class Trainer:
         o = self.opt
         return r * o.adaptive_scalar if o.use_grad_clip_per_layer else (r.norm(2) * o.adaptive_scalar).reshape(1)
 
+    def _set_adaptive_clip_norm(self, norms, join_penalty=False):
+        """train.py:225-243 on the device: per-sample norms [n_params, B] -> their mean or max per layer -> the engine's clip norm.
+        join_penalty: the fused pass has work on the penalty stream, which a segment boundary at the collective must join first."""
+        o = self.opt
+        r = norms.mean(dim=1) if o.adaptive_stat == "mean" else norms.max(dim=1).values
+        if self.world_size > 1:            # every rank must clip and noise with the same C (SURVEY.md §8e)
+            if join_penalty:
+                self._join_penalty_stream_at_boundary()
+            r = Dist.average_across_ranks(r.contiguous(), use_max=o.adaptive_stat == "max")
+        self.last["adaptive_stats"] = r
+        self.privacy_engine.set_max_grad_norm_device(self._adaptive_clip_norm(r))
+
     # ---- train.py:310-329 ---------------------------------------------------------------------
     def update_grad_logging(self):
         """Uses the norms / factors of the clip that just ran (same numbers the reference recomputes)."""
@@ -224,33 +239,33 @@ class Trainer:
         B = o.batch_size
         per_layer = pe.clipper.norm_clipper.is_per_layer
         keep = bool(self.explicit.get("keep"))
+        C = pe.max_grad_norm_device()
         if o.grad_clip_split:
             sq, f = pe.last_sq, pe.last_factors
             col = 1 if sq.shape[1] >= 2 * B else 0
-            if sq.is_cuda and sq.dtype == torch.float32 and sq.is_contiguous():
-                # mean / std / max of the logged column's norms, the clip norms and the clipped fraction in ONE launch, added in place
-                from . import ops
-                C = pe.max_grad_norm_device()
-                ops.grad_log_stats(sq, col * B, B, C, per_layer, E.CLIP_EPS, self._glog_acc(sq.device, sq.shape[0] if per_layer else 1))
-                if keep:
-                    norms = sq.sqrt() if per_layer else sq.sum(dim=0, keepdim=True).sqrt()
-                    self.last.update(norms=norms, clip_factors=f, clip_params=C.clone())
-                return
         else:
             # the reference logs column 0 = the first (generated-data) pass when passes are accumulated
             # (train.py:315); those norms come from the wgrad epilogue, the factors from the same formula
-            sq, col = pe.sample_sqnorms()[:, :B], 0
-            nrm = sq.sqrt() if per_layer else sq.sum(dim=0, keepdim=True).sqrt()
-            f = (pe.max_grad_norm_device().reshape(-1, 1) / (nrm + E.CLIP_EPS)).clamp(max=1.0)
+            sq, f, col = pe.sample_sqnorms()[:, :B], None, 0
+        one_launch = o.grad_clip_split and sq.is_cuda and sq.dtype == torch.float32 and sq.is_contiguous()
+        if one_launch:
+            # mean / std / max of the logged column's norms, the clip norms and the clipped fraction in ONE launch, added in place
+            rows = sq.shape[0] if per_layer else 1
+            ops.grad_log_stats(sq, col * B, B, C, per_layer, E.CLIP_EPS, self._stat_rows(self._GLOG_NAMES, (5, rows), sq.device))
+            if not keep:
+                return
         norms = sq.sqrt() if per_layer else sq.sum(dim=0, keepdim=True).sqrt()
-        nm = norms[:, col * B:(col + 1) * B]
-        fac = (f if per_layer else f.reshape(1, -1))[:, col * B:(col + 1) * B]
-        self._acc("D Layer Grad Norm Means", nm.mean(dim=1))
-        self._acc("D Layer Grad Norm Stds", nm.std(dim=1, unbiased=False))
-        self._acc("D Layer Grad Norm Maxes", nm.max(dim=1).values)
-        self._acc("Clipping Params", pe.max_grad_norm_device().clone())
-        self._acc("Grads Clipped", (fac < 0.999).float().mean(dim=1))
-        self.last.update(norms=norms, clip_factors=f, clip_params=pe.max_grad_norm_device().clone())
+        if f is None:
+            f = (C.reshape(-1, 1) / (norms + E.CLIP_EPS)).clamp(max=1.0)
+        if not one_launch:
+            nm = norms[:, col * B:(col + 1) * B]
+            fac = (f if per_layer else f.reshape(1, -1))[:, col * B:(col + 1) * B]
+            self._acc("D Layer Grad Norm Means", nm.mean(dim=1))
+            self._acc("D Layer Grad Norm Stds", nm.std(dim=1, unbiased=False))
+            self._acc("D Layer Grad Norm Maxes", nm.max(dim=1).values)
+            self._acc("Clipping Params", C.clone())
+            self._acc("Grads Clipped", (fac < 0.999).float().mean(dim=1))
+        self.last.update(norms=norms, clip_factors=f, clip_params=C.clone())
 
     # ---- train.py:247-249 ---------------------------------------------------------------------
     def update_sens_moving_avg(self):
@@ -269,50 +284,52 @@ class Trainer:
     def update_is_logging(self):
         """train.py:332-338 without the per-step host read: the mean accumulates on the device, the running minimum / maximum of
         the interval too; flush_stats folds them into the Logger with the reference's conventions (values scaled by the logging
-        interval because the Logger divides by it; the non-per-param minimum starts from 99999)."""
+        interval because the Logger divides by it; _fold_is_extrema)."""
         pe = self.privacy_engine
         s = getattr(pe, "batch_sensitivity_device", None)
         if s is None:                      # a foreign engine without the device view: the reference's host arithmetic
-            self._is_log_host(pe.batch_sensitivity)
+            self.logger.stats["IS Mean"] += pe.batch_sensitivity
+            self._fold_is_extrema(pe.batch_sensitivity, pe.batch_sensitivity)
             return
         s = s.detach().reshape(-1)
         self._acc("IS Mean", s.clone() if self.opt.imm_sens_per_param else s.reshape(()).clone())
         # running extrema of the logging interval in PERSISTENT buffers updated in place (a replayed step keeps updating the same
         # memory); +-inf marks "nothing seen since the last flush"
-        for key, op, init in (("_is_min", torch.minimum, float("inf")), ("_is_max", torch.maximum, float("-inf"))):
+        for key, op, init in self._IS_EXTREMA:
             cur = self.dev_stats.get(key)
             if cur is None or cur.shape != s.shape:
                 cur = self.dev_stats[key] = torch.full_like(s, init)
             op(cur, s, out=cur)
 
-    def _is_log_host(self, s):
+    _IS_EXTREMA = (("_is_min", torch.minimum, float("inf")), ("_is_max", torch.maximum, float("-inf")))
+
+    def _fold_is_extrema(self, mn, mx):
+        """train.py:334-338: a (min, max) pair of sensitivities, floats or per-parameter arrays, into the Logger.  Values are scaled
+        by the logging interval because the Logger divides by it; a minimum the Logger has reset to 0.0 restarts from the reference's
+        large constant (a float) or from the incoming array (per parameter)."""
         lg = self.logger
-        lg.stats["IS Mean"] += s
-        scaled = s * lg.interval
+        mn, mx = mn * lg.interval, mx * lg.interval
         if self.opt.imm_sens_per_param:
-            lg.stats["IS Min"] = scaled if isinstance(lg.stats["IS Min"], float) else np.minimum(lg.stats["IS Min"], scaled)
-            lg.stats["IS Max"] = np.maximum(lg.stats["IS Max"], scaled)
+            lg.stats["IS Min"] = mn if isinstance(lg.stats["IS Min"], float) else np.minimum(lg.stats["IS Min"], mn)
+            lg.stats["IS Max"] = np.maximum(lg.stats["IS Max"], mx)
         else:
-            lg.stats["IS Min"] = min(99999 if lg.stats["IS Min"] < 1e-8 else lg.stats["IS Min"], scaled)
-            lg.stats["IS Max"] = max(lg.stats["IS Max"], scaled)
+            lg.stats["IS Min"] = min(99999 if lg.stats["IS Min"] < 1e-8 else lg.stats["IS Min"], mn)
+            lg.stats["IS Max"] = max(lg.stats["IS Max"], mx)
 
     def _flush_is_extrema(self):
-        lg = self.logger
-        mn, mx = self.dev_stats.get("_is_min"), self.dev_stats.get("_is_max")
+        """The device-side extrema of the interval into the Logger; the buffers go back to "nothing seen"."""
+        mn, mx = (self.dev_stats.get(key) for key, _, _ in self._IS_EXTREMA)
         if mn is None:
             return
         mn_h, mx_h = mn.cpu().numpy().astype(np.float64), mx.cpu().numpy().astype(np.float64)
-        mn.fill_(float("inf"))
-        mx.fill_(float("-inf"))
-        if not np.isfinite(mn_h).all():          # no immediate-sensitivity step since the last flush
-            return
-        mn_h, mx_h = mn_h * lg.interval, mx_h * lg.interval
-        if self.opt.imm_sens_per_param:
-            lg.stats["IS Min"] = mn_h if isinstance(lg.stats["IS Min"], float) else np.minimum(lg.stats["IS Min"], mn_h)
-            lg.stats["IS Max"] = np.maximum(lg.stats["IS Max"], mx_h)
-        else:
-            lg.stats["IS Min"] = min(99999 if lg.stats["IS Min"] < 1e-8 else lg.stats["IS Min"], float(mn_h[0]))
-            lg.stats["IS Max"] = max(lg.stats["IS Max"], float(mx_h[0]))
+        self._reset_is_extrema()
+        if np.isfinite(mn_h).all():              # else: no immediate-sensitivity step since the last flush
+            self._fold_is_extrema(*((mn_h, mx_h) if self.opt.imm_sens_per_param else (float(mn_h[0]), float(mx_h[0]))))
+
+    def _reset_is_extrema(self):
+        for key, _, init in self._IS_EXTREMA:
+            if key in self.dev_stats:
+                self.dev_stats[key].fill_(init)
 
     # ---- train.py:345-358 ---------------------------------------------------------------------
     def calc_d_fake_loss(self, img, labels, z, y):
@@ -342,8 +359,6 @@ class Trainer:
         the critic pass over the private batch — and its 128-row launches (64-256 workgroups) leave most of the 256 CUs idle.  It
         runs on a second stream beside the fused 384-row pass and joins before its gradients are added to summed_grad.  Order of
         the activation-mask recordings differs, so parity tests with a recorder installed keep the serial order."""
-        import os
-        from . import nn as hnn
         o = self.opt
         return (os.environ.get("CSLGAN_GP_STREAM", "1") == "1" and use_dp and o.dp_mode == "gc" and o.per_sample_grad
                 and len(o.penalty) > 0 and o.penalty_use_public_data and hnn._mask_recorder is None and self.D is not None
@@ -353,15 +368,13 @@ class Trainer:
         """A segmented recording (distributed._boundary) ends the graph being captured at the next collective: work forked onto the
         penalty stream must be joined into the capturing stream first.  train_D's own join is then skipped (waiting, inside the NEXT
         capture, on an event of a finished one is not allowed)."""
-        from . import distributed as Dist
         if Dist._boundary is not None and self._pending_penalty is not None and not self._gp_joined:
             torch.cuda.current_stream().wait_stream(self._gp_stream)
             self._gp_joined = True
 
     def _launch_penalty(self, img, labels, fake_img, y):
-        from . import ops
-        o, D, pe = self.opt, self.D, self.privacy_engine
-        if getattr(self, "_gp_stream", None) is None:
+        D, pe = self.D, self.privacy_engine
+        if self._gp_stream is None:
             self._gp_stream = torch.cuda.Stream(device=next(D.parameters()).device)
         side, cur = self._gp_stream, torch.cuda.current_stream()
         ops.repack_cache.multi_stream = True
@@ -370,21 +383,26 @@ class Trainer:
         side.wait_stream(cur)
         try:
             with torch.cuda.stream(side):
-                pen_real, pen_labels = self.get_penalty_data(img, labels)
-                penalty = calc_penalty(D, o.penalty, pen_real, pen_labels, fake_img, y, device=o.d_device, aux_penalty=o.aux_penalty,
-                                       alpha=self.explicit.get("alpha"))
-                grads = self._penalty_param_grads(penalty)
+                self._pending_penalty = self._public_penalty(img, labels, fake_img, y)
         finally:
             if was_enabled:
                 pe.enable_hooks()
-        self._pending_penalty = (penalty, grads)
+
+    def _penalty_kw(self):
+        o = self.opt
+        return dict(device=o.d_device, aux_penalty=o.aux_penalty, alpha=self.explicit.get("alpha"))
+
+    def _public_penalty(self, img, labels, fake_img, y):
+        """train.py:423-427: (penalty, its parameter gradients) on public data or mean samples, on the current stream."""
+        pen_real, pen_labels = self.get_penalty_data(img, labels)
+        penalty = calc_penalty(self.D, self.opt.penalty, pen_real, pen_labels, fake_img, y, **self._penalty_kw())
+        return penalty, self._penalty_param_grads(penalty)
 
     def _penalty_param_grads(self, penalty):
         """autograd.grad(penalty, D.parameters()) (train.py:427).  With ONE penalty term every critic weight receives exactly one
         dense second-order weight gradient and nothing reads it before this call returns, so the column sums over the gradients'
-        slabs are queued and run as one multi-segment launch (ops.deferred_sums; they were five latency-sized launches).  Several
+        slabs are queued and run as one multi-segment launch (ops.deferred_sums; instead of five latency-sized launches).  Several
         terms (an auxiliary-logit penalty, two penalty types) make autograd ADD contributions inside the call: those run undeferred."""
-        from . import ops
         o, D = self.opt, self.D
         params = list(D.parameters())
         single_term = len(o.penalty) == 1 and not (o.aux_penalty and getattr(D, "linOutAux", None) is not None)
@@ -411,11 +429,11 @@ class Trainer:
         with torch.no_grad():
             # the generated rows' slice of the fused critic batch, when that buffer exists: the generator's output conv writes the
             # images there (channels-last) and _assemble_fused finds them in place
-            g_out, buf = None, getattr(self, "_fused_buf", None)
-            r0 = blocks[0].size(0) if blocks else 0
-            if (buf is not None and img.dim() == 4 and buf.is_cuda and str(o.g_device) == str(o.d_device) and buf.shape[0] == r0 + 2 * B
-                    and tuple(buf.shape[1:]) == tuple(img.shape[1:]) and self._g_takes_out()):
-                g_out = buf[r0:r0 + B].permute(0, 2, 3, 1)
+            g_out, r0 = None, blocks[0].size(0) if blocks else 0
+            if img.dim() == 4 and img.is_cuda and str(o.g_device) == str(o.d_device) and self._g_takes_out():
+                buf = self._fused_batch(r0 + 2 * B, img.shape[1:], img.device, make=False)
+                if buf is not None:
+                    g_out = buf[r0:r0 + B].permute(0, 2, 3, 1)
             fake_img = (self.G(z, yg, out=g_out) if g_out is not None else self.G(z, yg)).to(o.d_device)
         if on_fake is not None:
             on_fake(fake_img.detach())
@@ -435,7 +453,6 @@ class Trainer:
         if getattr(D, "linear_critic_losses", False) and not o.use_aux_loss and out_all.is_cuda:
             # real_loss = -mean, fake_loss = +mean (DCResNet_models.py:149-153) of every row block and their sum in ONE launch,
             # the constant cotangent in one more (csl_gan_amd.functional.SegmentMeans)
-            from . import functional as HF
             sizes = [n for _, n in roles]
             scale = [(1.0 if role == "dense" else -1.0) / n for role, n in roles]
             vec, total = HF.SegmentMeans.apply(out_all, sizes, scale)
@@ -453,7 +470,6 @@ class Trainer:
                 if o.use_aux_loss:
                     total = total + D.aux_loss(auxs[0], lab[0], o.d_device, fake=False)
         if total.is_cuda:
-            from . import ops
             total.backward(gradient=ops.ones_like_const(total))     # the constant cotangent: no fill launch per step
         else:
             total.backward()
@@ -465,36 +481,36 @@ class Trainer:
                     # one launch: the statistic, the clip norms, and the clip factors clip() is about to ask for
                     r = pe.adaptive_clip_fused(o.adaptive_stat, o.adaptive_scalar, bool(o.use_grad_clip_per_layer))
                 if r is None:
-                    norms = pe.norms_rows_sqnorms().sqrt()
-                    r = norms.mean(dim=1) if o.adaptive_stat == "mean" else norms.max(dim=1).values
-                    if self.world_size > 1:
-                        from .distributed import average_across_ranks
-                        self._join_penalty_stream_at_boundary()
-                        r = average_across_ranks(r.contiguous(), use_max=o.adaptive_stat == "max")
-                    pe.set_max_grad_norm_device(self._adaptive_clip_norm(r))
-                self.last["adaptive_stats"] = r
+                    self._set_adaptive_clip_norm(pe.norms_rows_sqnorms().sqrt(), join_penalty=True)
+                else:
+                    self.last["adaptive_stats"] = r
         pe.row_roles = None
         return d_fake, d_fake_aux, d_fake_loss, d_fake_aux_loss, fake_img.detach(), d_real, d_real_aux, d_real_loss, d_real_aux_loss
 
     def _g_takes_out(self):
-        if getattr(self, "_g_out_kw", None) is None:
-            import inspect
+        if self._g_out_kw is None:
             self._g_out_kw = "out" in inspect.signature(self.G.forward).parameters
         return self._g_out_kw
 
+    def _fused_batch(self, rows, shape, device, make=True):
+        """The persistent channels-last fp32 batch [rows, *shape] of the fused critic pass, allocated here and nowhere else.
+        make=False: None unless it already exists with that shape on that device."""
+        shp = (rows,) + tuple(shape)
+        buf = self._fused_buf
+        if buf is None or tuple(buf.shape) != shp or buf.device != torch.device(device):
+            if not make:
+                return None
+            buf = self._fused_buf = torch.empty(shp, device=device, dtype=torch.float32).contiguous(memory_format=torch.channels_last)
+        return buf
+
     def _assemble_fused(self, blocks):
-        """The row blocks of the fused critic pass as ONE channels-last batch.  Round 3 ran torch.cat (an NCHW copy of all rows) and
-        the critic's first conv then re-laid the result out channels-last (19 MB each way at bs = 128: 21 + 96 us).  Now the batch
-        lives in a persistent channels-last buffer: blocks that already ARE its slices (GraphedDStep hands the mean-sample and real
-        batches out as views of it) cost nothing, every other block is one copy_ straight into its slice (a layout change, where
-        there is one, rides in that copy)."""
+        """The row blocks of the fused critic pass as ONE channels-last batch, without torch.cat's NCHW copy that the critic's first
+        conv would re-lay out again: blocks that already ARE slices of the persistent buffer (the generator's output, the mean-sample
+        and real batches GraphedDStep hands out as views of it) cost nothing, every other block is one copy_ straight into its
+        slice (a layout change, where there is one, rides in that copy)."""
         if not blocks[0].is_cuda or blocks[0].dim() != 4:
             return torch.cat(blocks, dim=0)
-        rows = sum(b.shape[0] for b in blocks)
-        shp = (rows,) + tuple(blocks[0].shape[1:])
-        buf = getattr(self, "_fused_buf", None)
-        if buf is None or tuple(buf.shape) != shp or buf.device != blocks[0].device:
-            buf = self._fused_buf = torch.empty(shp, device=blocks[0].device, dtype=torch.float32).contiguous(memory_format=torch.channels_last)
+        buf = self._fused_batch(sum(b.shape[0] for b in blocks), blocks[0].shape[1:], blocks[0].device)
         r0 = 0
         with torch.no_grad():
             for b in blocks:
@@ -507,10 +523,7 @@ class Trainer:
     def fused_slices(self, B, shape, device):
         """(mean-sample slice, real-batch slice) of the fused buffer for a [B, *shape] batch in an adaptive-clipping run: views a
         caller may fill in place so that _assemble_fused finds them already where they belong."""
-        shp = (3 * B,) + tuple(shape)
-        buf = getattr(self, "_fused_buf", None)
-        if buf is None or tuple(buf.shape) != shp or buf.device != torch.device(device):
-            buf = self._fused_buf = torch.empty(shp, device=device, dtype=torch.float32).contiguous(memory_format=torch.channels_last)
+        buf = self._fused_batch(3 * B, shape, device)
         return buf[0:B], buf[2 * B:3 * B]
 
     # ---- train.py:360-500 ---------------------------------------------------------------------
@@ -556,51 +569,42 @@ class Trainer:
                 self.update_grad_logging()     # after clip(): reuses its norms (the reference logs first, train.py:397)
                 self.last["summed_clipped"] = [p.summed_grad.clone() for p in D.parameters()] if self.explicit.get("keep") else None
 
-        penalty = torch.zeros((), device=o.d_device) if self._pending_penalty is None else None
-        if self._pending_penalty is not None:
-            # launched on the second stream right after the generator forward (_launch_penalty): join, then train.py:429-431
-            penalty, penalty_grad = self._pending_penalty
-            self._pending_penalty = None
+        # ---- the penalty and what finishes the gradient (train.py:419-479): one route per step
+        pending, self._pending_penalty = self._pending_penalty, None
+        have_penalty, per_sample = len(o.penalty) > 0, use_dp and o.per_sample_grad
+        if pending is not None:
+            # overlapped: launched on the second stream right after the generator forward (_launch_penalty); join, then train.py:429-431
             if not self._gp_joined:
                 torch.cuda.current_stream().wait_stream(self._gp_stream)
             if use_grad_clip:
                 pe.accumulate_batch()
+            penalty, penalty_grad = pending
             self._add_penalty_grads(penalty_grad)
-        elif len(o.penalty) > 0:
-            pen_real, pen_labels = self.get_penalty_data(img, labels)
-            alpha = self.explicit.get("alpha")
-            kw = dict(device=o.d_device, aux_penalty=o.aux_penalty, alpha=alpha)
-            if use_dp and o.per_sample_grad:
-                if not o.penalty_use_public_data:
-                    penalty = self._per_sample_penalty(pen_real, pen_labels, fake_img, y, kw, use_grad_clip)
-                    penalty_grad = []
-                else:
-                    if use_grad_clip:
-                        pe.accumulate_batch()
-                    penalty = calc_penalty(D, o.penalty, pen_real, pen_labels, fake_img, y, **kw)
-                    penalty_grad = self._penalty_param_grads(penalty)
+        else:
+            penalty = torch.zeros((), device=o.d_device)
+            if have_penalty and per_sample and o.penalty_use_public_data:
+                # public penalty beside per-sample gradients (train.py:419-431): its dense gradients join the clipped sum
+                if use_grad_clip:
+                    pe.accumulate_batch()
+                penalty, penalty_grad = self._public_penalty(img, labels, fake_img, y)
                 self._add_penalty_grads(penalty_grad)
-            else:
-                penalty = calc_penalty(D, o.penalty, pen_real, pen_labels, fake_img, y, **kw)
+            elif have_penalty and per_sample:
+                # private per-sample penalty (train.py:433-450): clips and accumulates again itself
+                penalty = self._per_sample_penalty(*self.get_penalty_data(img, labels), fake_img, y, use_grad_clip)
+                self._add_penalty_grads([])
+            elif have_penalty:
+                # plain penalty (train.py:451-462): part of d_loss
+                pen_real, pen_labels = self.get_penalty_data(img, labels)
+                penalty = calc_penalty(D, o.penalty, pen_real, pen_labels, fake_img, y, **self._penalty_kw())
                 d_loss = d_loss + penalty
                 if use_imm_sens:
-                    pe.backward(d_loss, img)
-                    if o.imm_sens_scaling_mode == "moving-avg-pl":
-                        self.update_sens_moving_avg()
-                    self.update_is_logging()
-                    if self.explicit.get("keep"):
-                        self.last["is_param_grads"] = [torch.zeros_like(p) if p.grad is None else p.grad.clone() for p in D.parameters()]
+                    self._finish_imm_sens(d_loss, img, with_penalty=True)
                 else:
                     d_loss.backward()
-        else:
-            if use_grad_clip:
+            elif use_grad_clip:                # no penalty (train.py:464-479)
                 pe.accumulate_batch()
             elif use_imm_sens:
-                pe.backward(d_loss, img)
-                if o.imm_sens_scaling_mode == "moving-avg-pl":
-                    self.update_sens_moving_avg()
-                else:
-                    self.update_is_logging()
+                self._finish_imm_sens(d_loss, img, with_penalty=False)
             else:
                 d_loss.backward()
 
@@ -614,9 +618,9 @@ class Trainer:
         with torch.no_grad():
             if d_real.is_cuda and d_real.dtype == torch.float32 and torch.is_tensor(d_real_loss) and d_real_loss.dim() == 0:
                 # train.py:488-496 in one launch, added in place to the persistent device-side sums
-                from . import ops
+                names = self._DSTAT_NAMES if have_penalty else self._DSTAT_NAMES[:-1]
                 ops.dstep_stats(d_real.detach().contiguous(), d_fake.detach().contiguous(), d_real_loss.detach(), d_fake_loss.detach(),
-                                penalty.detach().reshape(()) if len(o.penalty) > 0 else None, self._dstats_acc(d_real.device))
+                                penalty.detach().reshape(()) if have_penalty else None, self._stat_rows(names, (7,), d_real.device))
             else:
                 adv = d_real_loss.detach() + d_fake_loss.detach()
                 self._acc("_d_adv_gate", adv)
@@ -625,7 +629,7 @@ class Trainer:
                 self._acc("D Fake Loss", d_fake_loss.detach())
                 self._acc("D Real Acc", 100 * (d_real.detach() > 0).float().mean())
                 self._acc("D Fake Acc", 100 * (d_fake.detach() < 0).float().mean())
-                if len(o.penalty) > 0:
+                if have_penalty:
                     self._acc("D Penalty", penalty.detach().reshape(()))
             if o.use_aux_loss:
                 self._acc("D Real Aux Loss", d_real_aux_loss.detach().reshape(()))
@@ -633,6 +637,20 @@ class Trainer:
             self.last.update(d_real_loss=d_real_loss.detach(), d_fake_loss=d_fake_loss.detach(), penalty=penalty.detach(),
                              d_real=d_real.detach(), d_fake=d_fake.detach(), fake_img=fake_img)
             self._commit_stats()
+
+    def _finish_imm_sens(self, d_loss, img, with_penalty):
+        """The immediate-sensitivity backward and what follows it in the reference."""
+        o, pe = self.opt, self.privacy_engine
+        pe.backward(d_loss, img)
+        moving_avg = o.imm_sens_scaling_mode == "moving-avg-pl"
+        if moving_avg:
+            self.update_sens_moving_avg()
+        # Reference parity, not an oversight: with a penalty (train.py:456-460) update_is_logging follows the moving-average update
+        # unconditionally; without one (train.py:468-473) it is the `elif` of that update, so moving-avg-pl does not log there.
+        if with_penalty or not moving_avg:
+            self.update_is_logging()
+        if with_penalty and self.explicit.get("keep"):
+            self.last["is_param_grads"] = [torch.zeros_like(p) if p.grad is None else p.grad.clone() for p in self.D.parameters()]
 
     def _add_penalty_grads(self, penalty_grad):
         """train.py:429-431: the penalty's parameter gradients join summed_grad — a sum, not a mean, hence x batch_size; one
@@ -645,22 +663,22 @@ class Trainer:
                 self.last["penalty_grads"] = [None if g is None else g.clone() for g in penalty_grad]
 
     # ---- train.py:433-450 ---------------------------------------------------------------------
-    def _per_sample_penalty(self, pen_real, pen_labels, fake_img, y, kw, use_grad_clip):
+    def _per_sample_penalty(self, pen_real, pen_labels, fake_img, y, use_grad_clip):
         """Gradient penalty evaluated on PRIVATE data (--penalty_use_public_data False): the penalty of sample i is part of that
         sample's loss, so its parameter gradient is added to p.grad_sample[0, i] (train.py:447 — pass index 0 as the reference
         writes it) and the batch is clipped again (train.py:449-450).  The reference takes B separate autograd.grad calls, each
         through the whole batch graph; penalties[i] depends on row i only, so ONE second-order sweep of sum_i penalties[i] with
         per-sample (group = 1) weight-gradient kernels gives the same B gradients (csl_gan_amd.functional.per_sample_param_grads).
         The first-order bias terms of the penalty are identically zero."""
-        from . import functional as HF
         o, D, pe = self.opt, self.D, self.privacy_engine
         if not use_grad_clip:
             raise NotImplementedError("per-sample gradient penalties are defined for dp_mode=gc (train.py:433-450)")
         if not all(hasattr(p, "grad_sample") for p in D.parameters()):
             raise RuntimeError("--penalty_use_public_data False edits p.grad_sample of every parameter: run with --materialize all")
-        print("WARNING: Per sample penalty currently causes a memory leak.") if getattr(self, "_warn_ps_pen", True) else None
-        self._warn_ps_pen = False          # the reference prints this every step (train.py:436); once is enough here
-        penalties = calc_penalty(D, o.penalty, pen_real, pen_labels, fake_img, y, per_sample=True, **kw)
+        if self._warn_ps_pen:              # the reference prints this every step (train.py:436); once is enough here
+            print("WARNING: Per sample penalty currently causes a memory leak.")
+            self._warn_ps_pen = False
+        penalties = calc_penalty(D, o.penalty, pen_real, pen_labels, fake_img, y, per_sample=True, **self._penalty_kw())
         seen = set()
 
         def sink(p, rows):
@@ -708,7 +726,7 @@ class Trainer:
         """G is replicated; its (non-private) gradients are averaged over ranks with ONE flat
         all-reduce (G64: 84 MB).  p.grad tensors are re-pointed at slices of the bucket, like the D side."""
         ps = [p for p in self.G.parameters() if p.grad is not None]
-        flat = getattr(self, "_g_flat", None)
+        flat = self._g_flat
         n = sum(p.numel() for p in ps)
         if flat is None or flat.numel() != n or flat.device != ps[0].device:
             flat = self._g_flat = torch.empty(n, device=ps[0].device, dtype=torch.float32)
@@ -718,8 +736,7 @@ class Trainer:
             v.copy_(p.grad)
             p.grad = v
             off += p.numel()
-        from .distributed import average_across_ranks
-        average_across_ranks(flat)
+        Dist.average_across_ranks(flat)
 
     # ---- train.py:521-546 ---------------------------------------------------------------------
     def train(self, epoch, batch_i, real_images_batch, real_labels_batch, use_dp=False):
@@ -737,8 +754,7 @@ class Trainer:
             if acc is not None:
                 acc.zero_()
             if gate is not None and self.world_size > 1:           # every rank must take the same branch
-                from .distributed import average_across_ranks
-                gate = average_across_ranks(gate)
+                gate = Dist.average_across_ranks(gate)
             d_adv = 0.0 if gate is None else float(gate)           # the one host sync, every n_d_steps iterations
             if d_adv / o.n_d_steps < o.train_d_until_threshold:
                 lg.log_g_iter += 1
@@ -767,7 +783,6 @@ class Trainer:
         o, G = self.opt, self.G
         if self.fixed_z is None or self.rank != 0:
             return None
-        import os
         G.eval()
         with torch.no_grad():
             fake = G(self.fixed_z, self.fixed_y).to("cpu")
@@ -781,8 +796,6 @@ class Trainer:
     def log(self, epoch, epoch_progress, print_dp=False):
         self.flush_stats()
         if self.rank != 0:          # --dist: every rank keeps its own CSV (log_rank<r>.csv); only rank 0 prints
-            import contextlib
-            import os
             with open(os.devnull, "w") as null, contextlib.redirect_stdout(null):
                 self.logger.log(epoch, epoch_progress)
             return
@@ -796,24 +809,16 @@ class Trainer:
     _DSTAT_NAMES = ("_d_adv_gate", "D Adv Loss", "D Real Loss", "D Fake Loss", "D Real Acc", "D Fake Acc", "D Penalty")
     _GLOG_NAMES = ("D Layer Grad Norm Means", "D Layer Grad Norm Stds", "D Layer Grad Norm Maxes", "Clipping Params", "Grads Clipped")
 
-    def _dstats_acc(self, dev):
-        """The seven scalar sums train_D's closing lines update (train.py:488-496) as ONE [7] device tensor written by
-        cslgan_dstep_stats_f32; dev_stats holds 0-d views of it, so flush / reset / the G gate see the same memory."""
-        a = getattr(self, "_dstat_buf", None)
-        if a is None or a.device != dev or self.dev_stats.get("D Adv Loss") is None:
-            a = self._dstat_buf = torch.zeros(7, device=dev, dtype=torch.float32)
-            for i, n in enumerate(self._DSTAT_NAMES):
-                if n == "D Penalty" and len(self.opt.penalty) == 0:
-                    continue
-                self.dev_stats[n] = a[i]
-        return a
-
-    def _glog_acc(self, dev, rows):
-        """[5, rows] sums of update_grad_logging (cslgan_grad_log_stats_f32); dev_stats holds its rows."""
-        a = getattr(self, "_glog_buf", None)
-        if a is None or a.device != dev or a.shape[1] != rows or self.dev_stats.get("Grads Clipped") is None:
-            a = self._glog_buf = torch.zeros((5, rows), device=dev, dtype=torch.float32)
-            for i, n in enumerate(self._GLOG_NAMES):
+    def _stat_rows(self, names, shape, dev):
+        """A persistent zeroed device buffer whose leading rows dev_stats holds under `names`, as views: a kernel adds to the whole
+        buffer in one launch, and flush / reset / the G gate see the same memory.  The [7] sums train_D's closing lines update
+        (train.py:488-496, cslgan_dstep_stats_f32; without a penalty the last row, "D Penalty", stays unregistered) and the
+        [5, rows] sums of update_grad_logging (cslgan_grad_log_stats_f32).  Made again, and registered again, when the device or the
+        shape changes or a caller has cleared dev_stats."""
+        a = self._stat_bufs.get(names[0])
+        if a is None or a.device != dev or tuple(a.shape) != tuple(shape) or self.dev_stats.get(names[0]) is None:
+            a = self._stat_bufs[names[0]] = torch.zeros(shape, device=dev, dtype=torch.float32)
+            for i, n in enumerate(names):
                 self.dev_stats[n] = a[i]
         return a
 
@@ -829,7 +834,7 @@ class Trainer:
             cur.add_(value.detach())
 
     def _commit_stats(self):
-        """The step's statistic updates as ONE multi-tensor launch (they were a dozen 4-us kernels)."""
+        """The step's statistic updates as ONE multi-tensor launch (instead of a dozen 4-us kernels)."""
         if self._pending_stats:
             torch._foreach_add_([c for c, _ in self._pending_stats], [v for _, v in self._pending_stats])
             self._pending_stats = []
@@ -840,9 +845,7 @@ class Trainer:
         tail of one epoch leaks into the first log line of the next."""
         self.logger.reset_stats()
         self._commit_stats()
-        for key, init in (("_is_min", float("inf")), ("_is_max", float("-inf"))):
-            if key in self.dev_stats:
-                self.dev_stats[key].fill_(init)
+        self._reset_is_extrema()
         for k, v in self.dev_stats.items():
             if not k.startswith("_"):
                 v.zero_()
@@ -885,6 +888,47 @@ class Trainer:
         return lg
 
 
+class _StepCounters:
+    """The host-side counters one D-step advances, which the accountant and checkpoints read: the engine's steps and its noise-call
+    mirror, and every Adam state's step.  A replay runs no Python, so GraphedDStep advances them itself; a failed recording ran the
+    Python without the device work, so it puts them back."""
+
+    def __init__(self, engine, optimizer):
+        self.pe, self.optimizer = engine, optimizer
+
+    def snapshot(self):
+        return self.pe.steps, self.pe._noise_calls, {id(st): st["step"] for st in self.optimizer.state.values()}
+
+    def restore(self, snap):
+        self.pe.steps, self.pe._noise_calls, adam = snap
+        for st in self.optimizer.state.values():       # (a state made since the snapshot keeps its count)
+            st["step"] = adam.get(id(st), st["step"])
+
+    def advance(self):
+        self.pe.steps += 1
+        self.pe._noise_calls += 1
+        for st in self.optimizer.state.values():
+            st["step"] += 1
+
+
+@contextlib.contextmanager
+def _no_gc():
+    """No cyclic garbage collection while the stream is capturing.  A dead cycle that owns device resources — an earlier
+    GraphedDStep's graph and its private pool, most of all — is finalised wherever the collector happens to run, which can be an
+    autograd worker thread in the middle of the recording; releasing a pool calls hipFree, which is not permitted during a
+    (global-mode) capture, and the failure surfaces inside a destructor: the process aborts.  (torch 2.10 no longer collects in
+    torch.cuda.graph.__enter__.)  So: collect now, on this thread, then keep the collector off until the capture has ended.  The
+    double backward of an is-mode step makes enough cycles to trip it within one recording."""
+    gc.collect()
+    was_on = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_on:
+            gc.enable()
+
+
 class GraphedDStep:
     """One `Trainer.train_D` recorded in a HIP graph and replayed (fixed batch size and configuration).
 
@@ -906,7 +950,8 @@ class GraphedDStep:
             raise NotImplementedError("GraphedDStep covers the DP D-steps whose host never reads the device inside the step: dp_mode=gc "
                                       "and dp_mode=is (not the moving-average scaling mode, which reads gradient norms on the host)")
         self.graph, self.bufs, self.capture_error = None, None, None
-        self.graphs, self.between, self.segmented = [], [], False      # segmented recording (N > 1): graphs and the collectives between them
+        # the recording: graphs and the collectives issued between them; a whole-step recording is one graph (`graph` is the first)
+        self.graphs, self.between, self.segmented = [], [], False
         self._pinned = []                  # generator filter workspaces pinned in ops.repack_cache for the recorded graph
         self._prev = (trainer.d_optimizer.capturable, trainer.explicit)
         trainer.d_optimizer.capturable = True
@@ -916,7 +961,6 @@ class GraphedDStep:
         self.tr.d_optimizer.capturable, self.tr.explicit = self._prev
         self.graph, self.graphs, self.between = None, [], []
         if self._pinned:
-            from . import ops
             ops.repack_cache.unpin(self._pinned)
             self._pinned = []
 
@@ -941,6 +985,8 @@ class GraphedDStep:
         if len(o.penalty) > 0:
             b["alpha"] = torch.empty(B, device=dev)
         self.bufs = b
+        self.tr.explicit = {k: b[s] for k, s in (("ms_adapt", "ms_adapt"), ("pen_real", "pen_real"), ("alpha", "alpha"),
+                                                 ("ms_adapt_labels", "ms_labels")) if s in b}
 
     @torch.no_grad()
     def _fill(self, img, labels):
@@ -953,14 +999,14 @@ class GraphedDStep:
             ms = self.tr.mean_sampler
             direct = b["ms_adapt"].is_cuda and b["ms_adapt"].dim() == 4 and ms.mean_samples.is_cuda and ms.mean_samples.dim() == 5
             req = b.get("labels") if labels is not None else None
-            xa, ya = ms.sample(img.shape[0], requested_labels=req, out=b["ms_adapt"] if direct else None)
-            if not direct:
-                b["ms_adapt"].copy_(xa)
-            xp, _ = ms.sample(img.shape[0], requested_labels=req, out=b["pen_real"] if direct else None)
-            if not direct:
-                b["pen_real"].copy_(xp)
+            drawn_labels = []
+            for key in ("ms_adapt", "pen_real"):
+                x, yl = ms.sample(img.shape[0], requested_labels=req, out=b[key] if direct else None)
+                if not direct:
+                    b[key].copy_(x)
+                drawn_labels.append(yl)
             if "ms_labels" in b:
-                b["ms_labels"].copy_(ya)
+                b["ms_labels"].copy_(drawn_labels[0])
         if "alpha" in b:
             b["alpha"].uniform_(0.0, 1.0)
 
@@ -969,8 +1015,6 @@ class GraphedDStep:
         self.tr.train_D(b["img"], b["labels"], b["z"], b["labels"], use_dp=True)
 
     def _replay(self):
-        if not self.segmented:
-            return self.graph.replay()
         for i, g in enumerate(self.graphs):      # graph, collective, graph, ... : the collectives are ordinary stream-ordered calls
             g.replay()
             if i < len(self.between):
@@ -980,7 +1024,6 @@ class GraphedDStep:
         """Record the step as several graphs that END at each collective (distributed._boundary): nothing of RCCL / gloo is inside a
         graph.  All graphs share the first one's memory pool (a tensor made in one segment is read in the next); the closures kept
         in self.between hold the tensors their collectives run on, so those addresses stay reserved."""
-        from . import distributed as Dist
         graphs, between, cur = [], [], [None]
         cap = torch.cuda.Stream()
         cap.wait_stream(torch.cuda.current_stream())
@@ -1022,13 +1065,58 @@ class GraphedDStep:
         torch.cuda.current_stream().wait_stream(cap)
         self.graphs, self.between = graphs, between
 
+    def _record(self):
+        """Record the step the static buffers hold; its host-side bookkeeping runs once, here.  False when the capture failed: the
+        host state is back where it was and the run goes on eagerly."""
+        tr, pe = self.tr, self.tr.privacy_engine
+        # state a replay must find in HBM exists BEFORE the capture (created inside it, torch.full would be re-run by every
+        # replay: a constant Adam step and a constant noise offset)
+        tr.d_optimizer.prepare_capture()
+        pe.ensure_noise_counter()
+        # every repacked / folded filter of the CRITIC must be RECORDED: a cache hit at capture time would bake in "no repack"
+        # plus a pointer to an eager buffer — stale weights (and freed memory) on every replay once a replayed Adam has moved the
+        # parameters.  The GENERATOR is frozen during D-steps: its folded / pre-split filters (made by the eager warm-up steps) are
+        # PINNED instead — the recording hits them, no replay re-makes them, and refresh_pinned() rebuilds them in place before a
+        # replay when a train_G step has changed the weights.
+        torch.cuda.synchronize()
+        self._pinned = ops.repack_cache.pin({m._wtoken for m in tr.G.modules() if hasattr(m, "_wtoken")})
+        ops.repack_cache.clear()
+        torch.cuda.synchronize()
+        counters = _StepCounters(pe, tr.d_optimizer)
+        snap = counters.snapshot()
+        self.segmented = tr.world_size > 1 and not Dist.collectives_capturable()
+        try:
+            with _no_gc():
+                if self.segmented:
+                    self._capture_segments()
+                else:
+                    graph = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(graph):
+                        self._eager()            # RECORDED, not executed
+                    self.graphs = [graph]
+        except Exception as e:                   # e.g. a collective this backend cannot record
+            warnings.warn("HIP-graph capture of the D-step failed (%s: %s); stepping eagerly from here on" % (type(e).__name__, str(e)[:200]))
+            torch.cuda.synchronize()
+            ops.repack_cache.clear()
+            # A whole-step recording executed nothing on the device.  A segmented one has issued, for real, the collectives it
+            # reached (boundary() in _capture_segments) on whatever the unexecuted graphs left in memory; no kernel of the step ran.
+            # Either way the host-side bookkeeping goes back and the half-built per-sample state is dropped; the caller then runs
+            # this step eagerly.
+            counters.restore(snap)
+            pe._reset_samples()
+            for p in pe.params:
+                if hasattr(p, "summed_grad"):
+                    del p.summed_grad
+            self.use_graph, self.capture_error = False, repr(e)[:300]
+            return False
+        self.graph = self.graphs[0]
+        ops.repack_cache.clear()                 # entries made during capture point into the graph's private pool (pinned ones stay)
+        return True
+
     def __call__(self, img, labels=None):
         tr = self.tr
         if self.bufs is None:
             self._alloc(img, labels)
-            b = self.bufs
-            tr.explicit = {k: b[s] for k, s in (("ms_adapt", "ms_adapt"), ("pen_real", "pen_real"), ("alpha", "alpha"),
-                                                ("ms_adapt_labels", "ms_labels")) if s in b}
         elif img.shape != self.bufs["img"].shape:
             raise RuntimeError("GraphedDStep was recorded for batch shape %s, got %s" % (tuple(self.bufs["img"].shape), tuple(img.shape)))
         self._fill(img, labels)
@@ -1038,78 +1126,12 @@ class GraphedDStep:
             if self.warmup > 0:
                 self.warmup -= 1
                 return self._eager()             # first steps run eagerly: allocator pools, caches and accumulators settle
-            from . import ops
-            pe = tr.privacy_engine
-            # state a replay must find in HBM exists BEFORE the capture (created inside it, torch.full would be re-run by every
-            # replay: a constant Adam step and a constant noise offset)
-            tr.d_optimizer.prepare_capture()
-            pe.ensure_noise_counter()
-            # every repacked / folded filter of the CRITIC must be RECORDED: a cache hit at capture time would bake in "no repack"
-            # plus a pointer to an eager buffer — stale weights (and freed memory) on every replay once a replayed Adam has moved the
-            # parameters.  The GENERATOR is frozen during D-steps: its folded / pre-split filters (made by the eager
-            # warm-up steps) are PINNED instead — the recording hits them, no replay re-makes them, and refresh_pinned() rebuilds
-            # them in place before a replay when a train_G step has changed the weights (round 4; 8 launches per step gone).
-            torch.cuda.synchronize()
-            self._pinned = ops.repack_cache.pin({m._wtoken for m in tr.G.modules() if hasattr(m, "_wtoken")})
-            ops.repack_cache.clear()
-            torch.cuda.synchronize()
-            steps0, calls0 = pe.steps, pe._noise_calls
-            adam0 = {id(st): st["step"] for st in tr.d_optimizer.state.values()}
-            graph = torch.cuda.CUDAGraph()
-            # No cyclic garbage collection while the stream is capturing.  A dead cycle that owns device resources — an earlier
-            # GraphedDStep's graph and its private pool, most of all — is finalised wherever the collector happens to run, which can
-            # be an autograd worker thread in the middle of this recording; releasing a pool calls hipFree, which is not permitted
-            # during a (global-mode) capture, and the failure surfaces inside a destructor: the process aborts.  (torch 2.10 no longer
-            # collects in torch.cuda.graph.__enter__.)  So: collect now, on this thread, then keep the collector off until the
-            # capture has ended.  The double backward of an is-mode step makes enough cycles to trip it within one recording.
-            import gc
-            gc.collect()
-            gc_was_on = gc.isenabled()
-            gc.disable()
-            err = None
-            from . import distributed as Dist
-            self.segmented = tr.world_size > 1 and not Dist.collectives_capturable()
-            try:
-                if self.segmented:
-                    self._capture_segments()
-                    graph = self.graphs[0]
-                else:
-                    with torch.cuda.graph(graph):
-                        self._eager()            # RECORDED, not executed; its host-side bookkeeping ran once
-            except Exception as e:               # e.g. a collective this backend cannot record: the run goes on eagerly
-                err = e
-            finally:
-                if gc_was_on:
-                    gc.enable()
-            if err is not None:
-                e = err
-                import warnings
-                warnings.warn("HIP-graph capture of the D-step failed (%s: %s); stepping eagerly from here on" % (type(e).__name__, str(e)[:200]))
-                torch.cuda.synchronize()
-                ops.repack_cache.clear()
-                # nothing of the recorded step ran on the device: put the host-side bookkeeping back and drop the half-built
-                # per-sample state, then run this step eagerly
-                pe.steps, pe._noise_calls = steps0, calls0
-                for st in tr.d_optimizer.state.values():
-                    st["step"] = adam0.get(id(st), st["step"])
-                pe._reset_samples()
-                for p in pe.params:
-                    if hasattr(p, "summed_grad"):
-                        del p.summed_grad
-                self.use_graph, self.capture_error = False, repr(e)[:300]
+            if not self._record():
                 return self._eager()
-            self.graph = graph
-            ops.repack_cache.clear()             # entries made during capture point into the graph's private pool (pinned ones stay)
-            self._replay()                       # the step itself
-            tr.d_optimizer.bump_versions()
-            return
-        if self._pinned:
-            from . import ops
-            ops.repack_cache.refresh_pinned()    # a train_G step since the last replay: the generator's filter workspaces, in place
-        self._replay()
-        pe = tr.privacy_engine                   # what the recorded python would have done on the host
-        pe.steps += 1
-        pe._noise_calls += 1
-        for st in tr.d_optimizer.state.values():
-            st["step"] += 1
+            self._replay()                       # the step itself; the recording has advanced the host counters
+        else:
+            if self._pinned:
+                ops.repack_cache.refresh_pinned()    # a train_G step since the last replay: the generator's filter workspaces, in place
+            self._replay()
+            _StepCounters(tr.privacy_engine, tr.d_optimizer).advance()     # what the recorded python would have done on the host
         tr.d_optimizer.bump_versions()           # the replayed Adam wrote D's weights: eager code (train_G) must re-pack them

@@ -402,3 +402,98 @@ def test_bench_options():
     assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout, r.stderr[-2000:]
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--dump-shapes", "x.txt"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 2 and "--dump-shapes needs --full" in r.stderr
+
+
+def _bare_trainer(tmp_path, **opt):
+    """A Trainer with nothing but the attributes the host-side helpers under test read (no models, no device)."""
+    from types import SimpleNamespace as NS
+    from csl_gan_amd.logger import Logger
+    from csl_gan_amd.trainer import Trainer
+    t = Trainer.__new__(Trainer)
+    t.opt = NS(**opt)
+    t.logger = Logger("{} {} {}", ["IS Mean", "IS Min", "IS Max"], 4, str(tmp_path / ("log%d.csv" % len(list(tmp_path.iterdir())))))
+    t.dev_stats, t._pending_stats, t.explicit, t.last = {}, [], {}, {}
+    return t
+
+
+@pytest.mark.parametrize("per_param", [True, False])
+def test_is_logging_device_and_host_routes_follow_the_reference(tmp_path, per_param):
+    """update_is_logging over three steps: through the device buffers (an engine with batch_sensitivity_device) and through the host
+    arithmetic (an engine without) the Logger ends up with the same IS Mean / Min / Max, and with what train.py:332-338 gives for the
+    sequence: sums for the mean, extrema times the logging interval (4 here), the non-per-param minimum starting from 99999."""
+    from types import SimpleNamespace as NS
+    seq = [[0.5, 2.0, 0.25], [0.125, 4.0, 0.25], [1.0, 3.0, 8.0]] if per_param else [[0.5], [0.125], [2.0]]    # exact in fp32
+
+    dev = _bare_trainer(tmp_path, imm_sens_per_param=per_param)
+    for i, s in enumerate(seq):
+        dev.privacy_engine = NS(batch_sensitivity_device=torch.tensor(s, dtype=torch.float32))
+        dev.update_is_logging()
+        if i == 1:
+            assert dev.logger.stats["IS Min"] == 0.0               # nothing reaches the Logger before a flush
+            dev.flush_stats()                                      # a flush inside the interval: the extrema fold across it
+    dev.flush_stats()
+
+    host = _bare_trainer(tmp_path, imm_sens_per_param=per_param)
+    for i, s in enumerate(seq):
+        host.privacy_engine = NS(batch_sensitivity=np.array(s, dtype=np.float64) if per_param else s[0])
+        host.update_is_logging()
+        if i == 1:
+            host.flush_stats()                                     # a flush between steps moves nothing on this route
+    host.flush_stats()
+
+    # train.py:332-338 written out
+    ref = dict.fromkeys(("IS Mean", "IS Min", "IS Max"), 0.0)
+    for s in seq:
+        v = np.array(s, dtype=np.float64) if per_param else s[0]
+        ref["IS Mean"] += v
+        if per_param:
+            ref["IS Min"] = v * 4 if isinstance(ref["IS Min"], float) else np.minimum(ref["IS Min"], v * 4)
+            ref["IS Max"] = np.maximum(ref["IS Max"], v * 4)
+        else:
+            ref["IS Min"] = min(99999 if ref["IS Min"] < 1e-8 else ref["IS Min"], v * 4)
+            ref["IS Max"] = max(ref["IS Max"], v * 4)
+    if not per_param:
+        assert (ref["IS Mean"], ref["IS Min"], ref["IS Max"]) == (2.625, 0.5, 8.0)
+    for k in ref:
+        assert np.array_equal(np.asarray(dev.logger.stats[k]), np.asarray(ref[k])), (k, dev.logger.stats[k], ref[k])
+        assert np.array_equal(np.asarray(host.logger.stats[k]), np.asarray(ref[k])), (k, host.logger.stats[k], ref[k])
+    before = {k: np.array(dev.logger.stats[k], copy=True) for k in ref}
+    dev.flush_stats()                                              # no step since the last flush
+    for k in ref:
+        assert np.array_equal(np.asarray(dev.logger.stats[k]), before[k]), k
+    assert all(not np.isfinite(v.numpy()).any() for k, v in dev.dev_stats.items() if k in ("_is_min", "_is_max"))
+
+
+@pytest.mark.parametrize("with_penalty,mode,moving_avg_updated,logged", [
+    (True, "moving-avg-pl", True, True),
+    (True, "standard", False, True),
+    (False, "moving-avg-pl", True, False),        # train.py:468-473: the logging is the `elif` of the moving-average update
+    (False, "standard", False, True),
+])
+def test_imm_sens_finish_keeps_the_reference_asymmetry(tmp_path, with_penalty, mode, moving_avg_updated, logged):
+    from types import SimpleNamespace as NS
+    calls = []
+    t = _bare_trainer(tmp_path, imm_sens_scaling_mode=mode)
+    t.privacy_engine = NS(backward=lambda loss, inputs: calls.append(("backward", loss, inputs)))
+    t.update_sens_moving_avg = lambda: calls.append("moving_avg")
+    t.update_is_logging = lambda: calls.append("log")
+    t._finish_imm_sens("loss", "img", with_penalty=with_penalty)
+    assert calls[0] == ("backward", "loss", "img")
+    assert calls[1:] == ["moving_avg"] * moving_avg_updated + ["log"] * logged
+    assert "is_param_grads" not in t.last
+
+
+def test_step_counters_snapshot_advance_restore():
+    from types import SimpleNamespace as NS
+    from csl_gan_amd.trainer import _StepCounters
+    pe = NS(steps=5, _noise_calls=11)
+    opt = NS(state={"a": {"step": 3}, "b": {"step": 3}, "c": {"step": 7}})
+    c = _StepCounters(pe, opt)
+    snap = c.snapshot()
+    c.advance()
+    assert (pe.steps, pe._noise_calls, [st["step"] for st in opt.state.values()]) == (6, 12, [4, 4, 8])
+    c.advance()
+    assert (pe.steps, pe._noise_calls, [st["step"] for st in opt.state.values()]) == (7, 13, [5, 5, 9])
+    opt.state["d"] = {"step": 1}                   # a state made after the snapshot keeps its own count
+    c.restore(snap)
+    assert (pe.steps, pe._noise_calls, [st["step"] for st in opt.state.values()]) == (5, 11, [3, 3, 7, 1])
