@@ -34,6 +34,7 @@ EXPORTS = [
     "cslgan_latent_normal_f32", "cslgan_f32_to_u8",
     "cslgan_attack_trials", "cslgan_rank_counts", "cslgan_softmax_max_rows_f32",
     "cslgan_ovr_logreg_ws_floats", "cslgan_ovr_logreg_eval_f32", "cslgan_ovr_logreg_proba_f32",
+    "cslgan_nn_padded_dim", "cslgan_nn_prepare_u8", "cslgan_nn_min_i8",
 ]
 
 
@@ -155,6 +156,9 @@ def lib():
         "cslgan_softmax_max_rows_f32": [vp, i64, i32, vp, vp],
         "cslgan_ovr_logreg_eval_f32": [vp, vp, vp, i64, i32, i32, vp, vp, vp, i64, vp],
         "cslgan_ovr_logreg_proba_f32": [vp, i32, vp, i64, i32, i32, vp, vp],
+        "cslgan_nn_padded_dim": [i32],
+        "cslgan_nn_prepare_u8": [vp, i64, i32, i32, vp, vp, vp],
+        "cslgan_nn_min_i8": [vp, vp, i64, vp, vp, i64, i32, i64, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

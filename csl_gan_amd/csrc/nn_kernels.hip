@@ -1,0 +1,291 @@
+// Nearest-neighbour audit kernels for gfx950 (csl_gan_amd.neighbours; DESIGN.md §6g, include/cslgan.h "Nearest-neighbour audit").
+//
+// Exact integer arithmetic on uint8 image caches: for every query row the smallest squared Euclidean distance to a reference row
+// and the index of that row, as one uint64 key (d2 << 32 | index).  The bytes are shifted to int8 (x - 128) once by
+// nn_prepare_u8_kernel, which also leaves |row|^2; nn_min_i8_kernel is then an nq x nr x Dp dot-product GEMM on the int8 matrix
+// instruction whose epilogue forms d2 = |a|^2 + |b|^2 - 2 a.b and keeps a running minimum per row: the nq x nr matrix never
+// reaches memory.
+#include "common.h"
+#include "device_prims.h"
+
+namespace cslgan {
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int NN_KT = 64;                         // bytes of K per LDS stage = the row pitch granule of the prepared operands
+constexpr int NN_TM = 128, NN_TN = 128;           // rows of Q x rows of R per workgroup tile: 2 x 2 waves of 64 x 64
+constexpr int NN_PITCH = NN_KT + 16;              // LDS row pitch: 20 dwords, so 16 consecutive rows of a 16-byte read cover all 64 banks
+constexpr int NN_THREADS = 256;
+constexpr int NN_MAX_D = 65536;                   // 255^2 D < 2^32
+constexpr unsigned long long NN_NONE = ~0ull;     // "nothing seen yet"
+
+__device__ __forceinline__ int wave_sum_i32(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// ---- prepare: uint8 [rows, D] -> int8 [rows, Dp] (x - 128, zero padding) and |row|^2 ------------------------------------------
+// One wave per row, one 16-byte store per lane and step.  A row starts at x + row * D, which is 16-byte aligned only when D is a
+// multiple of 16: a chunk is assembled from the two ALIGNED 16-byte words that hold it (v_alignbyte), so every access is 16 bytes
+// wide and aligned whatever D is.  Words that reach beyond the last byte of x are never touched: those chunks read byte by byte.
+__device__ __forceinline__ u32x4 nn_shift_bytes(const u32x4& lo, const u32x4& hi, int s) {
+    const unsigned w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    const int ds = s >> 2, bs = s & 3;
+    u32x4 o;
+    // ds is uniform over the wave (one row): four straight-line variants keep w[] in registers
+#define NN_PICK(d)                                                                                         \
+    o.x = __builtin_amdgcn_alignbyte(w[d + 1], w[d], bs); o.y = __builtin_amdgcn_alignbyte(w[d + 2], w[d + 1], bs); \
+    o.z = __builtin_amdgcn_alignbyte(w[d + 3], w[d + 2], bs); o.w = __builtin_amdgcn_alignbyte(w[d + 4], w[d + 3], bs);
+    if (ds == 0) { NN_PICK(0) } else if (ds == 1) { NN_PICK(1) } else if (ds == 2) { NN_PICK(2) } else { NN_PICK(3) }
+#undef NN_PICK
+    return o;
+}
+
+__device__ __forceinline__ int nn_sq4(unsigned v) {           // sum of the squares of the four int8 of v
+    const int a = (int)(signed char)(v & 0xffu), b = (int)(signed char)((v >> 8) & 0xffu), c = (int)(signed char)((v >> 16) & 0xffu),
+              d = (int)(signed char)(v >> 24);
+    return a * a + b * b + c * c + d * d;
+}
+
+__global__ __launch_bounds__(NN_THREADS) void nn_prepare_u8_kernel(const unsigned char* __restrict__ x, long long rows, int D, int Dp,
+                                                                   signed char* __restrict__ xs, int* __restrict__ sqnorm) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * (NN_THREADS / WAVE) + (threadIdx.x >> 6);
+    if (row >= rows) return;                                   // whole waves leave: no barrier follows
+    const unsigned long long total = (unsigned long long)rows * (unsigned long long)D;      // bytes of x
+    const unsigned long long start = (unsigned long long)row * (unsigned long long)D;       // first byte of this row
+    const int s = (int)(start & 15u);                          // x is 16-byte aligned (checked by the host)
+    const unsigned long long start_al = start - (unsigned long long)s;
+    const unsigned long long whole = total & ~15ull;           // the aligned 16-byte words below this offset lie inside x
+    u32x4* __restrict__ dst = reinterpret_cast<u32x4*>(xs + row * (long long)Dp);
+    int sq = 0;
+    for (int c = lane; c < Dp / 16; c += WAVE) {
+        const int valid = D - 16 * c;                          // bytes of this chunk that exist in the row (<= 0: padding only)
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if (valid > 0) {
+            const unsigned long long g = start_al + 16ull * (unsigned long long)c;          // aligned; the chunk is bytes g + s .. g + s + 15
+            if (g + 32ull <= whole) {
+                const u32x4 lo = *reinterpret_cast<const u32x4*>(x + g);
+                const u32x4 hi = *reinterpret_cast<const u32x4*>(x + g + 16);
+                v = nn_shift_bytes(lo, hi, s);
+            } else {                                           // the last words of x: byte by byte, nothing beyond total is read
+                unsigned b[4] = {0u, 0u, 0u, 0u};
+                for (int j = 0; j < 16; ++j) {
+                    const unsigned long long a = g + (unsigned long long)(s + j);
+                    const unsigned byte = a < total ? (unsigned)x[a] : 0u;
+                    b[j >> 2] |= byte << (8 * (j & 3));
+                }
+                v.x = b[0]; v.y = b[1]; v.z = b[2]; v.w = b[3];
+            }
+            v ^= 0x80808080u;                                  // byte - 128 as int8
+            if (valid < 16) {                                  // zero the bytes past the row's end (they hold the next row or nothing)
+                unsigned m[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int nb = valid - 4 * j;              // valid bytes of dword j
+                    m[j] = nb >= 4 ? 0xffffffffu : (nb <= 0 ? 0u : ((1u << (8 * nb)) - 1u));
+                }
+                v.x &= m[0]; v.y &= m[1]; v.z &= m[2]; v.w &= m[3];
+            }
+            sq += nn_sq4(v.x) + nn_sq4(v.y) + nn_sq4(v.z) + nn_sq4(v.w);
+        }
+        dst[c] = v;
+    }
+    sq = wave_sum_i32(sq);                                     // <= 2^14 D <= 2^30
+    if (lane == 0) sqnorm[row] = sq;
+}
+
+// ---- the search ------------------------------------------------------------------------------------------------------------------
+// Workgroup (bx, by): rows bx * 128 .. of Q against column tiles by * tiles_per .. of R.  The K loop runs flattened over
+// (column tile, K stage): stage i + 1 is fetched from HBM/L2 into registers while stage i is multiplied out of LDS, and stored to
+// the other LDS buffer before the single barrier of the iteration.  Both operands are K-contiguous and read with the same
+// lane -> k assignment (lane half h: 16 consecutive bytes), so the sums do not depend on the instruction's k order; the
+// row/column maps are those of every 32x32 form: operand row = lane & 31, C/D col = lane & 31, row = (reg & 3) + 8 (reg >> 2) +
+// 4 (lane >> 5); tests/test_nearest_gpu.py checks them with asymmetric exact-integer data.
+__global__ __launch_bounds__(NN_THREADS) void nn_min_i8_kernel(const signed char* __restrict__ q, const int* __restrict__ qn, int nq,
+                                                               const signed char* __restrict__ r, const int* __restrict__ rn, int nr, int Dp,
+                                                               uint32_t index_base, int tiles_per, int n_col_tiles,
+                                                               unsigned long long* __restrict__ best) {
+    __shared__ __attribute__((aligned(16))) unsigned char sA[2][NN_TM * NN_PITCH];
+    __shared__ __attribute__((aligned(16))) unsigned char sB[2][NN_TN * NN_PITCH];
+    __shared__ int qn_s[NN_TM];
+    __shared__ unsigned long long red[2][NN_TM];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;                   // this wave's 64 x 64 quadrant
+    const int l31 = lane & 31, lh = lane >> 5;
+    const long long row0 = (long long)blockIdx.x * NN_TM;
+    const int rows_here = (int)(nq - row0 < NN_TM ? nq - row0 : NN_TM);
+    const int tile_first = blockIdx.y * tiles_per;
+    const int tile_end = tile_first + tiles_per < n_col_tiles ? tile_first + tiles_per : n_col_tiles;
+    const int nk = Dp / NN_KT;
+    const int n_iter = (tile_end - tile_first) * nk;
+
+    if (tid < NN_TM) qn_s[tid] = tid < rows_here ? qn[row0 + tid] : 0;
+
+    // range-checked descriptors over the rows that exist: a row past nq / nr reads as zeros (and is masked in the epilogue anyway)
+    const __amdgpu_buffer_rsrc_t rq = make_rsrc(q + row0 * (long long)Dp, (unsigned)rows_here * (unsigned)Dp);
+    const int ld_row = tid >> 2, ld_chunk = (tid & 3) * 16;    // this thread's two 16-byte pieces of a stage: rows ld_row, ld_row + 64
+    const unsigned ld_off = (unsigned)ld_row * (unsigned)Dp + (unsigned)ld_chunk;
+    const unsigned ld_off2 = ld_off + 64u * (unsigned)Dp;
+    const int st_off = ld_row * NN_PITCH + ld_chunk;
+
+    u32x4 ga0, ga1, gb0, gb1;
+    int f_kt = 0, f_ct = tile_first;                           // the (column tile, K stage) of the next fetch
+    auto fetch = [&]() {
+        const unsigned k0 = (unsigned)f_kt * NN_KT;
+        const long long c0 = (long long)f_ct * NN_TN;
+        const int cols_here = (int)(nr - c0 < NN_TN ? nr - c0 : NN_TN);
+        const __amdgpu_buffer_rsrc_t rr = make_rsrc(r + c0 * (long long)Dp, (unsigned)cols_here * (unsigned)Dp);
+        ga0 = buf_load4_raw(rq, ld_off + k0);
+        ga1 = buf_load4_raw(rq, ld_off2 + k0);
+        gb0 = buf_load4_raw(rr, ld_off + k0);
+        gb1 = buf_load4_raw(rr, ld_off2 + k0);
+        if (++f_kt == nk) { f_kt = 0; ++f_ct; }
+    };
+    auto stash = [&](int buf) {
+        *reinterpret_cast<u32x4*>(&sA[buf][st_off]) = ga0;
+        *reinterpret_cast<u32x4*>(&sA[buf][st_off + 64 * NN_PITCH]) = ga1;
+        *reinterpret_cast<u32x4*>(&sB[buf][st_off]) = gb0;
+        *reinterpret_cast<u32x4*>(&sB[buf][st_off + 64 * NN_PITCH]) = gb1;
+    };
+
+    unsigned long long bk[2][16];
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) bk[mt][i] = NN_NONE;
+    i32x16 acc[2][2];
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[mt][nt][i] = 0;
+
+    if (n_iter > 0) {
+        fetch();
+        stash(0);
+    }
+    __syncthreads();                                           // also publishes qn_s
+
+    const int a_off = (wm * 64 + l31) * NN_PITCH + 16 * lh;
+    const int b_off = (wn * 64 + l31) * NN_PITCH + 16 * lh;
+    int kt = 0, ct = tile_first;
+    for (int it = 0; it < n_iter; ++it) {
+        const int buf = it & 1;
+        if (it + 1 < n_iter) fetch();
+#pragma unroll
+        for (int ks = 0; ks < NN_KT / 32; ++ks) {
+            i32x4 a[2], b[2];
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                a[t] = *reinterpret_cast<const i32x4*>(&sA[buf][a_off + t * 32 * NN_PITCH + ks * 32]);
+                b[t] = *reinterpret_cast<const i32x4*>(&sB[buf][b_off + t * 32 * NN_PITCH + ks * 32]);
+            }
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[mt], b[nt], acc[mt][nt], 0, 0, 0);
+        }
+        if (++kt == nk) {
+            // epilogue of one column tile: d2 = |a|^2 + |b|^2 - 2 a.b in uint32 (the true value is below 2^32, so arithmetic mod
+            // 2^32 returns it exactly; int32 would not hold it), key = d2 << 32 | index, running minimum per row in registers
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt) {
+                const long long col = (long long)ct * NN_TN + wn * 64 + nt * 32 + l31;
+                const bool live = col < nr;
+                const uint32_t bn = live ? (uint32_t)rn[col] : 0u;
+                const uint32_t idx = index_base + (uint32_t)col;
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) {
+                        const int rl = wm * 64 + mt * 32 + (i & 3) + 8 * (i >> 2) + 4 * lh;
+                        const uint32_t d2 = (uint32_t)qn_s[rl] + bn - 2u * (uint32_t)acc[mt][nt][i];
+                        const unsigned long long key = live ? (((unsigned long long)d2 << 32) | (unsigned long long)idx) : NN_NONE;
+                        bk[mt][i] = key < bk[mt][i] ? key : bk[mt][i];
+                        acc[mt][nt][i] = 0;
+                    }
+            }
+            kt = 0;
+            ++ct;
+        }
+        if (it + 1 < n_iter) stash(buf ^ 1);                   // last read in iteration it - 1, which every wave has left
+        __syncthreads();
+    }
+
+    // per-row minimum over the 32 lanes that share a row, then over the two waves of a row half, then ONE atomicMin per row
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            unsigned long long v = bk[mt][i];
+#pragma unroll
+            for (int o = 16; o > 0; o >>= 1) {
+                const unsigned long long u = __shfl_xor(v, o, 64);
+                v = u < v ? u : v;
+            }
+            if (l31 == 0) red[wn][wm * 64 + mt * 32 + (i & 3) + 8 * (i >> 2) + 4 * lh] = v;
+        }
+    __syncthreads();
+    if (tid < rows_here) {
+        const unsigned long long v0 = red[0][tid], v1 = red[1][tid];
+        const unsigned long long v = v0 < v1 ? v0 : v1;
+        if (v != NN_NONE) atomicMin(&best[row0 + tid], v);
+    }
+}
+
+}  // namespace cslgan
+
+using namespace cslgan;
+
+extern "C" {
+
+int cslgan_nn_padded_dim(int D) {
+    if (D < 1 || D > NN_MAX_D) return 0;
+    return (D + NN_KT - 1) / NN_KT * NN_KT;
+}
+
+int cslgan_nn_prepare_u8(const void* x, int64_t rows, int D, int Dp, void* xs, int32_t* sqnorm, void* stream) {
+    CSLGAN_REQUIRE(x && xs && sqnorm, "nn_prepare_u8: null argument");
+    CSLGAN_REQUIRE(D >= 1 && D <= NN_MAX_D, "nn_prepare_u8: D=%d must lie in 1 .. %d", D, NN_MAX_D);
+    CSLGAN_REQUIRE(Dp == cslgan_nn_padded_dim(D), "nn_prepare_u8: Dp=%d is not the padded width %d of D=%d", Dp, cslgan_nn_padded_dim(D), D);
+    CSLGAN_REQUIRE(rows >= 1 && rows < (1ll << 31), "nn_prepare_u8: rows=%lld out of range", (long long)rows);
+    CSLGAN_REQUIRE(aligned16(x) && aligned16(xs) && (reinterpret_cast<uintptr_t>(sqnorm) & 3u) == 0, "nn_prepare_u8: misaligned pointer");
+    note_kernel("nn_prepare_u8_kernel");
+    const int rows_per_wg = NN_THREADS / WAVE;
+    hipLaunchKernelGGL(nn_prepare_u8_kernel, dim3((unsigned)((rows + rows_per_wg - 1) / rows_per_wg)), dim3(NN_THREADS), 0, (hipStream_t)stream,
+                       (const unsigned char*)x, (long long)rows, D, Dp, (signed char*)xs, (int*)sqnorm);
+    return check_launch("nn_prepare_u8_kernel");
+}
+
+int cslgan_nn_min_i8(const void* q, const int32_t* qn, int64_t nq, const void* r, const int32_t* rn, int64_t nr, int Dp, int64_t index_base,
+                     uint64_t* best, void* stream) {
+    CSLGAN_REQUIRE(q && qn && r && rn && best, "nn_min_i8: null argument");
+    CSLGAN_REQUIRE(Dp >= NN_KT && Dp <= NN_MAX_D && Dp % NN_KT == 0, "nn_min_i8: Dp=%d must be a multiple of %d in %d .. %d", Dp, NN_KT, NN_KT,
+                   NN_MAX_D);
+    CSLGAN_REQUIRE(nq >= 1 && nq < (1ll << 31), "nn_min_i8: nq=%lld out of range", (long long)nq);
+    CSLGAN_REQUIRE(nr >= 1 && nr < (1ll << 31), "nn_min_i8: nr=%lld out of range", (long long)nr);
+    CSLGAN_REQUIRE(index_base >= 0 && index_base + nr <= 0xFFFFFFFFll, "nn_min_i8: index_base + nr = %lld exceeds 2^32 - 1",
+                   (long long)(index_base + nr));
+    CSLGAN_REQUIRE(aligned16(q) && aligned16(r) && (reinterpret_cast<uintptr_t>(qn) & 3u) == 0 && (reinterpret_cast<uintptr_t>(rn) & 3u) == 0 &&
+                       (reinterpret_cast<uintptr_t>(best) & 7u) == 0,
+                   "nn_min_i8: misaligned pointer");
+    const long long row_tiles = (nq + NN_TM - 1) / NN_TM, col_tiles = (nr + NN_TN - 1) / NN_TN;
+    // enough workgroups for every CU a few times over, and as few atomics per row as that allows
+    long long splits = (1024 + row_tiles - 1) / row_tiles;
+    splits = splits < 1 ? 1 : (splits > col_tiles ? col_tiles : splits);
+    const long long tiles_per = (col_tiles + splits - 1) / splits;
+    const long long gy = (col_tiles + tiles_per - 1) / tiles_per;
+    CSLGAN_REQUIRE(gy <= 65535, "nn_min_i8: nr=%lld needs %lld column ranges", (long long)nr, gy);
+    note_kernel("nn_min_i8_kernel");
+    hipLaunchKernelGGL(nn_min_i8_kernel, dim3((unsigned)row_tiles, (unsigned)gy), dim3(NN_THREADS), 0, (hipStream_t)stream, (const signed char*)q,
+                       (const int*)qn, (int)nq, (const signed char*)r, (const int*)rn, (int)nr, Dp, (uint32_t)index_base, (int)tiles_per,
+                       (int)col_tiles, (unsigned long long*)best);
+    return check_launch("nn_min_i8_kernel");
+}
+
+}  // extern "C"

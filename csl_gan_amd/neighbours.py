@@ -1,0 +1,216 @@
+"""Exact nearest-neighbour audit of a synthetic image cache (include/cslgan.h "Nearest-neighbour audit").
+
+For every query image the nearest reference image under the squared Euclidean distance on the cache BYTES, as one uint64 key:
+
+    d2(q, r) = sum_i (Q[q, i] - R[r, i])^2                       an integer in [0, 65025 D],  D = H W C <= 65536
+    key(q)   = min over r of (d2(q, r) << 32 | (index_base + r))
+
+The neighbour is the low word, its squared distance the high word, and ties go to the smallest index.  The key is a minimum over a
+set, so it does not depend on how the reference is cut into blocks.  Everything is integer arithmetic: `nearest_host` is the
+definition, and the device path (`ops.nn_prepare` + `ops.nn_min`) is held to it by equality.
+
+`NearestSearch` drives the device over a pipeline.CachedImages reference of any size; `dcr_metrics` turns keys into the
+"distance to closest record" figures and the share of samples that lie closer to the training set than to a held-out set — 0.5 for
+a generator that has not memorised.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+import torch
+
+MAX_D = 65536
+NONE_KEY = np.uint64(0xFFFFFFFFFFFFFFFF)
+MAX_INDEX = 2 ** 32 - 1
+
+
+def split_keys(keys):
+    """(d2, index) of uint64 keys, both as int64 arrays."""
+    k = np.asarray(keys, dtype=np.uint64)
+    return (k >> np.uint64(32)).astype(np.int64), (k & np.uint64(0xFFFFFFFF)).astype(np.int64)
+
+
+def _rows_u8(a):
+    a = np.asarray(a) if not isinstance(a, np.ndarray) else a
+    if a.dtype != np.uint8 or a.ndim < 2:
+        raise ValueError("need a uint8 array [n, ...], got %s %s" % (a.dtype, a.shape))
+    return a.reshape(a.shape[0], -1)
+
+
+def nearest_host(Q, R, index_base=0, best=None, block=1024):
+    """key(q) for every row of Q [nq, ...] over the rows of R [nr, ...] (uint8, same row size), merged into `best` (uint64 [nq], the
+    running minimum of earlier calls; all-ones when absent) — THE definition.  The shifted bytes (x - 128) go through a float64
+    matmul in blocks of `block` rows: every product sum is below 2^30 and every d2 below 2^32, far under 2^53, so the floats are
+    the integers."""
+    Q, R = _rows_u8(Q), _rows_u8(R)
+    nq, D = Q.shape
+    nr = R.shape[0]
+    if R.shape[1] != D or not 1 <= D <= MAX_D:
+        raise ValueError("rows of %d and %d bytes; need equal sizes in 1 .. %d" % (D, R.shape[1], MAX_D))
+    if index_base < 0 or index_base + nr > MAX_INDEX:
+        raise ValueError("index_base + nr = %d exceeds 2^32 - 1" % (index_base + nr))
+    out = np.full(nq, NONE_KEY, dtype=np.uint64) if best is None else np.array(best, dtype=np.uint64, copy=True)
+    if out.shape != (nq,):
+        raise ValueError("best has shape %s, expected (%d,)" % (out.shape, nq))
+    block = max(1, int(block))
+    for r0 in range(0, nr, block):
+        b = np.asarray(R[r0:r0 + block]).astype(np.float64) - 128.0
+        bn = (b * b).sum(1)
+        idx = np.arange(index_base + r0, index_base + r0 + len(b), dtype=np.uint64)
+        for q0 in range(0, nq, block):
+            a = np.asarray(Q[q0:q0 + block]).astype(np.float64) - 128.0
+            d2 = (a * a).sum(1)[:, None] + bn[None, :] - 2.0 * (a @ b.T)
+            keys = (d2.astype(np.uint64) << np.uint64(32)) | idx[None, :]
+            out[q0:q0 + block] = np.minimum(out[q0:q0 + block], keys.min(1))
+    return out
+
+
+class NearestSearch:
+    """`fit(reference cache)`, then `query(cache) -> uint64 keys[len(cache)]`, any number of times.
+
+    On a HIP device the reference is walked in blocks of `block_rows` images: pinned uint8 gather -> H2D on a side stream ->
+    ops.nn_prepare -> ops.nn_min with index_base = the block's first row.  Two pinned and two device staging buffers alternate, so
+    block k + 1 is gathered and uploaded while the kernel of block k runs.  Prepared blocks (int8 rows + norms) stay on the device
+    for later queries while they fit `resident_gb`; the rest is streamed again.  The query side goes up in chunks of `query_rows`.
+    On the CPU `nearest_host` runs.  The keys do not depend on block_rows, query_rows or the device."""
+
+    def __init__(self, device, block_rows=16384, resident_gb=8.0, query_rows=16384):
+        self.device = torch.device(device)
+        self.on_gpu = self.device.type == "cuda"
+        self.block_rows, self.query_rows = int(block_rows), int(query_rows)
+        if self.block_rows < 1 or self.query_rows < 1:
+            raise ValueError("block_rows and query_rows must be positive")
+        self.budget = int(float(resident_gb) * 2 ** 30)
+        self.ref = None
+        self._resident, self._resident_bytes, self._copy = {}, 0, None
+
+    def fit(self, cache):
+        if not 1 <= cache.H * cache.W * cache.C <= MAX_D:
+            raise ValueError("images of %d bytes; the search takes 1 .. %d" % (cache.H * cache.W * cache.C, MAX_D))
+        if not 1 <= len(cache) <= MAX_INDEX:
+            raise ValueError("a reference of %d images" % len(cache))
+        self.ref = cache
+        self._resident, self._resident_bytes = {}, 0
+        return self
+
+    def resident_rows(self):
+        return sum(xs.shape[0] for xs, _ in self._resident.values())
+
+    def query(self, cache):
+        if self.ref is None:
+            raise RuntimeError("fit() a reference cache first")
+        if (cache.H, cache.W, cache.C) != (self.ref.H, self.ref.W, self.ref.C):
+            raise ValueError("the query images are %dx%dx%d and the reference images %dx%dx%d: both caches must have one geometry"
+                             % (cache.H, cache.W, cache.C, self.ref.H, self.ref.W, self.ref.C))
+        if not self.on_gpu:
+            return nearest_host(cache.x, self.ref.x)
+        with torch.cuda.device(self.device):
+            return self._query_gpu(cache)
+
+    # ---- device path -------------------------------------------------------------------------------------------------------------
+    def _query_gpu(self, cache):
+        from . import ops
+        n = len(cache)
+        shape = (cache.H, cache.W, cache.C)
+        out = np.empty(n, dtype=np.uint64)
+        stage = torch.empty((min(self.query_rows, n),) + shape, dtype=torch.uint8, pin_memory=True)
+        for s in range(0, n, self.query_rows):
+            cnt = min(self.query_rows, n - s)
+            cache.gather(np.arange(s, s + cnt), stage[:cnt])
+            q, qn = ops.nn_prepare(stage[:cnt].to(self.device, non_blocking=True))
+            best = torch.full((cnt,), -1, device=self.device, dtype=torch.int64)        # all ones: nothing seen yet
+            self._walk_reference(lambda start, r, rn: ops.nn_min(q, qn, r, rn, start, best))
+            out[s:s + cnt] = best.cpu().numpy().view(np.uint64)                          # also: the stage buffer is free again
+        torch.cuda.synchronize(self.device)
+        return out
+
+    def _walk_reference(self, fn):
+        """fn(first row, prepared int8 block, its norms) for every block of the reference, in order, on the current stream."""
+        from . import ops
+        ref, B, dev = self.ref, self.block_rows, self.device
+        n = len(ref)
+        starts = list(range(0, n, B))
+        shape = (min(B, n), ref.H, ref.W, ref.C)
+        main = torch.cuda.current_stream(dev)
+        if self._copy is None:
+            self._copy = torch.cuda.Stream(device=dev)
+        slots = [dict(host=None, dev=None, sent=None, used=None) for _ in range(2)]
+
+        def upload(k):
+            s = starts[k]
+            if s in self._resident:
+                return
+            cnt, sl = min(B, n - s), slots[k % 2]
+            if sl["host"] is None:
+                sl["host"] = torch.empty(shape, dtype=torch.uint8, pin_memory=True)
+                sl["dev"] = torch.empty(shape, dtype=torch.uint8, device=dev)
+            if sl["sent"] is not None:
+                sl["sent"].synchronize()                        # the upload of block k - 2 has left this pinned buffer
+            ref.gather(np.arange(s, s + cnt), sl["host"][:cnt])
+            with torch.cuda.stream(self._copy):
+                if sl["used"] is not None:
+                    self._copy.wait_event(sl["used"])           # nn_prepare of block k - 2 has read the device buffer
+                sl["dev"][:cnt].copy_(sl["host"][:cnt], non_blocking=True)
+                sl["sent"] = torch.cuda.Event()
+                sl["sent"].record(self._copy)
+
+        upload(0)
+        for k, s in enumerate(starts):
+            cnt, sl = min(B, n - s), slots[k % 2]
+            if s in self._resident:
+                r, rn = self._resident[s]
+            else:
+                main.wait_event(sl["sent"])
+                r, rn = ops.nn_prepare(sl["dev"][:cnt])
+                sl["used"] = torch.cuda.Event()
+                sl["used"].record(main)
+                nbytes = r.numel() + 4 * rn.numel()
+                if self._resident_bytes + nbytes <= self.budget:
+                    self._resident[s] = (r, rn)
+                    self._resident_bytes += nbytes
+            fn(s, r, rn)
+            if k + 1 < len(starts):
+                upload(k + 1)                                   # gathered and sent while the kernel of block k runs
+        main.wait_stream(self._copy)
+        torch.cuda.synchronize(dev)                             # the staging buffers go out of scope below
+
+
+# ---- metrics -------------------------------------------------------------------------------------------------------------------------
+
+QUANTILES = (("min", 0.0), ("p01", 0.01), ("p05", 0.05), ("p50", 0.5))
+
+
+def _order_stats(d2):
+    """Order statistics of the integer distances: the p-quantile is element floor(p (n - 1)) of the sorted array (no
+    interpolation, so it is one of the integers); dcr = sqrt(d2) / 255 is the Euclidean distance in [0, 1]-pixel units."""
+    s = np.sort(np.asarray(d2, dtype=np.int64))
+    n = len(s)
+    out = {}
+    for name, p in QUANTILES:
+        v = int(s[int(math.floor(p * (n - 1)))])
+        out["d2_" + name] = v
+        out["dcr_" + name] = math.sqrt(v) / 255.0
+    return out
+
+
+def dcr_metrics(key_train, key_heldout=None):
+    """Figures of one query set from its keys against the training set (and a held-out set): exact up to the final divisions.
+    duplicates = #{d2 == 0}; closer_to_train_share = (#{d2_t < d2_h} + #{d2_t == d2_h} / 2) / n with its binomial standard error
+    sqrt(s (1 - s) / n)."""
+    dt, _ = split_keys(key_train)
+    n = len(dt)
+    if n < 1:
+        raise ValueError("no keys")
+    out = {"n": n, "duplicates": int((dt == 0).sum())}
+    out.update(_order_stats(dt))
+    if key_heldout is not None:
+        dh, _ = split_keys(key_heldout)
+        if len(dh) != n:
+            raise ValueError("%d train keys and %d held-out keys" % (n, len(dh)))
+        closer, ties = int((dt < dh).sum()), int((dt == dh).sum())
+        share = (closer + 0.5 * ties) / n
+        out.update(closer_to_train=closer, ties=ties, closer_to_train_share=share,
+                   closer_to_train_stderr=math.sqrt(share * (1.0 - share) / n), heldout_duplicates=int((dh == 0).sum()))
+        out.update({"heldout_" + k: v for k, v in _order_stats(dh).items()})
+    return out

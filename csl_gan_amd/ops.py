@@ -1532,6 +1532,56 @@ def ovr_logreg_proba(Xtest, U, out=None):
     return out
 
 
+def nn_padded_dim(D):
+    """Row pitch of the prepared operands of nn_min: D rounded up to the kernel's K tile (0: a D outside 1 .. 65536)."""
+    return int(_lib.lib().cslgan_nn_padded_dim(int(D)))
+
+
+def _chk_dev(t, name, dtype, what):
+    if not t.is_cuda:
+        raise RuntimeError("%s must be a device tensor (csl_gan_amd.ops has no CPU path)" % name)
+    if t.dtype != dtype or not t.is_contiguous():
+        raise RuntimeError("%s: %s must be a contiguous %s tensor" % (what, name, str(dtype).replace("torch.", "")))
+    return t
+
+
+def nn_prepare(u8, out=None, out_sqnorm=None):
+    """(int8 [rows, Dp], int32 [rows]) of a uint8 device tensor [rows, ...]: the bytes minus 128 with zero padding up to
+    Dp = nn_padded_dim(D), and the squared norm of every shifted row (include/cslgan.h "Nearest-neighbour audit")."""
+    _chk_dev(u8, "u8", torch.uint8, "nn_prepare")
+    rows = u8.shape[0]
+    D = u8.numel() // max(rows, 1)
+    Dp = nn_padded_dim(D)
+    if rows < 1 or Dp == 0:
+        raise RuntimeError("nn_prepare: need at least one row of 1 .. 65536 bytes, got %s" % (tuple(u8.shape),))
+    if out is None:
+        out = torch.empty((rows, Dp), device=u8.device, dtype=torch.int8)
+    elif _chk_dev(out, "out", torch.int8, "nn_prepare").numel() != rows * Dp:
+        raise RuntimeError("nn_prepare: out has %d entries, expected %d" % (out.numel(), rows * Dp))
+    if out_sqnorm is None:
+        out_sqnorm = torch.empty(rows, device=u8.device, dtype=torch.int32)
+    elif _chk_dev(out_sqnorm, "out_sqnorm", torch.int32, "nn_prepare").numel() != rows:
+        raise RuntimeError("nn_prepare: out_sqnorm has %d entries, expected %d" % (out_sqnorm.numel(), rows))
+    check(_lib.lib().cslgan_nn_prepare_u8(_p(u8), rows, D, Dp, _p(out), _p(out_sqnorm), _stream()), "nn_prepare")
+    return out, out_sqnorm
+
+
+def nn_min(q, qn, r, rn, index_base, best):
+    """best[i] = min(best[i], min_j (d2(q_i, r_j) << 32 | index_base + j)) as uint64, in place.  q [nq, Dp] / r [nr, Dp]: prepared
+    int8 operands of nn_prepare with their int32 squared norms qn / rn; best: int64 device tensor [nq] that the caller filled with
+    -1 (all ones) once.  Ties go to the smallest index.  csl_gan_amd.neighbours.nearest_host is the host model."""
+    for t, name, dt in ((q, "q", torch.int8), (r, "r", torch.int8), (qn, "qn", torch.int32), (rn, "rn", torch.int32), (best, "best", torch.int64)):
+        _chk_dev(t, name, dt, "nn_min")
+    if q.dim() != 2 or r.dim() != 2 or q.shape[1] != r.shape[1]:
+        raise RuntimeError("nn_min: need q [nq, Dp] and r [nr, Dp], got %s and %s" % (tuple(q.shape), tuple(r.shape)))
+    nq, Dp = q.shape
+    nr = r.shape[0]
+    if qn.numel() != nq or rn.numel() != nr or best.numel() != nq:
+        raise RuntimeError("nn_min: qn / rn / best have %d / %d / %d entries, expected %d / %d / %d" % (qn.numel(), rn.numel(), best.numel(), nq, nr, nq))
+    check(_lib.lib().cslgan_nn_min_i8(_p(q), _p(qn), nq, _p(r), _p(rn), nr, Dp, int(index_base), _p(best), _stream()), "nn_min")
+    return best
+
+
 def row_l2norm(t2d):
     _chk(t2d, "t")
     n, L = t2d.shape

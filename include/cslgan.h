@@ -593,6 +593,38 @@ int cslgan_ovr_logreg_eval_f32(const float* X, const int32_t* labels, const floa
  * Xtest: [M, D] fp32 (is_u8 = 0), or [M, D] bytes (is_u8 = 1) that become floats times 1/255 in the load (:106). */
 int cslgan_ovr_logreg_proba_f32(const void* Xtest, int is_u8, const float* U, int64_t M, int D, int K, float* P, void* stream);
 
+/* ---- Nearest-neighbour audit (nn_kernels.hip; backward-compatible additions, ABI stays 7) -----------------------------------------
+ * Exact nearest neighbour of every row of Q [nq, D] among the rows of R [nr, D], both uint8, D = H W C with 1 <= D <= 65536
+ * (so 255^2 D < 2^32):
+ *     d2(q, r) = sum_i (Q[q][i] - R[r][i])^2                                   an integer in [0, 65025 D]
+ *     key(q)   = min over r of (d2(q, r) << 32 | (index_base + r))             as uint64
+ * The neighbour's index is the low word of the key and its squared distance the high word; TIES GO TO THE SMALLEST INDEX.  The key
+ * is a minimum over a set: it does not depend on tiling, launch order or the number of calls that R is cut into.  The all-ones
+ * key means "nothing seen yet"; index_base + nr <= 2^32 - 1 keeps it out of reach.  The device works on a = Q - 128, b = R - 128
+ * as int8 (byte ^ 0x80): d2 = |a|^2 + |b|^2 - 2 a.b with |a.b| <= 2^14 D <= 2^30 in the int32 accumulator of the int8 matrix
+ * instruction, |a|^2 <= 2^30 in int32, and d2 (up to 4.26e9) formed in uint32 — never int32.  All entries validate on the host
+ * before any launch, never allocate and never synchronise.  csl_gan_amd.neighbours.nearest_host is the host model.
+ *
+ * cslgan_nn_padded_dim — the row pitch Dp of the prepared operands: D rounded up to the kernel's K tile, a multiple of 64
+ * (0 for a D outside 1 .. 65536). */
+int cslgan_nn_padded_dim(int D);
+
+/* cslgan_nn_prepare_u8 — x: uint8 [rows, D] (16-byte aligned base; D need not be a multiple of 16) becomes xs: int8 [rows, Dp]
+ * holding x - 128 with ZERO in bytes D .. Dp-1 of every row (zero in the shifted domain adds nothing to dots or norms), and
+ * sqnorm[row] = sum_i (x[row][i] - 128)^2 as int32.  One pass over x; 16-byte aligned loads and stores; no byte beyond
+ * x + rows * D is read.  1 <= rows < 2^31, Dp = cslgan_nn_padded_dim(D), xs 16-byte aligned. */
+int cslgan_nn_prepare_u8(const void* x, int64_t rows, int D, int Dp, void* xs, int32_t* sqnorm, void* stream);
+
+/* cslgan_nn_min_i8 — best[q] = min(best[q], key(q)) for q < nq over the nr rows of r, by unsigned 64-bit atomicMin: best is IN/OUT
+ * and the caller fills it with all-ones once (a torch int64 tensor of -1), then may call any number of times with different
+ * blocks of R and their index_base.  q / r: prepared int8 [nq, Dp] / [nr, Dp], qn / rn: their int32 squared norms.  An
+ * nq x nr x Dp product on v_mfma_i32_32x32x32_i8 whose nq x nr result never reaches memory: a workgroup owns 128 rows of q and a
+ * range of 128-row tiles of r, keeps the running minimum per row in registers and issues one atomicMin per row.  Rows past nq
+ * and nr never win, whatever lies behind them.  Dp a multiple of 64 in 64 .. 65536, 1 <= nq, nr < 2^31,
+ * 0 <= index_base, index_base + nr <= 2^32 - 1, q / r 16-byte, qn / rn 4-byte and best 8-byte aligned. */
+int cslgan_nn_min_i8(const void* q, const int32_t* qn, int64_t nq, const void* r, const int32_t* rn, int64_t nr, int Dp,
+                     int64_t index_base, uint64_t* best, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
