@@ -597,6 +597,88 @@ def test_wgrad_gram_norms_and_scaled_sum(case):
         ops.conv2d_wgrad_grouped(_nhwc(gy), _nhwc(x), R, R, stride=s, pad=p, group=N, row_scale=_dev(f[:-1]))
 
 
+_GHOST_REF = {}
+
+
+def _ghost_ref(case, rounded=False):
+    """Operands of tests.ghost_inputs and their fp64 per-sample squared norms, computed once per case and never modified."""
+    key = (case, rounded)
+    if key not in _GHOST_REF:
+        from tests import ghost_inputs as GI
+        x, gy = GI.operands(case)
+        if rounded:
+            x, gy = _bf(x), _bf(gy)
+        _GHOST_REF[key] = (x, gy, GI.reference_sq(x, gy, case[5], case[6], case[7], GI.ALPHA))
+    return _GHOST_REF[key]
+
+
+def _ghost_cases():
+    from tests.ghost_inputs import CASES
+    return [pytest.param(kernel, case, dead, id="%s-%s" % (kernel.replace("gram_sqnorm_", "").replace("_kernel", ""), "x".join(map(str, case))))
+            for kernel, case, dead in CASES]
+
+
+def _per_sample(sq, ref, tol, what):
+    """|sq_b - ref_b| <= tol_b for EVERY sample b: a per-sample quantity is judged per sample, not against the batch maximum."""
+    sq = sq.detach().cpu().double()
+    assert sq.shape == ref.shape, (what, sq.shape, ref.shape)
+    err = (sq - ref).abs()
+    print("%s: worst per-sample error %.3e of the sample's own norm, %.3e of its tolerance" % (what, (err / ref).max().item(), (err / tol).max().item()))
+    bad = (err > tol).nonzero().flatten().tolist()
+    assert not bad, "%s: samples %s off: got %s, expected %s" % (what, bad, sq[bad].tolist(), ref[bad].tolist())
+
+
+@pytest.mark.parametrize("kernel,case,dead", _ghost_cases())
+def test_wgrad_gram_norms_per_sample_on_correlated_inputs(kernel, case, dead):
+    """Ghost norms on operands whose p != p' Gram terms carry most of the norm (tests/test_ghost_inputs.py: >= 0.49 of it, >= 1.2e-2
+    from the least visible tap; white noise: 1e-3 and 1e-5) and whose scale spans six decades over the batch, each sample held to
+    1e-4 of ITS OWN squared norm against the fp64 norm of the materialised gradient.  Every kernel of the entry point is named, so a
+    routing change cannot drop one from the test."""
+    from csl_gan_amd import _lib
+    from tests.ghost_inputs import ALPHA, BF16_CASE, reference_weighted_sum
+    ops = _ops()
+    N, H, W, C, K, R, s, p = case
+    x, gy, ref = _ghost_ref(case)
+    xd, gd = _nhwc(x), _nhwc(gy)
+    run = lambda g_, **kw: ops.conv2d_wgrad_sqnorm_gram(g_, xd, R, R, stride=s, pad=p, alpha=ALPHA, **kw)
+    sq = run(gd)
+    name = _lib.lib().cslgan_last_kernel().decode()
+    assert name == kernel, "case %s ran %s" % (case, name)
+    _per_sample(sq, ref, 1e-4 * ref, "%s %s" % (kernel, case))
+    # accumulating form: the pre-fill is far above most samples' norms, so each of the `adds` atomic adds into sq[b] (one per
+    # workgroup of sample b: one per stride-parity class in cls64, one otherwise) rounds to the fp32 grid at the pre-fill — at most
+    # half a spacing each, the spacing anywhere in [fill, fill + max ref] being at most eps * 4 max ref.
+    fill = torch.tensor(3.0 * ref.max().item(), dtype=torch.float32)
+    sq2 = run(gd, sq=torch.full((N,), fill.item(), device="cuda"))
+    adds = s * s if kernel == "gram_sqnorm_cls64_kernel" else 1
+    spacing = torch.finfo(torch.float32).eps * 4.0 * ref.max().item()
+    _per_sample(sq2.cpu().double() - fill.double(), ref, 1e-4 * ref + adds * 0.5 * spacing, "%s %s accumulate" % (kernel, case))
+    if dead:
+        # a sample whose output gradient is zero has norm 0.0 exactly, and leaves every other sample's bits alone
+        g0 = gy.clone()
+        g0[1] = 0
+        sq0 = run(_nhwc(g0))
+        assert sq0[1].item() == 0.0, sq0
+        live = [b for b in range(N) if b != 1]
+        if kernel == "gram_sqnorm_cls64_kernel" and s > 1:
+            # one workgroup per (sample, class) adds into sq[b] atomically: the order of the s^2 addends is the scheduler's, so
+            # two runs may differ in the last bits
+            _per_sample(sq0[live], ref[live], 1e-4 * ref[live], "%s %s beside a dead sample" % (kernel, case))
+        else:
+            assert torch.equal(sq0[live], sq[live]), (sq0, sq)
+    # the clip weights these norms imply (C = the median norm), applied by the dense clip-weighted weight gradient
+    nrm = ref.sqrt()
+    f = (nrm.median() / nrm).clamp(max=1.0).float()
+    got = ops.conv2d_wgrad_grouped(gd, xd, R, R, stride=s, pad=p, group=N, alpha=ALPHA, row_scale=_dev(f))
+    _close(got[0].permute(0, 3, 1, 2), reference_weighted_sum(x, gy, f, R, s, p, ALPHA), what="clip-weighted dense wgrad %s" % (case,))
+    if case == BF16_CASE:
+        # bfloat16-stored gy and x: the entry casts them up, so the norms are those of the ROUNDED values, at the same tolerance
+        xr, gr, ref_r = _ghost_ref(case, rounded=True)
+        sq = ops.conv2d_wgrad_sqnorm_gram(_nhwc(gr).bfloat16(), _nhwc(xr).bfloat16(), R, R, stride=s, pad=p, alpha=ALPHA)
+        assert _lib.lib().cslgan_last_kernel().decode() == kernel
+        _per_sample(sq, ref_r, 1e-4 * ref_r, "%s %s bf16-stored operands" % (kernel, case))
+
+
 def test_wgrad_gram_rejects_unsupported_shapes():
     ops = _ops()
     gy, x = torch.zeros(2, 16, 16, 64, device="cuda"), torch.zeros(2, 32, 32, 32, device="cuda")
