@@ -34,7 +34,7 @@ EXPORTS = [
     "cslgan_latent_normal_f32", "cslgan_f32_to_u8",
     "cslgan_attack_trials", "cslgan_rank_counts", "cslgan_softmax_max_rows_f32",
     "cslgan_ovr_logreg_ws_floats", "cslgan_ovr_logreg_eval_f32", "cslgan_ovr_logreg_proba_f32",
-    "cslgan_nn_padded_dim", "cslgan_nn_prepare_u8", "cslgan_nn_min_i8",
+    "cslgan_nn_padded_dim", "cslgan_nn_prepare_u8", "cslgan_nn_min_i8", "cslgan_nn_count_i8",
 ]
 
 
@@ -159,6 +159,7 @@ def lib():
         "cslgan_nn_padded_dim": [i32],
         "cslgan_nn_prepare_u8": [vp, i64, i32, i32, vp, vp, vp],
         "cslgan_nn_min_i8": [vp, vp, i64, vp, vp, i64, i32, i64, vp, vp],
+        "cslgan_nn_count_i8": [vp, vp, i64, vp, vp, i64, i32, vp, i32, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

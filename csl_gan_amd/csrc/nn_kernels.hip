@@ -1,10 +1,11 @@
-// Nearest-neighbour audit kernels for gfx950 (csl_gan_amd.neighbours; DESIGN.md §6g, include/cslgan.h "Nearest-neighbour audit").
+// Nearest-neighbour audit kernels for gfx950 (csl_gan_amd.neighbours; DESIGN.md §6g, §6h, include/cslgan.h "Nearest-neighbour audit").
 //
 // Exact integer arithmetic on uint8 image caches: for every query row the smallest squared Euclidean distance to a reference row
 // and the index of that row, as one uint64 key (d2 << 32 | index).  The bytes are shifted to int8 (x - 128) once by
 // nn_prepare_u8_kernel, which also leaves |row|^2; nn_min_i8_kernel is then an nq x nr x Dp dot-product GEMM on the int8 matrix
 // instruction whose epilogue forms d2 = |a|^2 + |b|^2 - 2 a.b and keeps a running minimum per row: the nq x nr matrix never
-// reaches memory.
+// reaches memory.  nn_count_i8_kernel (csl_gan_amd.blackbox) runs the same tile loop with a counting epilogue: per row
+// the number of reference rows with d2 <= each of up to four thresholds.
 #include "common.h"
 #include "device_prims.h"
 
@@ -97,25 +98,34 @@ __global__ __launch_bounds__(NN_THREADS) void nn_prepare_u8_kernel(const unsigne
     if (lane == 0) sqnorm[row] = sq;
 }
 
-// ---- the search ------------------------------------------------------------------------------------------------------------------
+// ---- the tile loop that the search and the count share ---------------------------------------------------------------------------
 // Workgroup (bx, by): rows bx * 128 .. of Q against column tiles by * tiles_per .. of R.  The K loop runs flattened over
 // (column tile, K stage): stage i + 1 is fetched from HBM/L2 into registers while stage i is multiplied out of LDS, and stored to
 // the other LDS buffer before the single barrier of the iteration.  Both operands are K-contiguous and read with the same
 // lane -> k assignment (lane half h: 16 consecutive bytes), so the sums do not depend on the instruction's k order; the
 // row/column maps are those of every 32x32 form: operand row = lane & 31, C/D col = lane & 31, row = (reg & 3) + 8 (reg >> 2) +
 // 4 (lane >> 5); tests/test_nearest_gpu.py checks them with asymmetric exact-integer data.
-__global__ __launch_bounds__(NN_THREADS) void nn_min_i8_kernel(const signed char* __restrict__ q, const int* __restrict__ qn, int nq,
-                                                               const signed char* __restrict__ r, const int* __restrict__ rn, int nr, int Dp,
-                                                               uint32_t index_base, int tiles_per, int n_col_tiles,
-                                                               unsigned long long* __restrict__ best) {
+struct NNLane {                                                // where a lane sits in the 128 x 128 tile
+    int wm, wn, l31, lh;                                       // the wave's 64 x 64 quadrant; column and row half inside a 32 x 32 block
+    __device__ __forceinline__ explicit NNLane(int tid) : wm(tid >> 7), wn((tid >> 6) & 1), l31(tid & 31), lh((tid >> 5) & 1) {}
+    __device__ __forceinline__ int row(int mt, int i) const { return wm * 64 + mt * 32 + (i & 3) + 8 * (i >> 2) + 4 * lh; }      // of accumulator register i
+    __device__ __forceinline__ long long col(int ct, int nt) const { return (long long)ct * NN_TN + wn * 64 + nt * 32 + l31; }   // in R
+};
+
+// After the last K stage of a column tile the loop forms d2 = |a|^2 + |b|^2 - 2 a.b in uint32 (the true value is below 2^32, so
+// arithmetic mod 2^32 returns it exactly; int32 would not hold it) and hands every element to the epilogue:
+// `epi(int mt, int i, bool live, long long col, uint32_t d2)` for row ln.row(mt, i) and column col of R, live = col < nr (a column
+// past nr has a d2 that means nothing).  The epilogue is a lambda over the kernel's own running values, which stay locals of the
+// kernel so that they are promoted to registers.  The loop ends behind a barrier, every call done.
+template <class Epilogue>
+__device__ __forceinline__ void nn_tile_loop(const signed char* __restrict__ q, const int* __restrict__ qn, int nq, const signed char* __restrict__ r,
+                                             const int* __restrict__ rn, int nr, int Dp, int tiles_per, int n_col_tiles, Epilogue epi) {
     __shared__ __attribute__((aligned(16))) unsigned char sA[2][NN_TM * NN_PITCH];
     __shared__ __attribute__((aligned(16))) unsigned char sB[2][NN_TN * NN_PITCH];
     __shared__ int qn_s[NN_TM];
-    __shared__ unsigned long long red[2][NN_TM];
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;                   // this wave's 64 x 64 quadrant
-    const int l31 = lane & 31, lh = lane >> 5;
+    const int tid = threadIdx.x;
+    const NNLane ln(tid);
     const long long row0 = (long long)blockIdx.x * NN_TM;
     const int rows_here = (int)(nq - row0 < NN_TM ? nq - row0 : NN_TM);
     const int tile_first = blockIdx.y * tiles_per;
@@ -152,11 +162,6 @@ __global__ __launch_bounds__(NN_THREADS) void nn_min_i8_kernel(const signed char
         *reinterpret_cast<u32x4*>(&sB[buf][st_off + 64 * NN_PITCH]) = gb1;
     };
 
-    unsigned long long bk[2][16];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) bk[mt][i] = NN_NONE;
     i32x16 acc[2][2];
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
@@ -171,8 +176,8 @@ __global__ __launch_bounds__(NN_THREADS) void nn_min_i8_kernel(const signed char
     }
     __syncthreads();                                           // also publishes qn_s
 
-    const int a_off = (wm * 64 + l31) * NN_PITCH + 16 * lh;
-    const int b_off = (wn * 64 + l31) * NN_PITCH + 16 * lh;
+    const int a_off = (ln.wm * 64 + ln.l31) * NN_PITCH + 16 * ln.lh;
+    const int b_off = (ln.wn * 64 + ln.l31) * NN_PITCH + 16 * ln.lh;
     int kt = 0, ct = tile_first;
     for (int it = 0; it < n_iter; ++it) {
         const int buf = it & 1;
@@ -191,22 +196,16 @@ __global__ __launch_bounds__(NN_THREADS) void nn_min_i8_kernel(const signed char
                 for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[mt], b[nt], acc[mt][nt], 0, 0, 0);
         }
         if (++kt == nk) {
-            // epilogue of one column tile: d2 = |a|^2 + |b|^2 - 2 a.b in uint32 (the true value is below 2^32, so arithmetic mod
-            // 2^32 returns it exactly; int32 would not hold it), key = d2 << 32 | index, running minimum per row in registers
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt) {
-                const long long col = (long long)ct * NN_TN + wn * 64 + nt * 32 + l31;
+                const long long col = ln.col(ct, nt);
                 const bool live = col < nr;
                 const uint32_t bn = live ? (uint32_t)rn[col] : 0u;
-                const uint32_t idx = index_base + (uint32_t)col;
 #pragma unroll
                 for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
                     for (int i = 0; i < 16; ++i) {
-                        const int rl = wm * 64 + mt * 32 + (i & 3) + 8 * (i >> 2) + 4 * lh;
-                        const uint32_t d2 = (uint32_t)qn_s[rl] + bn - 2u * (uint32_t)acc[mt][nt][i];
-                        const unsigned long long key = live ? (((unsigned long long)d2 << 32) | (unsigned long long)idx) : NN_NONE;
-                        bk[mt][i] = key < bk[mt][i] ? key : bk[mt][i];
+                        epi(mt, i, live, col, (uint32_t)qn_s[ln.row(mt, i)] + bn - 2u * (uint32_t)acc[mt][nt][i]);
                         acc[mt][nt][i] = 0;
                     }
             }
@@ -216,8 +215,33 @@ __global__ __launch_bounds__(NN_THREADS) void nn_min_i8_kernel(const signed char
         if (it + 1 < n_iter) stash(buf ^ 1);                   // last read in iteration it - 1, which every wave has left
         __syncthreads();
     }
+}
+
+// ---- the search ------------------------------------------------------------------------------------------------------------------
+// Epilogue: key = d2 << 32 | index, running minimum per row in registers.
+
+__global__ __launch_bounds__(NN_THREADS) void nn_min_i8_kernel(const signed char* __restrict__ q, const int* __restrict__ qn, int nq,
+                                                               const signed char* __restrict__ r, const int* __restrict__ rn, int nr, int Dp,
+                                                               uint32_t index_base, int tiles_per, int n_col_tiles,
+                                                               unsigned long long* __restrict__ best) {
+    __shared__ unsigned long long red[2][NN_TM];
+
+    unsigned long long bk[2][16];
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) bk[mt][i] = NN_NONE;
+    nn_tile_loop(q, qn, nq, r, rn, nr, Dp, tiles_per, n_col_tiles, [&](int mt, int i, bool live, long long col, uint32_t d2) {
+        const uint32_t idx = index_base + (uint32_t)col;
+        const unsigned long long key = live ? (((unsigned long long)d2 << 32) | (unsigned long long)idx) : NN_NONE;
+        bk[mt][i] = key < bk[mt][i] ? key : bk[mt][i];
+    });
 
     // per-row minimum over the 32 lanes that share a row, then over the two waves of a row half, then ONE atomicMin per row
+    const int tid = threadIdx.x;
+    const NNLane ln(tid);
+    const long long row0 = (long long)blockIdx.x * NN_TM;
+    const int rows_here = (int)(nq - row0 < NN_TM ? nq - row0 : NN_TM);
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -228,13 +252,74 @@ __global__ __launch_bounds__(NN_THREADS) void nn_min_i8_kernel(const signed char
                 const unsigned long long u = __shfl_xor(v, o, 64);
                 v = u < v ? u : v;
             }
-            if (l31 == 0) red[wn][wm * 64 + mt * 32 + (i & 3) + 8 * (i >> 2) + 4 * lh] = v;
+            if (ln.l31 == 0) red[ln.wn][ln.row(mt, i)] = v;
         }
     __syncthreads();
     if (tid < rows_here) {
         const unsigned long long v0 = red[0][tid], v1 = red[1][tid];
         const unsigned long long v = v0 < v1 ? v0 : v1;
         if (v != NN_NONE) atomicMin(&best[row0 + tid], v);
+    }
+}
+
+// ---- the count ---------------------------------------------------------------------------------------------------------------------
+// counts[q][j] += #{r : d2(q, r) <= thr[j]}, compared as unsigned values.  The four running counters of a row are the four bytes of
+// ONE register: a lane meets two columns per row and tile, so a byte grows by at most 2 per tile and holds NN_COUNT_TILES tiles
+// (the host caps tiles_per there); no byte ever carries into its neighbour.  A column past nr adds nothing, whatever its bytes
+// are (zero padding has d2 = |a|^2, which a threshold may well reach).  All four compares always run: a threshold past n_thr is
+// zero on entry and its byte is never written out.
+constexpr int NN_COUNT_TILES = 127;                            // 2 * 127 = 254 <= 255
+constexpr int NN_MAX_THR = 4;
+
+struct NNThresholds { uint32_t t[NN_MAX_THR]; };
+
+__global__ __launch_bounds__(NN_THREADS) void nn_count_i8_kernel(const signed char* __restrict__ q, const int* __restrict__ qn, int nq,
+                                                                 const signed char* __restrict__ r, const int* __restrict__ rn, int nr, int Dp,
+                                                                 NNThresholds thr, int n_thr, int tiles_per, int n_col_tiles,
+                                                                 uint32_t* __restrict__ counts) {
+    __shared__ uint32_t red[2][NN_TM][2];                      // [column half][row][thresholds 0 2 | 1 3 as 16-bit pairs]
+
+    uint32_t cnt[2][16];
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) cnt[mt][i] = 0u;
+    nn_tile_loop(q, qn, nq, r, rn, nr, Dp, tiles_per, n_col_tiles, [&](int mt, int i, bool live, long long, uint32_t d2) {
+        const uint32_t one = live ? 1u : 0u;                   // the column mask, applied to every increment
+        uint32_t inc = 0u;
+#pragma unroll
+        for (int j = 0; j < NN_MAX_THR; ++j) inc |= (d2 <= thr.t[j] ? one : 0u) << (8 * j);
+        cnt[mt][i] += inc;
+    });
+
+    // unpack once: the bytes 0 2 and 1 3 of a register as two pairs of 16-bit fields, each summed over the 32 lanes that share a
+    // row (32 * 254 < 2^16), then over the two waves of a row half through LDS, then ONE atomicAdd per (row, threshold)
+    const int tid = threadIdx.x;
+    const NNLane ln(tid);
+    const long long row0 = (long long)blockIdx.x * NN_TM;
+    const int rows_here = (int)(nq - row0 < NN_TM ? nq - row0 : NN_TM);
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            uint32_t even = cnt[mt][i] & 0x00ff00ffu, odd = (cnt[mt][i] >> 8) & 0x00ff00ffu;
+#pragma unroll
+            for (int o = 16; o > 0; o >>= 1) {
+                even += (uint32_t)__shfl_xor((int)even, o, 64);
+                odd += (uint32_t)__shfl_xor((int)odd, o, 64);
+            }
+            if (ln.l31 == 0) {
+                red[ln.wn][ln.row(mt, i)][0] = even;
+                red[ln.wn][ln.row(mt, i)][1] = odd;
+            }
+        }
+    __syncthreads();
+    if (tid < rows_here) {                                     // rows past nq issue nothing
+        const uint32_t even = red[0][tid][0] + red[1][tid][0], odd = red[0][tid][1] + red[1][tid][1];       // 64 * 254 < 2^16 per field
+        const uint32_t c[NN_MAX_THR] = {even & 0xffffu, odd & 0xffffu, even >> 16, odd >> 16};
+#pragma unroll
+        for (int j = 0; j < NN_MAX_THR; ++j)
+            if (j < n_thr && c[j] != 0u) atomicAdd(&counts[(row0 + tid) * n_thr + j], c[j]);
     }
 }
 
@@ -286,6 +371,34 @@ int cslgan_nn_min_i8(const void* q, const int32_t* qn, int64_t nq, const void* r
                        (const int*)qn, (int)nq, (const signed char*)r, (const int*)rn, (int)nr, Dp, (uint32_t)index_base, (int)tiles_per,
                        (int)col_tiles, (unsigned long long*)best);
     return check_launch("nn_min_i8_kernel");
+}
+
+int cslgan_nn_count_i8(const void* q, const int32_t* qn, int64_t nq, const void* r, const int32_t* rn, int64_t nr, int Dp,
+                       const uint32_t* thresholds, int n_thr, uint32_t* counts, void* stream) {
+    CSLGAN_REQUIRE(q && qn && r && rn && thresholds && counts, "nn_count_i8: null argument");
+    CSLGAN_REQUIRE(n_thr >= 1 && n_thr <= NN_MAX_THR, "nn_count_i8: n_thr=%d must lie in 1 .. %d", n_thr, NN_MAX_THR);
+    CSLGAN_REQUIRE(Dp >= NN_KT && Dp <= NN_MAX_D && Dp % NN_KT == 0, "nn_count_i8: Dp=%d must be a multiple of %d in %d .. %d", Dp, NN_KT, NN_KT,
+                   NN_MAX_D);
+    CSLGAN_REQUIRE(nq >= 1 && nq < (1ll << 31), "nn_count_i8: nq=%lld out of range", (long long)nq);
+    CSLGAN_REQUIRE(nr >= 1 && nr < (1ll << 31), "nn_count_i8: nr=%lld out of range", (long long)nr);
+    CSLGAN_REQUIRE(aligned16(q) && aligned16(r) && (reinterpret_cast<uintptr_t>(qn) & 3u) == 0 && (reinterpret_cast<uintptr_t>(rn) & 3u) == 0 &&
+                       (reinterpret_cast<uintptr_t>(counts) & 3u) == 0 && (reinterpret_cast<uintptr_t>(thresholds) & 3u) == 0,
+                   "nn_count_i8: misaligned pointer");
+    const long long row_tiles = (nq + NN_TM - 1) / NN_TM, col_tiles = (nr + NN_TN - 1) / NN_TN;
+    // as nn_min_i8: enough workgroups for every CU a few times over; and no more tiles per workgroup than a byte counter holds
+    long long splits = (1024 + row_tiles - 1) / row_tiles;
+    splits = splits < 1 ? 1 : (splits > col_tiles ? col_tiles : splits);
+    long long tiles_per = (col_tiles + splits - 1) / splits;
+    tiles_per = tiles_per > NN_COUNT_TILES ? NN_COUNT_TILES : tiles_per;
+    const long long gy = (col_tiles + tiles_per - 1) / tiles_per;
+    CSLGAN_REQUIRE(gy <= 65535, "nn_count_i8: nr=%lld needs %lld column ranges", (long long)nr, gy);
+    NNThresholds thr = {{0u, 0u, 0u, 0u}};
+    for (int j = 0; j < n_thr; ++j) thr.t[j] = thresholds[j];  // read now: the caller's array may go when this returns
+    note_kernel("nn_count_i8_kernel");
+    hipLaunchKernelGGL(nn_count_i8_kernel, dim3((unsigned)row_tiles, (unsigned)gy), dim3(NN_THREADS), 0, (hipStream_t)stream, (const signed char*)q,
+                       (const int*)qn, (int)nq, (const signed char*)r, (const int*)rn, (int)nr, Dp, thr, n_thr, (int)tiles_per, (int)col_tiles,
+                       (uint32_t*)counts);
+    return check_launch("nn_count_i8_kernel");
 }
 
 }  // extern "C"

@@ -67,13 +67,15 @@ def nearest_host(Q, R, index_base=0, best=None, block=1024):
 
 
 class NearestSearch:
-    """`fit(reference cache)`, then `query(cache) -> uint64 keys[len(cache)]`, any number of times.
+    """`fit(reference cache)`, then `query(cache) -> uint64 keys[len(cache)]` and `count_within(cache, thresholds) -> int64
+    counts[len(cache), J]`, any number of times.
 
     On a HIP device the reference is walked in blocks of `block_rows` images: pinned uint8 gather -> H2D on a side stream ->
     ops.nn_prepare -> ops.nn_min with index_base = the block's first row.  Two pinned and two device staging buffers alternate, so
     block k + 1 is gathered and uploaded while the kernel of block k runs.  Prepared blocks (int8 rows + norms) stay on the device
     for later queries while they fit `resident_gb`; the rest is streamed again.  The query side goes up in chunks of `query_rows`.
-    On the CPU `nearest_host` runs.  The keys do not depend on block_rows, query_rows or the device."""
+    On the CPU `nearest_host` / `blackbox.count_within_host` run.  Keys and counts do not depend on block_rows, query_rows or the
+    device."""
 
     def __init__(self, device, block_rows=16384, resident_gb=8.0, query_rows=16384):
         self.device = torch.device(device)
@@ -98,30 +100,60 @@ class NearestSearch:
         return sum(xs.shape[0] for xs, _ in self._resident.values())
 
     def query(self, cache):
-        if self.ref is None:
-            raise RuntimeError("fit() a reference cache first")
-        if (cache.H, cache.W, cache.C) != (self.ref.H, self.ref.W, self.ref.C):
-            raise ValueError("the query images are %dx%dx%d and the reference images %dx%dx%d: both caches must have one geometry"
-                             % (cache.H, cache.W, cache.C, self.ref.H, self.ref.W, self.ref.C))
+        self._check_query(cache)
         if not self.on_gpu:
             return nearest_host(cache.x, self.ref.x)
         with torch.cuda.device(self.device):
             return self._query_gpu(cache)
 
+    def _check_query(self, cache):
+        if self.ref is None:
+            raise RuntimeError("fit() a reference cache first")
+        if (cache.H, cache.W, cache.C) != (self.ref.H, self.ref.W, self.ref.C):
+            raise ValueError("the query images are %dx%dx%d and the reference images %dx%dx%d: both caches must have one geometry"
+                             % (cache.H, cache.W, cache.C, self.ref.H, self.ref.W, self.ref.C))
+
+    def count_within(self, cache, thresholds):
+        """int64 [len(cache), J]: for every query image the number of reference images with d2 <= thresholds[j] (1 <= J <= 4
+        integers in [0, 2^32 - 1], any order) — blackbox.count_within_host on the CPU, ops.nn_count over the same walk of the
+        reference as `query` on a device.  The device counts in 32 bits, so a reference of 2^31 images or more is refused."""
+        from . import blackbox
+        self._check_query(cache)
+        thr = blackbox.check_thresholds(thresholds)
+        if len(self.ref) >= 2 ** 31:
+            raise ValueError("a reference of %d images: counts are held below 2^31" % len(self.ref))
+        if not self.on_gpu:
+            return blackbox.count_within_host(cache.x, self.ref.x, thr)
+        with torch.cuda.device(self.device):
+            from . import ops
+
+            def chunk(q, qn):
+                counts = torch.zeros((q.shape[0], len(thr)), device=self.device, dtype=torch.int32)
+                self._walk_reference(lambda start, r, rn: ops.nn_count(q, qn, r, rn, thr, counts))
+                return counts.cpu().numpy().astype(np.int64)
+            return self._query_chunks(cache, np.empty((len(cache), len(thr)), dtype=np.int64), chunk)
+
     # ---- device path -------------------------------------------------------------------------------------------------------------
     def _query_gpu(self, cache):
         from . import ops
+
+        def chunk(q, qn):
+            best = torch.full((q.shape[0],), -1, device=self.device, dtype=torch.int64)  # all ones: nothing seen yet
+            self._walk_reference(lambda start, r, rn: ops.nn_min(q, qn, r, rn, start, best))
+            return best.cpu().numpy().view(np.uint64)
+        return self._query_chunks(cache, np.empty(len(cache), dtype=np.uint64), chunk)
+
+    def _query_chunks(self, cache, out, fn):
+        """out[s : s + cnt] = fn(prepared int8 chunk, its norms) for the query side in chunks of query_rows."""
+        from . import ops
         n = len(cache)
         shape = (cache.H, cache.W, cache.C)
-        out = np.empty(n, dtype=np.uint64)
         stage = torch.empty((min(self.query_rows, n),) + shape, dtype=torch.uint8, pin_memory=True)
         for s in range(0, n, self.query_rows):
             cnt = min(self.query_rows, n - s)
             cache.gather(np.arange(s, s + cnt), stage[:cnt])
             q, qn = ops.nn_prepare(stage[:cnt].to(self.device, non_blocking=True))
-            best = torch.full((cnt,), -1, device=self.device, dtype=torch.int64)        # all ones: nothing seen yet
-            self._walk_reference(lambda start, r, rn: ops.nn_min(q, qn, r, rn, start, best))
-            out[s:s + cnt] = best.cpu().numpy().view(np.uint64)                          # also: the stage buffer is free again
+            out[s:s + cnt] = fn(q, qn)                                                   # its .cpu(): the stage buffer is free again
         torch.cuda.synchronize(self.device)
         return out
 

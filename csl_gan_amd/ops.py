@@ -1582,6 +1582,31 @@ def nn_min(q, qn, r, rn, index_base, best):
     return best
 
 
+def nn_count(q, qn, r, rn, thresholds, counts):
+    """counts[i, j] += #{k : d2(q_i, r_k) <= thresholds[j]}, in place.  q / qn / r / rn as for nn_min; thresholds: 1 .. 4 Python
+    integers in [0, 2^32 - 1], any order; counts: int32 device tensor [nq, J] that the caller zeroed once.  The device adds as
+    uint32 and torch reads int32: the TOTAL count of an entry over all calls must stay below 2^31 on this path.
+    csl_gan_amd.blackbox.count_within_host is the host model."""
+    args = ((q, "q", torch.int8), (r, "r", torch.int8), (qn, "qn", torch.int32), (rn, "rn", torch.int32), (counts, "counts", torch.int32))
+    for t, name, dt in args:                            # the types first: a wrong one is refused wherever the tensor lives
+        if t.dtype != dt:
+            raise RuntimeError("nn_count: %s must be a contiguous %s tensor" % (name, str(dt).replace("torch.", "")))
+    for t, name, dt in args:
+        _chk_dev(t, name, dt, "nn_count")
+    if q.dim() != 2 or r.dim() != 2 or q.shape[1] != r.shape[1]:
+        raise RuntimeError("nn_count: need q [nq, Dp] and r [nr, Dp], got %s and %s" % (tuple(q.shape), tuple(r.shape)))
+    thr = [int(t) for t in thresholds]
+    if not 1 <= len(thr) <= 4 or any(t < 0 or t > 0xFFFFFFFF for t in thr):
+        raise RuntimeError("nn_count: need 1 .. 4 thresholds in [0, 2^32 - 1], got %s" % (thr,))
+    nq, Dp = q.shape
+    nr, J = r.shape[0], len(thr)
+    if qn.numel() != nq or rn.numel() != nr or tuple(counts.shape) != (nq, J):
+        raise RuntimeError("nn_count: qn / rn have %d / %d entries and counts the shape %s, expected %d / %d and (%d, %d)"
+                           % (qn.numel(), rn.numel(), tuple(counts.shape), nq, nr, nq, J))
+    check(_lib.lib().cslgan_nn_count_i8(_p(q), _p(qn), nq, _p(r), _p(rn), nr, Dp, (C.c_uint32 * J)(*thr), J, _p(counts), _stream()), "nn_count")
+    return counts
+
+
 def row_l2norm(t2d):
     _chk(t2d, "t")
     n, L = t2d.shape

@@ -625,6 +625,20 @@ int cslgan_nn_prepare_u8(const void* x, int64_t rows, int D, int Dp, void* xs, i
 int cslgan_nn_min_i8(const void* q, const int32_t* qn, int64_t nq, const void* r, const int32_t* rn, int64_t nr, int Dp,
                      int64_t index_base, uint64_t* best, void* stream);
 
+/* cslgan_nn_count_i8 — counts[q][j] += #{r < nr : d2(q, r) <= thresholds[j]} for q < nq, j < n_thr, d2 as above and the compare on
+ * UNSIGNED 32-bit values (d2 reaches 4.26e9): the black-box membership scores of csl_gan_amd.blackbox, whose count_within_host is
+ * the host model.  q / r / qn / rn / Dp / nq / nr as for cslgan_nn_min_i8.  thresholds: a HOST array of n_thr in 1 .. 4 values in
+ * [0, 2^32 - 1], any order, read before the entry returns and passed to the kernel by value.  counts: device uint32 [nq, n_thr],
+ * IN/OUT: the caller zeroes it once (no memset here) and may call any number of times with different blocks of R; the sums are
+ * integer adds, so they do not depend on tiling, launch order or the number of calls.  A count must stay below 2^32 (2^31 where
+ * the caller reads it as int32).  Same tile loop as nn_min with a counting epilogue: a workgroup owns 128 rows of q and at most
+ * 127 128-row tiles of r, keeps the n_thr counters of a row as the bytes of one register (<= 2 columns per lane, row and tile, so
+ * <= 254 per byte), sums them over the lanes and waves of the row once at the end and issues ONE atomicAdd per (row, threshold)
+ * that counted anything.  Columns past nr are masked by their index, never by their data (zero padding has d2 = |a|^2, which a
+ * threshold may reach); rows past nq issue nothing.  nr <= 65535 * 127 * 128 per call; counts 4-byte aligned. */
+int cslgan_nn_count_i8(const void* q, const int32_t* qn, int64_t nq, const void* r, const int32_t* rn, int64_t nr, int Dp,
+                       const uint32_t* thresholds, int n_thr, uint32_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
