@@ -186,14 +186,11 @@ struct GramSmallParams {
 
 __global__ __launch_bounds__(256) void gram_sqnorm_small_kernel(const GramSmallParams p) {
     __shared__ float XXs[4][16 * 17];
-    __shared__ float G1s[16 * 17];
+    __shared__ float G1s[4][16 * 17];                   // one quarter of GY GY^T per wavefront, summed in wavefront order below
     __shared__ float s_red[4];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int b = blockIdx.x;
     const int row = lane & 15, q = lane >> 4;
-    for (int i = tid; i < 16 * 17; i += 256) G1s[i] = 0.f;
-    __syncthreads();
-
     // ---- XX_c for class c = wid ---------------------------------------------------------------------------
     const int nc = p.s * p.s;
     f32x4 accx = {0.f, 0.f, 0.f, 0.f};
@@ -239,7 +236,7 @@ __global__ __launch_bounds__(256) void gram_sqnorm_small_kernel(const GramSmallP
             }
         }
 #pragma unroll
-        for (int i = 0; i < 4; ++i) atomicAdd(&G1s[(4 * q + i) * 17 + row], accg[i]);
+        for (int i = 0; i < 4; ++i) G1s[wid][(4 * q + i) * 17 + row] = accg[i];
     }
     __syncthreads();
     // ---- sum_{p,p'} G1[p,p'] * sum_t XX_{c(t)}[loc(p,t), loc(p',t)] --------------------------------------
@@ -255,7 +252,8 @@ __global__ __launch_bounds__(256) void gram_sqnorm_small_kernel(const GramSmallP
                 if ((unsigned)ya < (unsigned)Hc && (unsigned)xa < (unsigned)Wc && (unsigned)yb < (unsigned)Hc && (unsigned)xb < (unsigned)Wc)
                     g2 += XXs[c][(ya * Wc + xa) * 17 + yb * Wc + xb];
             }
-            prod = G1s[pa * 17 + pb] * g2;
+            // a fixed order: the sum does not depend on which wavefront finished first, so two launches give the same bits
+            prod = (((G1s[0][pa * 17 + pb] + G1s[1][pa * 17 + pb]) + G1s[2][pa * 17 + pb]) + G1s[3][pa * 17 + pb]) * g2;
         }
     }
     const float tot = block_sum_256(prod, s_red);

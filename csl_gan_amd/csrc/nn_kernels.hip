@@ -117,9 +117,16 @@ struct NNLane {                                                // where a lane s
 // `epi(int mt, int i, bool live, long long col, uint32_t d2)` for row ln.row(mt, i) and column col of R, live = col < nr (a column
 // past nr has a d2 that means nothing).  The epilogue is a lambda over the kernel's own running values, which stay locals of the
 // kernel so that they are promoted to registers.  The loop ends behind a barrier, every call done.
-template <class Epilogue>
+// A kernel that needs a value per COLUMN (nn_count_radius_i8_kernel: the column's radius) passes `per_col(bool live, long long col)`
+// as well, which runs once per column and tile ahead of that column's 32 epilogue calls.
+struct NNNoColumn {
+    __device__ __forceinline__ void operator()(bool, long long) const {}
+};
+
+template <class PerColumn, class Epilogue>
 __device__ __forceinline__ void nn_tile_loop(const signed char* __restrict__ q, const int* __restrict__ qn, int nq, const signed char* __restrict__ r,
-                                             const int* __restrict__ rn, int nr, int Dp, int tiles_per, int n_col_tiles, Epilogue epi) {
+                                             const int* __restrict__ rn, int nr, int Dp, int tiles_per, int n_col_tiles, PerColumn per_col,
+                                             Epilogue epi) {
     __shared__ __attribute__((aligned(16))) unsigned char sA[2][NN_TM * NN_PITCH];
     __shared__ __attribute__((aligned(16))) unsigned char sB[2][NN_TN * NN_PITCH];
     __shared__ int qn_s[NN_TM];
@@ -201,6 +208,7 @@ __device__ __forceinline__ void nn_tile_loop(const signed char* __restrict__ q, 
                 const long long col = ln.col(ct, nt);
                 const bool live = col < nr;
                 const uint32_t bn = live ? (uint32_t)rn[col] : 0u;
+                per_col(live, col);
 #pragma unroll
                 for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -231,7 +239,7 @@ __global__ __launch_bounds__(NN_THREADS) void nn_min_i8_kernel(const signed char
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
         for (int i = 0; i < 16; ++i) bk[mt][i] = NN_NONE;
-    nn_tile_loop(q, qn, nq, r, rn, nr, Dp, tiles_per, n_col_tiles, [&](int mt, int i, bool live, long long col, uint32_t d2) {
+    nn_tile_loop(q, qn, nq, r, rn, nr, Dp, tiles_per, n_col_tiles, NNNoColumn(), [&](int mt, int i, bool live, long long col, uint32_t d2) {
         const uint32_t idx = index_base + (uint32_t)col;
         const unsigned long long key = live ? (((unsigned long long)d2 << 32) | (unsigned long long)idx) : NN_NONE;
         bk[mt][i] = key < bk[mt][i] ? key : bk[mt][i];
@@ -284,7 +292,7 @@ __global__ __launch_bounds__(NN_THREADS) void nn_count_i8_kernel(const signed ch
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
         for (int i = 0; i < 16; ++i) cnt[mt][i] = 0u;
-    nn_tile_loop(q, qn, nq, r, rn, nr, Dp, tiles_per, n_col_tiles, [&](int mt, int i, bool live, long long, uint32_t d2) {
+    nn_tile_loop(q, qn, nq, r, rn, nr, Dp, tiles_per, n_col_tiles, NNNoColumn(), [&](int mt, int i, bool live, long long, uint32_t d2) {
         const uint32_t one = live ? 1u : 0u;                   // the column mask, applied to every increment
         uint32_t inc = 0u;
 #pragma unroll
@@ -320,6 +328,148 @@ __global__ __launch_bounds__(NN_THREADS) void nn_count_i8_kernel(const signed ch
 #pragma unroll
         for (int j = 0; j < NN_MAX_THR; ++j)
             if (j < n_thr && c[j] != 0u) atomicAdd(&counts[(row0 + tid) * n_thr + j], c[j]);
+    }
+}
+
+// ---- the k smallest keys (csl_gan_amd.manifold) -----------------------------------------------------------------------
+// Per row the k <= 8 smallest keys over the live columns, minus the one column whose index is the row's own (self search).  A
+// wave keeps ONE uint32 per row in LDS: the d2 of the k-th key that it holds for the row so far (seeded with the k-th d2 of the
+// in/out `best`, which no later key above it can displace, and rewritten only once the list is full; the bound only falls, so
+// a stale read admits too much, never too little — the write by lane k - 1 and the later reads by the other lanes of the wave
+// are ordered by program order within the wave alone, no fence, and correctness does not rest on it: either value is a valid
+// bound).  A candidate above the bound costs one LDS read and one compare.  The others are taken one at a time by the whole
+// wave: a ballot, then a uniform loop over its set bits that inserts the key into the WAVE's own sorted list of the row in LDS —
+// lane j < k holds entry j, the position is a ballot, the shift a lane shuffle, so a lane reads and writes only its own LDS word
+// and no order between lanes is assumed.  Nothing waits for another wave.  After the last tile the two waves of a row merge
+// their lists and the workgroup writes k keys per row to its own slice of the workspace; every slice is written in full, so the
+// workspace needs no clearing.
+constexpr int NN_MAX_K = 8;
+
+// (amdgpu_waves_per_eu: the allocator otherwise stops a few registers above the two-waves-per-SIMD budget of the other kernels)
+__global__ __launch_bounds__(NN_THREADS) __attribute__((amdgpu_waves_per_eu(2))) void nn_kth_i8_kernel(
+    const signed char* __restrict__ q, const int* __restrict__ qn, int nq, const signed char* __restrict__ r, const int* __restrict__ rn, int nr,
+    int Dp, uint32_t index_base, long long self_first, int k, int tiles_per, int n_col_tiles, const unsigned long long* __restrict__ best,
+    unsigned long long* __restrict__ partial) {
+    __shared__ unsigned long long lists[2][NN_TM][NN_MAX_K];   // [column half = wave of the row][row][entry], sorted ascending
+    __shared__ uint32_t bound[2][NN_TM];                       // [wave of the row][row]: d2 of the k-th entry of its list, seeded from best
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const NNLane ln(tid);
+    const long long row0 = (long long)blockIdx.x * NN_TM;
+    const int rows_here = (int)(nq - row0 < NN_TM ? nq - row0 : NN_TM);
+    for (int e = tid; e < 2 * NN_TM * NN_MAX_K; e += NN_THREADS) (&lists[0][0][0])[e] = NN_NONE;
+    // a row past nq is never written out: bound 0 keeps (nearly) everything of it off the insert path
+    bound[tid >> 7][tid & 127] = (tid & 127) < rows_here ? (uint32_t)(best[(row0 + (tid & 127)) * k + (k - 1)] >> 32) : 0u;
+    // the column that row row0 + t must skip has index_base + col = self_first + row0 + t; without a self search no column has
+    const long long self0 = self_first < 0 ? (1ll << 62) : self_first + row0;
+
+    nn_tile_loop(q, qn, nq, r, rn, nr, Dp, tiles_per, n_col_tiles, NNNoColumn(), [&](int mt, int i, bool live, long long col, uint32_t d2) {
+        const uint32_t idx = index_base + (uint32_t)col;
+        const bool own = (long long)index_base + col - self0 == (long long)ln.row(mt, i);
+        unsigned long long m = __ballot(live && !own && d2 <= bound[ln.wn][ln.row(mt, i)]);
+        while (m != 0ull) {                                    // uniform over the wave
+            const int src = __builtin_ctzll(m);
+            m &= m - 1ull;
+            const unsigned long long key = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)d2, src) << 32) |
+                                           (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)idx, src);
+            const int srow = ln.wm * 64 + mt * 32 + (i & 3) + 8 * (i >> 2) + 4 * (src >> 5);        // ln.row(mt, i) of lane src
+            unsigned long long* lst = &lists[ln.wn][srow][0];
+            const unsigned long long cur = lane < k ? lst[lane] : NN_NONE;
+            const int pos = __popcll(__ballot(cur < key));     // entries below the key: a prefix of the sorted list
+            if (pos < k) {
+                const unsigned long long up = __shfl_up(cur, 1, 64);
+                const unsigned long long nv = lane < pos ? cur : (lane == pos ? key : up);
+                if (lane >= pos && lane < k) lst[lane] = nv;
+                // while the list is not full its k-th entry is all-ones: the seed stays, so the bound only ever falls
+                if (lane == k - 1 && nv != NN_NONE) bound[ln.wn][srow] = (uint32_t)(nv >> 32);
+            }
+        }
+    });
+
+    // the loop ended behind a barrier: merge the two sorted lists of a row, k steps, and write the row's slice
+    if (tid < rows_here) {
+        unsigned long long* out = partial + ((long long)blockIdx.y * nq + row0 + tid) * k;
+        int ia = 0, ib = 0;
+        for (int j = 0; j < k; ++j) {
+            const unsigned long long a = lists[0][tid][ia], b = lists[1][tid][ib];     // ia, ib <= j < k <= NN_MAX_K
+            const bool ta = a <= b;
+            out[j] = ta ? a : b;
+            ia += ta ? 1 : 0;
+            ib += ta ? 0 : 1;
+        }
+    }
+}
+
+// best[row] = the k smallest of best[row] and the n_ranges slices of the row, ascending.  One thread per row; the running list is
+// eight registers (entries past k start all-ones and only ever take keys that k larger ones displaced), inserted into by an
+// unrolled compare-and-shift from the top.
+__global__ __launch_bounds__(NN_THREADS) void nn_kth_merge_kernel(const unsigned long long* __restrict__ partial, int n_ranges, int nq, int k,
+                                                                  unsigned long long* __restrict__ best) {
+    const long long row = (long long)blockIdx.x * NN_THREADS + threadIdx.x;
+    if (row >= nq) return;
+    unsigned long long cur[NN_MAX_K];
+#pragma unroll
+    for (int t = 0; t < NN_MAX_K; ++t) cur[t] = t < k ? best[row * k + t] : NN_NONE;
+    unsigned long long kth = best[row * k + (k - 1)];           // cur[k - 1]: what a key must beat to enter
+    for (int g = 0; g < n_ranges; ++g) {
+        const unsigned long long* src = partial + ((long long)g * nq + row) * k;
+        for (int j = 0; j < k; ++j) {
+            const unsigned long long key = src[j];
+            if (key >= kth) break;                             // the slice is sorted: nothing after it gets in either
+#pragma unroll
+            for (int t = NN_MAX_K - 1; t >= 0; --t)
+                if (key < cur[t]) {
+                    if (t + 1 < NN_MAX_K) cur[t + 1] = cur[t];
+                    cur[t] = key;
+                }
+#pragma unroll
+            for (int t = 0; t < NN_MAX_K; ++t) kth = t == k - 1 ? cur[t] : kth;
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < NN_MAX_K; ++t)
+        if (t < k) best[row * k + t] = cur[t];
+}
+
+// ---- the count inside per-column radii ------------------------------------------------------------------------------
+// counts[q] += #{r : d2(q, r) <= radius[r]}, compared as unsigned values: the counting epilogue with the threshold of the column,
+// read once per column and tile beside rn[col], and one plain uint32 counter per row and
+// lane, so no cap on the tiles of a workgroup.  A column past nr adds nothing, whatever radius would lie behind it.
+__global__ __launch_bounds__(NN_THREADS) void nn_count_radius_i8_kernel(const signed char* __restrict__ q, const int* __restrict__ qn, int nq,
+                                                                        const signed char* __restrict__ r, const int* __restrict__ rn, int nr,
+                                                                        int Dp, const uint32_t* __restrict__ radius, int tiles_per,
+                                                                        int n_col_tiles, uint32_t* __restrict__ counts) {
+    __shared__ uint32_t red[2][NN_TM];
+
+    uint32_t cnt[2][16];
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) cnt[mt][i] = 0u;
+    uint32_t rad = 0u;                                         // of the column whose elements come next
+    nn_tile_loop(q, qn, nq, r, rn, nr, Dp, tiles_per, n_col_tiles, [&](bool live, long long col) { rad = live ? radius[col] : 0u; },
+                 [&](int mt, int i, bool live, long long, uint32_t d2) {
+                     cnt[mt][i] += (live && d2 <= rad) ? 1u : 0u;      // the column mask, applied to every increment
+                 });
+
+    const int tid = threadIdx.x;
+    const NNLane ln(tid);
+    const long long row0 = (long long)blockIdx.x * NN_TM;
+    const int rows_here = (int)(nq - row0 < NN_TM ? nq - row0 : NN_TM);
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            uint32_t v = cnt[mt][i];
+#pragma unroll
+            for (int o = 16; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
+            if (ln.l31 == 0) red[ln.wn][ln.row(mt, i)] = v;
+        }
+    __syncthreads();
+    if (tid < rows_here) {                                     // rows past nq issue nothing
+        const uint32_t c = red[0][tid] + red[1][tid];
+        if (c != 0u) atomicAdd(&counts[row0 + tid], c);
     }
 }
 
@@ -399,6 +549,78 @@ int cslgan_nn_count_i8(const void* q, const int32_t* qn, int64_t nq, const void*
                        (const int*)qn, (int)nq, (const signed char*)r, (const int*)rn, (int)nr, Dp, thr, n_thr, (int)tiles_per, (int)col_tiles,
                        (uint32_t*)counts);
     return check_launch("nn_count_i8_kernel");
+}
+
+// the launch rule that nn_kth_i8 and nn_count_radius_i8 share, which is nn_min_i8's: column ranges for about 1024 workgroups.
+// Returns the number of ranges, 0 for sizes out of range.
+static long long nn_column_ranges(int64_t nq, int64_t nr, long long* tiles_per_out) {
+    if (nq < 1 || nq >= (1ll << 31) || nr < 1 || nr >= (1ll << 31)) return 0;
+    const long long row_tiles = (nq + NN_TM - 1) / NN_TM, col_tiles = (nr + NN_TN - 1) / NN_TN;
+    long long splits = (1024 + row_tiles - 1) / row_tiles;
+    splits = splits < 1 ? 1 : (splits > col_tiles ? col_tiles : splits);
+    const long long tiles_per = (col_tiles + splits - 1) / splits;
+    if (tiles_per_out) *tiles_per_out = tiles_per;
+    return (col_tiles + tiles_per - 1) / tiles_per;
+}
+
+int64_t cslgan_nn_kth_workspace_bytes(int64_t nq, int64_t nr, int k) {
+    if (k < 1 || k > NN_MAX_K) return 0;
+    const long long gy = nn_column_ranges(nq, nr, nullptr);
+    if (gy < 1 || gy > 65535) return 0;
+    return (int64_t)(gy * nq * k * 8);
+}
+
+int cslgan_nn_kth_i8(const void* q, const int32_t* qn, int64_t nq, const void* r, const int32_t* rn, int64_t nr, int Dp, int64_t index_base,
+                     int64_t self_base, int k, uint64_t* best, void* workspace, int64_t workspace_bytes, void* stream) {
+    CSLGAN_REQUIRE(q && qn && r && rn && best && workspace, "nn_kth_i8: null argument");
+    CSLGAN_REQUIRE(k >= 1 && k <= NN_MAX_K, "nn_kth_i8: k=%d must lie in 1 .. %d", k, NN_MAX_K);
+    CSLGAN_REQUIRE(Dp >= NN_KT && Dp <= NN_MAX_D && Dp % NN_KT == 0, "nn_kth_i8: Dp=%d must be a multiple of %d in %d .. %d", Dp, NN_KT, NN_KT,
+                   NN_MAX_D);
+    CSLGAN_REQUIRE(nq >= 1 && nq < (1ll << 31), "nn_kth_i8: nq=%lld out of range", (long long)nq);
+    CSLGAN_REQUIRE(nr >= 1 && nr < (1ll << 31), "nn_kth_i8: nr=%lld out of range", (long long)nr);
+    CSLGAN_REQUIRE(index_base >= 0 && index_base + nr <= 0xFFFFFFFFll, "nn_kth_i8: index_base + nr = %lld exceeds 2^32 - 1",
+                   (long long)(index_base + nr));
+    CSLGAN_REQUIRE(self_base >= -1 && self_base + nq <= 0xFFFFFFFFll, "nn_kth_i8: self_base=%lld must be -1 or keep self_base + nq <= 2^32 - 1",
+                   (long long)self_base);
+    CSLGAN_REQUIRE(aligned16(q) && aligned16(r) && (reinterpret_cast<uintptr_t>(qn) & 3u) == 0 && (reinterpret_cast<uintptr_t>(rn) & 3u) == 0 &&
+                       (reinterpret_cast<uintptr_t>(best) & 7u) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0,
+                   "nn_kth_i8: misaligned pointer");
+    long long tiles_per = 0;
+    const long long gy = nn_column_ranges(nq, nr, &tiles_per);
+    CSLGAN_REQUIRE(gy >= 1 && gy <= 65535, "nn_kth_i8: nr=%lld needs %lld column ranges", (long long)nr, gy);
+    CSLGAN_REQUIRE(workspace_bytes >= gy * nq * k * 8, "nn_kth_i8: workspace of %lld bytes, need %lld", (long long)workspace_bytes,
+                   (long long)(gy * nq * k * 8));
+    const long long col_tiles = (nr + NN_TN - 1) / NN_TN;
+    note_kernel("nn_kth_i8_kernel");
+    hipLaunchKernelGGL(nn_kth_i8_kernel, dim3((unsigned)((nq + NN_TM - 1) / NN_TM), (unsigned)gy), dim3(NN_THREADS), 0, (hipStream_t)stream,
+                       (const signed char*)q, (const int*)qn, (int)nq, (const signed char*)r, (const int*)rn, (int)nr, Dp, (uint32_t)index_base,
+                       (long long)self_base, k, (int)tiles_per, (int)col_tiles, (const unsigned long long*)best, (unsigned long long*)workspace);
+    if (int rc = check_launch("nn_kth_i8_kernel")) return rc;
+    note_kernel("nn_kth_merge_kernel");
+    hipLaunchKernelGGL(nn_kth_merge_kernel, dim3((unsigned)((nq + NN_THREADS - 1) / NN_THREADS)), dim3(NN_THREADS), 0, (hipStream_t)stream,
+                       (const unsigned long long*)workspace, (int)gy, (int)nq, k, (unsigned long long*)best);
+    return check_launch("nn_kth_merge_kernel");
+}
+
+int cslgan_nn_count_radius_i8(const void* q, const int32_t* qn, int64_t nq, const void* r, const int32_t* rn, int64_t nr, int Dp,
+                              const uint32_t* radius, uint32_t* counts, void* stream) {
+    CSLGAN_REQUIRE(q && qn && r && rn && radius && counts, "nn_count_radius_i8: null argument");
+    CSLGAN_REQUIRE(Dp >= NN_KT && Dp <= NN_MAX_D && Dp % NN_KT == 0, "nn_count_radius_i8: Dp=%d must be a multiple of %d in %d .. %d", Dp, NN_KT,
+                   NN_KT, NN_MAX_D);
+    CSLGAN_REQUIRE(nq >= 1 && nq < (1ll << 31), "nn_count_radius_i8: nq=%lld out of range", (long long)nq);
+    CSLGAN_REQUIRE(nr >= 1 && nr < (1ll << 31), "nn_count_radius_i8: nr=%lld out of range", (long long)nr);
+    CSLGAN_REQUIRE(aligned16(q) && aligned16(r) && (reinterpret_cast<uintptr_t>(qn) & 3u) == 0 && (reinterpret_cast<uintptr_t>(rn) & 3u) == 0 &&
+                       (reinterpret_cast<uintptr_t>(counts) & 3u) == 0 && (reinterpret_cast<uintptr_t>(radius) & 3u) == 0,
+                   "nn_count_radius_i8: misaligned pointer");
+    long long tiles_per = 0;
+    const long long gy = nn_column_ranges(nq, nr, &tiles_per);
+    CSLGAN_REQUIRE(gy >= 1 && gy <= 65535, "nn_count_radius_i8: nr=%lld needs %lld column ranges", (long long)nr, gy);
+    const long long col_tiles = (nr + NN_TN - 1) / NN_TN;
+    note_kernel("nn_count_radius_i8_kernel");
+    hipLaunchKernelGGL(nn_count_radius_i8_kernel, dim3((unsigned)((nq + NN_TM - 1) / NN_TM), (unsigned)gy), dim3(NN_THREADS), 0,
+                       (hipStream_t)stream, (const signed char*)q, (const int*)qn, (int)nq, (const signed char*)r, (const int*)rn, (int)nr, Dp,
+                       radius, (int)tiles_per, (int)col_tiles, (uint32_t*)counts);
+    return check_launch("nn_count_radius_i8_kernel");
 }
 
 }  // extern "C"

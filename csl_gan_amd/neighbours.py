@@ -9,6 +9,9 @@ The neighbour is the low word, its squared distance the high word, and ties go t
 set, so it does not depend on how the reference is cut into blocks.  Everything is integer arithmetic: `nearest_host` is the
 definition, and the device path (`ops.nn_prepare` + `ops.nn_min`) is held to it by equality.
 
+`kth_host` is the definition of the k smallest keys per row, with an optional self-excluding search of a set in itself (DESIGN.md
+§6i; csl_gan_amd.manifold builds precision / recall / density / coverage on it).
+
 `NearestSearch` drives the device over a pipeline.CachedImages reference of any size; `dcr_metrics` turns keys into the
 "distance to closest record" figures and the share of samples that lie closer to the training set than to a held-out set — 0.5 for
 a generator that has not memorised.
@@ -66,9 +69,52 @@ def nearest_host(Q, R, index_base=0, best=None, block=1024):
     return out
 
 
+MAX_K = 8                               # the device keeps a list of at most eight keys per row (csrc/nn_kernels.hip)
+
+
+def kth_host(Q, R, k, index_base=0, self_base=-1, best=None, block=1024):
+    """uint64 [nq, k]: per row of Q the k smallest keys d2(q, r) << 32 | (index_base + r) over the rows of R, ascending, merged with
+    `best` (the lists of earlier calls; all-ones when absent) — THE definition of the k-nearest-neighbour lists, 1 <= k <= 8.  With
+    self_base >= 0 row q leaves out the ONE column with index_base + r == self_base + q: the row is excluded by its index, never
+    by its distance, so a different row with the same bytes stays in at d2 = 0.  Keys carry the index and are distinct, so ties in
+    d2 are ordered by index and the list is a function of the candidate set alone.  All-ones entries stay last while fewer than k
+    candidates have been seen.  PRECONDITION (the device entry has the same): successive calls bring disjoint index ranges — a key
+    presented twice would be kept twice.  The float64-matmul-in-blocks argument of `nearest_host` makes the floats the integers."""
+    Q, R = _rows_u8(Q), _rows_u8(R)
+    nq, D = Q.shape
+    nr = R.shape[0]
+    k = int(k)
+    if not 1 <= k <= MAX_K:
+        raise ValueError("k = %d; the lists hold 1 .. %d neighbours" % (k, MAX_K))
+    if R.shape[1] != D or not 1 <= D <= MAX_D:
+        raise ValueError("rows of %d and %d bytes; need equal sizes in 1 .. %d" % (D, R.shape[1], MAX_D))
+    if index_base < 0 or index_base + nr > MAX_INDEX:
+        raise ValueError("index_base + nr = %d exceeds 2^32 - 1" % (index_base + nr))
+    if self_base < -1 or self_base + nq > MAX_INDEX:
+        raise ValueError("self_base = %d must be -1 or keep self_base + nq <= 2^32 - 1" % self_base)
+    out = np.full((nq, k), NONE_KEY, dtype=np.uint64) if best is None else np.array(best, dtype=np.uint64, copy=True)
+    if out.shape != (nq, k):
+        raise ValueError("best has shape %s, expected (%d, %d)" % (out.shape, nq, k))
+    block = max(1, int(block))
+    for r0 in range(0, nr, block):
+        b = np.asarray(R[r0:r0 + block]).astype(np.float64) - 128.0
+        bn = (b * b).sum(1)
+        idx = np.arange(index_base + r0, index_base + r0 + len(b), dtype=np.uint64)
+        for q0 in range(0, nq, block):
+            a = np.asarray(Q[q0:q0 + block]).astype(np.float64) - 128.0
+            d2 = (a * a).sum(1)[:, None] + bn[None, :] - 2.0 * (a @ b.T)
+            keys = (d2.astype(np.uint64) << np.uint64(32)) | idx[None, :]
+            if self_base >= 0:
+                own = np.arange(self_base + q0, self_base + q0 + len(a), dtype=np.uint64)
+                keys[own[:, None] == idx[None, :]] = NONE_KEY
+            both = np.sort(np.concatenate([out[q0:q0 + block], keys], axis=1), axis=1)
+            out[q0:q0 + block] = both[:, :k]
+    return out
+
+
 class NearestSearch:
     """`fit(reference cache)`, then `query(cache) -> uint64 keys[len(cache)]` and `count_within(cache, thresholds) -> int64
-    counts[len(cache), J]`, any number of times.
+    counts[len(cache), J]`, any number of times; `kth` and `count_within_radii` walk the same way.
 
     On a HIP device the reference is walked in blocks of `block_rows` images: pinned uint8 gather -> H2D on a side stream ->
     ops.nn_prepare -> ops.nn_min with index_base = the block's first row.  Two pinned and two device staging buffers alternate, so
@@ -132,6 +178,51 @@ class NearestSearch:
                 self._walk_reference(lambda start, r, rn: ops.nn_count(q, qn, r, rn, thr, counts))
                 return counts.cpu().numpy().astype(np.int64)
             return self._query_chunks(cache, np.empty((len(cache), len(thr)), dtype=np.int64), chunk)
+
+    def kth(self, cache, k, exclude_self=False):
+        """uint64 [len(cache), k]: for every query image the k smallest keys over the reference, ascending (`kth_host`; 1 <= k <= 8).
+        exclude_self=True is the search of the reference in itself — `cache` must be the fitted reference — and leaves every
+        image's own index out of its list.  kth_host on the CPU, ops.nn_kth over the walk of `query` on a device: query chunk
+        start s and reference block start give self_base = s and index_base = start."""
+        self._check_query(cache)
+        k = int(k)
+        if not 1 <= k <= MAX_K:
+            raise ValueError("k = %d; the lists hold 1 .. %d neighbours" % (k, MAX_K))
+        if exclude_self and cache is not self.ref:
+            raise ValueError("exclude_self searches the fitted reference in itself: pass the cache that fit() was given")
+        if not self.on_gpu:
+            return kth_host(cache.x, self.ref.x, k, self_base=0 if exclude_self else -1)
+        with torch.cuda.device(self.device):
+            from . import ops
+            first = [0]                                                                  # first row of the next chunk: they come in order
+
+            def chunk(q, qn):
+                s, first[0] = first[0], first[0] + q.shape[0]
+                best = torch.full((q.shape[0], k), -1, device=self.device, dtype=torch.int64)
+                self._walk_reference(lambda start, r, rn: ops.nn_kth(q, qn, r, rn, start, best, s if exclude_self else -1))
+                return best.cpu().numpy().view(np.uint64)
+            return self._query_chunks(cache, np.empty((len(cache), k), dtype=np.uint64), chunk)
+
+    def count_within_radii(self, cache, radii):
+        """int64 [len(cache)]: for every query image the number of reference images r with d2 <= radii[r]; `radii` holds one
+        integer in [0, 2^32 - 1] per reference image — manifold.count_within_radii_host on the CPU, ops.nn_count_radius over the
+        walk of `query` on a device, where the radii stay on the device and are sliced per block."""
+        from . import manifold
+        self._check_query(cache)
+        rad = manifold.check_radii(radii, len(self.ref))
+        if len(self.ref) >= 2 ** 31:
+            raise ValueError("a reference of %d images: counts are held below 2^31" % len(self.ref))
+        if not self.on_gpu:
+            return manifold.count_within_radii_host(cache.x, self.ref.x, rad)
+        with torch.cuda.device(self.device):
+            from . import ops
+            rad_dev = torch.from_numpy(rad.astype(np.uint32).view(np.int32)).to(self.device)
+
+            def chunk(q, qn):
+                counts = torch.zeros(q.shape[0], device=self.device, dtype=torch.int32)
+                self._walk_reference(lambda start, r, rn: ops.nn_count_radius(q, qn, r, rn, rad_dev[start:start + r.shape[0]], counts))
+                return counts.cpu().numpy().astype(np.int64)
+            return self._query_chunks(cache, np.empty(len(cache), dtype=np.int64), chunk)
 
     # ---- device path -------------------------------------------------------------------------------------------------------------
     def _query_gpu(self, cache):

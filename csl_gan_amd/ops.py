@@ -1607,6 +1607,70 @@ def nn_count(q, qn, r, rn, thresholds, counts):
     return counts
 
 
+_NN_KTH_WS = {}                                         # device -> the cached workspace of nn_kth (int64, grown on demand)
+
+
+def nn_kth_workspace_bytes(nq, nr, k):
+    """Workspace of nn_kth in bytes (0: sizes or a k that the search refuses)."""
+    return int(_lib.lib().cslgan_nn_kth_workspace_bytes(int(nq), int(nr), int(k)))
+
+
+def nn_kth(q, qn, r, rn, index_base, best, self_base=-1):
+    """best[i, :] = the k smallest of best[i, :] and the keys d2(q_i, r_j) << 32 | index_base + j, ascending as uint64, in place; k is
+    best.shape[1], 1 .. 8.  With self_base >= 0 row i skips the one column whose index index_base + j equals self_base + i.  q / qn /
+    r / rn as for nn_min; best: int64 device tensor [nq, k] that the caller filled with -1 (all ones) once; successive calls must
+    bring disjoint index ranges.  The workspace is ONE device tensor cached per device, whatever the stream: calls on different streams
+    of one device would race on it, so keep nn_kth on one stream per device (NearestSearch does).  csl_gan_amd.neighbours.kth_host is the host
+    model."""
+    args = ((q, "q", torch.int8), (r, "r", torch.int8), (qn, "qn", torch.int32), (rn, "rn", torch.int32), (best, "best", torch.int64))
+    for t, name, dt in args:                            # the types first: a wrong one is refused wherever the tensor lives
+        if t.dtype != dt:
+            raise RuntimeError("nn_kth: %s must be a contiguous %s tensor" % (name, str(dt).replace("torch.", "")))
+    for t, name, dt in args:
+        _chk_dev(t, name, dt, "nn_kth")
+    if q.dim() != 2 or r.dim() != 2 or q.shape[1] != r.shape[1]:
+        raise RuntimeError("nn_kth: need q [nq, Dp] and r [nr, Dp], got %s and %s" % (tuple(q.shape), tuple(r.shape)))
+    nq, Dp = q.shape
+    nr = r.shape[0]
+    if best.dim() != 2 or best.shape[0] != nq or not 1 <= best.shape[1] <= 8:
+        raise RuntimeError("nn_kth: best has the shape %s, expected (%d, k) with k in 1 .. 8" % (tuple(best.shape), nq))
+    k = best.shape[1]
+    if qn.numel() != nq or rn.numel() != nr:
+        raise RuntimeError("nn_kth: qn / rn have %d / %d entries, expected %d / %d" % (qn.numel(), rn.numel(), nq, nr))
+    need = nn_kth_workspace_bytes(nq, nr, k)
+    if need <= 0:
+        raise RuntimeError("nn_kth: %d x %d rows with k = %d are out of range" % (nq, nr, k))
+    ws = _NN_KTH_WS.get(q.device)
+    if ws is None or ws.numel() * 8 < need:
+        ws = _NN_KTH_WS[q.device] = torch.empty((need + 7) // 8, device=q.device, dtype=torch.int64)
+    check(_lib.lib().cslgan_nn_kth_i8(_p(q), _p(qn), nq, _p(r), _p(rn), nr, Dp, int(index_base), int(self_base), k, _p(best), _p(ws),
+                                      ws.numel() * 8, _stream()), "nn_kth")
+    return best
+
+
+def nn_count_radius(q, qn, r, rn, radius, counts):
+    """counts[i] += #{j : d2(q_i, r_j) <= radius[j]}, in place, compared as unsigned values.  q / qn / r / rn as for nn_min; radius:
+    int32 device tensor [nr] holding the uint32 bits; counts: int32 device tensor [nq] that the caller zeroed once (the device adds
+    uint32: the total of an entry must stay below 2^31 on this path).  csl_gan_amd.manifold.count_within_radii_host is the host
+    model."""
+    args = ((q, "q", torch.int8), (r, "r", torch.int8), (qn, "qn", torch.int32), (rn, "rn", torch.int32), (radius, "radius", torch.int32),
+            (counts, "counts", torch.int32))
+    for t, name, dt in args:
+        if t.dtype != dt:
+            raise RuntimeError("nn_count_radius: %s must be a contiguous %s tensor" % (name, str(dt).replace("torch.", "")))
+    for t, name, dt in args:
+        _chk_dev(t, name, dt, "nn_count_radius")
+    if q.dim() != 2 or r.dim() != 2 or q.shape[1] != r.shape[1]:
+        raise RuntimeError("nn_count_radius: need q [nq, Dp] and r [nr, Dp], got %s and %s" % (tuple(q.shape), tuple(r.shape)))
+    nq, Dp = q.shape
+    nr = r.shape[0]
+    if qn.numel() != nq or rn.numel() != nr or tuple(radius.shape) != (nr,) or tuple(counts.shape) != (nq,):
+        raise RuntimeError("nn_count_radius: qn / rn have %d / %d entries, radius and counts the shapes %s and %s; expected %d / %d, (%d,) and (%d,)"
+                           % (qn.numel(), rn.numel(), tuple(radius.shape), tuple(counts.shape), nq, nr, nr, nq))
+    check(_lib.lib().cslgan_nn_count_radius_i8(_p(q), _p(qn), nq, _p(r), _p(rn), nr, Dp, _p(radius), _p(counts), _stream()), "nn_count_radius")
+    return counts
+
+
 def row_l2norm(t2d):
     _chk(t2d, "t")
     n, L = t2d.shape

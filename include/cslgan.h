@@ -639,6 +639,42 @@ int cslgan_nn_min_i8(const void* q, const int32_t* qn, int64_t nq, const void* r
 int cslgan_nn_count_i8(const void* q, const int32_t* qn, int64_t nq, const void* r, const int32_t* rn, int64_t nr, int Dp,
                        const uint32_t* thresholds, int n_thr, uint32_t* counts, void* stream);
 
+/* The k smallest keys and the counts inside per-row radii (csl_gan_amd.manifold: precision / recall / density / coverage; backward-
+ * compatible additions, ABI stays 7).  For 1 <= k <= 8, kth(q) is the ascending list of the k smallest keys
+ * d2(q, r) << 32 | (index_base + r) of row q over the candidate set {r < nr}, minus — when self_base >= 0 — the ONE column with
+ * index_base + r == self_base + q: a row is excluded by its INDEX, never by its distance, so another row with the same bytes
+ * stays in, at d2 = 0.  Keys are distinct (they carry the index): ties in d2 are ordered by index and the list is a function of
+ * the set alone, not of tiling, launch order, block size or the number of calls.  csl_gan_amd.neighbours.kth_host is the host
+ * model.
+ *
+ * cslgan_nn_kth_workspace_bytes — bytes of workspace that cslgan_nn_kth_i8 needs for these sizes: one list of k keys per row of q
+ * and per column range of the launch.  0 for arguments the search would refuse. */
+int64_t cslgan_nn_kth_workspace_bytes(int64_t nq, int64_t nr, int k);
+
+/* cslgan_nn_kth_i8 — best: device uint64 [nq, k], IN/OUT: the caller fills it with all-ones once; after a call row q holds the k
+ * smallest of (what it held) and (this call's candidates), ascending, all-ones entries last while fewer than k candidates have
+ * been seen.  Successive calls must present DISJOINT index ranges (a key met twice would be kept twice).  q / r / qn / rn / Dp /
+ * nq / nr / index_base as for cslgan_nn_min_i8; self_base = -1 excludes nothing, else 0 <= self_base, self_base + nq <= 2^32 - 1.
+ * Same tile loop as nn_min.  Per row and wave a running bound (the d2 of the wave's k-th key, seeded from best) turns a candidate
+ * that cannot enter into one compare; one that can is inserted by the whole wave into the wave's own sorted list of the row in
+ * LDS (a ballot, then one uniform loop over its set bits).  No lock, no loop that waits for another wave, no scratch.  After the
+ * last tile the two waves of a row merge their lists and the workgroup writes k keys per row to its slice of `workspace`
+ * ([column range][nq][k] uint64, written in full: it needs no clearing); a second small kernel folds the slices and best.  Columns
+ * past nr and the excluded column never enter a list, whatever bytes lie behind them; rows past nq write nothing.  k in 1 .. 8;
+ * best and workspace 8-byte aligned; workspace_bytes >= cslgan_nn_kth_workspace_bytes(nq, nr, k). */
+int cslgan_nn_kth_i8(const void* q, const int32_t* qn, int64_t nq, const void* r, const int32_t* rn, int64_t nr, int Dp,
+                     int64_t index_base, int64_t self_base, int k, uint64_t* best, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* cslgan_nn_count_radius_i8 — counts[q] += #{r < nr : d2(q, r) <= radius[r]} for q < nq: the counting epilogue with the threshold
+ * of the COLUMN, compared as UNSIGNED 32-bit values and with <= (Kynkaanniemi et al.; the `prdc` package uses <, which differs on
+ * exact ties only).  radius: device uint32 [nr], read beside rn; counts: device uint32 [nq], IN/OUT, zeroed by the caller once.
+ * One plain uint32 counter per row and lane (no cap on the tiles of a workgroup), summed over the lanes and waves of the row
+ * once, ONE atomicAdd per row and workgroup that counted anything.  Columns past nr are masked by their index, whatever radius
+ * or bytes lie behind them; rows past nq issue nothing.  csl_gan_amd.manifold.count_within_radii_host is the host model.
+ * q / r / qn / rn / Dp / nq / nr as for cslgan_nn_min_i8; radius and counts 4-byte aligned. */
+int cslgan_nn_count_radius_i8(const void* q, const int32_t* qn, int64_t nq, const void* r, const int32_t* rn, int64_t nr, int Dp,
+                              const uint32_t* radius, uint32_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
