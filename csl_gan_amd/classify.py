@@ -14,6 +14,10 @@ on generated samples, its probabilities on a real test set, and their micro-aver
     csl_gan_amd.audit.rank_metrics computes exactly from integer rank counts (cslgan_rank_counts on a device).
 
 Every piece has a host path (float64 torch) and a device path (fp32, csrc/logreg_kernels.hip) with the same definition.
+
+The `*_bytes` forms (csl_gan_amd.tstr) are the same estimator on uint8 cache rows, x = byte / 255, for any row size
+1 .. 65536: `objective_host_bytes` is THE definition, `OvrLogReg.fit_bytes` / `predict_proba_bytes` run it through
+cslgan_ovr_logreg_eval_u8 / cslgan_ovr_logreg_proba_u8 on a device, and `accuracy` is the argmax hit count.
 """
 from __future__ import annotations
 
@@ -50,6 +54,63 @@ def objective_host(X, labels, U):
     R = torch.sigmoid(Z) - T
     grad = torch.cat([X.t() @ R + 0.5 * U[:D], R.sum(0, keepdim=True)], 0)
     return loss, grad
+
+
+def _bytes_rows(Xu8):
+    X = torch.as_tensor(Xu8)
+    if X.dtype != torch.uint8 or X.dim() != 2:
+        raise ValueError("need uint8 rows [N, D], got %s %s" % (X.dtype, tuple(X.shape)))
+    return X
+
+
+def objective_host_bytes(Xu8, labels, U, block=2048):
+    """(loss [K], grad [D + 1, K]) of the K objectives on byte features x = byte / 255, float64 torch on the CPU, in row blocks of
+    `block` (a CelebA-sized cache never becomes one float64 matrix) — THE definition for byte features; equal to
+    objective_host(Xu8.double() / 255, labels, U)."""
+    X, U = _bytes_rows(Xu8).cpu(), torch.as_tensor(U).double().cpu()
+    y = torch.as_tensor(labels).long().reshape(-1).cpu()
+    N, D = X.shape
+    K = U.shape[1]
+    block = max(1, int(block))
+    cls = torch.arange(K)[None, :]
+    loss = 0.25 * (U[:D] ** 2).sum(0)
+    G = torch.zeros((D, K), dtype=torch.float64)
+    gb = torch.zeros(K, dtype=torch.float64)
+    for r0 in range(0, N, block):
+        Xb = X[r0:r0 + block].double() / 255.0
+        T = (y[r0:r0 + block, None] == cls).double()
+        Z = Xb @ U[:D] + U[D]
+        sz = (2 * T - 1) * Z
+        loss = loss + (torch.clamp(-sz, min=0) + torch.log1p(torch.exp(-sz.abs()))).sum(0)
+        R = torch.sigmoid(Z) - T
+        G += Xb.t() @ R
+        gb += R.sum(0)
+    return loss, torch.cat([G + 0.5 * U[:D], gb[None, :]], 0)
+
+
+def proba_host_bytes(Xu8, U, block=2048):
+    """P [M, K] in float64 of uint8 rows, x = byte / 255, in row blocks."""
+    X, U = _bytes_rows(Xu8).cpu(), torch.as_tensor(U).double().cpu()
+    out = torch.empty((X.shape[0], U.shape[1]), dtype=torch.float64)
+    block = max(1, int(block))
+    for r0 in range(0, X.shape[0], block):
+        S = torch.sigmoid((X[r0:r0 + block].double() / 255.0) @ U[:-1] + U[-1])
+        out[r0:r0 + block] = S / S.sum(1, keepdim=True)
+    return out
+
+
+def accuracy(P, y):
+    """{"hits", "n", "accuracy"} of scores P [M, K] against labels y [M]: the prediction is the argmax over the classes, ties to the
+    smallest class index; hits is the integer numerator."""
+    P = (P.detach().cpu() if torch.is_tensor(P) else torch.from_numpy(np.asarray(P)))
+    y = torch.as_tensor(y).reshape(-1).long().cpu()
+    if P.dim() != 2 or y.numel() != P.shape[0] or P.shape[0] < 1:
+        raise ValueError("need P [M, K] and y [M], got %s and %s" % (tuple(P.shape), tuple(y.shape)))
+    best = P.max(1, keepdim=True)[0]
+    cls = torch.arange(P.shape[1])[None, :].expand_as(P)
+    pred = torch.where(P == best, cls, torch.full_like(cls, P.shape[1])).min(1)[0]      # the first maximum
+    hits, n = int((pred == y).sum()), int(P.shape[0])
+    return {"hits": hits, "n": n, "accuracy": hits / n}
 
 
 def proba_host(Xtest, U):
@@ -188,6 +249,52 @@ class OvrLogReg:
         rep["gtol_rel"] = float(gtol_rel)
         self.coef, self.report = U, rep
         return rep
+
+    def _check_fit(self, X, y):
+        if X.dim() != 2 or y.numel() != X.shape[0]:
+            raise ValueError("need X [N, D] and y [N], got %s and %s" % (tuple(X.shape), tuple(y.shape)))
+        counts = np.bincount(y.detach().cpu().numpy().astype(np.int64).reshape(-1), minlength=self.K)
+        if len(counts) > self.K or (counts[:self.K] == 0).any():
+            raise ValueError("every class 0 .. %d needs a training sample; counts: %s" % (self.K - 1, counts.tolist()))
+
+    def fit_bytes(self, Xu8, y):
+        """fit on uint8 rows [N, D] with x = byte / 255, any D in 1 .. 65536.  On a HIP device the rows stay bytes and every
+        evaluation is one ops.ovr_logreg_eval_u8 call; elsewhere objective_host_bytes.  Same solver, same default gtol_rel per
+        path, same report as fit."""
+        X = _bytes_rows(Xu8)
+        y = torch.as_tensor(y)
+        self._check_fit(X, y)
+        N, D = X.shape
+        if X.is_cuda:
+            from . import ops
+            with torch.cuda.device(X.device):
+                Xd = X.contiguous()
+                yd = y.to(X.device).reshape(-1).to(torch.int32).contiguous()
+                ws = torch.empty(max(ops.ovr_logreg_u8_ws_floats(N, D), 2), device=X.device, dtype=torch.float32)
+                U0 = torch.zeros((D + 1, self.K), device=X.device, dtype=torch.float32)
+                ev = lambda U: ops.ovr_logreg_eval_u8(Xd, yd, U.contiguous(), ws=ws)
+                gtol_rel = GTOL_REL_DEVICE if self.gtol_rel is None else self.gtol_rel
+                U, rep = lbfgs_columns(ev, U0, N, gtol_rel, self.max_iter)
+        else:
+            yh = y.long().reshape(-1)
+            ev = lambda U: objective_host_bytes(X, yh, U)
+            gtol_rel = GTOL_REL_HOST if self.gtol_rel is None else self.gtol_rel
+            U, rep = lbfgs_columns(ev, torch.zeros((D + 1, self.K), dtype=torch.float64), N, gtol_rel, self.max_iter)
+        rep["gtol_rel"] = float(gtol_rel)
+        self.coef, self.report = U, rep
+        return rep
+
+    def predict_proba_bytes(self, Xu8):
+        """P [M, K] of uint8 rows, x = byte / 255, any D: ops.ovr_logreg_proba_u8 on a device (float32), the row-blocked float64
+        formula on the host."""
+        if self.coef is None:
+            raise RuntimeError("fit first")
+        X = _bytes_rows(Xu8)
+        if X.is_cuda:
+            from . import ops
+            with torch.cuda.device(X.device):
+                return ops.ovr_logreg_proba_u8(X.contiguous(), self.coef.to(X.device, torch.float32).contiguous())
+        return proba_host_bytes(X, self.coef.cpu())
 
     def predict_proba(self, Xtest):
         if self.coef is None:

@@ -3,6 +3,8 @@
 //   downstream.py:71-72, :87  OneVsRestClassifier(LogisticRegression(lbfgs, multinomial)).fit  -> ovr_logreg_eval_kernel + ovr_logreg_reduce_kernel
 //                                                                (one loss-and-gradient evaluation of all K <= 16 binary problems)
 //   downstream.py:87          .predict_proba(X_test)                                             -> ovr_logreg_proba_kernel
+//   (no counterpart)          the same evaluation and probabilities on uint8 cache rows of any size  -> ovr_logreg_u8_fwd_kernel + ovr_logreg_u8_grad_kernel
+//                                                                (csl_gan_amd.tstr; second half of this file)   + ovr_logreg_u8_reduce_kernel
 //
 // Objective of class k (include/cslgan.h "Downstream classifier"): sum_i softplus(-s_ik z_ik) + ||u_k||^2 / 4 with z = X u_k + b_k.
 // Both products, Z = X U and G = X^T (sigmoid(Z) - T), run on v_mfma_f32_16x16x4_f32 with the classes padded to the 16 columns of
@@ -266,6 +268,335 @@ __global__ __launch_bounds__(LR_THREADS) void ovr_logreg_proba_kernel(const void
     }
 }
 
+// ---- the same objective on cache BYTES, any row size (csl_gan_amd.tstr) ------------------------------------------------
+// x = byte / 255, 1 <= D <= 65536: a 16-row tile no longer fits in LDS, so an evaluation is two passes over X with the residuals
+// R = sigmoid(Z) - T [N, 16] kept in the workspace between them.  Bytes enter the matrix instruction as the exact floats 0 .. 255
+// and 1 / 255 is applied once to each sum.
+//
+//   ovr_logreg_u8_fwd_kernel    Z = X U, loss terms, R, the intercept gradient (or P when PROBA).  A workgroup walks blocks of
+//                               LRB_RT x 16 rows.  Wavefront w owns the 64-column groups w, w + 4, ...: lane (l16, lg) loads the
+//                               16 bytes [64 g + 16 lg, + 16) of row l16 of each of the LRB_RT row tiles and the 16 matching rows
+//                               of U, and issues 16 steps per row tile with ONE B fragment set for all LRB_RT tiles (U is
+//                               D x 16 floats, four times a 16-row tile of X: shared over 64 rows it costs what X costs, from
+//                               L2).  The k order inside a group is permuted the same way on both operands.  The four partial Z
+//                               meet in LDS and are added in a fixed order.
+//   ovr_logreg_u8_grad_kernel   G = X^T R.  Workgroup (slab, chunk) owns 256 columns and a chunk of rows; its four wavefronts
+//                               take the 4-row steps w, w + 4, ... of the chunk.  Lane (l16, lg) loads the 16 bytes
+//                               [d0 + 16 l16, + 16) of row lg of the step — a wave instruction reads four runs of 256 contiguous
+//                               bytes, so the transposed operand needs no LDS — and byte j is the A element of output block j,
+//                               whose row m = l16 stands for column d0 + 16 m + j.  16 [16, 16] accumulators per wavefront; the
+//                               four wavefronts meet in LDS in a fixed order and the workgroup writes ONE partial [256, 16].
+//   ovr_logreg_u8_reduce_kernel adds the partials in index order in double, scales by 1 / 255, adds u / 2 and ||u||^2 / 4.
+constexpr int LRB_MAX_D = 65536;
+constexpr int LRB_RT = 4;                         // row tiles of 16 per forward row block: 64 rows share one read of U
+constexpr int LRB_ROWS = 16 * LRB_RT;
+constexpr int LRB_FWD_BLOCKS = 1024;              // forward workgroups (4 per CU of an MI355X); also the number of loss partials
+constexpr int LRB_SLAB = 256;                     // columns of a gradient workgroup: 16 bytes x 16 lanes
+constexpr int LRB_GRAD_WGS = 768;                 // slabs x chunks aimed at: 3 workgroups per CU
+constexpr int LRB_MAX_CHUNKS = 64;                // bounds the workspace: chunks x Dp x 16 floats
+constexpr int LRB_BATCH = 4;                      // 4-row steps in flight per wavefront of the gradient pass
+
+static inline long long lrb_row_blocks(long long N) { return (N + LRB_ROWS - 1) / LRB_ROWS; }
+static inline int lrb_fwd_blocks(long long N) {
+    const long long rb = lrb_row_blocks(N);
+    return (int)(rb < LRB_FWD_BLOCKS ? rb : LRB_FWD_BLOCKS);
+}
+static inline int lrb_dp(int D) { return (D + LRB_SLAB - 1) / LRB_SLAB * LRB_SLAB; }
+// rows per chunk (a multiple of 16) and the number of chunks: slabs x chunks near LRB_GRAD_WGS, at most LRB_MAX_CHUNKS chunks
+static inline void lrb_chunks(long long N, int D, long long& rows_per_chunk, int& chunks) {
+    const long long slabs = lrb_dp(D) / LRB_SLAB;
+    long long want = (LRB_GRAD_WGS + slabs - 1) / slabs;
+    want = want > LRB_MAX_CHUNKS ? LRB_MAX_CHUNKS : want;
+    rows_per_chunk = ((N + want - 1) / want + 15) / 16 * 16;
+    chunks = (int)((N + rows_per_chunk - 1) / rows_per_chunk);
+}
+
+// Bytes [col, col + 16) of the row that starts at byte `start` of x (col a multiple of 16), zero from column D on and when !ok (a
+// row that does not exist).  AL: D % 16 == 0, so the 16 bytes are one aligned word inside the row; the load is unconditional, from
+// offset 0 where there is nothing to read, followed by a select: no branch, so the loads of one fetch stay in flight together.
+// Otherwise they are assembled from the two ALIGNED words that hold them (per-lane shift: lanes hold different rows), and words that
+// reach beyond the last byte of x (`total`; `whole` = total & ~15) are never touched: those bytes are read one by one.
+template <bool AL>
+__device__ __forceinline__ u32x4 lrb_load16(const unsigned char* __restrict__ x, unsigned long long total, unsigned long long whole,
+                                            unsigned long long start, int col, int D, bool ok) {
+    u32x4 v = {0u, 0u, 0u, 0u};
+    const int valid = D - col;
+    if (AL) {
+        const bool in = ok && valid > 0;
+        const u32x4 got = *reinterpret_cast<const u32x4*>(x + (in ? start + (unsigned long long)col : 0ull));      // total >= 16
+        v.x = in ? got.x : 0u; v.y = in ? got.y : 0u; v.z = in ? got.z : 0u; v.w = in ? got.w : 0u;
+        return v;
+    }
+    if (!ok || valid <= 0) return v;
+    const unsigned long long a = start + (unsigned long long)col;
+    const int s = (int)(a & 15u);
+    const unsigned long long g = a - (unsigned long long)s;
+    if (g + 32ull <= whole) {
+        const u32x4 lo = *reinterpret_cast<const u32x4*>(x + g);
+        const u32x4 hi = *reinterpret_cast<const u32x4*>(x + g + 16);
+        const unsigned w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        const int ds = s >> 2, bs = s & 3;
+        unsigned t[5];
+#pragma unroll
+        for (int j = 0; j < 5; ++j) t[j] = ds == 0 ? w[j] : (ds == 1 ? w[j + 1] : (ds == 2 ? w[j + 2] : w[(j + 3) & 7]));   // j + 3 <= 7
+        v.x = __builtin_amdgcn_alignbyte(t[1], t[0], bs);
+        v.y = __builtin_amdgcn_alignbyte(t[2], t[1], bs);
+        v.z = __builtin_amdgcn_alignbyte(t[3], t[2], bs);
+        v.w = __builtin_amdgcn_alignbyte(t[4], t[3], bs);
+    } else {
+        unsigned b[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const unsigned long long q = a + (unsigned long long)j;
+            const unsigned byte = q < total ? (unsigned)x[q] : 0u;
+            b[j >> 2] |= byte << (8 * (j & 3));
+        }
+        v.x = b[0]; v.y = b[1]; v.z = b[2]; v.w = b[3];
+    }
+    if (valid < 16) {                                           // the bytes past the row's end hold the next row or nothing
+        unsigned m[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int nb = valid - 4 * j;
+            m[j] = nb >= 4 ? 0xffffffffu : (nb <= 0 ? 0u : ((1u << (8 * nb)) - 1u));
+        }
+        v.x &= m[0]; v.y &= m[1]; v.z &= m[2]; v.w &= m[3];
+    }
+    return v;
+}
+
+// byte e (0 .. 15, a compile-time constant after unrolling) of a 16-byte word as the exact float 0 .. 255
+__device__ __forceinline__ float lrb_byte(const u32x4& v, int e) {
+    const unsigned d = (e >> 2) == 0 ? v.x : ((e >> 2) == 1 ? v.y : ((e >> 2) == 2 ? v.z : v.w));
+    return (float)((d >> (8 * (e & 3))) & 0xffu);
+}
+
+template <bool PROBA, bool AL>
+__global__ __launch_bounds__(LR_THREADS) void ovr_logreg_u8_fwd_kernel(const unsigned char* __restrict__ X, const int* __restrict__ labels,
+                                                                       const float* __restrict__ U, long long N, int D, int K,
+                                                                       float* __restrict__ R, double* __restrict__ lpart, float* __restrict__ P) {
+    __shared__ __attribute__((aligned(16))) float zpart[4 * LRB_RT * LR_ROWS * LR_MAX_K];      // 16 KB
+    __shared__ double lred[3 * LR_THREADS];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int l16 = lane & 15, lg = lane >> 4;
+    const unsigned long long total = (unsigned long long)N * (unsigned long long)D, whole = total & ~15ull;
+    const int groups = (D + 63) >> 6;
+    const long long row_blocks = (N + LRB_ROWS - 1) / LRB_ROWS;
+    const int c = tid & 15, r = tid >> 4;
+    const float bias = c < K ? U[(long long)D * K + c] : 0.f;
+    const bool cok = l16 < K;
+    double lacc = 0.0, bacc = 0.0;                      // thread (row r of every tile, class c) over this workgroup's row blocks
+
+    for (long long rb = blockIdx.x; rb < row_blocks; rb += gridDim.x) {
+        const long long row0 = rb * LRB_ROWS;
+        unsigned long long start[LRB_RT];
+        bool rok[LRB_RT];
+#pragma unroll
+        for (int rt = 0; rt < LRB_RT; ++rt) {
+            const long long row = row0 + 16 * rt + l16;
+            rok[rt] = row < N;
+            start[rt] = (unsigned long long)row * (unsigned long long)D;
+        }
+        f32x4 acc[LRB_RT];
+#pragma unroll
+        for (int rt = 0; rt < LRB_RT; ++rt) acc[rt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        u32x4 xn[LRB_RT];
+        float un[16];
+        // group g: columns 64 g + 16 lg + e, e = 0 .. 15, on this lane
+        auto fetch = [&](int g) {
+            const int col = 64 * g + 16 * lg;
+#pragma unroll
+            for (int rt = 0; rt < LRB_RT; ++rt) xn[rt] = lrb_load16<AL>(X, total, whole, start[rt], col, D, rok[rt]);
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {                // unconditional loads (U[0] where there is nothing to read), then a select
+                const bool in = cok && col + e < D;
+                const float u = U[in ? (long long)(col + e) * K + l16 : 0ll];
+                un[e] = in ? u : 0.f;
+            }
+        };
+        fetch(w);
+        for (int g = w; g < groups; g += 4) {
+            u32x4 xc[LRB_RT];
+            float uc[16];
+#pragma unroll
+            for (int rt = 0; rt < LRB_RT; ++rt) xc[rt] = xn[rt];
+#pragma unroll
+            for (int e = 0; e < 16; ++e) uc[e] = un[e];
+            fetch(g + 4);                                // in flight during the 64 instructions below; zeros past the last group
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+#pragma unroll
+                for (int rt = 0; rt < LRB_RT; ++rt) acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(lrb_byte(xc[rt], e), uc[e], acc[rt], 0, 0, 0);
+            }
+        }
+        // C layout: column (class) l16, row 4 lg + i
+#pragma unroll
+        for (int rt = 0; rt < LRB_RT; ++rt) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) zpart[((w * LRB_RT + rt) * LR_ROWS + 4 * lg + i) * LR_MAX_K + l16] = acc[rt][i];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int rt = 0; rt < LRB_RT; ++rt) {
+            const int o = rt * 256 + tid;
+            const float sum = ((zpart[o] + zpart[LRB_RT * 256 + o]) + zpart[2 * LRB_RT * 256 + o]) + zpart[3 * LRB_RT * 256 + o];
+            const float z = sum * (1.0f / 255.0f) + bias;
+            const long long row = row0 + 16 * rt + r;
+            if (PROBA) {
+                const float e = expf(-fabsf(z));
+                const float sig = c < K ? (z >= 0.f ? 1.f : e) / (1.f + e) : 0.f;
+                float tot = sig;                         // butterfly over the 16 lanes of a row: partners hold equal sums at every level
+                tot += __shfl_xor(tot, 1, 64);
+                tot += __shfl_xor(tot, 2, 64);
+                tot += __shfl_xor(tot, 4, 64);
+                tot += __shfl_xor(tot, 8, 64);
+                if (row < N && c < K) P[row * K + c] = sig / tot;
+            } else if (row < N) {
+                float ls = 0.f, rd = 0.f;
+                if (c < K) {
+                    lr_terms(z, labels[row] == c, ls, rd);
+                    lacc += (double)ls;
+                    bacc += (double)rd;
+                }
+                R[row * LR_MAX_K + c] = rd;              // columns >= K add nothing to the gradient
+            }
+        }
+        __syncthreads();                                // the next row block overwrites zpart
+    }
+    if (!PROBA) {
+        // the penalty ||u_k||^2 / 4 of rows [b per, (b + 1) per) of U, per = ceil(D / workgroups): D is up to 65536 rows, too long
+        // a chain of dependent loads for the one block that ends the reduction
+        double pacc = 0.0;
+        if (c < K) {
+            const int per = (D + (int)gridDim.x - 1) / (int)gridDim.x;
+            const int dlo = (int)blockIdx.x * per, dhi = dlo + per < D ? dlo + per : D;
+            for (int d = dlo + r; d < dhi; d += 8 * LR_ROWS) {
+                float u[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) u[j] = d + LR_ROWS * j < dhi ? U[(long long)(d + LR_ROWS * j) * K + c] : 0.f;      // 8 loads in flight
+#pragma unroll
+                for (int j = 0; j < 8; ++j) pacc += 0.25 * (double)u[j] * (double)u[j];
+            }
+        }
+        lred[tid] = lacc;
+        lred[LR_THREADS + tid] = bacc;
+        lred[2 * LR_THREADS + tid] = pacc;
+        __syncthreads();
+        if (tid < 3 * LR_MAX_K) {                       // threads 0 .. 15: the losses, 16 .. 31: the intercept gradients, 32 .. 47: the penalties
+            const int k = tid & 15, which = tid >> 4;
+            double s = 0.0;
+            for (int i = 0; i < LR_ROWS; ++i) s += lred[which * LR_THREADS + i * LR_MAX_K + k];
+            lpart[((long long)blockIdx.x * 3 + which) * LR_MAX_K + k] = s;
+        }
+    }
+}
+
+template <bool AL>
+__global__ __launch_bounds__(LR_THREADS) void ovr_logreg_u8_grad_kernel(const unsigned char* __restrict__ X, const float* __restrict__ R, long long N,
+                                                                        int D, int Dp, long long rows_per_chunk, float* __restrict__ gpart) {
+    __shared__ __attribute__((aligned(16))) float part[3 * 64 * 64];        // wavefronts 1 .. 3: [block j][i][lane], 48 KB
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int l16 = lane & 15, lg = lane >> 4;
+    const unsigned long long total = (unsigned long long)N * (unsigned long long)D, whole = total & ~15ull;
+    const int d0 = blockIdx.x * LRB_SLAB, col = d0 + 16 * l16;
+    const long long cs = (long long)blockIdx.y * rows_per_chunk;
+    const long long ce = cs + rows_per_chunk < N ? cs + rows_per_chunk : N;
+    const int steps = (int)((ce - cs + 3) >> 2);                            // 4-row steps of this chunk; wavefront w takes w, w + 4, ...
+    const int batches = (steps + 4 * LRB_BATCH - 1) / (4 * LRB_BATCH);      // the same for the four wavefronts
+
+    f32x4 acc[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    u32x4 xn[LRB_BATCH];
+    float rn[LRB_BATCH];
+    // step t: A[column d0 + 16 l16 + j][row cs + 4 t + lg] for block j, B[row cs + 4 t + lg][class l16]
+    auto fetch = [&](int b) {
+#pragma unroll
+        for (int q = 0; q < LRB_BATCH; ++q) {
+            const long long row = cs + 4ll * (w + 4 * (LRB_BATCH * b + q)) + lg;
+            const bool ok = row < ce;
+            xn[q] = lrb_load16<AL>(X, total, whole, (unsigned long long)row * (unsigned long long)D, col, D, ok);
+            const float rv = R[ok ? row * LR_MAX_K + l16 : 0ll];          // unconditional, then a select
+            rn[q] = ok ? rv : 0.f;
+        }
+    };
+    fetch(0);
+    for (int b = 0; b < batches; ++b) {
+        u32x4 xc[LRB_BATCH];
+        float rc[LRB_BATCH];
+#pragma unroll
+        for (int q = 0; q < LRB_BATCH; ++q) { xc[q] = xn[q]; rc[q] = rn[q]; }
+        fetch(b + 1);                                    // in flight during the 64 instructions below; zeros past the chunk's end
+#pragma unroll
+        for (int q = 0; q < LRB_BATCH; ++q) {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(lrb_byte(xc[q], j), rc[q], acc[j], 0, 0, 0);
+        }
+    }
+    if (w > 0) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) part[((w - 1) * 64 + 4 * j + i) * 64 + lane] = acc[j][i];
+        }
+    }
+    __syncthreads();
+    if (w == 0) {
+        // C layout of block j: class l16, row m = 4 lg + i, which stands for column d0 + 16 m + j < Dp
+        float* __restrict__ gp = gpart + ((long long)blockIdx.y * Dp + d0) * LR_MAX_K;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int o = (4 * j + i) * 64 + lane;
+                const float v = ((acc[j][i] + part[o]) + part[64 * 64 + o]) + part[2 * 64 * 64 + o];
+                gp[(16 * (4 * lg + i) + j) * LR_MAX_K + l16] = v;
+            }
+        }
+    }
+}
+
+// Blocks 0 .. ceil(D / 16) - 1: 16 rows d of the gradient each, thread (d, class): the chunk partials in index order (double), times
+// 1 / 255, + u / 2.  The last block: 16 slices of the forward partials (data term, intercept gradient, a slice of ||u_k||^2 / 4 each)
+// x 16 classes for the intercept gradients and the K losses, the slices added in order.
+__global__ __launch_bounds__(LR_THREADS) void ovr_logreg_u8_reduce_kernel(const float* __restrict__ gpart, const double* __restrict__ lpart,
+                                                                          const float* __restrict__ U, int chunks, int fwd_blocks, int D, int K,
+                                                                          int Dp, float* __restrict__ loss, float* __restrict__ grad) {
+    __shared__ double red[2 * LR_THREADS];
+    const int tid = threadIdx.x, c = tid & 15, sl = tid >> 4;
+    const int dblocks = (D + 15) >> 4;
+    if ((int)blockIdx.x < dblocks) {
+        const int d = blockIdx.x * 16 + sl;
+        if (d < D && c < K) {
+            double s = 0.0;
+#pragma unroll 4
+            for (int ch = 0; ch < chunks; ++ch) s += (double)gpart[((long long)ch * Dp + d) * LR_MAX_K + c];
+            grad[(long long)d * K + c] = (float)(s / 255.0 + 0.5 * (double)U[(long long)d * K + c]);
+        }
+        return;                                          // no barrier in this branch
+    }
+    double sl_loss = 0.0, sl_b = 0.0;
+    if (c < K) {
+#pragma unroll 4
+        for (int b = sl; b < fwd_blocks; b += 16) {
+            sl_loss += lpart[((long long)b * 3) * LR_MAX_K + c] + lpart[((long long)b * 3 + 2) * LR_MAX_K + c];
+            sl_b += lpart[((long long)b * 3 + 1) * LR_MAX_K + c];
+        }
+    }
+    red[tid] = sl_loss;
+    red[LR_THREADS + tid] = sl_b;
+    __syncthreads();
+    if (tid < K) {
+        double tl = 0.0, tb = 0.0;
+        for (int i = 0; i < 16; ++i) {
+            tl += red[i * 16 + tid];
+            tb += red[LR_THREADS + i * 16 + tid];
+        }
+        loss[tid] = (float)tl;
+        grad[(long long)D * K + tid] = (float)tb;        // the intercept carries no penalty
+    }
+}
+
 }  // namespace cslgan
 
 using namespace cslgan;
@@ -319,6 +650,63 @@ int cslgan_ovr_logreg_proba_f32(const void* Xtest, int is_u8, const float* U, in
         hipLaunchKernelGGL(ovr_logreg_proba_kernel<false>, dim3(blocks), dim3(LR_THREADS), 0, (hipStream_t)stream, Xtest, U, (long long)M, D, K, vec, P);
     }
     return check_launch("ovr_logreg_proba_kernel");
+}
+
+int64_t cslgan_ovr_logreg_u8_ws_floats(int64_t N, int D) {
+    if (N < 1 || N >= (1ll << 31) || D < 1 || D > LRB_MAX_D) return 0;
+    long long rpc;
+    int chunks;
+    lrb_chunks(N, D, rpc, chunks);
+    // the forward partials as doubles (loss, intercept gradient and a slice of the penalty per workgroup), the residuals, the
+    // partial gradients
+    return 6 * (int64_t)lrb_fwd_blocks(N) * LR_MAX_K + N * LR_MAX_K + (int64_t)chunks * lrb_dp(D) * LR_MAX_K;
+}
+
+int cslgan_ovr_logreg_eval_u8(const void* X, const int32_t* labels, const float* U, int64_t N, int D, int K, float* loss, float* grad, float* ws,
+                              int64_t ws_floats, void* stream) {
+    CSLGAN_REQUIRE(X && labels && U && loss && grad && ws, "ovr_logreg_eval_u8: null argument");
+    CSLGAN_REQUIRE(K >= 2 && K <= LR_MAX_K, "ovr_logreg_eval_u8: K=%d must lie in 2 .. %d", K, LR_MAX_K);
+    CSLGAN_REQUIRE(D >= 1 && D <= LRB_MAX_D, "ovr_logreg_eval_u8: D=%d must lie in 1 .. %d", D, LRB_MAX_D);
+    CSLGAN_REQUIRE(N >= 1 && N < (1ll << 31), "ovr_logreg_eval_u8: N=%lld out of range", (long long)N);
+    const int64_t need = cslgan_ovr_logreg_u8_ws_floats(N, D);
+    CSLGAN_REQUIRE(ws_floats >= need, "ovr_logreg_eval_u8: workspace of %lld floats, need %lld", (long long)ws_floats, (long long)need);
+    CSLGAN_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 7u) == 0, "ovr_logreg_eval_u8: workspace misaligned (8 bytes)");
+    CSLGAN_REQUIRE(aligned16(X), "ovr_logreg_eval_u8: X misaligned (16 bytes)");
+    const int nb = lrb_fwd_blocks(N), Dp = lrb_dp(D);
+    const bool al = D % 16 == 0;
+    long long rpc;
+    int chunks;
+    lrb_chunks(N, D, rpc, chunks);
+    double* lpart = reinterpret_cast<double*>(ws);
+    float* R = ws + 6 * (int64_t)nb * LR_MAX_K;
+    float* gpart = R + N * LR_MAX_K;
+    const hipStream_t st = (hipStream_t)stream;
+    note_kernel("ovr_logreg_u8_fwd_kernel<eval>");
+    const auto fwd = al ? ovr_logreg_u8_fwd_kernel<false, true> : ovr_logreg_u8_fwd_kernel<false, false>;
+    hipLaunchKernelGGL(fwd, dim3((unsigned)nb), dim3(LR_THREADS), 0, st, (const unsigned char*)X, labels, U, (long long)N, D, K, R, lpart, (float*)nullptr);
+    int rc = check_launch("ovr_logreg_u8_fwd_kernel");
+    if (rc != CSLGAN_OK) return rc;
+    note_kernel("ovr_logreg_u8_grad_kernel");
+    const auto bwd = al ? ovr_logreg_u8_grad_kernel<true> : ovr_logreg_u8_grad_kernel<false>;
+    hipLaunchKernelGGL(bwd, dim3((unsigned)(Dp / LRB_SLAB), (unsigned)chunks), dim3(LR_THREADS), 0, st, (const unsigned char*)X, (const float*)R, (long long)N, D, Dp, rpc, gpart);
+    rc = check_launch("ovr_logreg_u8_grad_kernel");
+    if (rc != CSLGAN_OK) return rc;
+    hipLaunchKernelGGL(ovr_logreg_u8_reduce_kernel, dim3((unsigned)((D + 15) / 16 + 1)), dim3(LR_THREADS), 0, st, (const float*)gpart,
+                       (const double*)lpart, U, chunks, nb, D, K, Dp, loss, grad);
+    return check_launch("ovr_logreg_u8_reduce_kernel");
+}
+
+int cslgan_ovr_logreg_proba_u8(const void* Xtest, const float* U, int64_t M, int D, int K, float* P, void* stream) {
+    CSLGAN_REQUIRE(Xtest && U && P, "ovr_logreg_proba_u8: null argument");
+    CSLGAN_REQUIRE(K >= 2 && K <= LR_MAX_K, "ovr_logreg_proba_u8: K=%d must lie in 2 .. %d", K, LR_MAX_K);
+    CSLGAN_REQUIRE(D >= 1 && D <= LRB_MAX_D, "ovr_logreg_proba_u8: D=%d must lie in 1 .. %d", D, LRB_MAX_D);
+    CSLGAN_REQUIRE(M >= 1 && M < (1ll << 31), "ovr_logreg_proba_u8: M=%lld out of range", (long long)M);
+    CSLGAN_REQUIRE(aligned16(Xtest), "ovr_logreg_proba_u8: Xtest misaligned (16 bytes)");
+    note_kernel("ovr_logreg_u8_fwd_kernel<proba>");
+    const auto fwd = D % 16 == 0 ? ovr_logreg_u8_fwd_kernel<true, true> : ovr_logreg_u8_fwd_kernel<true, false>;
+    hipLaunchKernelGGL(fwd, dim3((unsigned)lrb_fwd_blocks(M)), dim3(LR_THREADS), 0, (hipStream_t)stream, (const unsigned char*)Xtest, (const int*)nullptr, U, (long long)M, D, K, (float*)nullptr,
+                       (double*)nullptr, P);
+    return check_launch("ovr_logreg_u8_fwd_kernel");
 }
 
 }  // extern "C"

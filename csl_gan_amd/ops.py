@@ -1532,6 +1532,56 @@ def ovr_logreg_proba(Xtest, U, out=None):
     return out
 
 
+def _chk_bytes(t, name):
+    if not t.is_cuda:
+        raise RuntimeError("%s must be a device tensor (csl_gan_amd.ops has no CPU path)" % name)
+    if t.dtype != torch.uint8 or not t.is_contiguous():
+        raise RuntimeError("%s must be a contiguous uint8 tensor" % name)
+    return t
+
+
+def ovr_logreg_eval_u8(X, labels, U, out_loss=None, out_grad=None, ws=None):
+    """(loss [K], grad [D + 1, K]) of the objectives of ovr_logreg_eval on cache bytes: X [N, D] uint8 with x = byte / 255, any
+    1 <= D <= 65536 (include/cslgan.h "The same estimator on cache BYTES"): two passes over X.  ws: a float32 device tensor of at least
+    ovr_logreg_u8_ws_floats(N, D) entries; allocated when absent.  csl_gan_amd.classify.objective_host_bytes is the host model."""
+    _chk_bytes(X, "X"); _chk(U, "U")
+    N, D, K = _logreg_shapes(X, U, "ovr_logreg_eval_u8")
+    if not labels.is_cuda or labels.dtype != torch.int32 or labels.numel() != N or not labels.is_contiguous():
+        raise RuntimeError("ovr_logreg_eval_u8: labels must be a contiguous int32 device tensor of %d entries" % N)
+    if out_loss is None:
+        out_loss = torch.empty(K, device=X.device, dtype=torch.float32)
+    elif _chk(out_loss, "out_loss").numel() != K:
+        raise RuntimeError("ovr_logreg_eval_u8: out_loss has %d entries, expected %d" % (out_loss.numel(), K))
+    if out_grad is None:
+        out_grad = torch.empty((D + 1, K), device=X.device, dtype=torch.float32)
+    elif _chk(out_grad, "out_grad").numel() != (D + 1) * K:
+        raise RuntimeError("ovr_logreg_eval_u8: out_grad has %d entries, expected %d" % (out_grad.numel(), (D + 1) * K))
+    if ws is None:
+        ws = torch.empty(max(ovr_logreg_u8_ws_floats(N, D), 2), device=X.device, dtype=torch.float32)
+    else:
+        _chk(ws, "ws")
+    check(_lib.lib().cslgan_ovr_logreg_eval_u8(_p(X), _p(labels), _p(U), N, D, K, _p(out_loss), _p(out_grad), _p(ws), ws.numel(), _stream()),
+          "ovr_logreg_eval_u8")
+    return out_loss, out_grad
+
+
+def ovr_logreg_u8_ws_floats(N, D):
+    """Workspace of ovr_logreg_eval_u8 in floats (0: a shape the kernels do not take)."""
+    return int(_lib.lib().cslgan_ovr_logreg_u8_ws_floats(int(N), int(D)))
+
+
+def ovr_logreg_proba_u8(Xtest, U, out=None):
+    """P [M, K] = sigmoid(z) / sum_k sigmoid(z), z = (Xtest / 255) U[:D] + U[D], for uint8 Xtest [M, D] with any 1 <= D <= 65536."""
+    _chk(U, "U"); _chk_bytes(Xtest, "Xtest")
+    M, D, K = _logreg_shapes(Xtest, U, "ovr_logreg_proba_u8")
+    if out is None:
+        out = torch.empty((M, K), device=U.device, dtype=torch.float32)
+    elif _chk(out, "out").numel() != M * K:
+        raise RuntimeError("ovr_logreg_proba_u8: out has %d entries, expected %d" % (out.numel(), M * K))
+    check(_lib.lib().cslgan_ovr_logreg_proba_u8(_p(Xtest), _p(U), M, D, K, _p(out), _stream()), "ovr_logreg_proba_u8")
+    return out
+
+
 def nn_padded_dim(D):
     """Row pitch of the prepared operands of nn_min: D rounded up to the kernel's K tile (0: a D outside 1 .. 65536)."""
     return int(_lib.lib().cslgan_nn_padded_dim(int(D)))

@@ -1,0 +1,135 @@
+"""Are the samples any use?  `python -m csl_gan_amd.tstr --syn_cache out/syn [more ...] --test_cache out/test
+[--train_cache out/train --baseline] [-d cuda:0] [--gtol_rel G] [--max_iter 2000] [--values_dir DIR]
+[--save --outputs_dir outputs/ --name tstr]`.
+
+Train on synthetic, test on real: per labelled synthetic cache (what `gensamples --cache` of a conditional generator
+wrote: images and the labels `index mod n_classes`) a one-vs-rest logistic regression (csl_gan_amd.classify.OvrLogReg.fit_bytes) is
+fitted on the cache BYTES / 255 and scores the real test cache: micro and per-class AUROC (exact rank counts), accuracy with its
+integer numerator, the solver's report.  K = 1 + the largest synthetic label.  The utility figure of `downstream`, for any dataset
+whose rows are at most 65536 bytes — CelebA with `--label_attr Male` (K = 2) included.  --baseline fits on --train_cache instead and
+reports it as `baseline_train`: the real-data line that puts the synthetic figures in context.  The test cache goes to the device
+once, for all fits.  --values_dir keeps P (test probabilities) and U (coefficients, intercepts in the last row) per cache as .npy;
+with --save the figures are merged into `<outputs_dir>/<name>.json`.  `-d cpu` runs the host model (float64), the definition the
+device (fp32 kernels on the bytes) is held to.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+from . import classify, pipeline
+from .nearest import _label, _same_geometry
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(description="Train-on-synthetic, test-on-real classifier utility of labelled image caches")
+    ap.add_argument("--syn_cache", type=str, nargs="+", required=True, help="labelled uint8 image cache(s) of synthetic samples")
+    ap.add_argument("--test_cache", type=str, required=True, help="labelled uint8 image cache of real test images")
+    ap.add_argument("--train_cache", type=str, default=None, help="labelled uint8 image cache of the training set (for --baseline)")
+    ap.add_argument("--baseline", default=False, action="store_true", help="also fit on the training set itself")
+    ap.add_argument("-d", "--device", type=str, default="cpu")
+    ap.add_argument("--gtol_rel", type=float, default=None, help="a class has converged when max|gradient| <= gtol_rel * n")
+    ap.add_argument("--max_iter", type=int, default=2000, help="L-BFGS iterations per class")
+    ap.add_argument("--values_dir", type=str, default=None, help="keep the test probabilities and the coefficients as .npy here")
+    ap.add_argument("--outputs_dir", type=str, default="outputs/")
+    ap.add_argument("--name", type=str, default="tstr")
+    ap.add_argument("--save", default=False, action="store_true", help="merge the figures into <outputs_dir>/<name>.json")
+    return ap
+
+
+def cache_rows(cache):
+    """(bytes [n, H*W*C] uint8, a copy in memory; labels [n] int64)."""
+    return np.array(cache.x, dtype=np.uint8).reshape(len(cache), -1), np.asarray(cache.labels, dtype=np.int64).reshape(-1)
+
+
+def n_classes_of(labels, path):
+    """K = 1 + the largest label, refused outside 2 .. 16 and when a class of 0 .. K-1 has no row."""
+    if len(labels) < 1 or int(labels.min()) < 0:
+        raise SystemExit("%s: needs rows with labels >= 0" % path)
+    K = 1 + int(labels.max())
+    if not 2 <= K <= classify.MAX_CLASSES:
+        raise SystemExit("%s: labels 0 .. %d give K = %d classes; the classifier takes 2 .. %d (an unconditional generator leaves an "
+                         "unlabelled or single-class cache: train one with -cond)" % (path, K - 1, K, classify.MAX_CLASSES))
+    counts = np.bincount(labels, minlength=K)
+    if (counts == 0).any():
+        raise SystemExit("%s: every class 0 .. %d needs a row; counts: %s" % (path, K - 1, counts.tolist()))
+    return K
+
+
+def fit_and_score(train_x, train_y, K, test_x, test_y, device, gtol_rel=None, max_iter=2000):
+    """One fit on bytes train_x [n, D] (numpy) and its figures on test_x (a uint8 tensor already on `device`): (stats, P, U)."""
+    clf = classify.OvrLogReg(K, gtol_rel=gtol_rel, max_iter=max_iter)
+    X = torch.from_numpy(train_x).to(device)
+    report = clf.fit_bytes(X, torch.from_numpy(train_y))
+    del X
+    P = clf.predict_proba_bytes(test_x)
+    a = classify.auroc(P, test_y)
+    acc = classify.accuracy(P, test_y)
+    stats = {"n_train": int(len(train_y)), "n_test": int(len(test_y)), "classes": int(K), "auroc_micro": a["micro"],
+             "auroc_per_class": a["per_class"], "accuracy": acc["accuracy"], "accuracy_hits": acc["hits"], "solver": report}
+    return stats, P.cpu().numpy(), clf.coef.cpu().numpy()
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
+    if a.baseline and not a.train_cache:
+        raise SystemExit("--baseline fits on the training set: give --train_cache")
+    test = pipeline.CachedImages(a.test_cache)
+    sets = [(_label(p), p, pipeline.CachedImages(p)) for p in a.syn_cache]
+    if len({lab for lab, _, _ in sets}) != len(sets):
+        raise SystemExit("two --syn_cache share the name %s" % ", ".join(sorted(lab for lab, _, _ in sets)))
+    if a.baseline:
+        sets.append(("baseline_train", a.train_cache, pipeline.CachedImages(a.train_cache)))
+    for _, p, c in sets:
+        _same_geometry(test, a.test_cache, c, p)
+    D = test.H * test.W * test.C
+    if not 1 <= D <= 65536:
+        raise SystemExit("%s: rows of %d bytes; the classifier takes 1 .. 65536" % (a.test_cache, D))
+    test_bytes, test_y = cache_rows(test)
+    if len(test_y) < 1:
+        raise SystemExit("%s holds no image" % a.test_cache)
+    classes = {}
+    for lab, p, c in sets:
+        K = classes[lab] = n_classes_of(np.asarray(c.labels, dtype=np.int64).reshape(-1), p)
+        if int(test_y.min()) < 0 or int(test_y.max()) >= K:
+            raise SystemExit("%s: test labels span %d .. %d; %s has the classes 0 .. %d" % (a.test_cache, int(test_y.min()), int(test_y.max()), p, K - 1))
+
+    device = torch.device(a.device)
+    test_x = torch.from_numpy(test_bytes).to(device)       # once, for all fits
+    test_yt = torch.from_numpy(test_y)
+    stats, values = {}, {}
+    for lab, _, c in sets:
+        x, y = cache_rows(c)
+        m, P, U = fit_and_score(x, y, classes[lab], test_x, test_yt, device, a.gtol_rel, a.max_iter)
+        stats[lab] = m
+        values[lab + "_P"], values[lab + "_U"] = P, U
+        s = m["solver"]
+        print("%s: fitted on %d rows, scored %d: AUROC %.6f, accuracy %.4f (%d / %d)" % (
+            lab, m["n_train"], m["n_test"], m["auroc_micro"], m["accuracy"], m["accuracy_hits"], m["n_test"]))
+        print("   per class: %s" % " ".join("%.4f" % v for v in m["auroc_per_class"]))
+        print("   solver: iterations %s  evaluations %s  max|g| %.3g (stop at %.3g)  stalled %s" % (
+            s["iterations"], s["evaluations"], max(s["grad_norm"]), s["gtol"], [k for k, v in enumerate(s["stalled"]) if v] or "none"))
+    if a.values_dir:
+        os.makedirs(a.values_dir, exist_ok=True)
+        for name, arr in values.items():
+            np.save(os.path.join(a.values_dir, name + ".npy"), arr)
+    print(json.dumps(stats, indent=4))
+    if a.save:
+        os.makedirs(a.outputs_dir, exist_ok=True)
+        json_path = os.path.join(a.outputs_dir, a.name + ".json")
+        merged = {}
+        if os.path.exists(json_path):
+            with open(json_path) as f:
+                merged = json.load(f)
+        merged.update(stats)
+        with open(json_path, "w") as f:
+            json.dump(merged, f)
+        print("saved %s" % json_path)
+    return stats
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

@@ -593,6 +593,24 @@ int cslgan_ovr_logreg_eval_f32(const float* X, const int32_t* labels, const floa
  * Xtest: [M, D] fp32 (is_u8 = 0), or [M, D] bytes (is_u8 = 1) that become floats times 1/255 in the load (:106). */
 int cslgan_ovr_logreg_proba_f32(const void* Xtest, int is_u8, const float* U, int64_t M, int D, int K, float* P, void* stream);
 
+/* The same estimator on cache BYTES, for any row size (csl_gan_amd.tstr; backward-compatible additions, ABI stays 7).
+ * The objective, U, loss, grad and P are those above with x_id = byte_id / 255, whatever scale the cache header records:
+ *     z_ik = (sum_{d < D} byte_id U[d][k]) / 255 + U[D][k]
+ * X / Xtest: uint8 [N, D] row-major, base 16-byte aligned, 1 <= D <= 65536 (as in the nearest-neighbour audit); D need not be a
+ * multiple of 4 or 16 — rows are then unaligned and are assembled from aligned 16-byte words; no byte beyond X + N D is read.
+ * 2 <= K <= 16, 1 <= N, M < 2^31; labels outside 0 .. K-1 belong to no class.  A 16-row tile of such rows does not fit in LDS, so
+ * cslgan_ovr_logreg_eval_u8 makes two passes over X: a forward pass (Z = X U, the loss terms, the residuals R = sigmoid(Z) - T
+ * [N, 16] into the workspace, the intercept gradient) and a gradient pass (G = X^T R, one partial [256, 16] per workgroup), then a
+ * reduction of the partials in index order in double.  Both products run on the exact fp32 matrix instruction with the bytes as
+ * the exact floats 0 .. 255 and 1 / 255 applied once to each sum; softplus and sigmoid are the stable forms (finite for every
+ * finite z).  All entries validate on the host before any launch, never allocate and never synchronise; no atomics, no memset:
+ * two calls on the same inputs return the same bits.  ws: caller workspace of cslgan_ovr_logreg_u8_ws_floats(N, D) floats (0 for
+ * sizes the evaluation refuses), 8-byte aligned.  csl_gan_amd.classify.objective_host_bytes is the host model. */
+int64_t cslgan_ovr_logreg_u8_ws_floats(int64_t N, int D);
+int cslgan_ovr_logreg_eval_u8(const void* X, const int32_t* labels, const float* U, int64_t N, int D, int K, float* loss, float* grad,
+                              float* ws, int64_t ws_floats, void* stream);
+int cslgan_ovr_logreg_proba_u8(const void* Xtest, const float* U, int64_t M, int D, int K, float* P, void* stream);
+
 /* ---- Nearest-neighbour audit (nn_kernels.hip; backward-compatible additions, ABI stays 7) -----------------------------------------
  * Exact nearest neighbour of every row of Q [nq, D] among the rows of R [nr, D], both uint8, D = H W C with 1 <= D <= 65536
  * (so 255^2 D < 2^32):
