@@ -35,6 +35,7 @@ EXPORTS = [
     "cslgan_attack_trials", "cslgan_rank_counts", "cslgan_softmax_max_rows_f32",
     "cslgan_ovr_logreg_ws_floats", "cslgan_ovr_logreg_eval_f32", "cslgan_ovr_logreg_proba_f32",
     "cslgan_ovr_logreg_u8_ws_floats", "cslgan_ovr_logreg_eval_u8", "cslgan_ovr_logreg_proba_u8",
+    "cslgan_ovr_mlp_u8_ws_floats", "cslgan_ovr_mlp_eval_u8", "cslgan_ovr_mlp_proba_u8",
     "cslgan_nn_padded_dim", "cslgan_nn_prepare_u8", "cslgan_nn_min_i8", "cslgan_nn_count_i8",
     "cslgan_nn_kth_workspace_bytes", "cslgan_nn_kth_i8", "cslgan_nn_count_radius_i8",
 ]
@@ -160,6 +161,8 @@ def lib():
         "cslgan_ovr_logreg_proba_f32": [vp, i32, vp, i64, i32, i32, vp, vp],
         "cslgan_ovr_logreg_eval_u8": [vp, vp, vp, i64, i32, i32, vp, vp, vp, i64, vp],
         "cslgan_ovr_logreg_proba_u8": [vp, vp, i64, i32, i32, vp, vp],
+        "cslgan_ovr_mlp_eval_u8": [vp, vp, vp, i64, i32, i32, i32, f32, vp, vp, vp, vp],
+        "cslgan_ovr_mlp_proba_u8": [vp, vp, i64, i32, i32, i32, vp, vp],
         "cslgan_nn_padded_dim": [i32],
         "cslgan_nn_prepare_u8": [vp, i64, i32, i32, vp, vp, vp],
         "cslgan_nn_min_i8": [vp, vp, i64, vp, vp, i64, i32, i64, vp, vp],
@@ -177,6 +180,8 @@ def lib():
     L.cslgan_ovr_logreg_ws_floats.restype = C.c_int64
     L.cslgan_ovr_logreg_u8_ws_floats.argtypes = [i64, i32]
     L.cslgan_ovr_logreg_u8_ws_floats.restype = C.c_int64
+    L.cslgan_ovr_mlp_u8_ws_floats.argtypes = [i64, i32, i32, i32]
+    L.cslgan_ovr_mlp_u8_ws_floats.restype = C.c_int64
     L.cslgan_nn_kth_workspace_bytes.argtypes = [i64, i64, i32]
     L.cslgan_nn_kth_workspace_bytes.restype = C.c_int64
     if L.cslgan_version() != ABI_VERSION:

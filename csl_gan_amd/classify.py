@@ -18,6 +18,10 @@ Every piece has a host path (float64 torch) and a device path (fp32, csrc/logreg
 The `*_bytes` forms (csl_gan_amd.tstr) are the same estimator on uint8 cache rows, x = byte / 255, for any row size
 1 .. 65536: `objective_host_bytes` is THE definition, `OvrLogReg.fit_bytes` / `predict_proba_bytes` run it through
 cslgan_ovr_logreg_eval_u8 / cslgan_ovr_logreg_proba_u8 on a device, and `accuracy` is the argmax hit count.
+
+`OvrMlp` is the reference's second classifier, OneVsRestClassifier(MLPClassifier(alpha=1)) of downstream.py:82, on the
+same byte rows: one hidden ReLU layer per class, `objective_mlp_host_bytes` / `proba_mlp_host_bytes` THE definition, the same
+`lbfgs_columns`, cslgan_ovr_mlp_eval_u8 / cslgan_ovr_mlp_proba_u8 (csrc/mlp_kernels.hip) on a device.
 """
 from __future__ import annotations
 
@@ -33,6 +37,7 @@ MAX_BACKTRACKS = 30
 GTOL_REL_DEVICE = 2e-8             # fp32: max|g_k| <= 2e-8 N.  5e-7 passes the golden test too but leaves 2e-3 in probability on an
                                    # ill-conditioned fit (512 samples of 784 features); DESIGN.md §6f has the runs
 GTOL_REL_HOST = 1e-8               # float64: the model the device is held to
+MAX_HIDDEN = 128                   # hidden units per class of OvrMlp: H K <= 2048 first-layer columns (include/cslgan.h)
 
 
 def _check_classes(n_classes):
@@ -95,6 +100,72 @@ def proba_host_bytes(Xu8, U, block=2048):
     block = max(1, int(block))
     for r0 in range(0, X.shape[0], block):
         S = torch.sigmoid((X[r0:r0 + block].double() / 255.0) @ U[:-1] + U[-1])
+        out[r0:r0 + block] = S / S.sum(1, keepdim=True)
+    return out
+
+
+def _mlp_split(U, D, H):
+    """(W1 [D, C], b1 [C], w2 [C], b2 [K]) views of U [(D + 2) H + 1, K], C = H K with column c = h K + k."""
+    K = U.shape[1]
+    if U.dim() != 2 or H < 1 or U.shape[0] != (D + 2) * H + 1:
+        raise ValueError("need U [(D + 2) H + 1, K] with D = %d, H = %d, got %s" % (D, H, tuple(U.shape)))
+    C = H * K
+    return U[:D * H].reshape(D, C), U[D * H:(D + 1) * H].reshape(C), U[(D + 1) * H:(D + 2) * H].reshape(C), U[-1]
+
+
+def objective_mlp_host_bytes(Xu8, labels, U, hidden, alpha=1.0, block=2048):
+    """(loss [K], grad like U) of K one-vs-rest networks with `hidden` ReLU units each on byte features x = byte / 255, float64
+    torch on the CPU, in row blocks of `block` — THE definition of csl_gan_amd.classify.OvrMlp.
+
+    U [(D + 2) H + 1, K]: row d H + h is W1[d][h], rows D H + h are b1, rows (D + 1) H + h are w2, the last row is b2; a column is
+    one class.  Z1 = (bytes W1) / 255 + b1 (the bytes enter as the integers 0 .. 255 and 1 / 255 is applied once to each sum, so a sum
+    that is exactly zero stays exactly zero), A = max(Z1, 0), z = sum_h A w2 + b2, t = [label == k] (labels outside 0 .. K-1
+    belong to no class), s = 2 t - 1,
+        f_k = sum_i log(1 + exp(-s z)) + (alpha / 2) (||W1_k||^2 + ||w2_k||^2)
+    — N times scikit-learn's MLPClassifier loss on a binary target, intercepts unpenalised.  R = sigmoid(z) - T,
+    dZ1 = [Z1 > 0] w2 R (the derivative at exactly 0 is 0), dW1 = X^T dZ1 + alpha W1, db1 = sum_i dZ1, dw2 = sum_i A R + alpha w2,
+    db2 = sum_i R."""
+    X, U = _bytes_rows(Xu8).cpu(), torch.as_tensor(U).double().cpu()
+    y = torch.as_tensor(labels).long().reshape(-1).cpu()
+    N, D = X.shape
+    H, K, alpha = int(hidden), U.shape[1], float(alpha)
+    W1, b1, w2, b2 = _mlp_split(U, D, H)
+    C = H * K
+    block = max(1, int(block))
+    cls = torch.arange(K)[None, :]
+    loss = 0.5 * alpha * ((W1 ** 2).reshape(D * H, K).sum(0) + (w2 ** 2).reshape(H, K).sum(0))
+    G1 = torch.zeros((D, C), dtype=torch.float64)
+    gb1, gw2 = torch.zeros(C, dtype=torch.float64), torch.zeros(C, dtype=torch.float64)
+    gb2 = torch.zeros(K, dtype=torch.float64)
+    for r0 in range(0, N, block):
+        Xb = X[r0:r0 + block].double()                                    # the integers 0 .. 255
+        T = (y[r0:r0 + block, None] == cls).double()
+        Z1 = (Xb @ W1) / 255.0 + b1
+        A = torch.clamp(Z1, min=0)
+        Z = (A * w2).reshape(-1, H, K).sum(1) + b2
+        sz = (2 * T - 1) * Z
+        loss = loss + (torch.clamp(-sz, min=0) + torch.log1p(torch.exp(-sz.abs()))).sum(0)
+        R = torch.sigmoid(Z) - T
+        Rc = R.repeat(1, H)                                               # [n, C]: column c = h K + k holds R[:, k]
+        dZ1 = (Z1 > 0).double() * w2 * Rc
+        G1 += Xb.t() @ dZ1
+        gb1 += dZ1.sum(0)
+        gw2 += (A * Rc).sum(0)
+        gb2 += R.sum(0)
+    grad = torch.cat([(G1 / 255.0 + alpha * W1).reshape(D * H, K), gb1.reshape(H, K), (gw2 + alpha * w2).reshape(H, K), gb2[None, :]], 0)
+    return loss, grad
+
+
+def proba_mlp_host_bytes(Xu8, U, hidden, block=2048):
+    """P [M, K] in float64 of uint8 rows under the networks of objective_mlp_host_bytes: sigmoid(z) / sum_k sigmoid(z), in row blocks."""
+    X, U = _bytes_rows(Xu8).cpu(), torch.as_tensor(U).double().cpu()
+    H, K = int(hidden), U.shape[1]
+    W1, b1, w2, b2 = _mlp_split(U, X.shape[1], H)
+    out = torch.empty((X.shape[0], K), dtype=torch.float64)
+    block = max(1, int(block))
+    for r0 in range(0, X.shape[0], block):
+        A = torch.clamp((X[r0:r0 + block].double() @ W1) / 255.0 + b1, min=0)
+        S = torch.sigmoid((A * w2).reshape(-1, H, K).sum(1) + b2)
         out[r0:r0 + block] = S / S.sum(1, keepdim=True)
     return out
 
@@ -208,6 +279,15 @@ def lbfgs_columns(evaluate, U0, n_rows, gtol_rel, max_iter, memory=MEMORY):
     return U, report
 
 
+def _check_rows(K, X, y):
+    """What a fit on rows refuses: shapes that do not match, and a class of 0 .. K-1 without a training sample."""
+    if X.dim() != 2 or y.numel() != X.shape[0]:
+        raise ValueError("need X [N, D] and y [N], got %s and %s" % (tuple(X.shape), tuple(y.shape)))
+    counts = np.bincount(y.detach().cpu().numpy().astype(np.int64).reshape(-1), minlength=K)
+    if len(counts) > K or (counts[:K] == 0).any():
+        raise ValueError("every class 0 .. %d needs a training sample; counts: %s" % (K - 1, counts.tolist()))
+
+
 class OvrLogReg:
     """`OvrLogReg(n_classes).fit(X, y)` then `.predict_proba(Xtest)`.
 
@@ -251,11 +331,7 @@ class OvrLogReg:
         return rep
 
     def _check_fit(self, X, y):
-        if X.dim() != 2 or y.numel() != X.shape[0]:
-            raise ValueError("need X [N, D] and y [N], got %s and %s" % (tuple(X.shape), tuple(y.shape)))
-        counts = np.bincount(y.detach().cpu().numpy().astype(np.int64).reshape(-1), minlength=self.K)
-        if len(counts) > self.K or (counts[:self.K] == 0).any():
-            raise ValueError("every class 0 .. %d needs a training sample; counts: %s" % (self.K - 1, counts.tolist()))
+        _check_rows(self.K, X, y)
 
     def fit_bytes(self, Xu8, y):
         """fit on uint8 rows [N, D] with x = byte / 255, any D in 1 .. 65536.  On a HIP device the rows stay bytes and every
@@ -306,6 +382,77 @@ class OvrLogReg:
                 Xt = Xtest.contiguous() if Xtest.dtype == torch.uint8 else Xtest.float().contiguous()
                 return ops.ovr_logreg_proba(Xt, self.coef.to(Xtest.device, torch.float32).contiguous())
         return proba_host(Xtest, self.coef.cpu())
+
+
+class OvrMlp:
+    """`OvrMlp(n_classes, hidden).fit_bytes(Xu8, y)` then `.predict_proba_bytes(Xu8)`: OneVsRestClassifier(MLPClassifier(alpha=1)) of
+    downstream.py:82 on uint8 rows with x = byte / 255 — per class one hidden layer of `hidden` ReLU units (1 .. 128) and the
+    objective of objective_mlp_host_bytes, minimised by lbfgs_columns (max_iter 200 is scikit-learn's default).  The objective is
+    not convex: the fit is a local minimiser that depends on the initial point, which depends on `seed` alone.
+
+    Initial point, as scikit-learn's Glorot-uniform with the intercepts at zero: ONE draw of (D hidden + hidden) K float64 uniforms
+    from torch.Generator().manual_seed(seed) on the host, taken in the row-major order of U's rows — the D hidden rows of W1, then
+    the `hidden` rows of w2 (the b1 rows between them and the b2 row stay zero) — and mapped to (2 u - 1) bound with
+    bound = sqrt(6 / (D + hidden)) for W1 and sqrt(6 / (hidden + 1)) for w2.  Both paths start from these numbers (the device from
+    their float32 rounding).
+
+    Rows on a HIP device select the device path (fp32, one ops.ovr_mlp_eval_u8 call per trial point); anything else the host path
+    (float64).  `coef` is U [(D + 2) hidden + 1, K], `report` the solver's report."""
+
+    def __init__(self, n_classes, hidden=100, alpha=1.0, seed=0, gtol_rel=None, max_iter=200):
+        self.K = _check_classes(n_classes)
+        self.H, self.alpha, self.seed = int(hidden), float(alpha), int(seed)
+        if not 1 <= self.H <= MAX_HIDDEN:
+            raise ValueError("hidden must lie in 1 .. %d, got %d" % (MAX_HIDDEN, self.H))
+        if not 0 <= self.alpha < float("inf"):
+            raise ValueError("alpha must be a finite number >= 0, got %r" % (alpha,))
+        self.gtol_rel, self.max_iter = gtol_rel, int(max_iter)
+        self.coef, self.report = None, None
+
+    def initial_point(self, D):
+        """U0 [(D + 2) hidden + 1, K] in float64 on the host (the class docstring has the order of the draw)."""
+        H, K = self.H, self.K
+        g = torch.Generator().manual_seed(self.seed)
+        u = 2.0 * torch.rand(((D + 1) * H, K), dtype=torch.float64, generator=g) - 1.0
+        U0 = torch.zeros(((D + 2) * H + 1, K), dtype=torch.float64)
+        U0[:D * H] = u[:D * H] * float(np.sqrt(6.0 / (D + H)))
+        U0[(D + 1) * H:(D + 2) * H] = u[D * H:] * float(np.sqrt(6.0 / (H + 1)))
+        return U0
+
+    def fit_bytes(self, Xu8, y):
+        X = _bytes_rows(Xu8)
+        y = torch.as_tensor(y)
+        _check_rows(self.K, X, y)
+        N, D = X.shape
+        U0 = self.initial_point(D)
+        if X.is_cuda:
+            from . import ops
+            with torch.cuda.device(X.device):
+                Xd = X.contiguous()
+                yd = y.to(X.device).reshape(-1).to(torch.int32).contiguous()
+                ws = torch.empty(ops.ovr_mlp_u8_ws_floats(N, D, self.K, self.H), device=X.device, dtype=torch.float32)
+                ev = lambda U: ops.ovr_mlp_eval_u8(Xd, yd, U.contiguous(), self.H, self.alpha, ws=ws)
+                gtol_rel = GTOL_REL_DEVICE if self.gtol_rel is None else self.gtol_rel
+                U, rep = lbfgs_columns(ev, U0.to(X.device, torch.float32), N, gtol_rel, self.max_iter)
+        else:
+            yh = y.long().reshape(-1)
+            ev = lambda U: objective_mlp_host_bytes(X, yh, U, self.H, self.alpha)
+            gtol_rel = GTOL_REL_HOST if self.gtol_rel is None else self.gtol_rel
+            U, rep = lbfgs_columns(ev, U0, N, gtol_rel, self.max_iter)
+        rep["gtol_rel"] = float(gtol_rel)
+        self.coef, self.report = U, rep
+        return rep
+
+    def predict_proba_bytes(self, Xu8):
+        """P [M, K]: ops.ovr_mlp_proba_u8 on a device (float32), proba_mlp_host_bytes on the host (float64)."""
+        if self.coef is None:
+            raise RuntimeError("fit first")
+        X = _bytes_rows(Xu8)
+        if X.is_cuda:
+            from . import ops
+            with torch.cuda.device(X.device):
+                return ops.ovr_mlp_proba_u8(X.contiguous(), self.coef.to(X.device, torch.float32).contiguous(), self.H)
+        return proba_mlp_host_bytes(X, self.coef.cpu(), self.H)
 
 
 def _auc(pos, neg):

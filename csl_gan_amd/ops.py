@@ -1582,6 +1582,61 @@ def ovr_logreg_proba_u8(Xtest, U, out=None):
     return out
 
 
+def _mlp_shapes(X, U, hidden, what):
+    H = int(hidden)
+    if X.dim() != 2 or U.dim() != 2 or H < 1 or U.shape[0] != (X.shape[1] + 2) * H + 1:
+        raise RuntimeError("%s: need X [N, D] and U [(D + 2) hidden + 1, K] with hidden >= 1, got %s, %s and hidden = %d" % (
+            what, tuple(X.shape), tuple(U.shape), H))
+    return X.shape[0], X.shape[1], U.shape[1], H
+
+
+def ovr_mlp_u8_ws_floats(N, D, K, hidden):
+    """Workspace of ovr_mlp_eval_u8 in floats (0: a shape the kernels do not take)."""
+    return int(_lib.lib().cslgan_ovr_mlp_u8_ws_floats(int(N), int(D), int(K), int(hidden)))
+
+
+def ovr_mlp_eval_u8(X, labels, U, hidden, alpha=1.0, out_loss=None, out_grad=None, ws=None):
+    """(loss [K], grad like U) of the K one-vs-rest MLP objectives of include/cslgan.h "One-vs-rest MLP on cache bytes" at
+    U [(D + 2) hidden + 1, K] on X [N, D] uint8 with x = byte / 255 and int32 labels [N].  ws: a float32 device tensor of exactly
+    ovr_mlp_u8_ws_floats(N, D, K, hidden) entries (an optimiser keeps one across its evaluations); allocated when absent.
+    csl_gan_amd.classify.objective_mlp_host_bytes is the host model."""
+    _chk_bytes(X, "X"); _chk(U, "U")
+    N, D, K, H = _mlp_shapes(X, U, hidden, "ovr_mlp_eval_u8")
+    if not labels.is_cuda or labels.dtype != torch.int32 or labels.numel() != N or not labels.is_contiguous():
+        raise RuntimeError("ovr_mlp_eval_u8: labels must be a contiguous int32 device tensor of %d entries" % N)
+    if out_loss is None:
+        out_loss = torch.empty(K, device=X.device, dtype=torch.float32)
+    elif _chk(out_loss, "out_loss").numel() != K:
+        raise RuntimeError("ovr_mlp_eval_u8: out_loss has %d entries, expected %d" % (out_loss.numel(), K))
+    if out_grad is None:
+        out_grad = torch.empty_like(U)
+    elif _chk(out_grad, "out_grad").numel() != U.numel():
+        raise RuntimeError("ovr_mlp_eval_u8: out_grad has %d entries, expected %d" % (out_grad.numel(), U.numel()))
+    need = ovr_mlp_u8_ws_floats(N, D, K, H)
+    if need == 0:
+        raise RuntimeError("ovr_mlp_eval_u8: N = %d, D = %d, K = %d, hidden = %d is outside 1 <= N < 2^31, 1 <= D <= 65536, 2 <= K <= 16, "
+                           "1 <= hidden <= 128" % (N, D, K, H))
+    if ws is None:
+        ws = torch.empty(need, device=X.device, dtype=torch.float32)
+    elif _chk(ws, "ws").numel() != need:                # the entry takes no size: the wrapper is where a wrong one can be told
+        raise RuntimeError("ovr_mlp_eval_u8: workspace of %d floats, need %d" % (ws.numel(), need))
+    check(_lib.lib().cslgan_ovr_mlp_eval_u8(_p(X), _p(labels), _p(U), N, D, K, H, float(alpha), _p(out_loss), _p(out_grad), _p(ws), _stream()),
+          "ovr_mlp_eval_u8")
+    return out_loss, out_grad
+
+
+def ovr_mlp_proba_u8(Xtest, U, hidden, out=None):
+    """P [M, K] = sigmoid(z) / sum_k sigmoid(z) of the K networks of ovr_mlp_eval_u8 on uint8 Xtest [M, D]."""
+    _chk(U, "U"); _chk_bytes(Xtest, "Xtest")
+    M, D, K, H = _mlp_shapes(Xtest, U, hidden, "ovr_mlp_proba_u8")
+    if out is None:
+        out = torch.empty((M, K), device=U.device, dtype=torch.float32)
+    elif _chk(out, "out").numel() != M * K:
+        raise RuntimeError("ovr_mlp_proba_u8: out has %d entries, expected %d" % (out.numel(), M * K))
+    check(_lib.lib().cslgan_ovr_mlp_proba_u8(_p(Xtest), _p(U), M, D, K, H, _p(out), _stream()), "ovr_mlp_proba_u8")
+    return out
+
+
 def nn_padded_dim(D):
     """Row pitch of the prepared operands of nn_min: D rounded up to the kernel's K tile (0: a D outside 1 .. 65536)."""
     return int(_lib.lib().cslgan_nn_padded_dim(int(D)))

@@ -1,6 +1,6 @@
 """Are the samples any use?  `python -m csl_gan_amd.tstr --syn_cache out/syn [more ...] --test_cache out/test
 [--train_cache out/train --baseline] [-d cuda:0] [--gtol_rel G] [--max_iter 2000] [--values_dir DIR]
-[--save --outputs_dir outputs/ --name tstr]`.
+[--classifier {lr,mlp} --hidden 100 --alpha 1.0 --seed 0] [--save --outputs_dir outputs/ --name tstr]`.
 
 Train on synthetic, test on real: per labelled synthetic cache (what `gensamples --cache` of a conditional generator
 wrote: images and the labels `index mod n_classes`) a one-vs-rest logistic regression (csl_gan_amd.classify.OvrLogReg.fit_bytes) is
@@ -11,6 +11,10 @@ reports it as `baseline_train`: the real-data line that puts the synthetic figur
 once, for all fits.  --values_dir keeps P (test probabilities) and U (coefficients, intercepts in the last row) per cache as .npy;
 with --save the figures are merged into `<outputs_dir>/<name>.json`.  `-d cpu` runs the host model (float64), the definition the
 device (fp32 kernels on the bytes) is held to.
+
+--classifier mlp fits the reference's other classifier instead, a one-vs-rest MLP with --hidden ReLU units per class
+and L2 penalty --alpha (csl_gan_amd.classify.OvrMlp, started from --seed; --max_iter then defaults to 200): the figures carry
+"classifier", "hidden", "alpha" and "seed" as well, and U is kept in OvrMlp's layout [(D + 2) hidden + 1, K].
 """
 import argparse
 import json
@@ -32,7 +36,11 @@ def build_parser():
     ap.add_argument("--baseline", default=False, action="store_true", help="also fit on the training set itself")
     ap.add_argument("-d", "--device", type=str, default="cpu")
     ap.add_argument("--gtol_rel", type=float, default=None, help="a class has converged when max|gradient| <= gtol_rel * n")
-    ap.add_argument("--max_iter", type=int, default=2000, help="L-BFGS iterations per class")
+    ap.add_argument("--max_iter", type=int, default=None, help="L-BFGS iterations per class (default: 2000 for lr, 200 for mlp)")
+    ap.add_argument("--classifier", type=str, default="lr", choices=["lr", "mlp"], help="one-vs-rest logistic regression or MLP")
+    ap.add_argument("--hidden", type=int, default=100, help="mlp: hidden ReLU units per class, 1 .. %d" % classify.MAX_HIDDEN)
+    ap.add_argument("--alpha", type=float, default=1.0, help="mlp: L2 penalty on the weights, >= 0")
+    ap.add_argument("--seed", type=int, default=0, help="mlp: seed of the initial point")
     ap.add_argument("--values_dir", type=str, default=None, help="keep the test probabilities and the coefficients as .npy here")
     ap.add_argument("--outputs_dir", type=str, default="outputs/")
     ap.add_argument("--name", type=str, default="tstr")
@@ -59,9 +67,13 @@ def n_classes_of(labels, path):
     return K
 
 
-def fit_and_score(train_x, train_y, K, test_x, test_y, device, gtol_rel=None, max_iter=2000):
-    """One fit on bytes train_x [n, D] (numpy) and its figures on test_x (a uint8 tensor already on `device`): (stats, P, U)."""
-    clf = classify.OvrLogReg(K, gtol_rel=gtol_rel, max_iter=max_iter)
+def fit_and_score(train_x, train_y, K, test_x, test_y, device, gtol_rel=None, max_iter=2000, mlp=None):
+    """One fit on bytes train_x [n, D] (numpy) and its figures on test_x (a uint8 tensor already on `device`): (stats, P, U).
+    mlp: None for the logistic regression, or {"hidden", "alpha", "seed"} for classify.OvrMlp — then part of the stats."""
+    if mlp is None:
+        clf = classify.OvrLogReg(K, gtol_rel=gtol_rel, max_iter=max_iter)
+    else:
+        clf = classify.OvrMlp(K, gtol_rel=gtol_rel, max_iter=max_iter, **mlp)
     X = torch.from_numpy(train_x).to(device)
     report = clf.fit_bytes(X, torch.from_numpy(train_y))
     del X
@@ -70,6 +82,8 @@ def fit_and_score(train_x, train_y, K, test_x, test_y, device, gtol_rel=None, ma
     acc = classify.accuracy(P, test_y)
     stats = {"n_train": int(len(train_y)), "n_test": int(len(test_y)), "classes": int(K), "auroc_micro": a["micro"],
              "auroc_per_class": a["per_class"], "accuracy": acc["accuracy"], "accuracy_hits": acc["hits"], "solver": report}
+    if mlp is not None:
+        stats.update({"classifier": "mlp", "hidden": int(mlp["hidden"]), "alpha": float(mlp["alpha"]), "seed": int(mlp["seed"])})
     return stats, P.cpu().numpy(), clf.coef.cpu().numpy()
 
 
@@ -77,6 +91,12 @@ def main(argv=None):
     a = build_parser().parse_args(argv)
     if a.baseline and not a.train_cache:
         raise SystemExit("--baseline fits on the training set: give --train_cache")
+    if not 1 <= a.hidden <= classify.MAX_HIDDEN:
+        raise SystemExit("--hidden %d: the MLP takes 1 .. %d hidden units per class" % (a.hidden, classify.MAX_HIDDEN))
+    if not 0 <= a.alpha < float("inf"):
+        raise SystemExit("--alpha %r: the penalty must be a finite number >= 0" % a.alpha)
+    mlp = {"hidden": a.hidden, "alpha": a.alpha, "seed": a.seed} if a.classifier == "mlp" else None
+    max_iter = a.max_iter if a.max_iter is not None else (2000 if mlp is None else 200)
     test = pipeline.CachedImages(a.test_cache)
     sets = [(_label(p), p, pipeline.CachedImages(p)) for p in a.syn_cache]
     if len({lab for lab, _, _ in sets}) != len(sets):
@@ -103,7 +123,7 @@ def main(argv=None):
     stats, values = {}, {}
     for lab, _, c in sets:
         x, y = cache_rows(c)
-        m, P, U = fit_and_score(x, y, classes[lab], test_x, test_yt, device, a.gtol_rel, a.max_iter)
+        m, P, U = fit_and_score(x, y, classes[lab], test_x, test_yt, device, a.gtol_rel, max_iter, mlp)
         stats[lab] = m
         values[lab + "_P"], values[lab + "_U"] = P, U
         s = m["solver"]

@@ -611,6 +611,30 @@ int cslgan_ovr_logreg_eval_u8(const void* X, const int32_t* labels, const float*
                               float* ws, int64_t ws_floats, void* stream);
 int cslgan_ovr_logreg_proba_u8(const void* Xtest, const float* U, int64_t M, int D, int K, float* P, void* stream);
 
+/* ---- One-vs-rest MLP on cache bytes (mlp_kernels.hip; csl_gan_amd.tstr --classifier mlp; backward-compatible additions,
+ * ABI stays 7).  downstream.py:82's OneVsRestClassifier(MLPClassifier(alpha=1)): class k owns a network with H hidden ReLU units on
+ * x_id = byte_id / 255.  U [P, K] row-major, P = (D + 2) H + 1: row d H + h holds W1[d][h], rows D H + h hold b1, rows (D + 1) H + h
+ * hold w2, the last row holds b2 — a column of U is one class.  With t_ik = [labels[i] == k] and s = 2 t - 1
+ *     Z1_ihk = (sum_d byte_id W1[d][h][k]) / 255 + b1[h][k],     A = max(Z1, 0),     z_ik = sum_h A_ihk w2[h][k] + b2[k]
+ *     f_k    = sum_i log(1 + exp(-s_ik z_ik)) + (alpha / 2) (||W1_k||^2 + ||w2_k||^2)                (intercepts unpenalised)
+ * which is N times scikit-learn's MLPClassifier loss on a binary target.  With R = sigmoid(z) - T and dZ1 = [Z1 > 0] w2 R (the
+ * derivative at exactly 0 is 0):  dW1 = X^T dZ1 + alpha W1,  db1 = sum_i dZ1,  dw2 = sum_i A R + alpha w2,  db2 = sum_i R.
+ * X / Xtest: uint8 [N, D] row-major, base 16-byte aligned, 1 <= D <= 65536, rows need not be aligned; no byte beyond X + N D is read.
+ * 2 <= K <= 16, 1 <= H <= 128, 1 <= N, M < 2^31; labels outside 0 .. K-1 belong to no class.
+ *
+ * cslgan_ovr_mlp_eval_u8 — loss[k] = f_k(U), grad [P, K] like U.  A forward pass (Z1 = X W1 tiled 64 x 64 over the H K columns, the
+ * logits, the loss terms, dZ1 [N, H K] into the workspace, per-workgroup partials of the loss, dw2, db1, db2), a gradient pass
+ * (X^T dZ1, one partial per chunk of rows) and a reduction of all partials in index order in double.  Both products run on the exact
+ * fp32 matrix instruction with the bytes as the exact floats 0 .. 255 and 1 / 255 applied once to each sum.  alpha >= 0.  All entries
+ * validate on the host before any launch, never allocate and never synchronise; no atomics, no memset: two calls on the same
+ * inputs return the same bits.  ws: caller workspace of cslgan_ovr_mlp_u8_ws_floats(N, D, K, H) floats (0 for sizes the evaluation
+ * refuses), 8-byte aligned.  cslgan_ovr_mlp_proba_u8 — P[i][k] = sigmoid(z_ik) / sum_k' sigmoid(z_ik') ([M, K] row-major).
+ * csl_gan_amd.classify.objective_mlp_host_bytes / proba_mlp_host_bytes are the host model. */
+int64_t cslgan_ovr_mlp_u8_ws_floats(int64_t N, int D, int K, int H);
+int cslgan_ovr_mlp_eval_u8(const void* X, const int32_t* labels, const float* U, int64_t N, int D, int K, int H, float alpha, float* loss,
+                           float* grad, float* ws, void* stream);
+int cslgan_ovr_mlp_proba_u8(const void* Xtest, const float* U, int64_t M, int D, int K, int H, float* P, void* stream);
+
 /* ---- Nearest-neighbour audit (nn_kernels.hip; backward-compatible additions, ABI stays 7) -----------------------------------------
  * Exact nearest neighbour of every row of Q [nq, D] among the rows of R [nr, D], both uint8, D = H W C with 1 <= D <= 65536
  * (so 255^2 D < 2^32):
