@@ -9,7 +9,7 @@ is an integer function of the cache BYTES under d2 of csl_gan_amd.neighbours, an
     s_mc,p(x)  = #{s in S : d2(x, s) <= eps2_p}                   Monte-Carlo attack of Hilprecht et al. (PoPETs 2019)
 
 eps2_p is element floor(p (n - 1)) of the sorted pooled d2min over train and held-out together — the order-statistic rule of
-neighbours.dcr_metrics, no interpolation, no membership label.  `count_within_host` is THE definition of the counts, and the
+neighbours.dcr_metrics, no interpolation, no membership label.  `neighbours.count_within_host` is THE definition of the counts, and the
 device path (ops.nn_count through NearestSearch.count_within) is held to it by equality.  Scores reach 2^32 and audit's rank
 kernels take float32, so `dense_ranks` maps the pooled scores to their rank among the pooled distinct values first: order and ties
 survive exactly, and audit.attack_metrics turns them into ASR, AUC and TPR at a fixed FPR, the same integers on every device.
@@ -22,48 +22,10 @@ from fractions import Fraction
 import numpy as np
 
 from . import audit, neighbours
-from .neighbours import MAX_D, _rows_u8
+from .neighbours import MAX_THRESHOLD, MAX_THRESHOLDS, check_thresholds, count_within_host  # noqa: F401  (the names stay reachable here)
 
-MAX_THRESHOLDS = 4                      # the counters of a row are the four bytes of one register (csrc/nn_kernels.hip)
-MAX_THRESHOLD = 2 ** 32 - 1
 MAX_DISTINCT = 2 ** 24                  # float32 holds every integer up to here
 DEFAULT_PERCENTILES = (50.0, 10.0, 1.0, 0.1)
-
-
-def check_thresholds(thresholds):
-    """The thresholds as a list of 1 .. 4 Python integers in [0, 2^32 - 1]."""
-    thr = [int(t) for t in np.asarray(thresholds, dtype=object).reshape(-1)]
-    if not 1 <= len(thr) <= MAX_THRESHOLDS:
-        raise ValueError("need 1 .. %d thresholds, got %d" % (MAX_THRESHOLDS, len(thr)))
-    if any(t < 0 or t > MAX_THRESHOLD for t in thr):
-        raise ValueError("thresholds must lie in [0, 2^32 - 1], got %s" % (thr,))
-    return thr
-
-
-def count_within_host(Q, R, thresholds, counts=None, block=1024):
-    """counts[q, j] += #{r : d2(q, r) <= thresholds[j]} as int64 [nq, J] for the rows of Q [nq, ...] and R [nr, ...] (uint8, same row
-    size D, 1 <= D <= 65536) and 1 <= J <= 4 integer thresholds in [0, 2^32 - 1], in any order — THE definition.  `counts` holds
-    the sums of earlier calls (zeros when absent) and is not written.  As in neighbours.nearest_host the shifted bytes go through
-    a float64 matmul in blocks of `block` rows: every d2 is below 2^32, far under 2^53, so the floats are the integers."""
-    Q, R = _rows_u8(Q), _rows_u8(R)
-    nq, D = Q.shape
-    nr = R.shape[0]
-    if R.shape[1] != D or not 1 <= D <= MAX_D:
-        raise ValueError("rows of %d and %d bytes; need equal sizes in 1 .. %d" % (D, R.shape[1], MAX_D))
-    thr = np.array(check_thresholds(thresholds), dtype=np.float64)
-    out = np.zeros((nq, len(thr)), dtype=np.int64) if counts is None else np.array(counts, dtype=np.int64, copy=True)
-    if out.shape != (nq, len(thr)):
-        raise ValueError("counts has shape %s, expected (%d, %d)" % (out.shape, nq, len(thr)))
-    block = max(1, int(block))
-    for r0 in range(0, nr, block):
-        b = np.asarray(R[r0:r0 + block]).astype(np.float64) - 128.0
-        bn = (b * b).sum(1)
-        for q0 in range(0, nq, block):
-            a = np.asarray(Q[q0:q0 + block]).astype(np.float64) - 128.0
-            d2 = (a * a).sum(1)[:, None] + bn[None, :] - 2.0 * (a @ b.T)
-            for j, t in enumerate(thr):
-                out[q0:q0 + block, j] += (d2 <= t).sum(1)
-    return out
 
 
 def epsilon2(d2_pooled, percentiles=DEFAULT_PERCENTILES):
@@ -130,13 +92,9 @@ def sample_attack_metrics(d2_train, d2_heldout, counts_train, counts_heldout, pe
     return out
 
 
-def _search(ref, device, block_rows, resident_gb, query_rows):
-    return neighbours.NearestSearch(device, block_rows=block_rows, resident_gb=resident_gb, query_rows=query_rows).fit(ref)
-
-
 def d2min_to(ref, caches, device="cpu", block_rows=16384, resident_gb=8.0, query_rows=16384):
     """[d2min of every image of c to the images of `ref`, int64, for c in caches]: the reference is fitted once."""
-    s = _search(ref, device, block_rows, resident_gb, query_rows)
+    s = neighbours.fitted_search(ref, device, block_rows, resident_gb, query_rows)
     return [neighbours.split_keys(s.query(c))[0] for c in caches]
 
 
@@ -144,7 +102,7 @@ def run_attack(syn, train, heldout, percentiles=DEFAULT_PERCENTILES, device="cpu
     """The integers of the attack on one synthetic cache (pipeline.CachedImages all): S is fitted once, train and held-out are
     queried for d2min, eps2 comes from the pooled d2min, and one counting walk per side gives the Monte-Carlo scores.  Returns
     dict(d2_train, d2_heldout, eps2, counts_train, counts_heldout)."""
-    s = _search(syn, device, block_rows, resident_gb, query_rows)
+    s = neighbours.fitted_search(syn, device, block_rows, resident_gb, query_rows)
     out = {"d2_train": neighbours.split_keys(s.query(train))[0], "d2_heldout": neighbours.split_keys(s.query(heldout))[0]}
     out["eps2"] = epsilon2(np.concatenate([out["d2_train"], out["d2_heldout"]]), percentiles)
     out["counts_train"], out["counts_heldout"] = s.count_within(train, out["eps2"]), s.count_within(heldout, out["eps2"])

@@ -28,7 +28,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import audit
+from . import audit, ops
 
 MAX_CLASSES = 16                   # the 16 columns of the matrix instruction (include/cslgan.h)
 MEMORY = 10                        # L-BFGS pairs (SciPy's default maxcor, what the reference's solver keeps)
@@ -288,6 +288,49 @@ def _check_rows(K, X, y):
         raise ValueError("every class 0 .. %d needs a training sample; counts: %s" % (K - 1, counts.tolist()))
 
 
+def _fit(est, X, y, host_objective, device_objective, ws_floats, start):
+    """The fit of both estimators on rows X [N, D] and labels y from U0 = start(D), float64 on the host; stores est.coef and
+    est.report and returns the report.  X on a HIP device: fp32 — int32 labels, ONE workspace of ws_floats(N, D) floats for all
+    evaluations, U0 rounded to float32, device_objective(X, labels, U, ws) per trial point, GTOL_REL_DEVICE unless the estimator
+    has its own gtol_rel.  Anything else: float64 — host_objective(X, labels, U) and GTOL_REL_HOST."""
+    y = torch.as_tensor(y)
+    _check_rows(est.K, X, y)
+    N, D = X.shape
+    U0 = start(D)
+    if X.is_cuda:
+        with torch.cuda.device(X.device):
+            yd = y.to(X.device).reshape(-1).to(torch.int32).contiguous()
+            ws = torch.empty(ws_floats(N, D), device=X.device, dtype=torch.float32)
+            ev = lambda U: device_objective(X, yd, U.contiguous(), ws)
+            gtol_rel = GTOL_REL_DEVICE if est.gtol_rel is None else est.gtol_rel
+            U, rep = lbfgs_columns(ev, U0.to(X.device, torch.float32), N, gtol_rel, est.max_iter)
+    else:
+        yh = y.long().reshape(-1)
+        gtol_rel = GTOL_REL_HOST if est.gtol_rel is None else est.gtol_rel
+        U, rep = lbfgs_columns(lambda U: host_objective(X, yh, U), U0, N, gtol_rel, est.max_iter)
+    rep["gtol_rel"] = float(gtol_rel)
+    est.coef, est.report = U, rep
+    return rep
+
+
+def _proba(est, X, host_proba, device_proba):
+    """P [M, K] of a fitted estimator: device_proba(X, its coefficients in fp32 on X's device) for rows on a HIP device,
+    host_proba(X, its coefficients on the host) for anything else."""
+    if est.coef is None:
+        raise RuntimeError("fit first")
+    if X.is_cuda:
+        with torch.cuda.device(X.device):
+            return device_proba(X, est.coef.to(X.device, torch.float32).contiguous())
+    return host_proba(X, est.coef.cpu())
+
+
+def solver_line(report):
+    """The "solver:" line that tstr and downstream print under a fit's figures."""
+    return "   solver: iterations %s  evaluations %s  max|g| %.3g (stop at %.3g)  stalled %s" % (
+        report["iterations"], report["evaluations"], max(report["grad_norm"]), report["gtol"],
+        [k for k, v in enumerate(report["stalled"]) if v] or "none")
+
+
 class OvrLogReg:
     """`OvrLogReg(n_classes).fit(X, y)` then `.predict_proba(Xtest)`.
 
@@ -302,86 +345,30 @@ class OvrLogReg:
         self.gtol_rel, self.max_iter = gtol_rel, int(max_iter)
         self.coef, self.report = None, None
 
+    def _start(self, D):
+        return torch.zeros((D + 1, self.K), dtype=torch.float64)
+
     def fit(self, X, y):
         X = torch.as_tensor(X)
-        y = torch.as_tensor(y)
-        if X.dim() != 2 or y.numel() != X.shape[0]:
-            raise ValueError("need X [N, D] and y [N], got %s and %s" % (tuple(X.shape), tuple(y.shape)))
-        counts = np.bincount(y.detach().cpu().numpy().astype(np.int64).reshape(-1), minlength=self.K)
-        if len(counts) > self.K or (counts[:self.K] == 0).any():
-            raise ValueError("every class 0 .. %d needs a training sample; counts: %s" % (self.K - 1, counts.tolist()))
-        N, D = X.shape
-        if X.is_cuda:
-            from . import ops
-            with torch.cuda.device(X.device):
-                Xd = X.float().contiguous()
-                yd = y.to(X.device).reshape(-1).to(torch.int32).contiguous()
-                ws = torch.empty(max(ops.ovr_logreg_ws_floats(N, D), 2), device=X.device, dtype=torch.float32)
-                U0 = torch.zeros((D + 1, self.K), device=X.device, dtype=torch.float32)
-                ev = lambda U: ops.ovr_logreg_eval(Xd, yd, U.contiguous(), ws=ws)
-                gtol_rel = GTOL_REL_DEVICE if self.gtol_rel is None else self.gtol_rel
-                U, rep = lbfgs_columns(ev, U0, N, gtol_rel, self.max_iter)
-        else:
-            Xh, yh = X.double(), y.long().reshape(-1)
-            ev = lambda U: objective_host(Xh, yh, U)
-            gtol_rel = GTOL_REL_HOST if self.gtol_rel is None else self.gtol_rel
-            U, rep = lbfgs_columns(ev, torch.zeros((D + 1, self.K), dtype=torch.float64), N, gtol_rel, self.max_iter)
-        rep["gtol_rel"] = float(gtol_rel)
-        self.coef, self.report = U, rep
-        return rep
-
-    def _check_fit(self, X, y):
-        _check_rows(self.K, X, y)
+        X = X.float().contiguous() if X.is_cuda else X.double()
+        return _fit(self, X, y, objective_host, lambda X, y, U, ws: ops.ovr_logreg_eval(X, y, U, ws=ws),
+                    lambda N, D: max(ops.ovr_logreg_ws_floats(N, D), 2), self._start)
 
     def fit_bytes(self, Xu8, y):
         """fit on uint8 rows [N, D] with x = byte / 255, any D in 1 .. 65536.  On a HIP device the rows stay bytes and every
         evaluation is one ops.ovr_logreg_eval_u8 call; elsewhere objective_host_bytes.  Same solver, same default gtol_rel per
         path, same report as fit."""
-        X = _bytes_rows(Xu8)
-        y = torch.as_tensor(y)
-        self._check_fit(X, y)
-        N, D = X.shape
-        if X.is_cuda:
-            from . import ops
-            with torch.cuda.device(X.device):
-                Xd = X.contiguous()
-                yd = y.to(X.device).reshape(-1).to(torch.int32).contiguous()
-                ws = torch.empty(max(ops.ovr_logreg_u8_ws_floats(N, D), 2), device=X.device, dtype=torch.float32)
-                U0 = torch.zeros((D + 1, self.K), device=X.device, dtype=torch.float32)
-                ev = lambda U: ops.ovr_logreg_eval_u8(Xd, yd, U.contiguous(), ws=ws)
-                gtol_rel = GTOL_REL_DEVICE if self.gtol_rel is None else self.gtol_rel
-                U, rep = lbfgs_columns(ev, U0, N, gtol_rel, self.max_iter)
-        else:
-            yh = y.long().reshape(-1)
-            ev = lambda U: objective_host_bytes(X, yh, U)
-            gtol_rel = GTOL_REL_HOST if self.gtol_rel is None else self.gtol_rel
-            U, rep = lbfgs_columns(ev, torch.zeros((D + 1, self.K), dtype=torch.float64), N, gtol_rel, self.max_iter)
-        rep["gtol_rel"] = float(gtol_rel)
-        self.coef, self.report = U, rep
-        return rep
+        return _fit(self, _bytes_rows(Xu8).contiguous(), y, objective_host_bytes, lambda X, y, U, ws: ops.ovr_logreg_eval_u8(X, y, U, ws=ws),
+                    lambda N, D: max(ops.ovr_logreg_u8_ws_floats(N, D), 2), self._start)
 
     def predict_proba_bytes(self, Xu8):
         """P [M, K] of uint8 rows, x = byte / 255, any D: ops.ovr_logreg_proba_u8 on a device (float32), the row-blocked float64
         formula on the host."""
-        if self.coef is None:
-            raise RuntimeError("fit first")
-        X = _bytes_rows(Xu8)
-        if X.is_cuda:
-            from . import ops
-            with torch.cuda.device(X.device):
-                return ops.ovr_logreg_proba_u8(X.contiguous(), self.coef.to(X.device, torch.float32).contiguous())
-        return proba_host_bytes(X, self.coef.cpu())
+        return _proba(self, _bytes_rows(Xu8), proba_host_bytes, lambda X, U: ops.ovr_logreg_proba_u8(X.contiguous(), U))
 
     def predict_proba(self, Xtest):
-        if self.coef is None:
-            raise RuntimeError("fit first")
-        Xtest = torch.as_tensor(Xtest)
-        if Xtest.is_cuda:
-            from . import ops
-            with torch.cuda.device(Xtest.device):
-                Xt = Xtest.contiguous() if Xtest.dtype == torch.uint8 else Xtest.float().contiguous()
-                return ops.ovr_logreg_proba(Xt, self.coef.to(Xtest.device, torch.float32).contiguous())
-        return proba_host(Xtest, self.coef.cpu())
+        return _proba(self, torch.as_tensor(Xtest), proba_host,
+                      lambda X, U: ops.ovr_logreg_proba(X.contiguous() if X.dtype == torch.uint8 else X.float().contiguous(), U))
 
 
 class OvrMlp:
@@ -420,44 +407,18 @@ class OvrMlp:
         return U0
 
     def fit_bytes(self, Xu8, y):
-        X = _bytes_rows(Xu8)
-        y = torch.as_tensor(y)
-        _check_rows(self.K, X, y)
-        N, D = X.shape
-        U0 = self.initial_point(D)
-        if X.is_cuda:
-            from . import ops
-            with torch.cuda.device(X.device):
-                Xd = X.contiguous()
-                yd = y.to(X.device).reshape(-1).to(torch.int32).contiguous()
-                ws = torch.empty(ops.ovr_mlp_u8_ws_floats(N, D, self.K, self.H), device=X.device, dtype=torch.float32)
-                ev = lambda U: ops.ovr_mlp_eval_u8(Xd, yd, U.contiguous(), self.H, self.alpha, ws=ws)
-                gtol_rel = GTOL_REL_DEVICE if self.gtol_rel is None else self.gtol_rel
-                U, rep = lbfgs_columns(ev, U0.to(X.device, torch.float32), N, gtol_rel, self.max_iter)
-        else:
-            yh = y.long().reshape(-1)
-            ev = lambda U: objective_mlp_host_bytes(X, yh, U, self.H, self.alpha)
-            gtol_rel = GTOL_REL_HOST if self.gtol_rel is None else self.gtol_rel
-            U, rep = lbfgs_columns(ev, U0, N, gtol_rel, self.max_iter)
-        rep["gtol_rel"] = float(gtol_rel)
-        self.coef, self.report = U, rep
-        return rep
+        return _fit(self, _bytes_rows(Xu8).contiguous(), y, lambda X, y, U: objective_mlp_host_bytes(X, y, U, self.H, self.alpha),
+                    lambda X, y, U, ws: ops.ovr_mlp_eval_u8(X, y, U, self.H, self.alpha, ws=ws),
+                    lambda N, D: ops.ovr_mlp_u8_ws_floats(N, D, self.K, self.H), self.initial_point)
 
     def predict_proba_bytes(self, Xu8):
         """P [M, K]: ops.ovr_mlp_proba_u8 on a device (float32), proba_mlp_host_bytes on the host (float64)."""
-        if self.coef is None:
-            raise RuntimeError("fit first")
-        X = _bytes_rows(Xu8)
-        if X.is_cuda:
-            from . import ops
-            with torch.cuda.device(X.device):
-                return ops.ovr_mlp_proba_u8(X.contiguous(), self.coef.to(X.device, torch.float32).contiguous(), self.H)
-        return proba_mlp_host_bytes(X, self.coef.cpu(), self.H)
+        return _proba(self, _bytes_rows(Xu8), lambda X, U: proba_mlp_host_bytes(X, U, self.H),
+                      lambda X, U: ops.ovr_mlp_proba_u8(X.contiguous(), U, self.H))
 
 
 def _auc(pos, neg):
     if torch.is_tensor(pos) and pos.is_cuda:
-        from . import ops
         with torch.cuda.device(pos.device):
             gt, eq = (t.cpu().numpy().astype(np.int64) for t in ops.rank_counts(pos.contiguous(), neg.contiguous()))
     else:

@@ -497,96 +497,94 @@ int cslgan_nn_prepare_u8(const void* x, int64_t rows, int D, int Dp, void* xs, i
     return check_launch("nn_prepare_u8_kernel");
 }
 
-int cslgan_nn_min_i8(const void* q, const int32_t* qn, int64_t nq, const void* r, const int32_t* rn, int64_t nr, int Dp, int64_t index_base,
-                     uint64_t* best, void* stream) {
-    CSLGAN_REQUIRE(q && qn && r && rn && best, "nn_min_i8: null argument");
-    CSLGAN_REQUIRE(Dp >= NN_KT && Dp <= NN_MAX_D && Dp % NN_KT == 0, "nn_min_i8: Dp=%d must be a multiple of %d in %d .. %d", Dp, NN_KT, NN_KT,
+// What a valid pair of prepared operands is, for the four entries below: q / r non-null and 16-byte aligned, their norms qn / rn
+// non-null and 4-byte aligned, a row pitch Dp that nn_prepare_u8 can have produced, and row counts that fit an int.  `entry`
+// prefixes the message.  An entry checks its own arguments itself.
+static int nn_check_operands(const char* entry, const void* q, const int32_t* qn, int64_t nq, const void* r, const int32_t* rn, int64_t nr, int Dp) {
+    CSLGAN_REQUIRE(q && qn && r && rn, "%s: null argument", entry);
+    CSLGAN_REQUIRE(Dp >= NN_KT && Dp <= NN_MAX_D && Dp % NN_KT == 0, "%s: Dp=%d must be a multiple of %d in %d .. %d", entry, Dp, NN_KT, NN_KT,
                    NN_MAX_D);
-    CSLGAN_REQUIRE(nq >= 1 && nq < (1ll << 31), "nn_min_i8: nq=%lld out of range", (long long)nq);
-    CSLGAN_REQUIRE(nr >= 1 && nr < (1ll << 31), "nn_min_i8: nr=%lld out of range", (long long)nr);
-    CSLGAN_REQUIRE(index_base >= 0 && index_base + nr <= 0xFFFFFFFFll, "nn_min_i8: index_base + nr = %lld exceeds 2^32 - 1",
-                   (long long)(index_base + nr));
-    CSLGAN_REQUIRE(aligned16(q) && aligned16(r) && (reinterpret_cast<uintptr_t>(qn) & 3u) == 0 && (reinterpret_cast<uintptr_t>(rn) & 3u) == 0 &&
-                       (reinterpret_cast<uintptr_t>(best) & 7u) == 0,
-                   "nn_min_i8: misaligned pointer");
+    CSLGAN_REQUIRE(nq >= 1 && nq < (1ll << 31), "%s: nq=%lld out of range", entry, (long long)nq);
+    CSLGAN_REQUIRE(nr >= 1 && nr < (1ll << 31), "%s: nr=%lld out of range", entry, (long long)nr);
+    CSLGAN_REQUIRE(aligned16(q) && aligned16(r) && (reinterpret_cast<uintptr_t>(qn) & 3u) == 0 && (reinterpret_cast<uintptr_t>(rn) & 3u) == 0,
+                   "%s: misaligned pointer", entry);
+    return CSLGAN_OK;
+}
+
+constexpr long long NN_ANY_TILES = 1ll << 31;                  // no cap on the tiles of a workgroup: more than any nr has
+
+// The launch rule of the four entries: the column tiles are cut into ranges of tiles_per tiles, one workgroup per row tile and
+// range — enough workgroups (about 1024) for every CU a few times over, and as few ranges, hence atomics or partial lists per row,
+// as that allows; never more than max_tiles tiles per workgroup.  Returns the number of ranges, 0 for sizes out of range.
+static long long nn_column_ranges(int64_t nq, int64_t nr, long long max_tiles, long long* tiles_per_out) {
+    if (nq < 1 || nq >= (1ll << 31) || nr < 1 || nr >= (1ll << 31)) return 0;
     const long long row_tiles = (nq + NN_TM - 1) / NN_TM, col_tiles = (nr + NN_TN - 1) / NN_TN;
-    // enough workgroups for every CU a few times over, and as few atomics per row as that allows
     long long splits = (1024 + row_tiles - 1) / row_tiles;
     splits = splits < 1 ? 1 : (splits > col_tiles ? col_tiles : splits);
-    const long long tiles_per = (col_tiles + splits - 1) / splits;
-    const long long gy = (col_tiles + tiles_per - 1) / tiles_per;
+    long long tiles_per = (col_tiles + splits - 1) / splits;
+    tiles_per = tiles_per > max_tiles ? max_tiles : tiles_per;
+    if (tiles_per_out) *tiles_per_out = tiles_per;
+    return (col_tiles + tiles_per - 1) / tiles_per;
+}
+
+int cslgan_nn_min_i8(const void* q, const int32_t* qn, int64_t nq, const void* r, const int32_t* rn, int64_t nr, int Dp, int64_t index_base,
+                     uint64_t* best, void* stream) {
+    CSLGAN_REQUIRE(best, "nn_min_i8: null argument");
+    if (int rc = nn_check_operands("nn_min_i8", q, qn, nq, r, rn, nr, Dp)) return rc;
+    CSLGAN_REQUIRE(index_base >= 0 && index_base + nr <= 0xFFFFFFFFll, "nn_min_i8: index_base + nr = %lld exceeds 2^32 - 1",
+                   (long long)(index_base + nr));
+    CSLGAN_REQUIRE((reinterpret_cast<uintptr_t>(best) & 7u) == 0, "nn_min_i8: misaligned pointer");
+    long long tiles_per = 0;
+    const long long gy = nn_column_ranges(nq, nr, NN_ANY_TILES, &tiles_per);
     CSLGAN_REQUIRE(gy <= 65535, "nn_min_i8: nr=%lld needs %lld column ranges", (long long)nr, gy);
+    const long long col_tiles = (nr + NN_TN - 1) / NN_TN;
     note_kernel("nn_min_i8_kernel");
-    hipLaunchKernelGGL(nn_min_i8_kernel, dim3((unsigned)row_tiles, (unsigned)gy), dim3(NN_THREADS), 0, (hipStream_t)stream, (const signed char*)q,
-                       (const int*)qn, (int)nq, (const signed char*)r, (const int*)rn, (int)nr, Dp, (uint32_t)index_base, (int)tiles_per,
-                       (int)col_tiles, (unsigned long long*)best);
+    hipLaunchKernelGGL(nn_min_i8_kernel, dim3((unsigned)((nq + NN_TM - 1) / NN_TM), (unsigned)gy), dim3(NN_THREADS), 0, (hipStream_t)stream,
+                       (const signed char*)q, (const int*)qn, (int)nq, (const signed char*)r, (const int*)rn, (int)nr, Dp, (uint32_t)index_base,
+                       (int)tiles_per, (int)col_tiles, (unsigned long long*)best);
     return check_launch("nn_min_i8_kernel");
 }
 
 int cslgan_nn_count_i8(const void* q, const int32_t* qn, int64_t nq, const void* r, const int32_t* rn, int64_t nr, int Dp,
                        const uint32_t* thresholds, int n_thr, uint32_t* counts, void* stream) {
-    CSLGAN_REQUIRE(q && qn && r && rn && thresholds && counts, "nn_count_i8: null argument");
+    CSLGAN_REQUIRE(thresholds && counts, "nn_count_i8: null argument");
     CSLGAN_REQUIRE(n_thr >= 1 && n_thr <= NN_MAX_THR, "nn_count_i8: n_thr=%d must lie in 1 .. %d", n_thr, NN_MAX_THR);
-    CSLGAN_REQUIRE(Dp >= NN_KT && Dp <= NN_MAX_D && Dp % NN_KT == 0, "nn_count_i8: Dp=%d must be a multiple of %d in %d .. %d", Dp, NN_KT, NN_KT,
-                   NN_MAX_D);
-    CSLGAN_REQUIRE(nq >= 1 && nq < (1ll << 31), "nn_count_i8: nq=%lld out of range", (long long)nq);
-    CSLGAN_REQUIRE(nr >= 1 && nr < (1ll << 31), "nn_count_i8: nr=%lld out of range", (long long)nr);
-    CSLGAN_REQUIRE(aligned16(q) && aligned16(r) && (reinterpret_cast<uintptr_t>(qn) & 3u) == 0 && (reinterpret_cast<uintptr_t>(rn) & 3u) == 0 &&
-                       (reinterpret_cast<uintptr_t>(counts) & 3u) == 0 && (reinterpret_cast<uintptr_t>(thresholds) & 3u) == 0,
+    if (int rc = nn_check_operands("nn_count_i8", q, qn, nq, r, rn, nr, Dp)) return rc;
+    CSLGAN_REQUIRE((reinterpret_cast<uintptr_t>(counts) & 3u) == 0 && (reinterpret_cast<uintptr_t>(thresholds) & 3u) == 0,
                    "nn_count_i8: misaligned pointer");
-    const long long row_tiles = (nq + NN_TM - 1) / NN_TM, col_tiles = (nr + NN_TN - 1) / NN_TN;
-    // as nn_min_i8: enough workgroups for every CU a few times over; and no more tiles per workgroup than a byte counter holds
-    long long splits = (1024 + row_tiles - 1) / row_tiles;
-    splits = splits < 1 ? 1 : (splits > col_tiles ? col_tiles : splits);
-    long long tiles_per = (col_tiles + splits - 1) / splits;
-    tiles_per = tiles_per > NN_COUNT_TILES ? NN_COUNT_TILES : tiles_per;
-    const long long gy = (col_tiles + tiles_per - 1) / tiles_per;
+    long long tiles_per = 0;                                   // no more tiles per workgroup than a byte counter holds
+    const long long gy = nn_column_ranges(nq, nr, NN_COUNT_TILES, &tiles_per);
     CSLGAN_REQUIRE(gy <= 65535, "nn_count_i8: nr=%lld needs %lld column ranges", (long long)nr, gy);
+    const long long col_tiles = (nr + NN_TN - 1) / NN_TN;
     NNThresholds thr = {{0u, 0u, 0u, 0u}};
     for (int j = 0; j < n_thr; ++j) thr.t[j] = thresholds[j];  // read now: the caller's array may go when this returns
     note_kernel("nn_count_i8_kernel");
-    hipLaunchKernelGGL(nn_count_i8_kernel, dim3((unsigned)row_tiles, (unsigned)gy), dim3(NN_THREADS), 0, (hipStream_t)stream, (const signed char*)q,
-                       (const int*)qn, (int)nq, (const signed char*)r, (const int*)rn, (int)nr, Dp, thr, n_thr, (int)tiles_per, (int)col_tiles,
-                       (uint32_t*)counts);
+    hipLaunchKernelGGL(nn_count_i8_kernel, dim3((unsigned)((nq + NN_TM - 1) / NN_TM), (unsigned)gy), dim3(NN_THREADS), 0, (hipStream_t)stream,
+                       (const signed char*)q, (const int*)qn, (int)nq, (const signed char*)r, (const int*)rn, (int)nr, Dp, thr, n_thr, (int)tiles_per,
+                       (int)col_tiles, (uint32_t*)counts);
     return check_launch("nn_count_i8_kernel");
-}
-
-// the launch rule that nn_kth_i8 and nn_count_radius_i8 share, which is nn_min_i8's: column ranges for about 1024 workgroups.
-// Returns the number of ranges, 0 for sizes out of range.
-static long long nn_column_ranges(int64_t nq, int64_t nr, long long* tiles_per_out) {
-    if (nq < 1 || nq >= (1ll << 31) || nr < 1 || nr >= (1ll << 31)) return 0;
-    const long long row_tiles = (nq + NN_TM - 1) / NN_TM, col_tiles = (nr + NN_TN - 1) / NN_TN;
-    long long splits = (1024 + row_tiles - 1) / row_tiles;
-    splits = splits < 1 ? 1 : (splits > col_tiles ? col_tiles : splits);
-    const long long tiles_per = (col_tiles + splits - 1) / splits;
-    if (tiles_per_out) *tiles_per_out = tiles_per;
-    return (col_tiles + tiles_per - 1) / tiles_per;
 }
 
 int64_t cslgan_nn_kth_workspace_bytes(int64_t nq, int64_t nr, int k) {
     if (k < 1 || k > NN_MAX_K) return 0;
-    const long long gy = nn_column_ranges(nq, nr, nullptr);
+    const long long gy = nn_column_ranges(nq, nr, NN_ANY_TILES, nullptr);
     if (gy < 1 || gy > 65535) return 0;
     return (int64_t)(gy * nq * k * 8);
 }
 
 int cslgan_nn_kth_i8(const void* q, const int32_t* qn, int64_t nq, const void* r, const int32_t* rn, int64_t nr, int Dp, int64_t index_base,
                      int64_t self_base, int k, uint64_t* best, void* workspace, int64_t workspace_bytes, void* stream) {
-    CSLGAN_REQUIRE(q && qn && r && rn && best && workspace, "nn_kth_i8: null argument");
+    CSLGAN_REQUIRE(best && workspace, "nn_kth_i8: null argument");
     CSLGAN_REQUIRE(k >= 1 && k <= NN_MAX_K, "nn_kth_i8: k=%d must lie in 1 .. %d", k, NN_MAX_K);
-    CSLGAN_REQUIRE(Dp >= NN_KT && Dp <= NN_MAX_D && Dp % NN_KT == 0, "nn_kth_i8: Dp=%d must be a multiple of %d in %d .. %d", Dp, NN_KT, NN_KT,
-                   NN_MAX_D);
-    CSLGAN_REQUIRE(nq >= 1 && nq < (1ll << 31), "nn_kth_i8: nq=%lld out of range", (long long)nq);
-    CSLGAN_REQUIRE(nr >= 1 && nr < (1ll << 31), "nn_kth_i8: nr=%lld out of range", (long long)nr);
+    if (int rc = nn_check_operands("nn_kth_i8", q, qn, nq, r, rn, nr, Dp)) return rc;
     CSLGAN_REQUIRE(index_base >= 0 && index_base + nr <= 0xFFFFFFFFll, "nn_kth_i8: index_base + nr = %lld exceeds 2^32 - 1",
                    (long long)(index_base + nr));
     CSLGAN_REQUIRE(self_base >= -1 && self_base + nq <= 0xFFFFFFFFll, "nn_kth_i8: self_base=%lld must be -1 or keep self_base + nq <= 2^32 - 1",
                    (long long)self_base);
-    CSLGAN_REQUIRE(aligned16(q) && aligned16(r) && (reinterpret_cast<uintptr_t>(qn) & 3u) == 0 && (reinterpret_cast<uintptr_t>(rn) & 3u) == 0 &&
-                       (reinterpret_cast<uintptr_t>(best) & 7u) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0,
+    CSLGAN_REQUIRE((reinterpret_cast<uintptr_t>(best) & 7u) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0,
                    "nn_kth_i8: misaligned pointer");
     long long tiles_per = 0;
-    const long long gy = nn_column_ranges(nq, nr, &tiles_per);
+    const long long gy = nn_column_ranges(nq, nr, NN_ANY_TILES, &tiles_per);
     CSLGAN_REQUIRE(gy >= 1 && gy <= 65535, "nn_kth_i8: nr=%lld needs %lld column ranges", (long long)nr, gy);
     CSLGAN_REQUIRE(workspace_bytes >= gy * nq * k * 8, "nn_kth_i8: workspace of %lld bytes, need %lld", (long long)workspace_bytes,
                    (long long)(gy * nq * k * 8));
@@ -604,16 +602,12 @@ int cslgan_nn_kth_i8(const void* q, const int32_t* qn, int64_t nq, const void* r
 
 int cslgan_nn_count_radius_i8(const void* q, const int32_t* qn, int64_t nq, const void* r, const int32_t* rn, int64_t nr, int Dp,
                               const uint32_t* radius, uint32_t* counts, void* stream) {
-    CSLGAN_REQUIRE(q && qn && r && rn && radius && counts, "nn_count_radius_i8: null argument");
-    CSLGAN_REQUIRE(Dp >= NN_KT && Dp <= NN_MAX_D && Dp % NN_KT == 0, "nn_count_radius_i8: Dp=%d must be a multiple of %d in %d .. %d", Dp, NN_KT,
-                   NN_KT, NN_MAX_D);
-    CSLGAN_REQUIRE(nq >= 1 && nq < (1ll << 31), "nn_count_radius_i8: nq=%lld out of range", (long long)nq);
-    CSLGAN_REQUIRE(nr >= 1 && nr < (1ll << 31), "nn_count_radius_i8: nr=%lld out of range", (long long)nr);
-    CSLGAN_REQUIRE(aligned16(q) && aligned16(r) && (reinterpret_cast<uintptr_t>(qn) & 3u) == 0 && (reinterpret_cast<uintptr_t>(rn) & 3u) == 0 &&
-                       (reinterpret_cast<uintptr_t>(counts) & 3u) == 0 && (reinterpret_cast<uintptr_t>(radius) & 3u) == 0,
+    CSLGAN_REQUIRE(radius && counts, "nn_count_radius_i8: null argument");
+    if (int rc = nn_check_operands("nn_count_radius_i8", q, qn, nq, r, rn, nr, Dp)) return rc;
+    CSLGAN_REQUIRE((reinterpret_cast<uintptr_t>(counts) & 3u) == 0 && (reinterpret_cast<uintptr_t>(radius) & 3u) == 0,
                    "nn_count_radius_i8: misaligned pointer");
     long long tiles_per = 0;
-    const long long gy = nn_column_ranges(nq, nr, &tiles_per);
+    const long long gy = nn_column_ranges(nq, nr, NN_ANY_TILES, &tiles_per);
     CSLGAN_REQUIRE(gy >= 1 && gy <= 65535, "nn_count_radius_i8: nr=%lld needs %lld column ranges", (long long)nr, gy);
     const long long col_tiles = (nr + NN_TN - 1) / NN_TN;
     note_kernel("nn_count_radius_i8_kernel");

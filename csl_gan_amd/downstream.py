@@ -30,7 +30,7 @@ import sys
 import numpy as np
 import torch
 
-from . import classify, datasets, generate, init_util, options, pipeline, util
+from . import cache_cli, classify, datasets, generate, init_util, options, pipeline, util
 
 CLASSIFIERS = ["svm", "dt", "lr", "rf", "gnb", "bnb", "ab", "mlp"]
 
@@ -58,8 +58,7 @@ def build_parser():
 def load_test_set(train_opt, test_cache):
     """(bytes [M, H*W*C] uint8, labels [M] int64).  The features are bytes / 255 whatever scale a cache records."""
     if test_cache is not None:
-        c = pipeline.CachedImages(test_cache)
-        return np.array(c.x, dtype=np.uint8).reshape(len(c), -1), np.asarray(c.labels, dtype=np.int64)
+        return cache_cli.cache_rows(pipeline.CachedImages(test_cache))
     root = train_opt.data_path
     for d in (os.path.join(root, "MNIST", "raw"), root):                  # downstream.py:103-105 reads <data_path>MNIST/raw/
         for suf in ("", ".gz"):
@@ -141,9 +140,7 @@ def main(argv=None):
             res = evaluate_checkpoint(G, train_opt, a, seed, device, test_x, test_y)
             print("lr AUROC ({}):  {}".format(epoch, res["micro"]))
             print("   per class: %s" % " ".join("%.4f" % v for v in res["per_class"]))
-            s = res["solver"]
-            print("   solver: iterations %s  evaluations %s  max|g| %.3g (stop at %.3g)  stalled %s" % (
-                s["iterations"], s["evaluations"], max(s["grad_norm"]), s["gtol"], [k for k, v in enumerate(s["stalled"]) if v] or "none"))
+            print(classify.solver_line(res["solver"]))
             logger.writerow([epoch, res["micro"]])
             log.flush()
             results[epoch] = res

@@ -13,7 +13,7 @@ synthetic rows S, 1 <= k <= 8:
 
 The compare is `<=`, as in Kynkäänniemi et al. and as in cslgan_nn_count_i8.  The `prdc` PyPI package uses `<`; the two differ on
 exact ties only, which integer distances do produce.  Every numerator is an integer and is reported, so the figures are
-bit-identical on the CPU (`neighbours.kth_host`, `count_within_radii_host`: THE definitions) and on a device
+bit-identical on the CPU (`neighbours.kth_host`, `neighbours.count_within_radii_host`: THE definitions) and on a device
 (ops.nn_kth / ops.nn_count_radius through NearestSearch), which is held to them by equality.
 """
 from __future__ import annotations
@@ -21,48 +21,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import neighbours
-from .neighbours import MAX_D, MAX_K, NONE_KEY, _rows_u8
-
-MAX_RADIUS = 2 ** 32 - 1
-
-
-def check_radii(radii, n):
-    """The radii as an int64 array [n] of integers in [0, 2^32 - 1]."""
-    rad = np.asarray(radii)
-    if rad.dtype.kind not in "iu" or rad.shape != (n,):
-        raise ValueError("need %d integer radii, one per reference row, got %s %s" % (n, rad.dtype, rad.shape))
-    if rad.dtype == np.uint64 and len(rad) and int(rad.max()) > MAX_RADIUS:
-        raise ValueError("radii must lie in [0, 2^32 - 1]")
-    rad = rad.astype(np.int64)
-    if len(rad) and (int(rad.min()) < 0 or int(rad.max()) > MAX_RADIUS):
-        raise ValueError("radii must lie in [0, 2^32 - 1]")
-    return rad
-
-
-def count_within_radii_host(Q, R, radii, counts=None, block=1024):
-    """counts[q] += #{r : d2(q, r) <= radii[r]} as int64 [nq] for the rows of Q [nq, ...] and R [nr, ...] (uint8, same row size D,
-    1 <= D <= 65536) and one integer radius in [0, 2^32 - 1] per row of R — THE definition.  `counts` holds the sums of earlier
-    calls (zeros when absent) and is not written.  The float64-matmul-in-blocks argument of neighbours.nearest_host: every d2 and
-    radius is below 2^32, far under 2^53, so the floats are the integers."""
-    Q, R = _rows_u8(Q), _rows_u8(R)
-    nq, D = Q.shape
-    nr = R.shape[0]
-    if R.shape[1] != D or not 1 <= D <= MAX_D:
-        raise ValueError("rows of %d and %d bytes; need equal sizes in 1 .. %d" % (D, R.shape[1], MAX_D))
-    rad = check_radii(radii, nr).astype(np.float64)
-    out = np.zeros(nq, dtype=np.int64) if counts is None else np.array(counts, dtype=np.int64, copy=True)
-    if out.shape != (nq,):
-        raise ValueError("counts has shape %s, expected (%d,)" % (out.shape, nq))
-    block = max(1, int(block))
-    for r0 in range(0, nr, block):
-        b = np.asarray(R[r0:r0 + block]).astype(np.float64) - 128.0
-        bn = (b * b).sum(1)
-        for q0 in range(0, nq, block):
-            a = np.asarray(Q[q0:q0 + block]).astype(np.float64) - 128.0
-            d2 = (a * a).sum(1)[:, None] + bn[None, :] - 2.0 * (a @ b.T)
-            out[q0:q0 + block] += (d2 <= rad[None, r0:r0 + block]).sum(1)
-    return out
-
+from .neighbours import MAX_K, MAX_RADIUS, NONE_KEY, check_radii, count_within_radii_host  # noqa: F401  (the names stay reachable here)
 
 def knn_radii(keys):
     """int64 [n]: the k-NN radius of every row from its list of a self-excluding search (uint64 [n, k]): the d2 of the last entry.
@@ -92,10 +51,6 @@ def prdc_metrics(counts_syn, counts_real, d2min_real, rad_real, k):
             "precision": p / M, "density": d / (k * M), "recall": r / N, "coverage": c / N}
 
 
-def _search(ref, device, block_rows, resident_gb, query_rows):
-    return neighbours.NearestSearch(device, block_rows=block_rows, resident_gb=resident_gb, query_rows=query_rows).fit(ref)
-
-
 def check_sizes(k, **sets):
     """k in 1 .. 8 and every named cache with more than k rows (its k-NN radius needs k other rows)."""
     k = int(k)
@@ -110,7 +65,7 @@ def check_sizes(k, **sets):
 def real_side(real, k, device="cpu", block_rows=16384, resident_gb=8.0, query_rows=16384):
     """(the fitted search of the real cache, rad_X): the self-search that all synthetic caches of one run share."""
     k = check_sizes(k, real=real)
-    s = _search(real, device, block_rows, resident_gb, query_rows)
+    s = neighbours.fitted_search(real, device, block_rows, resident_gb, query_rows)
     return s, knn_radii(s.kth(real, k, exclude_self=True))
 
 
@@ -122,7 +77,7 @@ def run_prdc(real, syn, k, real_search=None, rad_real=None, device="cpu", block_
     if real_search is None or rad_real is None:
         real_search, rad_real = real_side(real, k, device, block_rows, resident_gb, query_rows)
     out = {"rad_real": rad_real, "counts_syn": real_search.count_within_radii(syn, rad_real)}
-    s = _search(syn, device, block_rows, resident_gb, query_rows)
+    s = neighbours.fitted_search(syn, device, block_rows, resident_gb, query_rows)
     out["rad_syn"] = knn_radii(s.kth(syn, k, exclude_self=True))
     out["counts_real"] = s.count_within_radii(real, out["rad_syn"])
     out["d2min_real"] = neighbours.split_keys(s.query(real))[0]

@@ -15,41 +15,24 @@ train | nearest held-out.  With --save the figures are merged into `<outputs_dir
 the same on `-d cpu` (the host model) and on a device.
 """
 import argparse
-import json
 import os
 import sys
 
 import numpy as np
 import torch
 
-from . import neighbours, pipeline, util
+from . import cache_cli, neighbours, pipeline, util
 
 
 def build_parser():
     ap = argparse.ArgumentParser(description="Exact nearest-neighbour audit of a synthetic image cache")
-    ap.add_argument("--syn_cache", type=str, nargs="+", required=True, help="uint8 image cache(s) of synthetic samples")
+    cache_cli.add_common_arguments(ap, "nearest", "uint8 image cache(s) of synthetic samples", "keep the key arrays as .npy here")
+    cache_cli.add_search_arguments(ap, "reference images per device block", "device memory for prepared reference blocks kept between queries")
     ap.add_argument("--train_cache", type=str, required=True, help="uint8 image cache of the training set")
     ap.add_argument("--nontrain_cache", type=str, default=None, help="uint8 image cache of the held-out set")
-    ap.add_argument("-d", "--device", type=str, default="cpu")
-    ap.add_argument("--block_rows", type=int, default=16384, help="reference images per device block")
-    ap.add_argument("--resident_gb", type=float, default=8.0, help="device memory for prepared reference blocks kept between queries")
     ap.add_argument("--baseline", default=False, action="store_true", help="also report held-out -> train")
     ap.add_argument("--grid", type=int, default=0, help="picture grid of the K samples closest to the training set")
-    ap.add_argument("--values_dir", type=str, default=None, help="keep the key arrays as .npy here")
-    ap.add_argument("--outputs_dir", type=str, default="outputs/")
-    ap.add_argument("--name", type=str, default="nearest")
-    ap.add_argument("--save", default=False, action="store_true", help="merge the figures into <outputs_dir>/<name>.json")
     return ap
-
-
-def _label(path):
-    return os.path.basename(os.path.normpath(path))
-
-
-def _same_geometry(a, pa, b, pb):
-    if (a.H, a.W, a.C) != (b.H, b.W, b.C):
-        raise SystemExit("%s holds %dx%dx%d images and %s %dx%dx%d images: the caches of one audit must have one geometry"
-                         % (pa, a.H, a.W, a.C, pb, b.H, b.W, b.C))
 
 
 def _rows(cache, idx):
@@ -76,33 +59,23 @@ def main(argv=None):
         raise SystemExit("--baseline compares the held-out set with the training set: give --nontrain_cache")
     train = pipeline.CachedImages(a.train_cache)
     heldout = pipeline.CachedImages(a.nontrain_cache) if a.nontrain_cache else None
-    syns = [(p, pipeline.CachedImages(p)) for p in a.syn_cache]
-    if heldout is not None:
-        _same_geometry(train, a.train_cache, heldout, a.nontrain_cache)
-    for p, c in syns:
-        _same_geometry(train, a.train_cache, c, p)
-    if len({_label(p) for p, _ in syns}) != len(syns):
-        raise SystemExit("two --syn_cache share the name %s" % ", ".join(sorted(_label(p) for p, _ in syns)))
-
-    def search(ref):
-        return neighbours.NearestSearch(a.device, block_rows=a.block_rows, resident_gb=a.resident_gb).fit(ref)
+    syns = cache_cli.open_syn_caches(a.syn_cache, train, a.train_cache, [(a.nontrain_cache, heldout)] if heldout is not None else [])
 
     # one reference at a time on the device: all queries against the training set, then all against the held-out set
     keys = {}
-    s = search(train)
-    for p, c in syns:
-        keys[_label(p), "train"] = s.query(c)
+    s = neighbours.fitted_search(train, **cache_cli.search_kw(a))
+    for lab, _, c in syns:
+        keys[lab, "train"] = s.query(c)
     if a.baseline:
         keys["baseline", "train"] = s.query(heldout)
     if heldout is not None:
-        s = search(heldout)
-        for p, c in syns:
-            keys[_label(p), "heldout"] = s.query(c)
+        s = neighbours.fitted_search(heldout, **cache_cli.search_kw(a))
+        for lab, _, c in syns:
+            keys[lab, "heldout"] = s.query(c)
     del s
 
     stats = {}
-    for p, c in syns:
-        lab = _label(p)
+    for lab, _, c in syns:
         stats[lab] = neighbours.dcr_metrics(keys[lab, "train"], keys.get((lab, "heldout")))
         m = stats[lab]
         print("%s: %d samples, %d duplicates of a training image, d2 min / 1%% / 50%% = %d / %d / %d" % (lab, m["n"], m["duplicates"], m["d2_min"],
@@ -110,30 +83,14 @@ def main(argv=None):
               + ("" if heldout is None else ", closer to train: %.4f (+- %.4f)" % (m["closer_to_train_share"], m["closer_to_train_stderr"])))
     if a.baseline:
         stats["baseline_heldout_to_train"] = neighbours.dcr_metrics(keys["baseline", "train"])
-    if a.values_dir:
-        os.makedirs(a.values_dir, exist_ok=True)
-        for (lab, side), k in keys.items():
-            np.save(os.path.join(a.values_dir, "%s_keys_%s.npy" % (lab, side)), k)
+    cache_cli.save_values(a.values_dir, {"%s_keys_%s" % (lab, side): k for (lab, side), k in keys.items()})
     if a.grid > 0:
         os.makedirs(a.outputs_dir, exist_ok=True)
-        for p, c in syns:
-            lab = _label(p)
+        for lab, _, c in syns:
             png = os.path.join(a.outputs_dir, "%s_%s_nearest.png" % (a.name, lab))
             write_grid(png, a.grid, c, train, keys[lab, "train"], heldout, keys.get((lab, "heldout")))
             print("saved %s" % png)
-    print(json.dumps(stats, indent=4))
-    if a.save:
-        os.makedirs(a.outputs_dir, exist_ok=True)
-        json_path = os.path.join(a.outputs_dir, a.name + ".json")
-        merged = {}
-        if os.path.exists(json_path):
-            with open(json_path) as f:
-                merged = json.load(f)
-        merged.update(stats)
-        with open(json_path, "w") as f:
-            json.dump(merged, f)
-        print("saved %s" % json_path)
-    return stats
+    return cache_cli.report(a, stats)
 
 
 if __name__ == "__main__":

@@ -10,7 +10,8 @@ set, so it does not depend on how the reference is cut into blocks.  Everything 
 definition, and the device path (`ops.nn_prepare` + `ops.nn_min`) is held to it by equality.
 
 `kth_host` is the definition of the k smallest keys per row, with an optional self-excluding search of a set in itself (DESIGN.md
-§6i; csl_gan_amd.manifold builds precision / recall / density / coverage on it).
+§6i; csl_gan_amd.manifold builds precision / recall / density / coverage on it).  `count_within_host` (§6h) and
+`count_within_radii_host` (§6i) are the definitions of the two counts.  All four reduce the distances of one host walk, `_d2_blocks`.
 
 `NearestSearch` drives the device over a pipeline.CachedImages reference of any size; `dcr_metrics` turns keys into the
 "distance to closest record" figures and the share of samples that lie closer to the training set than to a held-out set — 0.5 for
@@ -41,31 +42,50 @@ def _rows_u8(a):
     return a.reshape(a.shape[0], -1)
 
 
-def nearest_host(Q, R, index_base=0, best=None, block=1024):
-    """key(q) for every row of Q [nq, ...] over the rows of R [nr, ...] (uint8, same row size), merged into `best` (uint64 [nq], the
-    running minimum of earlier calls; all-ones when absent) — THE definition.  The shifted bytes (x - 128) go through a float64
-    matmul in blocks of `block` rows: every product sum is below 2^30 and every d2 below 2^32, far under 2^53, so the floats are
-    the integers."""
+def _d2_blocks(Q, R, block):
+    """(nq, nr, blocks) for the rows of Q [nq, ...] and R [nr, ...] (uint8, same row size D, 1 <= D <= 65536): `blocks` yields
+    (q0, r0, d2) with d2[i, j] = d2(Q[q0 + i], R[r0 + j]) as float64, for every pair of blocks of `block` rows, the reference
+    blocks outermost — the ONE place where the host forms d2, which every definition below reduces.  The shifted bytes (x - 128)
+    go through a float64 matmul: every product sum is below 2^30 and every d2 below 2^32, far under 2^53, so the floats are the
+    integers.  The operands are checked here, before the first block is asked for."""
     Q, R = _rows_u8(Q), _rows_u8(R)
     nq, D = Q.shape
     nr = R.shape[0]
     if R.shape[1] != D or not 1 <= D <= MAX_D:
         raise ValueError("rows of %d and %d bytes; need equal sizes in 1 .. %d" % (D, R.shape[1], MAX_D))
+    block = max(1, int(block))
+
+    def shifted(rows):
+        return np.asarray(rows).astype(np.float64) - 128.0
+
+    def blocks():
+        for r0 in range(0, nr, block):
+            b = shifted(R[r0:r0 + block])
+            bn = (b * b).sum(1)
+            for q0 in range(0, nq, block):
+                a = shifted(Q[q0:q0 + block])
+                yield q0, r0, (a * a).sum(1)[:, None] + bn[None, :] - 2.0 * (a @ b.T)
+    return nq, nr, blocks()
+
+
+def _block_keys(d2, first_index):
+    """(uint64 keys d2 << 32 | index, the uint64 indices first_index + column) of one block of distances."""
+    idx = np.arange(first_index, first_index + d2.shape[1], dtype=np.uint64)
+    return (d2.astype(np.uint64) << np.uint64(32)) | idx[None, :], idx
+
+
+def nearest_host(Q, R, index_base=0, best=None, block=1024):
+    """key(q) for every row of Q [nq, ...] over the rows of R [nr, ...] (uint8, same row size), merged into `best` (uint64 [nq], the
+    running minimum of earlier calls; all-ones when absent) — THE definition, a minimum over the blocks of `_d2_blocks`."""
+    nq, nr, blocks = _d2_blocks(Q, R, block)
     if index_base < 0 or index_base + nr > MAX_INDEX:
         raise ValueError("index_base + nr = %d exceeds 2^32 - 1" % (index_base + nr))
     out = np.full(nq, NONE_KEY, dtype=np.uint64) if best is None else np.array(best, dtype=np.uint64, copy=True)
     if out.shape != (nq,):
         raise ValueError("best has shape %s, expected (%d,)" % (out.shape, nq))
-    block = max(1, int(block))
-    for r0 in range(0, nr, block):
-        b = np.asarray(R[r0:r0 + block]).astype(np.float64) - 128.0
-        bn = (b * b).sum(1)
-        idx = np.arange(index_base + r0, index_base + r0 + len(b), dtype=np.uint64)
-        for q0 in range(0, nq, block):
-            a = np.asarray(Q[q0:q0 + block]).astype(np.float64) - 128.0
-            d2 = (a * a).sum(1)[:, None] + bn[None, :] - 2.0 * (a @ b.T)
-            keys = (d2.astype(np.uint64) << np.uint64(32)) | idx[None, :]
-            out[q0:q0 + block] = np.minimum(out[q0:q0 + block], keys.min(1))
+    for q0, r0, d2 in blocks:
+        rows = slice(q0, q0 + d2.shape[0])
+        out[rows] = np.minimum(out[rows], _block_keys(d2, index_base + r0)[0].min(1))
     return out
 
 
@@ -79,15 +99,11 @@ def kth_host(Q, R, k, index_base=0, self_base=-1, best=None, block=1024):
     by its distance, so a different row with the same bytes stays in at d2 = 0.  Keys carry the index and are distinct, so ties in
     d2 are ordered by index and the list is a function of the candidate set alone.  All-ones entries stay last while fewer than k
     candidates have been seen.  PRECONDITION (the device entry has the same): successive calls bring disjoint index ranges — a key
-    presented twice would be kept twice.  The float64-matmul-in-blocks argument of `nearest_host` makes the floats the integers."""
-    Q, R = _rows_u8(Q), _rows_u8(R)
-    nq, D = Q.shape
-    nr = R.shape[0]
+    presented twice would be kept twice.  The distances are those of `_d2_blocks`."""
     k = int(k)
     if not 1 <= k <= MAX_K:
         raise ValueError("k = %d; the lists hold 1 .. %d neighbours" % (k, MAX_K))
-    if R.shape[1] != D or not 1 <= D <= MAX_D:
-        raise ValueError("rows of %d and %d bytes; need equal sizes in 1 .. %d" % (D, R.shape[1], MAX_D))
+    nq, nr, blocks = _d2_blocks(Q, R, block)
     if index_base < 0 or index_base + nr > MAX_INDEX:
         raise ValueError("index_base + nr = %d exceeds 2^32 - 1" % (index_base + nr))
     if self_base < -1 or self_base + nq > MAX_INDEX:
@@ -95,20 +111,72 @@ def kth_host(Q, R, k, index_base=0, self_base=-1, best=None, block=1024):
     out = np.full((nq, k), NONE_KEY, dtype=np.uint64) if best is None else np.array(best, dtype=np.uint64, copy=True)
     if out.shape != (nq, k):
         raise ValueError("best has shape %s, expected (%d, %d)" % (out.shape, nq, k))
-    block = max(1, int(block))
-    for r0 in range(0, nr, block):
-        b = np.asarray(R[r0:r0 + block]).astype(np.float64) - 128.0
-        bn = (b * b).sum(1)
-        idx = np.arange(index_base + r0, index_base + r0 + len(b), dtype=np.uint64)
-        for q0 in range(0, nq, block):
-            a = np.asarray(Q[q0:q0 + block]).astype(np.float64) - 128.0
-            d2 = (a * a).sum(1)[:, None] + bn[None, :] - 2.0 * (a @ b.T)
-            keys = (d2.astype(np.uint64) << np.uint64(32)) | idx[None, :]
-            if self_base >= 0:
-                own = np.arange(self_base + q0, self_base + q0 + len(a), dtype=np.uint64)
-                keys[own[:, None] == idx[None, :]] = NONE_KEY
-            both = np.sort(np.concatenate([out[q0:q0 + block], keys], axis=1), axis=1)
-            out[q0:q0 + block] = both[:, :k]
+    for q0, r0, d2 in blocks:
+        rows = slice(q0, q0 + d2.shape[0])
+        keys, idx = _block_keys(d2, index_base + r0)
+        if self_base >= 0:
+            own = np.arange(self_base + q0, self_base + q0 + d2.shape[0], dtype=np.uint64)
+            keys[own[:, None] == idx[None, :]] = NONE_KEY
+        out[rows] = np.sort(np.concatenate([out[rows], keys], axis=1), axis=1)[:, :k]
+    return out
+
+
+MAX_THRESHOLDS = 4                      # the counters of a row are the four bytes of one register (csrc/nn_kernels.hip)
+MAX_THRESHOLD = 2 ** 32 - 1
+MAX_RADIUS = 2 ** 32 - 1
+
+
+def check_thresholds(thresholds):
+    """The thresholds as a list of 1 .. 4 Python integers in [0, 2^32 - 1]."""
+    thr = [int(t) for t in np.asarray(thresholds, dtype=object).reshape(-1)]
+    if not 1 <= len(thr) <= MAX_THRESHOLDS:
+        raise ValueError("need 1 .. %d thresholds, got %d" % (MAX_THRESHOLDS, len(thr)))
+    if any(t < 0 or t > MAX_THRESHOLD for t in thr):
+        raise ValueError("thresholds must lie in [0, 2^32 - 1], got %s" % (thr,))
+    return thr
+
+
+def count_within_host(Q, R, thresholds, counts=None, block=1024):
+    """counts[q, j] += #{r : d2(q, r) <= thresholds[j]} as int64 [nq, J] for the rows of Q [nq, ...] and R [nr, ...] (uint8, same row
+    size D, 1 <= D <= 65536) and 1 <= J <= 4 integer thresholds in [0, 2^32 - 1], in any order — THE definition (DESIGN.md §6h;
+    csl_gan_amd.blackbox builds the Monte-Carlo attack on it).  `counts` holds the sums of earlier calls (zeros when absent) and is
+    not written.  The distances are those of `_d2_blocks`: they and the thresholds are integers below 2^32 held in float64."""
+    nq, nr, blocks = _d2_blocks(Q, R, block)
+    thr = np.array(check_thresholds(thresholds), dtype=np.float64)
+    out = np.zeros((nq, len(thr)), dtype=np.int64) if counts is None else np.array(counts, dtype=np.int64, copy=True)
+    if out.shape != (nq, len(thr)):
+        raise ValueError("counts has shape %s, expected (%d, %d)" % (out.shape, nq, len(thr)))
+    for q0, r0, d2 in blocks:
+        for j, t in enumerate(thr):
+            out[q0:q0 + d2.shape[0], j] += (d2 <= t).sum(1)
+    return out
+
+
+def check_radii(radii, n):
+    """The radii as an int64 array [n] of integers in [0, 2^32 - 1]."""
+    rad = np.asarray(radii)
+    if rad.dtype.kind not in "iu" or rad.shape != (n,):
+        raise ValueError("need %d integer radii, one per reference row, got %s %s" % (n, rad.dtype, rad.shape))
+    if rad.dtype == np.uint64 and len(rad) and int(rad.max()) > MAX_RADIUS:
+        raise ValueError("radii must lie in [0, 2^32 - 1]")
+    rad = rad.astype(np.int64)
+    if len(rad) and (int(rad.min()) < 0 or int(rad.max()) > MAX_RADIUS):
+        raise ValueError("radii must lie in [0, 2^32 - 1]")
+    return rad
+
+
+def count_within_radii_host(Q, R, radii, counts=None, block=1024):
+    """counts[q] += #{r : d2(q, r) <= radii[r]} as int64 [nq] for the rows of Q [nq, ...] and R [nr, ...] (uint8, same row size D,
+    1 <= D <= 65536) and one integer radius in [0, 2^32 - 1] per row of R — THE definition (csl_gan_amd.manifold
+    builds precision / recall / density / coverage on it).  `counts` holds the sums of earlier calls (zeros when absent) and is not
+    written.  The distances are those of `_d2_blocks`: they and the radii are integers below 2^32 held in float64."""
+    nq, nr, blocks = _d2_blocks(Q, R, block)
+    rad = check_radii(radii, nr).astype(np.float64)
+    out = np.zeros(nq, dtype=np.int64) if counts is None else np.array(counts, dtype=np.int64, copy=True)
+    if out.shape != (nq,):
+        raise ValueError("counts has shape %s, expected (%d,)" % (out.shape, nq))
+    for q0, r0, d2 in blocks:
+        out[q0:q0 + d2.shape[0]] += (d2 <= rad[None, r0:r0 + d2.shape[1]]).sum(1)
     return out
 
 
@@ -120,7 +188,7 @@ class NearestSearch:
     ops.nn_prepare -> ops.nn_min with index_base = the block's first row.  Two pinned and two device staging buffers alternate, so
     block k + 1 is gathered and uploaded while the kernel of block k runs.  Prepared blocks (int8 rows + norms) stay on the device
     for later queries while they fit `resident_gb`; the rest is streamed again.  The query side goes up in chunks of `query_rows`.
-    On the CPU `nearest_host` / `blackbox.count_within_host` run.  Keys and counts do not depend on block_rows, query_rows or the
+    On the CPU `nearest_host` / `count_within_host` run.  Keys and counts do not depend on block_rows, query_rows or the
     device."""
 
     def __init__(self, device, block_rows=16384, resident_gb=8.0, query_rows=16384):
@@ -149,8 +217,10 @@ class NearestSearch:
         self._check_query(cache)
         if not self.on_gpu:
             return nearest_host(cache.x, self.ref.x)
-        with torch.cuda.device(self.device):
-            return self._query_gpu(cache)
+        from . import ops
+        return self._pass(cache, np.empty(len(cache), dtype=np.uint64),
+                          lambda n: torch.full((n,), -1, device=self.device, dtype=torch.int64),      # all ones: nothing seen yet
+                          lambda q, qn, r, rn, s, start, best: ops.nn_min(q, qn, r, rn, start, best), _key_rows)
 
     def _check_query(self, cache):
         if self.ref is None:
@@ -161,23 +231,18 @@ class NearestSearch:
 
     def count_within(self, cache, thresholds):
         """int64 [len(cache), J]: for every query image the number of reference images with d2 <= thresholds[j] (1 <= J <= 4
-        integers in [0, 2^32 - 1], any order) — blackbox.count_within_host on the CPU, ops.nn_count over the same walk of the
-        reference as `query` on a device.  The device counts in 32 bits, so a reference of 2^31 images or more is refused."""
-        from . import blackbox
+        integers in [0, 2^32 - 1], any order) — count_within_host on the CPU, ops.nn_count over the same walk of the reference as
+        `query` on a device.  The device counts in 32 bits, so a reference of 2^31 images or more is refused."""
         self._check_query(cache)
-        thr = blackbox.check_thresholds(thresholds)
+        thr = check_thresholds(thresholds)
         if len(self.ref) >= 2 ** 31:
             raise ValueError("a reference of %d images: counts are held below 2^31" % len(self.ref))
         if not self.on_gpu:
-            return blackbox.count_within_host(cache.x, self.ref.x, thr)
-        with torch.cuda.device(self.device):
-            from . import ops
-
-            def chunk(q, qn):
-                counts = torch.zeros((q.shape[0], len(thr)), device=self.device, dtype=torch.int32)
-                self._walk_reference(lambda start, r, rn: ops.nn_count(q, qn, r, rn, thr, counts))
-                return counts.cpu().numpy().astype(np.int64)
-            return self._query_chunks(cache, np.empty((len(cache), len(thr)), dtype=np.int64), chunk)
+            return count_within_host(cache.x, self.ref.x, thr)
+        from . import ops
+        return self._pass(cache, np.empty((len(cache), len(thr)), dtype=np.int64),
+                          lambda n: torch.zeros((n, len(thr)), device=self.device, dtype=torch.int32),
+                          lambda q, qn, r, rn, s, start, counts: ops.nn_count(q, qn, r, rn, thr, counts), _count_rows)
 
     def kth(self, cache, k, exclude_self=False):
         """uint64 [len(cache), k]: for every query image the k smallest keys over the reference, ascending (`kth_host`; 1 <= k <= 8).
@@ -192,47 +257,42 @@ class NearestSearch:
             raise ValueError("exclude_self searches the fitted reference in itself: pass the cache that fit() was given")
         if not self.on_gpu:
             return kth_host(cache.x, self.ref.x, k, self_base=0 if exclude_self else -1)
+        from . import ops
+        return self._pass(cache, np.empty((len(cache), k), dtype=np.uint64),
+                          lambda n: torch.full((n, k), -1, device=self.device, dtype=torch.int64),
+                          lambda q, qn, r, rn, s, start, best: ops.nn_kth(q, qn, r, rn, start, best, s if exclude_self else -1), _key_rows)
+
+    def count_within_radii(self, cache, radii):
+        """int64 [len(cache)]: for every query image the number of reference images r with d2 <= radii[r]; `radii` holds one
+        integer in [0, 2^32 - 1] per reference image — count_within_radii_host on the CPU, ops.nn_count_radius over the walk of
+        `query` on a device, where the radii stay on the device and are sliced per block."""
+        self._check_query(cache)
+        rad = check_radii(radii, len(self.ref))
+        if len(self.ref) >= 2 ** 31:
+            raise ValueError("a reference of %d images: counts are held below 2^31" % len(self.ref))
+        if not self.on_gpu:
+            return count_within_radii_host(cache.x, self.ref.x, rad)
+        from . import ops
+        rad_dev = torch.from_numpy(rad.astype(np.uint32).view(np.int32)).to(self.device)
+        return self._pass(cache, np.empty(len(cache), dtype=np.int64),
+                          lambda n: torch.zeros(n, device=self.device, dtype=torch.int32),
+                          lambda q, qn, r, rn, s, start, counts: ops.nn_count_radius(q, qn, r, rn, rad_dev[start:start + r.shape[0]], counts),
+                          _count_rows)
+
+    # ---- device path -------------------------------------------------------------------------------------------------------------
+    def _pass(self, cache, out, make, step, rows):
+        """One pass of the query cache over the reference on the device, the frame of all four searches: per query chunk (first row
+        s, prepared q / qn) acc = make(rows of the chunk) is its device accumulator, step(q, qn, r, rn, s, start, acc) is issued for
+        every reference block (first row start, prepared r / rn), and rows(acc) are the chunk's numpy rows of `out`."""
         with torch.cuda.device(self.device):
-            from . import ops
             first = [0]                                                                  # first row of the next chunk: they come in order
 
             def chunk(q, qn):
                 s, first[0] = first[0], first[0] + q.shape[0]
-                best = torch.full((q.shape[0], k), -1, device=self.device, dtype=torch.int64)
-                self._walk_reference(lambda start, r, rn: ops.nn_kth(q, qn, r, rn, start, best, s if exclude_self else -1))
-                return best.cpu().numpy().view(np.uint64)
-            return self._query_chunks(cache, np.empty((len(cache), k), dtype=np.uint64), chunk)
-
-    def count_within_radii(self, cache, radii):
-        """int64 [len(cache)]: for every query image the number of reference images r with d2 <= radii[r]; `radii` holds one
-        integer in [0, 2^32 - 1] per reference image — manifold.count_within_radii_host on the CPU, ops.nn_count_radius over the
-        walk of `query` on a device, where the radii stay on the device and are sliced per block."""
-        from . import manifold
-        self._check_query(cache)
-        rad = manifold.check_radii(radii, len(self.ref))
-        if len(self.ref) >= 2 ** 31:
-            raise ValueError("a reference of %d images: counts are held below 2^31" % len(self.ref))
-        if not self.on_gpu:
-            return manifold.count_within_radii_host(cache.x, self.ref.x, rad)
-        with torch.cuda.device(self.device):
-            from . import ops
-            rad_dev = torch.from_numpy(rad.astype(np.uint32).view(np.int32)).to(self.device)
-
-            def chunk(q, qn):
-                counts = torch.zeros(q.shape[0], device=self.device, dtype=torch.int32)
-                self._walk_reference(lambda start, r, rn: ops.nn_count_radius(q, qn, r, rn, rad_dev[start:start + r.shape[0]], counts))
-                return counts.cpu().numpy().astype(np.int64)
-            return self._query_chunks(cache, np.empty(len(cache), dtype=np.int64), chunk)
-
-    # ---- device path -------------------------------------------------------------------------------------------------------------
-    def _query_gpu(self, cache):
-        from . import ops
-
-        def chunk(q, qn):
-            best = torch.full((q.shape[0],), -1, device=self.device, dtype=torch.int64)  # all ones: nothing seen yet
-            self._walk_reference(lambda start, r, rn: ops.nn_min(q, qn, r, rn, start, best))
-            return best.cpu().numpy().view(np.uint64)
-        return self._query_chunks(cache, np.empty(len(cache), dtype=np.uint64), chunk)
+                acc = make(q.shape[0])
+                self._walk_reference(lambda start, r, rn: step(q, qn, r, rn, s, start, acc))
+                return rows(acc)
+            return self._query_chunks(cache, out, chunk)
 
     def _query_chunks(self, cache, out, fn):
         """out[s : s + cnt] = fn(prepared int8 chunk, its norms) for the query side in chunks of query_rows."""
@@ -297,6 +357,21 @@ class NearestSearch:
                 upload(k + 1)                                   # gathered and sent while the kernel of block k runs
         main.wait_stream(self._copy)
         torch.cuda.synchronize(dev)                             # the staging buffers go out of scope below
+
+
+def _key_rows(best):
+    """The uint64 keys of an int64 device accumulator, on the host."""
+    return best.cpu().numpy().view(np.uint64)
+
+
+def _count_rows(counts):
+    """The int64 counts of an int32 device accumulator, on the host."""
+    return counts.cpu().numpy().astype(np.int64)
+
+
+def fitted_search(ref, device, block_rows=16384, resident_gb=8.0, query_rows=16384):
+    """A NearestSearch on `device`, fitted to the reference cache."""
+    return NearestSearch(device, block_rows=block_rows, resident_gb=resident_gb, query_rows=query_rows).fit(ref)
 
 
 # ---- metrics -------------------------------------------------------------------------------------------------------------------------

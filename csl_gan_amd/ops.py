@@ -1480,6 +1480,33 @@ def _logreg_shapes(X, U, what):
     return X.shape[0], X.shape[1], U.shape[1]
 
 
+def _ovr_eval_outputs(what, X, labels, U, out_loss, out_grad):
+    """What the three ovr_*_eval wrappers share once X [N, D] and U [P, K] have their shapes: labels must be N int32 entries on the
+    device, and (out_loss [K], out_grad like U) are checked, or allocated when absent."""
+    N, K = X.shape[0], U.shape[1]
+    if not labels.is_cuda or labels.dtype != torch.int32 or labels.numel() != N or not labels.is_contiguous():
+        raise RuntimeError("%s: labels must be a contiguous int32 device tensor of %d entries" % (what, N))
+    if out_loss is None:
+        out_loss = torch.empty(K, device=X.device, dtype=torch.float32)
+    elif _chk(out_loss, "out_loss").numel() != K:
+        raise RuntimeError("%s: out_loss has %d entries, expected %d" % (what, out_loss.numel(), K))
+    if out_grad is None:
+        out_grad = torch.empty(tuple(U.shape), device=X.device, dtype=torch.float32)
+    elif _chk(out_grad, "out_grad").numel() != U.numel():
+        raise RuntimeError("%s: out_grad has %d entries, expected %d" % (what, out_grad.numel(), U.numel()))
+    return out_loss, out_grad
+
+
+def _ovr_proba_out(what, M, U, out):
+    """The [M, K] float32 output of the three ovr_*_proba wrappers on U's device: checked, or allocated when absent."""
+    K = U.shape[1]
+    if out is None:
+        out = torch.empty((M, K), device=U.device, dtype=torch.float32)
+    elif _chk(out, "out").numel() != M * K:
+        raise RuntimeError("%s: out has %d entries, expected %d" % (what, out.numel(), M * K))
+    return out
+
+
 def ovr_logreg_eval(X, labels, U, out_loss=None, out_grad=None, ws=None):
     """(loss [K], grad [D + 1, K]) of the K one-vs-rest logistic-regression objectives of include/cslgan.h "downstream classifier" at
     U [D + 1, K] (last row: the intercepts) on X [N, D] fp32 with int32 labels [N] — one evaluation of downstream.py:87's fit, all
@@ -1487,16 +1514,7 @@ def ovr_logreg_eval(X, labels, U, out_loss=None, out_grad=None, ws=None):
     across its evaluations); allocated when absent.  csl_gan_amd.classify.objective_host is the host model."""
     _chk(X, "X"); _chk(U, "U")
     N, D, K = _logreg_shapes(X, U, "ovr_logreg_eval")
-    if not labels.is_cuda or labels.dtype != torch.int32 or labels.numel() != N or not labels.is_contiguous():
-        raise RuntimeError("ovr_logreg_eval: labels must be a contiguous int32 device tensor of %d entries" % N)
-    if out_loss is None:
-        out_loss = torch.empty(K, device=X.device, dtype=torch.float32)
-    elif _chk(out_loss, "out_loss").numel() != K:
-        raise RuntimeError("ovr_logreg_eval: out_loss has %d entries, expected %d" % (out_loss.numel(), K))
-    if out_grad is None:
-        out_grad = torch.empty((D + 1, K), device=X.device, dtype=torch.float32)
-    elif _chk(out_grad, "out_grad").numel() != (D + 1) * K:
-        raise RuntimeError("ovr_logreg_eval: out_grad has %d entries, expected %d" % (out_grad.numel(), (D + 1) * K))
+    out_loss, out_grad = _ovr_eval_outputs("ovr_logreg_eval", X, labels, U, out_loss, out_grad)
     if ws is None:
         ws = torch.empty(max(ovr_logreg_ws_floats(N, D), 2), device=X.device, dtype=torch.float32)
     else:
@@ -1523,10 +1541,7 @@ def ovr_logreg_proba(Xtest, U, out=None):
     else:
         _chk(Xtest, "Xtest")
     M, D, K = _logreg_shapes(Xtest, U, "ovr_logreg_proba")
-    if out is None:
-        out = torch.empty((M, K), device=U.device, dtype=torch.float32)
-    elif _chk(out, "out").numel() != M * K:
-        raise RuntimeError("ovr_logreg_proba: out has %d entries, expected %d" % (out.numel(), M * K))
+    out = _ovr_proba_out("ovr_logreg_proba", M, U, out)
     check(_lib.lib().cslgan_ovr_logreg_proba_f32(_p(Xtest), 1 if Xtest.dtype == torch.uint8 else 0, _p(U), M, D, K, _p(out), _stream()),
           "ovr_logreg_proba")
     return out
@@ -1546,16 +1561,7 @@ def ovr_logreg_eval_u8(X, labels, U, out_loss=None, out_grad=None, ws=None):
     ovr_logreg_u8_ws_floats(N, D) entries; allocated when absent.  csl_gan_amd.classify.objective_host_bytes is the host model."""
     _chk_bytes(X, "X"); _chk(U, "U")
     N, D, K = _logreg_shapes(X, U, "ovr_logreg_eval_u8")
-    if not labels.is_cuda or labels.dtype != torch.int32 or labels.numel() != N or not labels.is_contiguous():
-        raise RuntimeError("ovr_logreg_eval_u8: labels must be a contiguous int32 device tensor of %d entries" % N)
-    if out_loss is None:
-        out_loss = torch.empty(K, device=X.device, dtype=torch.float32)
-    elif _chk(out_loss, "out_loss").numel() != K:
-        raise RuntimeError("ovr_logreg_eval_u8: out_loss has %d entries, expected %d" % (out_loss.numel(), K))
-    if out_grad is None:
-        out_grad = torch.empty((D + 1, K), device=X.device, dtype=torch.float32)
-    elif _chk(out_grad, "out_grad").numel() != (D + 1) * K:
-        raise RuntimeError("ovr_logreg_eval_u8: out_grad has %d entries, expected %d" % (out_grad.numel(), (D + 1) * K))
+    out_loss, out_grad = _ovr_eval_outputs("ovr_logreg_eval_u8", X, labels, U, out_loss, out_grad)
     if ws is None:
         ws = torch.empty(max(ovr_logreg_u8_ws_floats(N, D), 2), device=X.device, dtype=torch.float32)
     else:
@@ -1574,10 +1580,7 @@ def ovr_logreg_proba_u8(Xtest, U, out=None):
     """P [M, K] = sigmoid(z) / sum_k sigmoid(z), z = (Xtest / 255) U[:D] + U[D], for uint8 Xtest [M, D] with any 1 <= D <= 65536."""
     _chk(U, "U"); _chk_bytes(Xtest, "Xtest")
     M, D, K = _logreg_shapes(Xtest, U, "ovr_logreg_proba_u8")
-    if out is None:
-        out = torch.empty((M, K), device=U.device, dtype=torch.float32)
-    elif _chk(out, "out").numel() != M * K:
-        raise RuntimeError("ovr_logreg_proba_u8: out has %d entries, expected %d" % (out.numel(), M * K))
+    out = _ovr_proba_out("ovr_logreg_proba_u8", M, U, out)
     check(_lib.lib().cslgan_ovr_logreg_proba_u8(_p(Xtest), _p(U), M, D, K, _p(out), _stream()), "ovr_logreg_proba_u8")
     return out
 
@@ -1602,16 +1605,7 @@ def ovr_mlp_eval_u8(X, labels, U, hidden, alpha=1.0, out_loss=None, out_grad=Non
     csl_gan_amd.classify.objective_mlp_host_bytes is the host model."""
     _chk_bytes(X, "X"); _chk(U, "U")
     N, D, K, H = _mlp_shapes(X, U, hidden, "ovr_mlp_eval_u8")
-    if not labels.is_cuda or labels.dtype != torch.int32 or labels.numel() != N or not labels.is_contiguous():
-        raise RuntimeError("ovr_mlp_eval_u8: labels must be a contiguous int32 device tensor of %d entries" % N)
-    if out_loss is None:
-        out_loss = torch.empty(K, device=X.device, dtype=torch.float32)
-    elif _chk(out_loss, "out_loss").numel() != K:
-        raise RuntimeError("ovr_mlp_eval_u8: out_loss has %d entries, expected %d" % (out_loss.numel(), K))
-    if out_grad is None:
-        out_grad = torch.empty_like(U)
-    elif _chk(out_grad, "out_grad").numel() != U.numel():
-        raise RuntimeError("ovr_mlp_eval_u8: out_grad has %d entries, expected %d" % (out_grad.numel(), U.numel()))
+    out_loss, out_grad = _ovr_eval_outputs("ovr_mlp_eval_u8", X, labels, U, out_loss, out_grad)
     need = ovr_mlp_u8_ws_floats(N, D, K, H)
     if need == 0:
         raise RuntimeError("ovr_mlp_eval_u8: N = %d, D = %d, K = %d, hidden = %d is outside 1 <= N < 2^31, 1 <= D <= 65536, 2 <= K <= 16, "
@@ -1629,10 +1623,7 @@ def ovr_mlp_proba_u8(Xtest, U, hidden, out=None):
     """P [M, K] = sigmoid(z) / sum_k sigmoid(z) of the K networks of ovr_mlp_eval_u8 on uint8 Xtest [M, D]."""
     _chk(U, "U"); _chk_bytes(Xtest, "Xtest")
     M, D, K, H = _mlp_shapes(Xtest, U, hidden, "ovr_mlp_proba_u8")
-    if out is None:
-        out = torch.empty((M, K), device=U.device, dtype=torch.float32)
-    elif _chk(out, "out").numel() != M * K:
-        raise RuntimeError("ovr_mlp_proba_u8: out has %d entries, expected %d" % (out.numel(), M * K))
+    out = _ovr_proba_out("ovr_mlp_proba_u8", M, U, out)
     check(_lib.lib().cslgan_ovr_mlp_proba_u8(_p(Xtest), _p(U), M, D, K, H, _p(out), _stream()), "ovr_mlp_proba_u8")
     return out
 
@@ -1671,16 +1662,27 @@ def nn_prepare(u8, out=None, out_sqnorm=None):
     return out, out_sqnorm
 
 
+def _nn_operands(what, q, qn, r, rn, extra):
+    """(nq, nr, Dp) of the prepared operands q [nq, Dp] / r [nr, Dp] (int8) with their norms qn / rn (int32), the check that the
+    four nn_* wrappers share; `extra`: the entry's further tensors as (tensor, name, dtype).  The types first — a wrong one is
+    refused wherever the tensor lives — then device and contiguity, then the shapes of the operands; the shapes of `extra` are the
+    caller's."""
+    args = ((q, "q", torch.int8), (r, "r", torch.int8), (qn, "qn", torch.int32), (rn, "rn", torch.int32)) + tuple(extra)
+    for t, name, dt in args:
+        if t.dtype != dt:
+            raise RuntimeError("%s: %s must be a contiguous %s tensor" % (what, name, str(dt).replace("torch.", "")))
+    for t, name, dt in args:
+        _chk_dev(t, name, dt, what)
+    if q.dim() != 2 or r.dim() != 2 or q.shape[1] != r.shape[1]:
+        raise RuntimeError("%s: need q [nq, Dp] and r [nr, Dp], got %s and %s" % (what, tuple(q.shape), tuple(r.shape)))
+    return q.shape[0], r.shape[0], q.shape[1]
+
+
 def nn_min(q, qn, r, rn, index_base, best):
     """best[i] = min(best[i], min_j (d2(q_i, r_j) << 32 | index_base + j)) as uint64, in place.  q [nq, Dp] / r [nr, Dp]: prepared
     int8 operands of nn_prepare with their int32 squared norms qn / rn; best: int64 device tensor [nq] that the caller filled with
     -1 (all ones) once.  Ties go to the smallest index.  csl_gan_amd.neighbours.nearest_host is the host model."""
-    for t, name, dt in ((q, "q", torch.int8), (r, "r", torch.int8), (qn, "qn", torch.int32), (rn, "rn", torch.int32), (best, "best", torch.int64)):
-        _chk_dev(t, name, dt, "nn_min")
-    if q.dim() != 2 or r.dim() != 2 or q.shape[1] != r.shape[1]:
-        raise RuntimeError("nn_min: need q [nq, Dp] and r [nr, Dp], got %s and %s" % (tuple(q.shape), tuple(r.shape)))
-    nq, Dp = q.shape
-    nr = r.shape[0]
+    nq, nr, Dp = _nn_operands("nn_min", q, qn, r, rn, [(best, "best", torch.int64)])
     if qn.numel() != nq or rn.numel() != nr or best.numel() != nq:
         raise RuntimeError("nn_min: qn / rn / best have %d / %d / %d entries, expected %d / %d / %d" % (qn.numel(), rn.numel(), best.numel(), nq, nr, nq))
     check(_lib.lib().cslgan_nn_min_i8(_p(q), _p(qn), nq, _p(r), _p(rn), nr, Dp, int(index_base), _p(best), _stream()), "nn_min")
@@ -1691,20 +1693,12 @@ def nn_count(q, qn, r, rn, thresholds, counts):
     """counts[i, j] += #{k : d2(q_i, r_k) <= thresholds[j]}, in place.  q / qn / r / rn as for nn_min; thresholds: 1 .. 4 Python
     integers in [0, 2^32 - 1], any order; counts: int32 device tensor [nq, J] that the caller zeroed once.  The device adds as
     uint32 and torch reads int32: the TOTAL count of an entry over all calls must stay below 2^31 on this path.
-    csl_gan_amd.blackbox.count_within_host is the host model."""
-    args = ((q, "q", torch.int8), (r, "r", torch.int8), (qn, "qn", torch.int32), (rn, "rn", torch.int32), (counts, "counts", torch.int32))
-    for t, name, dt in args:                            # the types first: a wrong one is refused wherever the tensor lives
-        if t.dtype != dt:
-            raise RuntimeError("nn_count: %s must be a contiguous %s tensor" % (name, str(dt).replace("torch.", "")))
-    for t, name, dt in args:
-        _chk_dev(t, name, dt, "nn_count")
-    if q.dim() != 2 or r.dim() != 2 or q.shape[1] != r.shape[1]:
-        raise RuntimeError("nn_count: need q [nq, Dp] and r [nr, Dp], got %s and %s" % (tuple(q.shape), tuple(r.shape)))
+    csl_gan_amd.neighbours.count_within_host is the host model."""
+    nq, nr, Dp = _nn_operands("nn_count", q, qn, r, rn, [(counts, "counts", torch.int32)])
     thr = [int(t) for t in thresholds]
     if not 1 <= len(thr) <= 4 or any(t < 0 or t > 0xFFFFFFFF for t in thr):
         raise RuntimeError("nn_count: need 1 .. 4 thresholds in [0, 2^32 - 1], got %s" % (thr,))
-    nq, Dp = q.shape
-    nr, J = r.shape[0], len(thr)
+    J = len(thr)
     if qn.numel() != nq or rn.numel() != nr or tuple(counts.shape) != (nq, J):
         raise RuntimeError("nn_count: qn / rn have %d / %d entries and counts the shape %s, expected %d / %d and (%d, %d)"
                            % (qn.numel(), rn.numel(), tuple(counts.shape), nq, nr, nq, J))
@@ -1727,16 +1721,7 @@ def nn_kth(q, qn, r, rn, index_base, best, self_base=-1):
     bring disjoint index ranges.  The workspace is ONE device tensor cached per device, whatever the stream: calls on different streams
     of one device would race on it, so keep nn_kth on one stream per device (NearestSearch does).  csl_gan_amd.neighbours.kth_host is the host
     model."""
-    args = ((q, "q", torch.int8), (r, "r", torch.int8), (qn, "qn", torch.int32), (rn, "rn", torch.int32), (best, "best", torch.int64))
-    for t, name, dt in args:                            # the types first: a wrong one is refused wherever the tensor lives
-        if t.dtype != dt:
-            raise RuntimeError("nn_kth: %s must be a contiguous %s tensor" % (name, str(dt).replace("torch.", "")))
-    for t, name, dt in args:
-        _chk_dev(t, name, dt, "nn_kth")
-    if q.dim() != 2 or r.dim() != 2 or q.shape[1] != r.shape[1]:
-        raise RuntimeError("nn_kth: need q [nq, Dp] and r [nr, Dp], got %s and %s" % (tuple(q.shape), tuple(r.shape)))
-    nq, Dp = q.shape
-    nr = r.shape[0]
+    nq, nr, Dp = _nn_operands("nn_kth", q, qn, r, rn, [(best, "best", torch.int64)])
     if best.dim() != 2 or best.shape[0] != nq or not 1 <= best.shape[1] <= 8:
         raise RuntimeError("nn_kth: best has the shape %s, expected (%d, k) with k in 1 .. 8" % (tuple(best.shape), nq))
     k = best.shape[1]
@@ -1756,19 +1741,9 @@ def nn_kth(q, qn, r, rn, index_base, best, self_base=-1):
 def nn_count_radius(q, qn, r, rn, radius, counts):
     """counts[i] += #{j : d2(q_i, r_j) <= radius[j]}, in place, compared as unsigned values.  q / qn / r / rn as for nn_min; radius:
     int32 device tensor [nr] holding the uint32 bits; counts: int32 device tensor [nq] that the caller zeroed once (the device adds
-    uint32: the total of an entry must stay below 2^31 on this path).  csl_gan_amd.manifold.count_within_radii_host is the host
+    uint32: the total of an entry must stay below 2^31 on this path).  csl_gan_amd.neighbours.count_within_radii_host is the host
     model."""
-    args = ((q, "q", torch.int8), (r, "r", torch.int8), (qn, "qn", torch.int32), (rn, "rn", torch.int32), (radius, "radius", torch.int32),
-            (counts, "counts", torch.int32))
-    for t, name, dt in args:
-        if t.dtype != dt:
-            raise RuntimeError("nn_count_radius: %s must be a contiguous %s tensor" % (name, str(dt).replace("torch.", "")))
-    for t, name, dt in args:
-        _chk_dev(t, name, dt, "nn_count_radius")
-    if q.dim() != 2 or r.dim() != 2 or q.shape[1] != r.shape[1]:
-        raise RuntimeError("nn_count_radius: need q [nq, Dp] and r [nr, Dp], got %s and %s" % (tuple(q.shape), tuple(r.shape)))
-    nq, Dp = q.shape
-    nr = r.shape[0]
+    nq, nr, Dp = _nn_operands("nn_count_radius", q, qn, r, rn, [(radius, "radius", torch.int32), (counts, "counts", torch.int32)])
     if qn.numel() != nq or rn.numel() != nr or tuple(radius.shape) != (nr,) or tuple(counts.shape) != (nq,):
         raise RuntimeError("nn_count_radius: qn / rn have %d / %d entries, radius and counts the shapes %s and %s; expected %d / %d, (%d,) and (%d,)"
                            % (qn.numel(), rn.numel(), tuple(radius.shape), tuple(counts.shape), nq, nr, nr, nq))

@@ -11,30 +11,21 @@ distances as int64 .npy; with --save the figures are merged into `<outputs_dir>/
 the same on `-d cpu` (the host models) and on a device, and so are the four ratios.
 """
 import argparse
-import json
-import os
 import sys
 
 import numpy as np
 
-from . import manifold, pipeline
-from .nearest import _label, _same_geometry
+from . import cache_cli, manifold, pipeline
 
 
 def build_parser():
     ap = argparse.ArgumentParser(description="Precision, recall, density and coverage of a synthetic image cache")
-    ap.add_argument("--syn_cache", type=str, nargs="+", required=True, help="uint8 image cache(s) of synthetic samples")
+    cache_cli.add_common_arguments(ap, "prdc", "uint8 image cache(s) of synthetic samples", "keep radii, counts and distances as .npy here")
+    cache_cli.add_search_arguments(ap, "reference images per device block", "device memory for prepared reference blocks kept between queries")
     ap.add_argument("--train_cache", type=str, required=True, help="uint8 image cache of the training set")
     ap.add_argument("--nontrain_cache", type=str, default=None, help="uint8 image cache of the held-out set")
     ap.add_argument("--baseline", default=False, action="store_true", help="also report the held-out set as if it were the samples")
     ap.add_argument("-k", type=int, default=5, help="neighbours of the radius, 1 .. 8")
-    ap.add_argument("-d", "--device", type=str, default="cpu")
-    ap.add_argument("--block_rows", type=int, default=16384, help="reference images per device block")
-    ap.add_argument("--resident_gb", type=float, default=8.0, help="device memory for prepared reference blocks kept between queries")
-    ap.add_argument("--values_dir", type=str, default=None, help="keep radii, counts and distances as .npy here")
-    ap.add_argument("--outputs_dir", type=str, default="outputs/")
-    ap.add_argument("--name", type=str, default="prdc")
-    ap.add_argument("--save", default=False, action="store_true", help="merge the figures into <outputs_dir>/<name>.json")
     return ap
 
 
@@ -45,19 +36,14 @@ def main(argv=None):
     if not 1 <= a.k <= manifold.MAX_K:
         raise SystemExit("-k %d: the radius is that of neighbour 1 .. %d" % (a.k, manifold.MAX_K))
     train = pipeline.CachedImages(a.train_cache)
-    sets = [(_label(p), p, pipeline.CachedImages(p)) for p in a.syn_cache]
-    if len({lab for lab, _, _ in sets}) != len(sets):
-        raise SystemExit("two --syn_cache share the name %s" % ", ".join(sorted(lab for lab, _, _ in sets)))
-    if a.baseline:
-        sets.append(("baseline_heldout", a.nontrain_cache, pipeline.CachedImages(a.nontrain_cache)))
-    for _, p, c in sets:
-        _same_geometry(train, a.train_cache, c, p)
+    extra = [("baseline_heldout", a.nontrain_cache, pipeline.CachedImages(a.nontrain_cache))] if a.baseline else []
+    sets = cache_cli.open_syn_caches(a.syn_cache, train, a.train_cache, [(p, c) for _, p, c in extra]) + extra
     try:
         manifold.check_sizes(a.k, **dict([(a.train_cache, train)] + [(p, c) for _, p, c in sets]))
     except ValueError as e:
         raise SystemExit(str(e))
 
-    kw = dict(device=a.device, block_rows=a.block_rows, resident_gb=a.resident_gb)
+    kw = cache_cli.search_kw(a)
     search, rad_real = manifold.real_side(train, a.k, **kw)              # once for all synthetic caches
     stats, values = {}, {"rad_real": rad_real}
     for lab, _, c in sets:
@@ -67,23 +53,8 @@ def main(argv=None):
         values.update({"%s_%s" % (lab, name): arr for name, arr in v.items()})
         print("%s: %d samples against %d images, k = %d: precision %.4f, recall %.4f, density %.4f, coverage %.4f"
               % (lab, m["n_syn"], m["n_real"], m["k"], m["precision"], m["recall"], m["density"], m["coverage"]))
-    if a.values_dir:
-        os.makedirs(a.values_dir, exist_ok=True)
-        for name, arr in values.items():
-            np.save(os.path.join(a.values_dir, name + ".npy"), np.asarray(arr, dtype=np.int64))
-    print(json.dumps(stats, indent=4))
-    if a.save:
-        os.makedirs(a.outputs_dir, exist_ok=True)
-        json_path = os.path.join(a.outputs_dir, a.name + ".json")
-        merged = {}
-        if os.path.exists(json_path):
-            with open(json_path) as f:
-                merged = json.load(f)
-        merged.update(stats)
-        with open(json_path, "w") as f:
-            json.dump(merged, f)
-        print("saved %s" % json_path)
-    return stats
+    cache_cli.save_values(a.values_dir, {name: np.asarray(arr, dtype=np.int64) for name, arr in values.items()})
+    return cache_cli.report(a, stats)
 
 
 if __name__ == "__main__":

@@ -15,19 +15,17 @@ the Monte-Carlo scores.  --values_dir keeps the distances and counts (int64) as 
 `<outputs_dir>/<name>.json`.  Every integer printed is exact and the same on `-d cpu` (the host model) and on a device.
 """
 import argparse
-import json
-import os
 import sys
 
 import numpy as np
 
-from . import audit, blackbox, pipeline
-from .nearest import _label, _same_geometry
+from . import audit, blackbox, cache_cli, pipeline
 
 
 def build_parser():
     ap = argparse.ArgumentParser(description="Black-box membership audit of a synthetic image cache")
-    ap.add_argument("--syn_cache", type=str, nargs="+", required=True, help="uint8 image cache(s) of synthetic samples")
+    cache_cli.add_common_arguments(ap, "sample_attack", "uint8 image cache(s) of synthetic samples", "keep the distances and counts as .npy here")
+    cache_cli.add_search_arguments(ap, "synthetic images per device block", "device memory for prepared blocks kept between queries")
     ap.add_argument("--train_cache", type=str, required=True, help="uint8 image cache of the training set")
     ap.add_argument("--nontrain_cache", type=str, required=True, help="uint8 image cache of the held-out set")
     ap.add_argument("--calib_cache", type=str, default=None, help="uint8 image cache of a reference generator's samples (calibrated attack)")
@@ -37,13 +35,6 @@ def build_parser():
     ap.add_argument("--data_prop", type=float, default=0.1, help="share of training data in the adversary's pool")
     ap.add_argument("--asr_iters", type=int, default=10000, help="subset pairs drawn for the attack success rate")
     ap.add_argument("--seed", type=int, default=0, help="seed of the subset stream")
-    ap.add_argument("-d", "--device", type=str, default="cpu")
-    ap.add_argument("--block_rows", type=int, default=16384, help="synthetic images per device block")
-    ap.add_argument("--resident_gb", type=float, default=8.0, help="device memory for prepared blocks kept between queries")
-    ap.add_argument("--values_dir", type=str, default=None, help="keep the distances and counts as .npy here")
-    ap.add_argument("--outputs_dir", type=str, default="outputs/")
-    ap.add_argument("--name", type=str, default="sample_attack")
-    ap.add_argument("--save", default=False, action="store_true", help="merge the figures into <outputs_dir>/<name>.json")
     return ap
 
 
@@ -55,25 +46,18 @@ def main(argv=None):
         raise SystemExit("--percentiles must be distinct values in [0, 100], got %s" % a.percentiles)
     train, heldout = pipeline.CachedImages(a.train_cache), pipeline.CachedImages(a.nontrain_cache)
     calib = pipeline.CachedImages(a.calib_cache) if a.calib_cache else None
-    syns = [(p, pipeline.CachedImages(p)) for p in a.syn_cache]
-    _same_geometry(train, a.train_cache, heldout, a.nontrain_cache)
-    if calib is not None:
-        _same_geometry(train, a.train_cache, calib, a.calib_cache)
-    for p, c in syns:
-        _same_geometry(train, a.train_cache, c, p)
-    if len({_label(p) for p, _ in syns}) != len(syns):
-        raise SystemExit("two --syn_cache share the name %s" % ", ".join(sorted(_label(p) for p, _ in syns)))
+    syns = cache_cli.open_syn_caches(a.syn_cache, train, a.train_cache,
+                                     [(a.nontrain_cache, heldout)] + ([(a.calib_cache, calib)] if calib is not None else []))
     n, m = int(a.pool * a.data_prop), int(a.pool * (1 - a.data_prop))
     try:
         audit.check_sizes(len(train), len(heldout), n, m)
     except ValueError as e:
         raise SystemExit("the pool of %d does not fit the caches: %s" % (a.pool, e))
 
-    kw = dict(device=a.device, block_rows=a.block_rows, resident_gb=a.resident_gb)
+    kw = cache_cli.search_kw(a)
     ref = dict(zip(("d2ref_train", "d2ref_heldout"), blackbox.d2min_to(calib, (train, heldout), **kw))) if calib is not None else {}
     stats, values = {}, {}
-    for p, c in syns:
-        lab = _label(p)
+    for lab, _, c in syns:
         v = dict(blackbox.run_attack(c, train, heldout, a.percentiles, **kw), **ref)
         values[lab] = v
         m_ = blackbox.sample_attack_metrics(v["d2_train"], v["d2_heldout"], v["counts_train"], v["counts_heldout"], a.percentiles, v["eps2"],
@@ -85,25 +69,9 @@ def main(argv=None):
             s = m_[name]
             print("  %-8s ASR %.4f (+- %.4f)  AUC %.4f  TPR at 1 %% / 0.1 %% FPR %.4f / %.4f"
                   % (name, s["asr"], s["asr_stderr"], s["auc"], s["tpr_at_fpr_0.01"], s["tpr_at_fpr_0.001"]))
-    if a.values_dir:
-        os.makedirs(a.values_dir, exist_ok=True)
-        for lab, v in values.items():
-            for k, arr in v.items():
-                if k != "eps2":
-                    np.save(os.path.join(a.values_dir, "%s_%s.npy" % (lab, k)), np.asarray(arr, dtype=np.int64))
-    print(json.dumps(stats, indent=4))
-    if a.save:
-        os.makedirs(a.outputs_dir, exist_ok=True)
-        json_path = os.path.join(a.outputs_dir, a.name + ".json")
-        merged = {}
-        if os.path.exists(json_path):
-            with open(json_path) as f:
-                merged = json.load(f)
-        merged.update(stats)
-        with open(json_path, "w") as f:
-            json.dump(merged, f)
-        print("saved %s" % json_path)
-    return stats
+    cache_cli.save_values(a.values_dir, {"%s_%s" % (lab, k): np.asarray(arr, dtype=np.int64)
+                                         for lab, v in values.items() for k, arr in v.items() if k != "eps2"})
+    return cache_cli.report(a, stats)
 
 
 if __name__ == "__main__":

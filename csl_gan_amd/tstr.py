@@ -17,40 +17,29 @@ and L2 penalty --alpha (csl_gan_amd.classify.OvrMlp, started from --seed; --max_
 "classifier", "hidden", "alpha" and "seed" as well, and U is kept in OvrMlp's layout [(D + 2) hidden + 1, K].
 """
 import argparse
-import json
-import os
 import sys
 
 import numpy as np
 import torch
 
-from . import classify, pipeline
-from .nearest import _label, _same_geometry
+from . import cache_cli, classify, pipeline
+from .cache_cli import cache_rows  # noqa: F401  (scripts/tstr_bench.py and scripts/mlp_bench.py reach it as tstr.cache_rows)
 
 
 def build_parser():
     ap = argparse.ArgumentParser(description="Train-on-synthetic, test-on-real classifier utility of labelled image caches")
-    ap.add_argument("--syn_cache", type=str, nargs="+", required=True, help="labelled uint8 image cache(s) of synthetic samples")
+    cache_cli.add_common_arguments(ap, "tstr", "labelled uint8 image cache(s) of synthetic samples",
+                                   "keep the test probabilities and the coefficients as .npy here")
     ap.add_argument("--test_cache", type=str, required=True, help="labelled uint8 image cache of real test images")
     ap.add_argument("--train_cache", type=str, default=None, help="labelled uint8 image cache of the training set (for --baseline)")
     ap.add_argument("--baseline", default=False, action="store_true", help="also fit on the training set itself")
-    ap.add_argument("-d", "--device", type=str, default="cpu")
     ap.add_argument("--gtol_rel", type=float, default=None, help="a class has converged when max|gradient| <= gtol_rel * n")
     ap.add_argument("--max_iter", type=int, default=None, help="L-BFGS iterations per class (default: 2000 for lr, 200 for mlp)")
     ap.add_argument("--classifier", type=str, default="lr", choices=["lr", "mlp"], help="one-vs-rest logistic regression or MLP")
     ap.add_argument("--hidden", type=int, default=100, help="mlp: hidden ReLU units per class, 1 .. %d" % classify.MAX_HIDDEN)
     ap.add_argument("--alpha", type=float, default=1.0, help="mlp: L2 penalty on the weights, >= 0")
     ap.add_argument("--seed", type=int, default=0, help="mlp: seed of the initial point")
-    ap.add_argument("--values_dir", type=str, default=None, help="keep the test probabilities and the coefficients as .npy here")
-    ap.add_argument("--outputs_dir", type=str, default="outputs/")
-    ap.add_argument("--name", type=str, default="tstr")
-    ap.add_argument("--save", default=False, action="store_true", help="merge the figures into <outputs_dir>/<name>.json")
     return ap
-
-
-def cache_rows(cache):
-    """(bytes [n, H*W*C] uint8, a copy in memory; labels [n] int64)."""
-    return np.array(cache.x, dtype=np.uint8).reshape(len(cache), -1), np.asarray(cache.labels, dtype=np.int64).reshape(-1)
 
 
 def n_classes_of(labels, path):
@@ -98,13 +87,8 @@ def main(argv=None):
     mlp = {"hidden": a.hidden, "alpha": a.alpha, "seed": a.seed} if a.classifier == "mlp" else None
     max_iter = a.max_iter if a.max_iter is not None else (2000 if mlp is None else 200)
     test = pipeline.CachedImages(a.test_cache)
-    sets = [(_label(p), p, pipeline.CachedImages(p)) for p in a.syn_cache]
-    if len({lab for lab, _, _ in sets}) != len(sets):
-        raise SystemExit("two --syn_cache share the name %s" % ", ".join(sorted(lab for lab, _, _ in sets)))
-    if a.baseline:
-        sets.append(("baseline_train", a.train_cache, pipeline.CachedImages(a.train_cache)))
-    for _, p, c in sets:
-        _same_geometry(test, a.test_cache, c, p)
+    extra = [("baseline_train", a.train_cache, pipeline.CachedImages(a.train_cache))] if a.baseline else []
+    sets = cache_cli.open_syn_caches(a.syn_cache, test, a.test_cache, [(p, c) for _, p, c in extra]) + extra
     D = test.H * test.W * test.C
     if not 1 <= D <= 65536:
         raise SystemExit("%s: rows of %d bytes; the classifier takes 1 .. 65536" % (a.test_cache, D))
@@ -126,29 +110,12 @@ def main(argv=None):
         m, P, U = fit_and_score(x, y, classes[lab], test_x, test_yt, device, a.gtol_rel, max_iter, mlp)
         stats[lab] = m
         values[lab + "_P"], values[lab + "_U"] = P, U
-        s = m["solver"]
         print("%s: fitted on %d rows, scored %d: AUROC %.6f, accuracy %.4f (%d / %d)" % (
             lab, m["n_train"], m["n_test"], m["auroc_micro"], m["accuracy"], m["accuracy_hits"], m["n_test"]))
         print("   per class: %s" % " ".join("%.4f" % v for v in m["auroc_per_class"]))
-        print("   solver: iterations %s  evaluations %s  max|g| %.3g (stop at %.3g)  stalled %s" % (
-            s["iterations"], s["evaluations"], max(s["grad_norm"]), s["gtol"], [k for k, v in enumerate(s["stalled"]) if v] or "none"))
-    if a.values_dir:
-        os.makedirs(a.values_dir, exist_ok=True)
-        for name, arr in values.items():
-            np.save(os.path.join(a.values_dir, name + ".npy"), arr)
-    print(json.dumps(stats, indent=4))
-    if a.save:
-        os.makedirs(a.outputs_dir, exist_ok=True)
-        json_path = os.path.join(a.outputs_dir, a.name + ".json")
-        merged = {}
-        if os.path.exists(json_path):
-            with open(json_path) as f:
-                merged = json.load(f)
-        merged.update(stats)
-        with open(json_path, "w") as f:
-            json.dump(merged, f)
-        print("saved %s" % json_path)
-    return stats
+        print(classify.solver_line(m["solver"]))
+    cache_cli.save_values(a.values_dir, values)
+    return cache_cli.report(a, stats)
 
 
 if __name__ == "__main__":

@@ -290,3 +290,5 @@ def test_the_ops_refuse_cpu_tensors_and_wrong_types():
     z8, z32, z64 = torch.zeros(4, 64, dtype=torch.int8), torch.zeros(4, dtype=torch.int32), torch.zeros(4, dtype=torch.int64)
     with pytest.raises(RuntimeError, match="device tensor"):
         ops.nn_min(z8, z32, z8, z32, 0, z64)
+    with pytest.raises(RuntimeError, match="nn_min: best must be a contiguous int64 tensor"):
+        ops.nn_min(z8, z32, z8, z32, 0, z32)
