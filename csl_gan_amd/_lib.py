@@ -36,6 +36,7 @@ EXPORTS = [
     "cslgan_ovr_logreg_ws_floats", "cslgan_ovr_logreg_eval_f32", "cslgan_ovr_logreg_proba_f32",
     "cslgan_ovr_logreg_u8_ws_floats", "cslgan_ovr_logreg_eval_u8", "cslgan_ovr_logreg_proba_u8",
     "cslgan_ovr_mlp_u8_ws_floats", "cslgan_ovr_mlp_eval_u8", "cslgan_ovr_mlp_proba_u8",
+    "cslgan_class_moments_u8", "cslgan_nb_score_gauss_u8", "cslgan_nb_score_bern_u8",
     "cslgan_nn_padded_dim", "cslgan_nn_prepare_u8", "cslgan_nn_min_i8", "cslgan_nn_count_i8",
     "cslgan_nn_kth_workspace_bytes", "cslgan_nn_kth_i8", "cslgan_nn_count_radius_i8",
 ]
@@ -163,6 +164,9 @@ def lib():
         "cslgan_ovr_logreg_proba_u8": [vp, vp, i64, i32, i32, vp, vp],
         "cslgan_ovr_mlp_eval_u8": [vp, vp, vp, i64, i32, i32, i32, f32, vp, vp, vp, vp],
         "cslgan_ovr_mlp_proba_u8": [vp, vp, i64, i32, i32, i32, vp, vp],
+        "cslgan_class_moments_u8": [vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp],
+        "cslgan_nb_score_gauss_u8": [vp, vp, vp, i64, i32, i32, vp, vp],
+        "cslgan_nb_score_bern_u8": [vp, vp, i64, i32, i32, i32, vp, vp],
         "cslgan_nn_padded_dim": [i32],
         "cslgan_nn_prepare_u8": [vp, i64, i32, i32, vp, vp, vp],
         "cslgan_nn_min_i8": [vp, vp, i64, vp, vp, i64, i32, i64, vp, vp],

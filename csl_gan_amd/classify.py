@@ -22,6 +22,11 @@ cslgan_ovr_logreg_eval_u8 / cslgan_ovr_logreg_proba_u8 on a device, and `accurac
 `OvrMlp` is the reference's second classifier, OneVsRestClassifier(MLPClassifier(alpha=1)) of downstream.py:82, on the
 same byte rows: one hidden ReLU layer per class, `objective_mlp_host_bytes` / `proba_mlp_host_bytes` THE definition, the same
 `lbfgs_columns`, cslgan_ovr_mlp_eval_u8 / cslgan_ovr_mlp_proba_u8 (csrc/mlp_kernels.hip) on a device.
+
+`NaiveBayes` is GaussianNB() and BernoulliNB(alpha=.01) of downstream.py:76-78 on the same byte rows: closed forms of
+per-class, per-feature moments, which on bytes are integers — `class_moments_host_bytes` THE definition, equalled exactly by
+cslgan_class_moments_u8 — and one derivation of the tables on the host for both paths (`gnb_tables`, `bnb_tables`), so a host fit
+and a device fit are the same bits; `jll_host_bytes` is the float64 model of cslgan_nb_score_gauss_u8 / _bern_u8 (csrc/nb_kernels.hip).
 """
 from __future__ import annotations
 
@@ -415,6 +420,199 @@ class OvrMlp:
         """P [M, K]: ops.ovr_mlp_proba_u8 on a device (float32), proba_mlp_host_bytes on the host (float64)."""
         return _proba(self, _bytes_rows(Xu8), lambda X, U: proba_mlp_host_bytes(X, U, self.H),
                       lambda X, U: ops.ovr_mlp_proba_u8(X.contiguous(), U, self.H))
+
+
+# ---- naive Bayes on cache bytes (DESIGN.md §6l) -----------------------------------------------------------------------------------------
+
+NB_KINDS = ("gnb", "bnb")
+
+
+def _check_binarize(binarize):
+    b = int(binarize)
+    if b != binarize or not 0 <= b <= 254:
+        raise ValueError("binarize must be a byte threshold in 0 .. 254, got %r" % (binarize,))
+    return b
+
+
+def _check_row_size(X):
+    if X.dim() != 2 or not 1 <= X.shape[1] <= 65536:
+        raise ValueError("need rows of 1 .. 65536 bytes, got %s" % (tuple(X.shape),))
+    return X
+
+
+def class_moments_host_bytes(Xu8, labels, K, binarize=0, block=2048):
+    """{"n": [K], "s1": [K, D], "s2": [K, D], "cnt": [K, D]}, int64 torch on the CPU: per class k the number of rows with that label, and
+    per feature sum b, sum b^2 and the number of those rows with b > binarize (a byte threshold in 0 .. 254; 0 is scikit-learn's
+    binarize=0.0 on x = b / 255).  A label outside 0 .. K-1 belongs to no class.  In row blocks of `block`; a block's sums are
+    products of small integers in float64 (exact below 2^53) and are added in int64 — THE definition of the moments."""
+    X = _check_row_size(_bytes_rows(Xu8)).cpu()
+    y = torch.as_tensor(labels).long().reshape(-1).cpu()
+    K, thr = _check_classes(K), _check_binarize(binarize)
+    N, D = X.shape
+    if y.numel() != N:
+        raise ValueError("need X [N, D] and labels [N], got %s and %s" % (tuple(X.shape), tuple(y.shape)))
+    block = max(1, min(int(block), 1 << 20))                         # 2^20 rows of 255^2 stay far below 2^53
+    cls = torch.arange(K)[None, :]
+    out = {"n": torch.zeros(K, dtype=torch.int64), "s1": torch.zeros((K, D), dtype=torch.int64),
+           "s2": torch.zeros((K, D), dtype=torch.int64), "cnt": torch.zeros((K, D), dtype=torch.int64)}
+    for r0 in range(0, N, block):
+        Xb = X[r0:r0 + block]
+        T = (y[r0:r0 + block, None] == cls).double().t()             # [K, n]
+        Xd = Xb.double()
+        out["n"] += T.sum(1).long()
+        out["s1"] += (T @ Xd).long()
+        out["s2"] += (T @ (Xd * Xd)).long()
+        out["cnt"] += (T @ (Xb > thr).double()).long()
+    return out
+
+
+def _variance_times_n2(n, s1, s2):
+    """n s2 - s1^2 as exact integers in a float64 array: int64 where it cannot overflow (n^2 255^2 < 2^62), Python ints elsewhere."""
+    n, s1, s2 = np.asarray(n, dtype=np.int64), np.asarray(s1, dtype=np.int64), np.asarray(s2, dtype=np.int64)
+    if int(n.max()) ** 2 * 65025 < 2 ** 62:
+        return (n * s2 - s1 * s1).astype(np.float64)
+    return (n.astype(object) * s2.astype(object) - s1.astype(object) * s1.astype(object)).astype(np.float64)
+
+
+def gnb_tables(mom, var_smoothing=1e-9):
+    """(m [K, D] float32, w [K, D] float32, c [K] float64, eps) of GaussianNB on x = b / 255, in byte units, from the moments:
+    m = s1 / n_k,  v = (n_k s2 - s1^2) / n_k^2 (the numerator in exact integers),  eps = var_smoothing max_j V_j with V the same
+    expression on the moments summed over the classes,  w = 1 / (2 (v + eps)),  c_k = log(n_k / N) - 1/2 sum_j log(2 pi (v + eps) / 255^2);
+    jll[i, k] = c_k - sum_j w (b_ij - m)^2.  Derived in float64; m and w are rounded to float32 ONCE, here, for both paths."""
+    n = mom["n"].numpy().astype(np.int64)
+    s1, s2 = mom["s1"].numpy(), mom["s2"].numpy()
+    if not float(var_smoothing) >= 0 or (n < 1).any():
+        raise ValueError("need var_smoothing >= 0 and a row in every class, got %r and counts %s" % (var_smoothing, n.tolist()))
+    N = int(n.sum())
+    nf = n.astype(np.float64)[:, None]
+    m = s1.astype(np.float64) / nf
+    v = _variance_times_n2(n[:, None], s1, s2) / (nf * nf)
+    V = _variance_times_n2(np.int64(N), s1.sum(0), s2.sum(0)) / (float(N) * float(N))
+    eps = float(var_smoothing) * float(V.max())
+    if not eps > 0:
+        raise ValueError("var_smoothing times the largest feature variance is %r: every feature is constant (or var_smoothing is 0), "
+                         "the Gaussian model has no variance to work with" % eps)
+    w = 1.0 / (2.0 * (v + eps))
+    c = np.log(nf[:, 0] / N) - 0.5 * np.log(2.0 * np.pi * (v + eps) / 65025.0).sum(1)
+    m32, w32 = m.astype(np.float32), w.astype(np.float32)
+    if not np.isfinite(w32).all():
+        raise ValueError("var_smoothing = %r leaves 1 / (2 (variance + eps)) beyond float32: eps = %.3g" % (var_smoothing, eps))
+    return m32, w32, c, eps
+
+
+def bnb_tables(mom, alpha=0.01):
+    """(delta [K, D] float32, c [K] float64) of BernoulliNB(alpha) on the features [b > binarize], from the moments:
+    lp = log(cnt + alpha) - log(n_k + 2 alpha),  ln = log1p(-exp(lp)),  delta = lp - ln,  c_k = log(n_k / N) + sum_j ln;
+    jll[i, k] = c_k + sum_j [b_ij > binarize] delta.  Derived in float64; delta is rounded to float32 ONCE, here, for both paths."""
+    alpha = float(alpha)
+    n = mom["n"].numpy().astype(np.float64)
+    if not 0 < alpha < float("inf") or (n < 1).any():
+        raise ValueError("need a finite alpha > 0 and a row in every class, got %r and counts %s" % (alpha, n.tolist()))
+    lp = np.log(mom["cnt"].numpy().astype(np.float64) + alpha) - np.log(n + 2.0 * alpha)[:, None]
+    ln = np.log1p(-np.exp(lp))
+    c = np.log(n / n.sum()) + ln.sum(1)
+    return (lp - ln).astype(np.float32), c
+
+
+def jll_host_bytes(Xu8, kind, tables, c, binarize=0, block=2048):
+    """jll [M, K] in float64 of uint8 rows under the float32 tables of gnb_tables / bnb_tables and the float64 constants c, in row
+    blocks — the model of the device scores: gnb c_k - sum_j w (b - m)^2, bnb c_k + sum_j [b > binarize] delta, the sums in float64."""
+    X = _bytes_rows(Xu8).cpu()
+    tabs = [torch.from_numpy(np.asarray(t, dtype=np.float32)).double() for t in tables]
+    c = torch.from_numpy(np.asarray(c, dtype=np.float64))
+    K = tabs[0].shape[0]
+    out = torch.empty((X.shape[0], K), dtype=torch.float64)
+    block = max(1, int(block))
+    for r0 in range(0, X.shape[0], block):
+        Xb = X[r0:r0 + block]
+        if kind == "gnb":
+            Xd = Xb.double()
+            for k in range(K):
+                out[r0:r0 + block, k] = c[k] - (tabs[1][k] * (Xd - tabs[0][k]) ** 2).sum(1)
+        else:
+            out[r0:r0 + block] = c + (Xb > int(binarize)).double() @ tabs[0].t()
+    return out
+
+
+def log_odds(jll):
+    """L[i, k] = jll[i, k] - logsumexp_{l != k} jll[i, l]: the log-odds of class k, a strictly increasing function of the posterior
+    that keeps its order where the posterior has saturated to exactly 0 or 1."""
+    J = torch.as_tensor(jll).double()
+    K = J.shape[1]
+    L = torch.empty_like(J)
+    for k in range(K):
+        L[:, k] = J[:, k] - torch.logsumexp(J[:, [l for l in range(K) if l != k]], 1)
+    return L
+
+
+class NaiveBayes:
+    """`NaiveBayes(n_classes, kind).fit_bytes(Xu8, y)` then `.jll_bytes(Xu8)`, `.predict_proba_bytes(Xu8)`, `.log_odds_bytes(Xu8)`:
+    kind "gnb" is GaussianNB(var_smoothing) and "bnb" BernoulliNB(alpha, binarize) of downstream.py:76-78 on uint8 rows with
+    x = byte / 255 (binarize is a byte threshold, 0 .. 254: the feature is [byte > binarize]).  The fit is a closed form of integer
+    moments: rows on a HIP device select ops.class_moments_u8, anything else class_moments_host_bytes — the same integers — and the
+    tables come from them by the same host code, so `coef` is the same bits on both paths.  Scores: rows on a HIP device select
+    ops.nb_score_gauss_u8 / nb_score_bern_u8 (fp32 sums), anything else jll_host_bytes (float64 sums); the constants c_k are added
+    in float64 on the host and every result is a float64 CPU tensor [M, K].
+    `coef` (float64): gnb [2 D + 1, K] — D rows of m, D rows of w (both the float32 values used), then c; bnb [D + 1, K] — delta, c.
+    fit_bytes returns the report {"kind", "n_per_class", "eps" (gnb) | "binarize" (bnb)}."""
+
+    def __init__(self, n_classes, kind, var_smoothing=1e-9, alpha=0.01, binarize=0):
+        self.K = _check_classes(n_classes)
+        if kind not in NB_KINDS:
+            raise ValueError("kind must be one of %s, got %r" % (NB_KINDS, kind))
+        self.kind, self.var_smoothing, self.alpha = kind, float(var_smoothing), float(alpha)
+        if not 0 <= self.var_smoothing < float("inf"):
+            raise ValueError("var_smoothing must be a finite number >= 0, got %r" % (var_smoothing,))
+        if not 0 < self.alpha < float("inf"):
+            raise ValueError("alpha must be a finite number > 0, got %r" % (alpha,))
+        self.binarize = _check_binarize(binarize)
+        self.coef, self.report, self.tables, self.c = None, None, None, None
+
+    def fit_bytes(self, Xu8, y):
+        X, y = _check_row_size(_bytes_rows(Xu8)).contiguous(), torch.as_tensor(y)
+        _check_rows(self.K, X, y)
+        if X.is_cuda:
+            with torch.cuda.device(X.device):
+                yd = y.to(X.device).reshape(-1).to(torch.int32).contiguous()
+                mom = {k: v.cpu() for k, v in ops.class_moments_u8(X, yd, self.K, self.binarize).items()}
+        else:
+            mom = class_moments_host_bytes(X, y, self.K, self.binarize)
+        rep = {"kind": self.kind, "n_per_class": [int(v) for v in mom["n"].tolist()]}
+        if self.kind == "gnb":
+            m, w, c, eps = gnb_tables(mom, self.var_smoothing)
+            self.tables, rep["eps"] = (m, w), eps
+        else:
+            delta, c = bnb_tables(mom, self.alpha)
+            self.tables, rep["binarize"] = (delta,), self.binarize
+        self.c = c
+        self.coef = torch.from_numpy(np.concatenate([t.astype(np.float64).T for t in self.tables] + [c[None, :]], 0))
+        self.report = rep
+        return rep
+
+    def jll_bytes(self, Xu8):
+        """jll [M, K], float64 on the CPU."""
+        if self.coef is None:
+            raise RuntimeError("fit first")
+        X = _bytes_rows(Xu8)
+        if X.dim() != 2 or X.shape[1] != self.tables[0].shape[1]:
+            raise ValueError("need uint8 rows [M, %d], got %s" % (self.tables[0].shape[1], tuple(X.shape)))
+        if not X.is_cuda:
+            return jll_host_bytes(X, self.kind, self.tables, self.c, self.binarize)
+        with torch.cuda.device(X.device):
+            tabs = [torch.from_numpy(t).to(X.device) for t in self.tables]
+            if self.kind == "gnb":
+                S = -ops.nb_score_gauss_u8(X.contiguous(), tabs[0], tabs[1]).cpu().double()
+            else:
+                S = ops.nb_score_bern_u8(X.contiguous(), tabs[0], self.binarize).cpu().double()
+        return torch.from_numpy(self.c) + S
+
+    def predict_proba_bytes(self, Xu8):
+        """P [M, K] = softmax_k(jll), float64 on the CPU."""
+        return torch.softmax(self.jll_bytes(Xu8), 1)
+
+    def log_odds_bytes(self, Xu8):
+        """L [M, K] = log_odds(jll): what AUROC ranks."""
+        return log_odds(self.jll_bytes(Xu8))
 
 
 def _auc(pos, neg):

@@ -1628,6 +1628,63 @@ def ovr_mlp_proba_u8(Xtest, U, hidden, out=None):
     return out
 
 
+def class_moments_u8(X, labels, n_classes, binarize=0, out=None):
+    """{"n": [K], "s1": [K, D], "s2": [K, D], "cnt": [K, D]}, int64 device tensors: per class the row count, sum b, sum b^2 and the
+    number of rows with b > binarize of X [N, D] uint8 with int32 labels [N] (include/cslgan.h "naive Bayes"): one pass over X, exact,
+    the same integers in every schedule.  out: such a dict to write into (whatever it holds is overwritten); allocated when absent.
+    csl_gan_amd.classify.class_moments_host_bytes is the host model."""
+    _chk_bytes(X, "X")
+    if X.dim() != 2:
+        raise RuntimeError("class_moments_u8: need X [N, D], got %s" % (tuple(X.shape),))
+    N, D, K = X.shape[0], X.shape[1], int(n_classes)
+    if not labels.is_cuda or labels.dtype != torch.int32 or labels.numel() != N or not labels.is_contiguous():
+        raise RuntimeError("class_moments_u8: labels must be a contiguous int32 device tensor of %d entries" % N)
+    shapes = {"n": (K,), "s1": (K, D), "s2": (K, D), "cnt": (K, D)}
+    if out is None:
+        out = {k: torch.empty(s, device=X.device, dtype=torch.int64) for k, s in shapes.items()}
+    for k, s in shapes.items():
+        t = out[k]
+        if not t.is_cuda or t.dtype != torch.int64 or not t.is_contiguous() or tuple(t.shape) != s:
+            raise RuntimeError("class_moments_u8: out[%r] must be a contiguous int64 device tensor of shape %s" % (k, s))
+    check(_lib.lib().cslgan_class_moments_u8(_p(X), _p(labels), N, D, K, int(binarize), _p(out["n"]), _p(out["s1"]), _p(out["s2"]), _p(out["cnt"]),
+                                             None, _stream()), "class_moments_u8")
+    return out
+
+
+def _nb_tables(what, Xtest, tables):
+    _chk_bytes(Xtest, "Xtest")
+    for t in tables:
+        _chk(t, "table")
+    if Xtest.dim() != 2 or any(t.dim() != 2 or t.shape[1] != Xtest.shape[1] or t.shape != tables[0].shape for t in tables):
+        raise RuntimeError("%s: need Xtest [M, D] and tables [K, D], got %s and %s" % (what, tuple(Xtest.shape), [tuple(t.shape) for t in tables]))
+    return Xtest.shape[0], Xtest.shape[1], tables[0].shape[0]
+
+
+def _nb_out(what, M, K, device, out):
+    if out is None:
+        out = torch.empty((M, K), device=device, dtype=torch.float32)
+    elif _chk(out, "out").numel() != M * K:
+        raise RuntimeError("%s: out has %d entries, expected %d" % (what, out.numel(), M * K))
+    return out
+
+
+def nb_score_gauss_u8(Xtest, m, w, out=None):
+    """S [M, K] fp32, S[i][k] = sum_j w[k][j] (byte_ij - m[k][j])^2 for uint8 Xtest [M, D] and fp32 tables m, w [K, D]: the sum of a
+    Gaussian naive-Bayes log-likelihood in byte units (include/cslgan.h "naive Bayes"); fixed order, the same bits on every call."""
+    M, D, K = _nb_tables("nb_score_gauss_u8", Xtest, (m, w))
+    out = _nb_out("nb_score_gauss_u8", M, K, Xtest.device, out)
+    check(_lib.lib().cslgan_nb_score_gauss_u8(_p(Xtest), _p(m), _p(w), M, D, K, _p(out), _stream()), "nb_score_gauss_u8")
+    return out
+
+
+def nb_score_bern_u8(Xtest, delta, binarize=0, out=None):
+    """S [M, K] fp32, S[i][k] = sum_j [byte_ij > binarize] delta[k][j] for uint8 Xtest [M, D] and the fp32 table delta [K, D]."""
+    M, D, K = _nb_tables("nb_score_bern_u8", Xtest, (delta,))
+    out = _nb_out("nb_score_bern_u8", M, K, Xtest.device, out)
+    check(_lib.lib().cslgan_nb_score_bern_u8(_p(Xtest), _p(delta), M, D, K, int(binarize), _p(out), _stream()), "nb_score_bern_u8")
+    return out
+
+
 def nn_padded_dim(D):
     """Row pitch of the prepared operands of nn_min: D rounded up to the kernel's K tile (0: a D outside 1 .. 65536)."""
     return int(_lib.lib().cslgan_nn_padded_dim(int(D)))

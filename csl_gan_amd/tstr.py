@@ -1,6 +1,7 @@
 """Are the samples any use?  `python -m csl_gan_amd.tstr --syn_cache out/syn [more ...] --test_cache out/test
 [--train_cache out/train --baseline] [-d cuda:0] [--gtol_rel G] [--max_iter 2000] [--values_dir DIR]
-[--classifier {lr,mlp} --hidden 100 --alpha 1.0 --seed 0] [--save --outputs_dir outputs/ --name tstr]`.
+[--classifier {lr,mlp,gnb,bnb} --hidden 100 --alpha 1.0 --seed 0 --var_smoothing 1e-9 --nb_alpha 0.01 --binarize 0]
+[--save --outputs_dir outputs/ --name tstr]`.
 
 Train on synthetic, test on real: per labelled synthetic cache (what `gensamples --cache` of a conditional generator
 wrote: images and the labels `index mod n_classes`) a one-vs-rest logistic regression (csl_gan_amd.classify.OvrLogReg.fit_bytes) is
@@ -15,6 +16,13 @@ device (fp32 kernels on the bytes) is held to.
 --classifier mlp fits the reference's other classifier instead, a one-vs-rest MLP with --hidden ReLU units per class
 and L2 penalty --alpha (csl_gan_amd.classify.OvrMlp, started from --seed; --max_iter then defaults to 200): the figures carry
 "classifier", "hidden", "alpha" and "seed" as well, and U is kept in OvrMlp's layout [(D + 2) hidden + 1, K].
+
+--classifier gnb / bnb fit the reference's two naive-Bayes classifiers (csl_gan_amd.classify.NaiveBayes): GaussianNB
+with --var_smoothing, BernoulliNB with --nb_alpha on the features [byte > --binarize].  No solver: one pass over the training bytes
+gives exact integer moments and the model follows in closed form, the same bits with -d cpu and on a device.  The figures carry
+"classifier", "fit" (the class counts; eps for gnb) and the parameters used instead of "solver"; AUROC ranks the log-odds (the
+posteriors saturate to exactly 0 and 1), accuracy is the argmax of the joint log-likelihood; --values_dir keeps P (float64
+posteriors), J (the joint log-likelihood) and U (NaiveBayes.coef).  A flag of another classifier is ignored.
 """
 import argparse
 import sys
@@ -35,10 +43,14 @@ def build_parser():
     ap.add_argument("--baseline", default=False, action="store_true", help="also fit on the training set itself")
     ap.add_argument("--gtol_rel", type=float, default=None, help="a class has converged when max|gradient| <= gtol_rel * n")
     ap.add_argument("--max_iter", type=int, default=None, help="L-BFGS iterations per class (default: 2000 for lr, 200 for mlp)")
-    ap.add_argument("--classifier", type=str, default="lr", choices=["lr", "mlp"], help="one-vs-rest logistic regression or MLP")
+    ap.add_argument("--classifier", type=str, default="lr", choices=["lr", "mlp", "gnb", "bnb"],
+                    help="one-vs-rest logistic regression or MLP, Gaussian or Bernoulli naive Bayes")
     ap.add_argument("--hidden", type=int, default=100, help="mlp: hidden ReLU units per class, 1 .. %d" % classify.MAX_HIDDEN)
     ap.add_argument("--alpha", type=float, default=1.0, help="mlp: L2 penalty on the weights, >= 0")
     ap.add_argument("--seed", type=int, default=0, help="mlp: seed of the initial point")
+    ap.add_argument("--var_smoothing", type=float, default=1e-9, help="gnb: share of the largest feature variance added to every variance, >= 0")
+    ap.add_argument("--nb_alpha", type=float, default=0.01, help="bnb: additive smoothing of the counts, > 0")
+    ap.add_argument("--binarize", type=int, default=0, help="bnb: the feature is [byte > binarize], 0 .. 254")
     return ap
 
 
@@ -56,24 +68,39 @@ def n_classes_of(labels, path):
     return K
 
 
-def fit_and_score(train_x, train_y, K, test_x, test_y, device, gtol_rel=None, max_iter=2000, mlp=None):
-    """One fit on bytes train_x [n, D] (numpy) and its figures on test_x (a uint8 tensor already on `device`): (stats, P, U).
-    mlp: None for the logistic regression, or {"hidden", "alpha", "seed"} for classify.OvrMlp — then part of the stats."""
+def _scores(stats, a, acc):
+    stats.update({"auroc_micro": a["micro"], "auroc_per_class": a["per_class"], "accuracy": acc["accuracy"], "accuracy_hits": acc["hits"]})
+    return stats
+
+
+def fit_and_score(train_x, train_y, K, test_x, test_y, device, gtol_rel=None, max_iter=2000, mlp=None, nb=None):
+    """One fit on bytes train_x [n, D] (numpy) and its figures on test_x (a uint8 tensor already on `device`): (stats, values), values
+    the arrays --values_dir keeps ("P", "U"; "J" as well for naive Bayes).  The estimator: nb = {"kind": "gnb", "var_smoothing"} or
+    {"kind": "bnb", "alpha", "binarize"} for classify.NaiveBayes; else mlp = {"hidden", "alpha", "seed"} for classify.OvrMlp; else the
+    logistic regression.  The parameters are part of the stats."""
+    stats = {"n_train": int(len(train_y)), "n_test": int(len(test_y)), "classes": int(K)}
+    X = torch.from_numpy(train_x).to(device)
+    if nb is not None:
+        clf = classify.NaiveBayes(K, **nb)
+        report = clf.fit_bytes(X, torch.from_numpy(train_y))
+        del X
+        J = clf.jll_bytes(test_x)
+        L = classify.log_odds(J).to(test_x.device)                   # on a device the rank counts are the device's
+        _scores(stats, classify.auroc(L, test_y), classify.accuracy(J, test_y))
+        stats.update({"classifier": nb["kind"], "fit": report}, **{k: v for k, v in nb.items() if k != "kind"})
+        return stats, {"P": torch.softmax(J, 1).numpy(), "J": J.numpy(), "U": clf.coef.numpy()}
     if mlp is None:
         clf = classify.OvrLogReg(K, gtol_rel=gtol_rel, max_iter=max_iter)
     else:
         clf = classify.OvrMlp(K, gtol_rel=gtol_rel, max_iter=max_iter, **mlp)
-    X = torch.from_numpy(train_x).to(device)
     report = clf.fit_bytes(X, torch.from_numpy(train_y))
     del X
     P = clf.predict_proba_bytes(test_x)
-    a = classify.auroc(P, test_y)
-    acc = classify.accuracy(P, test_y)
-    stats = {"n_train": int(len(train_y)), "n_test": int(len(test_y)), "classes": int(K), "auroc_micro": a["micro"],
-             "auroc_per_class": a["per_class"], "accuracy": acc["accuracy"], "accuracy_hits": acc["hits"], "solver": report}
+    _scores(stats, classify.auroc(P, test_y), classify.accuracy(P, test_y))
+    stats["solver"] = report
     if mlp is not None:
         stats.update({"classifier": "mlp", "hidden": int(mlp["hidden"]), "alpha": float(mlp["alpha"]), "seed": int(mlp["seed"])})
-    return stats, P.cpu().numpy(), clf.coef.cpu().numpy()
+    return stats, {"P": P.cpu().numpy(), "U": clf.coef.cpu().numpy()}
 
 
 def main(argv=None):
@@ -84,7 +111,14 @@ def main(argv=None):
         raise SystemExit("--hidden %d: the MLP takes 1 .. %d hidden units per class" % (a.hidden, classify.MAX_HIDDEN))
     if not 0 <= a.alpha < float("inf"):
         raise SystemExit("--alpha %r: the penalty must be a finite number >= 0" % a.alpha)
+    if not 0 <= a.var_smoothing < float("inf"):
+        raise SystemExit("--var_smoothing %r: must be a finite number >= 0" % a.var_smoothing)
+    if not 0 < a.nb_alpha < float("inf"):
+        raise SystemExit("--nb_alpha %r: the smoothing must be a finite number > 0" % a.nb_alpha)
+    if not 0 <= a.binarize <= 254:
+        raise SystemExit("--binarize %d: a byte threshold, 0 .. 254" % a.binarize)
     mlp = {"hidden": a.hidden, "alpha": a.alpha, "seed": a.seed} if a.classifier == "mlp" else None
+    nb = {"gnb": {"kind": "gnb", "var_smoothing": a.var_smoothing}, "bnb": {"kind": "bnb", "alpha": a.nb_alpha, "binarize": a.binarize}}.get(a.classifier)
     max_iter = a.max_iter if a.max_iter is not None else (2000 if mlp is None else 200)
     test = pipeline.CachedImages(a.test_cache)
     extra = [("baseline_train", a.train_cache, pipeline.CachedImages(a.train_cache))] if a.baseline else []
@@ -107,13 +141,16 @@ def main(argv=None):
     stats, values = {}, {}
     for lab, _, c in sets:
         x, y = cache_rows(c)
-        m, P, U = fit_and_score(x, y, classes[lab], test_x, test_yt, device, a.gtol_rel, max_iter, mlp)
+        m, vals = fit_and_score(x, y, classes[lab], test_x, test_yt, device, a.gtol_rel, max_iter, mlp, nb)
         stats[lab] = m
-        values[lab + "_P"], values[lab + "_U"] = P, U
+        values.update({lab + "_" + k: v for k, v in vals.items()})
         print("%s: fitted on %d rows, scored %d: AUROC %.6f, accuracy %.4f (%d / %d)" % (
             lab, m["n_train"], m["n_test"], m["auroc_micro"], m["accuracy"], m["accuracy_hits"], m["n_test"]))
         print("   per class: %s" % " ".join("%.4f" % v for v in m["auroc_per_class"]))
-        print(classify.solver_line(m["solver"]))
+        if nb is None:
+            print(classify.solver_line(m["solver"]))
+        else:
+            print("   fit: rows per class %s%s" % (m["fit"]["n_per_class"], "  eps %.6g" % m["fit"]["eps"] if "eps" in m["fit"] else ""))
     cache_cli.save_values(a.values_dir, values)
     return cache_cli.report(a, stats)
 

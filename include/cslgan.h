@@ -635,6 +635,34 @@ int cslgan_ovr_mlp_eval_u8(const void* X, const int32_t* labels, const float* U,
                            float* grad, float* ws, void* stream);
 int cslgan_ovr_mlp_proba_u8(const void* Xtest, const float* U, int64_t M, int D, int K, int H, float* P, void* stream);
 
+/* ---- naive Bayes on cache bytes (nb_kernels.hip; csl_gan_amd.tstr --classifier gnb / bnb; backward-compatible additions,
+ * ABI stays 7).  GaussianNB() and BernoulliNB(alpha=.01) of downstream.py:76-78 on x = byte / 255 are closed forms of per-class,
+ * per-feature moments, and on bytes those are integers.  X / Xtest: uint8 [N, D] row-major, base 16-byte aligned, 1 <= D <= 65536, rows
+ * need not be aligned; no byte beyond X + N D is read.  2 <= K <= 16, 1 <= N, M < 2^31, 0 <= binarize <= 254.  All entries validate
+ * on the host before any launch (null pointers, D, K, N / M, binarize, alignment), never allocate and never synchronise.
+ *
+ * cslgan_class_moments_u8 — one pass over the N D bytes.  With b = X[i][j] and the sums over the rows i with labels[i] == k (a label
+ * outside 0 .. K-1 belongs to no class):  n[k] = the number of rows,  s1[k][j] = sum b,  s2[k][j] = sum b^2,  cnt[k][j] = the number
+ * of rows with b > binarize;  int64, [K] and [K, D] row-major, 8-byte aligned.  The result is EXACT — equal to
+ * csl_gan_amd.classify.class_moments_host_bytes for every N — and does not depend on scheduling: a workgroup keeps 32-bit partials
+ * in LDS for a chunk of at most 2048 rows (sum b^2 <= 2048 * 65025 < 2^28; a 32-bit sum would wrap after 66 051 rows of 255) and adds
+ * them to the outputs at the end of its chunk with 64-bit integer vector atomics, whose order cannot change an integer sum.  The
+ * outputs are zeroed by the library's own kernel on the stream before that launch, whatever they held.  ws: unused by this form
+ * (reserved for a two-stage reduction), may be NULL.
+ *
+ * cslgan_nb_score_gauss_u8 — S[i][k] = sum_j w[k][j] (b_ij - m[k][j])^2, the subtraction first (the expanded quadratic cancels at
+ * small variances and is never formed).  cslgan_nb_score_bern_u8 — S[i][k] = sum_j [b_ij > binarize] delta[k][j].  m, w, delta:
+ * fp32 [K, D] row-major; S: fp32 [M, K] row-major, every entry written.  One pass over the M D bytes (16-byte loads), every table
+ * element reused over the rows of a tile through LDS.  No atomics: thread-strided partials and a butterfly in a fixed order, so the
+ * same inputs return the same bits, and no sum passes through more than s = 275 fp32 additions at any D:
+ *     |S - S_float64| <= (s + 3) 2^-24 T <= 2e-5 T,      T[i][k] = the float64 sum of the absolute terms (for gauss S itself).
+ * The joint log-likelihoods are c_k - S (gauss) and c_k + S (bern) with the float64 constants c_k added by the caller
+ * (csl_gan_amd.classify.NaiveBayes holds the derivation of m, w, delta and c from the moments). */
+int cslgan_class_moments_u8(const void* X, const int32_t* labels, int64_t N, int D, int K, int binarize, int64_t* n, int64_t* s1, int64_t* s2,
+                            int64_t* cnt, void* ws, void* stream);
+int cslgan_nb_score_gauss_u8(const void* Xtest, const float* m, const float* w, int64_t M, int D, int K, float* S, void* stream);
+int cslgan_nb_score_bern_u8(const void* Xtest, const float* delta, int64_t M, int D, int K, int binarize, float* S, void* stream);
+
 /* ---- Nearest-neighbour audit (nn_kernels.hip; backward-compatible additions, ABI stays 7) -----------------------------------------
  * Exact nearest neighbour of every row of Q [nq, D] among the rows of R [nr, D], both uint8, D = H W C with 1 <= D <= 65536
  * (so 255^2 D < 2^32):
