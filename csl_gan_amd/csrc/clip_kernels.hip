@@ -349,11 +349,11 @@ __global__ void l2_clip_scale_kernel(const float* __restrict__ in, float* __rest
         o[j] = nrm > C ? p[j] * f : p[j];
 }
 
-// gin[r][j] = gnorm[r] * in[r][j] / norm[r]
+// gin[r][j] = gnorm[r] * in[r][j] / norm[r]   (0 where norm[r] == 0, as torch's norm backward)
 __global__ void row_l2norm_bwd_kernel(const float* __restrict__ in, const float* __restrict__ norm,
                                       const float* __restrict__ gnorm, long long len, float* __restrict__ gin) {
     const long long row = blockIdx.y;
-    const float f = gnorm[row] / norm[row];
+    const float f = norm[row] == 0.f ? 0.f : gnorm[row] / norm[row];
     const float* p = in + row * len;
     float* o = gin + row * len;
     for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < len; j += (long long)gridDim.x * blockDim.x)

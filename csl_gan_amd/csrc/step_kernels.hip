@@ -209,7 +209,7 @@ __global__ void lipschitz_term_kernel(const float* __restrict__ t, long long len
     }
 }
 
-// gt[b, :] = (g_total + g_per[b]) * coef * 2 (n_b - 1)[n_b > 1 if one-sided] * t[b, :] / n_b
+// gt[b, :] = (g_total + g_per[b]) * coef * 2 (n_b - 1)[n_b > 1 if one-sided] * t[b, :] / n_b   (0 where n_b == 0)
 __global__ void lipschitz_term_bwd_kernel(const float* __restrict__ t, const float* __restrict__ norm, const float* __restrict__ g_total,
                                           const float* __restrict__ g_per, long long len, int one_sided, float coef, float* __restrict__ gt) {
     const long long row = blockIdx.y;
@@ -218,7 +218,7 @@ __global__ void lipschitz_term_bwd_kernel(const float* __restrict__ t, const flo
     if (one_sided) d = fmaxf(d, 0.f);
     float g = g_total ? *g_total : 0.f;
     if (g_per) g += g_per[row];
-    const float f = g * coef * 2.f * d / n;
+    const float f = n == 0.f ? 0.f : g * coef * 2.f * d / n;     // a zero row: torch's norm backward gives 0 there, not 0 * inf
     const float* p = t + row * len;
     float* o = gt + row * len;
     if ((len & 3) == 0 && aligned16_dev(p) && aligned16_dev(o)) {

@@ -130,7 +130,9 @@ class LipschitzTerm(Function):
             n = t.norm(2, dim=1)
             d = (n - 1).clamp(min=0) if one_sided else n - 1
             gb = g if per_sample else g.expand(t.shape[0])
-            return (gb * coef * 2 * d / n).unsqueeze(1) * t, None, None, None
+            # a zero row has factor 0, as torch's norm backward gives it (the kernel does the same), not 0 * inf
+            f = torch.where(n > 0, gb * coef * 2 * d / torch.where(n > 0, n, torch.ones_like(n)), torch.zeros_like(n))
+            return f.unsqueeze(1) * t, None, None, None
         g = g.contiguous()
         return ops.lipschitz_term_bwd(t, norm, None if per_sample else g, g if per_sample else None, one_sided, coef), None, None, None
 
@@ -404,5 +406,6 @@ class RowL2Norm(Function):
         if torch.is_grad_enabled() and (gn.requires_grad or t.requires_grad):
             # differentiable form for higher-order use (never hit by the D-step: the norm's backward is
             # the last first-order node before the parameter gradients)
-            return gn.unsqueeze(1) * t / n.unsqueeze(1)
+            # a zero row divides by 1 and stays 0, as torch's norm backward leaves it (the kernel does the same), not 0 / 0
+            return gn.unsqueeze(1) * t / torch.where(n > 0, n, torch.ones_like(n)).unsqueeze(1)
         return ops.row_l2norm_bwd(t, n, gn.contiguous())

@@ -158,7 +158,8 @@ int cslgan_latent_normal_f32(uint64_t seed, uint64_t first_index, const unsigned
                              int n_classes, int fixed_label, int64_t* labels, void* stream);
 
 /* Row L2 norms of a [n_rows, len] matrix (gradient_penalty.py:52-53) and the backward of
- * norm: gin[r][j] = gnorm[r] * in[r][j] / norm[r]. */
+ * norm: gin[r][j] = gnorm[r] * in[r][j] / norm[r].  A row whose norm is exactly 0 gets a gradient of 0, as torch's 2-norm
+ * backward gives it, not 0 / 0. */
 int cslgan_row_l2norm_f32(const float* in, int64_t n_rows, int64_t len, float* out_norm, void* stream);
 int cslgan_row_l2norm_bwd_f32(const float* in, const float* norm, const float* gnorm, int64_t n_rows,
                               int64_t len, float* gin, void* stream);
@@ -518,7 +519,8 @@ int cslgan_lerp_rows_f32(const float* real, const float* fake, const float* alph
  * kernel uses to find its last workgroup and leaves at zero. */
 int cslgan_lipschitz_term_f32(const float* t, int64_t n_rows, int64_t len, int one_sided, float coef, float* norm, float* per,
                               float* total, uint32_t* ticket, void* stream);
-/* gt[b,:] = (g_total + g_per[b]) * coef * 2 (norm_b - 1)[clamped] * t[b,:] / norm_b; either gradient may be NULL, not both. */
+/* gt[b,:] = (g_total + g_per[b]) * coef * 2 (norm_b - 1)[clamped] * t[b,:] / norm_b; either gradient may be NULL, not both.
+ * A row with norm_b == 0 gets a gradient of 0 (torch's 2-norm backward at the origin), not 0 * inf. */
 int cslgan_lipschitz_term_bwd_f32(const float* t, const float* norm, const float* g_total, const float* g_per, int64_t n_rows,
                                   int64_t len, int one_sided, float coef, float* gt, void* stream);
 
