@@ -35,9 +35,16 @@ __global__ void act_bwd_kernel(const float* __restrict__ g, const float* __restr
 //   BatchNorm   : rows_per_stat = R,   cpg = 1,   n_groups = C        (per channel over the batch)
 // ONE pass over x accumulates shifted moments  S1 = sum(x - k_s),  S2 = sum((x - k_s)^2)  with the shift k_s = the
 // statistic's first element (x[first row of s][first channel of s]): mean = k + S1/n, var = S2/n - (S1/n)^2.
-// The shift is a sample of the same distribution, so the subtraction loses about one bit instead of the
-// catastrophic cancellation of raw E[x^2] - mean^2, and x is read once instead of twice.  A tiny finalize
-// kernel turns (S1, S2) into the (sum, centred sum of squares) pair the apply / backward kernels consume.
+// x is read once instead of twice, and the cancellation of raw E[x^2] - mean^2 (about (mean/sigma)^2) is replaced by that of
+// S2 - S1^2/n about the shift: the rounding error of the variance grows with  1 + ((k_s - mean)/sigma)^2.  k_s is the FIRST pixel of
+// the statistic, one sample: among the 64 statistics of a layer some sit 2-3 sigma off (a factor 5-10), and for a zero-padded conv's
+// output k_s is the image's corner pixel, the least typical one.  Measured against float64 (tests/test_norm_kernels_gpu.py, 300
+// values per channel, sigma 1): mean 8 with k = 2.9 (factor 29) — variance error 6.5e-6, output error 2.4e-5, 39x and 9x a float32
+// two-pass; mean 30 with k = 10.8 (factor 178) — 1.2e-4 and 4.4e-4, 108x and 106x a two-pass; both are 0.04-0.16 of what the factor
+// allows.  The one-pass form is kept where it pays, the partials route of the training step (launch_norm); the routes with global
+// atomics run a second statistics pass about the first pass's mean, which takes the factor back to 1.  With a scratch buffer (the float entries)
+// the mean reaches the apply kernels rounded once (k + S1/n, not sum * (1/n)): a group of constant values comes out as beta exactly.
+// A tiny finalize kernel turns (S1, S2) into the (sum, centred sum of squares) pair the apply / backward kernels consume.
 // Rows are read with 16-byte loads, coalesced along C; partial sums go thread -> LDS (per channel) -> one
 // global atomic per channel per block.
 constexpr int NS_ROWS_MIN = 64;   // rows per block, lower bound (the launch picks a multiple: ~1024 blocks in all)
@@ -66,7 +73,9 @@ __device__ __forceinline__ void st4(bf16_t* p, long long i, float a, float b, fl
 template <bool VEC, bool PART, typename TX>
 __global__ __launch_bounds__(256) void norm_stats_kernel(const TX* __restrict__ x, long long rows_per_stat, int C, int cpg,
                                                          int n_groups, int rows_per_block, float* __restrict__ stats,
-                                                         float* __restrict__ final_stats, long long n_stats) {
+                                                         float* __restrict__ final_stats, long long n_stats,
+                                                         const float* __restrict__ shift) {
+    // shift (nullable): k_s per statistic from a first pass (launch_norm's refined scalar route) instead of the first element
     extern __shared__ float s_acc[];   // [2*C]: S1, S2 per channel
     const int tid = threadIdx.x;
     for (int c = tid; c < 2 * C; c += 256) s_acc[c] = 0.f;
@@ -82,7 +91,7 @@ __global__ __launch_bounds__(256) void norm_stats_kernel(const TX* __restrict__ 
         const int c4 = tid % c4n, rl = tid / c4n, rstep = 256 / c4n;
         float k[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) k[e] = ldf(x, row_first * C + ((4 * c4 + e) / cpg) * cpg);
+        for (int e = 0; e < 4; ++e) k[e] = shift ? shift[sr * n_groups + (4 * c4 + e) / cpg] : ldf(x, row_first * C + ((4 * c4 + e) / cpg) * cpg);
         float a1[4] = {0.f, 0.f, 0.f, 0.f}, a2[4] = {0.f, 0.f, 0.f, 0.f};
         long long r = r0 + rl;
         for (; r + 3 * rstep < r1; r += 4 * rstep) {      // four independent 16-byte loads in flight
@@ -111,7 +120,7 @@ __global__ __launch_bounds__(256) void norm_stats_kernel(const TX* __restrict__ 
         const long long n = (r1 - r0) * C;
         for (long long i = tid; i < n; i += 256) {
             const int c = (int)(i % C);
-            const float d = ldf(x, r0 * C + i) - ldf(x, row_first * C + (c / cpg) * cpg);
+            const float d = ldf(x, r0 * C + i) - (shift ? shift[sr * n_groups + c / cpg] : ldf(x, row_first * C + (c / cpg) * cpg));
             atomicAdd(&s_acc[2 * c], d);
             atomicAdd(&s_acc[2 * c + 1], d * d);
         }
@@ -129,18 +138,27 @@ __global__ __launch_bounds__(256) void norm_stats_kernel(const TX* __restrict__ 
     }
 }
 
-// (S1, S2) about the shift k  ->  (sum x, sum (x-mean)^2)
+// (S1, S2) about the shift k  ->  (sum x, sum (x-mean)^2).  shift (nullable): the table the statistics kernel used.  mean_out (nullable,
+// may be the same table): receives mean_s = k + S1/n, rounded once — the apply kernel reads it instead of sum * (1/n).  first_pass:
+// that mean is the second pass's shift; zero the accumulators for it and leave.
 template <typename TX>
 __global__ void norm_stats_finalize_kernel(const TX* __restrict__ x, long long rows_per_stat, int C, int cpg, int n_groups,
-                                           long long n_stats, float* __restrict__ stats) {
+                                           long long n_stats, float* __restrict__ stats, const float* shift, float* mean_out,
+                                           int first_pass) {
     const long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n_stats) return;
     const long long sr = s / n_groups;
     const int g = (int)(s - sr * n_groups);
-    const float k = ldf(x, sr * rows_per_stat * C + g * cpg);
+    const float k = shift ? shift[s] : ldf(x, sr * rows_per_stat * C + g * cpg);
     const float cnt = (float)rows_per_stat * (float)cpg;
     const float S1 = stats[2 * s], S2 = stats[2 * s + 1];
     const float m1 = S1 / cnt;
+    if (mean_out) mean_out[s] = k + m1;
+    if (first_pass) {
+        stats[2 * s] = 0.f;
+        stats[2 * s + 1] = 0.f;
+        return;
+    }
     float css = S2 - S1 * m1;           // sum (x-mean)^2 = S2 - S1^2/n
     if (css < 0.f) css = 0.f;
     stats[2 * s] = (k + m1) * cnt;      // sum x
@@ -165,7 +183,9 @@ __device__ __forceinline__ long long d2s_offset(long long r, int p, int H, int W
 template <bool VEC, bool D2S, typename TX, typename TY>
 __global__ void norm_apply_kernel(const TX* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
                                   const float* __restrict__ stats, long long total, long long rows_per_stat, int C, int cpg,
-                                  int n_groups, float eps, int relu, TY* __restrict__ y, int H, int W, TY* __restrict__ xs) {
+                                  int n_groups, float eps, int relu, TY* __restrict__ y, int H, int W, TY* __restrict__ xs,
+                                  const float* __restrict__ mean_tab) {
+    // mean_tab (nullable): mean_s rounded once (norm_stats_finalize_kernel) instead of sum * (1/n)
     const float inv_cnt = 1.f / ((float)rows_per_stat * (float)cpg);
     const long long per_stat_elems = rows_per_stat * C;
     const long long stride = (long long)gridDim.x * blockDim.x;
@@ -180,7 +200,7 @@ __global__ void norm_apply_kernel(const TX* __restrict__ x, const float* __restr
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const long long s = sr * n_groups + (c + e) / cpg;
-                const float mean = stats[2 * s] * inv_cnt;
+                const float mean = mean_tab ? mean_tab[s] : stats[2 * s] * inv_cnt;
                 const float rstd = rsqrtf(stats[2 * s + 1] * inv_cnt + eps);
                 float t = (in[e] - mean) * rstd * gamma[c + e] + beta[c + e];
                 o[e] = (relu && t < 0.f) ? 0.f : t;
@@ -202,7 +222,7 @@ __global__ void norm_apply_kernel(const TX* __restrict__ x, const float* __restr
         for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
             const int c = (int)(i % C);
             const long long s = (i / per_stat_elems) * n_groups + c / cpg;
-            const float mean = stats[2 * s] * inv_cnt;
+            const float mean = mean_tab ? mean_tab[s] : stats[2 * s] * inv_cnt;
             const float rstd = rsqrtf(stats[2 * s + 1] * inv_cnt + eps);
             const float xi = ldf(x, i);
             float t = (xi - mean) * rstd * gamma[c] + beta[c];
@@ -227,7 +247,8 @@ template <bool D2S, typename TX, typename TY>
 __global__ __launch_bounds__(256) void norm_apply_rows_kernel(const TX* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                               const float* __restrict__ stats, long long rows_per_stat, int C, int cpg, int n_groups,
                                                               float eps, int relu, TY* __restrict__ y, int H, int W, TY* __restrict__ xs,
-                                                              const float* __restrict__ part, int n_part, float* __restrict__ stats_out, int chan) {
+                                                              const float* __restrict__ part, int n_part, float* __restrict__ stats_out, int chan,
+                                                              const float* __restrict__ mean_tab) {
     const int c4n = C >> 2;                           // a power of two (256 % c4n == 0)
     const int lg = __ffs(c4n) - 1;
     const int c = (threadIdx.x & (c4n - 1)) << 2;
@@ -240,7 +261,7 @@ __global__ __launch_bounds__(256) void norm_apply_rows_kernel(const TX* __restri
         // Two-launch form (round 4): the statistics kernel left one (S1, S2) pair about the shift k per workgroup and group; add the
         // row group's n_part slots here (2 * n_groups threads, n_part loads each), finish them in LDS, and let the row group's first
         // workgroup publish the final (sum x, centred sum of squares) pairs for whoever reads the statistics later (the backward).
-        extern __shared__ float s_st[];               // [2 * n_groups]: (sum x, centred sum of squares)
+        extern __shared__ float s_st[];               // [2 * n_groups]: (mean, centred sum of squares)
         for (int i = threadIdx.x; chan && i < n_groups; i += 256) {
             // chan: the partials come from a conv epilogue (cslgan_conv_t.gn_part): per slot the sum of its cnt / n_part values and
             // their sum of squares about the slot's own mean — combined exactly: M2 = sum_b M2_b + n_b (mean_b - mean)^2
@@ -253,7 +274,7 @@ __global__ __launch_bounds__(256) void norm_apply_rows_kernel(const TX* __restri
                 const float dm = q[0] / nb - mean_all;
                 css += q[1] + nb * dm * dm;
             }
-            s_st[2 * i] = sum;
+            s_st[2 * i] = mean_all;
             s_st[2 * i + 1] = css;
             if (stats_out && blockIdx.x == 0) {
                 stats_out[2 * (sr * n_groups + i)] = sum;
@@ -271,7 +292,7 @@ __global__ __launch_bounds__(256) void norm_apply_rows_kernel(const TX* __restri
             const float m1 = S1 / cnt;
             float css = S2 - S1 * m1;
             css = css < 0.f ? 0.f : css;
-            s_st[2 * i] = (k + m1) * cnt;
+            s_st[2 * i] = k + m1;
             s_st[2 * i + 1] = css;
             if (stats_out && blockIdx.x == 0) {
                 stats_out[2 * (sr * n_groups + i)] = (k + m1) * cnt;
@@ -282,14 +303,14 @@ __global__ __launch_bounds__(256) void norm_apply_rows_kernel(const TX* __restri
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int g = (c + e) / cpg;
-            mean[e] = s_st[2 * g] * inv_cnt;
+            mean[e] = s_st[2 * g];
             rstd[e] = rsqrtf(s_st[2 * g + 1] * inv_cnt + eps);
         }
     } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const long long s = sr * n_groups + (c + e) / cpg;
-            mean[e] = stats[2 * s] * inv_cnt;
+            mean[e] = mean_tab ? mean_tab[s] : stats[2 * s] * inv_cnt;
             rstd[e] = rsqrtf(stats[2 * s + 1] * inv_cnt + eps);
         }
     }
@@ -391,6 +412,8 @@ __global__ void bn_eval_stats_kernel(const float* __restrict__ rm, const float* 
 //   d gamma[c] = sum_sr Bq,  d beta[c] = sum_sr A
 //   per statistic s: s1 = sum_{c in s} gamma_c A, s2 = sum_{c in s} gamma_c Bq
 //   dx = rstd_s * (gamma_c dy' - s1/cnt - xh * s2/cnt)
+// xh is formed as fma(x, cnt, -sum_s) * (rstd_s / cnt): the statistics carry sum_s, and x - sum_s * (1/cnt) would give xh the absolute
+// error of a rounded mean times rstd (up to 316 on a nearly constant group); the fused form rounds x * cnt - sum_s once, relative to itself.
 template <bool VEC>
 __global__ __launch_bounds__(256) void norm_bwd_stats_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                              const float* __restrict__ y, const float* __restrict__ stats,
@@ -405,16 +428,17 @@ __global__ __launch_bounds__(256) void norm_bwd_stats_kernel(const float* __rest
     long long r1 = r0 + rows_per_block;
     const long long rend = (sr + 1) * rows_per_stat;
     if (r1 > rend) r1 = rend;
-    const float inv_cnt = 1.f / ((float)rows_per_stat * (float)cpg);
+    const float cnt = (float)rows_per_stat * (float)cpg;
+    const float inv_cnt = 1.f / cnt;
     if (VEC) {
         const int c4n = C >> 2;
         const int c4 = tid % c4n, rl = tid / c4n, rstep = 256 / c4n;
-        float mean[4], rstd[4], a[4] = {0.f, 0.f, 0.f, 0.f}, b[4] = {0.f, 0.f, 0.f, 0.f};
+        float sum[4], rn[4], a[4] = {0.f, 0.f, 0.f, 0.f}, b[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const long long s = sr * n_groups + (4 * c4 + e) / cpg;
-            mean[e] = stats[2 * s] * inv_cnt;
-            rstd[e] = rsqrtf(stats[2 * s + 1] * inv_cnt + eps);
+            sum[e] = stats[2 * s];
+            rn[e] = rsqrtf(stats[2 * s + 1] * inv_cnt + eps) * inv_cnt;
         }
         for (long long r = r0 + rl; r < r1; r += rstep) {
             const float4 xv = *reinterpret_cast<const float4*>(x + r * C + 4 * c4);
@@ -426,7 +450,7 @@ __global__ __launch_bounds__(256) void norm_bwd_stats_kernel(const float* __rest
             for (int e = 0; e < 4; ++e) {
                 const float g = yi[e] > 0.f ? gi[e] : 0.f;
                 a[e] += g;
-                b[e] = fmaf(g, (xi[e] - mean[e]) * rstd[e], b[e]);
+                b[e] = fmaf(g, fmaf(xi[e], cnt, -sum[e]) * rn[e], b[e]);
             }
         }
 #pragma unroll
@@ -439,11 +463,11 @@ __global__ __launch_bounds__(256) void norm_bwd_stats_kernel(const float* __rest
         for (long long i = tid; i < n; i += 256) {
             const int c = (int)(i % C);
             const long long s = sr * n_groups + c / cpg;
-            const float m = stats[2 * s] * inv_cnt, rs = rsqrtf(stats[2 * s + 1] * inv_cnt + eps);
+            const float rn = rsqrtf(stats[2 * s + 1] * inv_cnt + eps) * inv_cnt;
             const long long off = r0 * C + i;
             const float g = (!relu || y[off] > 0.f) ? dy[off] : 0.f;
             atomicAdd(&s_acc[2 * c], g);
-            atomicAdd(&s_acc[2 * c + 1], g * (x[off] - m) * rs);
+            atomicAdd(&s_acc[2 * c + 1], g * (fmaf(x[off], cnt, -stats[2 * s]) * rn));
         }
     }
     __syncthreads();
@@ -482,13 +506,14 @@ __global__ void norm_bwd_apply_kernel(const float* __restrict__ x, const float* 
                                       const float* __restrict__ gamma, const float* __restrict__ stats, const float* __restrict__ gs,
                                       long long total, long long rows_per_stat, int C, int cpg, int n_groups, float eps, int relu,
                                       float* __restrict__ dx) {
-    const float inv_cnt = 1.f / ((float)rows_per_stat * (float)cpg);
+    const float cnt = (float)rows_per_stat * (float)cpg;
+    const float inv_cnt = 1.f / cnt;
     const long long per_stat_elems = rows_per_stat * C;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const int c = (int)(i % C);
         const long long s = (i / per_stat_elems) * n_groups + c / cpg;
-        const float mean = stats[2 * s] * inv_cnt, rstd = rsqrtf(stats[2 * s + 1] * inv_cnt + eps);
-        const float xh = (x[i] - mean) * rstd;
+        const float rstd = rsqrtf(stats[2 * s + 1] * inv_cnt + eps);
+        const float xh = fmaf(x[i], cnt, -stats[2 * s]) * (rstd * inv_cnt);
         const float g = (!relu || y[i] > 0.f) ? dy[i] : 0.f;
         dx[i] = rstd * (gamma[c] * g - gs[2 * s] * inv_cnt - xh * gs[2 * s + 1] * inv_cnt);
     }
@@ -508,7 +533,8 @@ __global__ void bn_running_kernel(const float* __restrict__ stats, int C, float 
 template <typename TX, typename TY>
 static int launch_norm_apply(const TX* x, const float* gamma, const float* beta, long long R, long long rows_per_stat, int C,
                              int cpg, int n_groups, float eps, int relu, float* stats, TY* y, int d2s_H, int d2s_W,
-                             TY* xs, bool vec, hipStream_t st, const float* part = nullptr, int n_part = 0, int chan = 0) {
+                             TY* xs, bool vec, hipStream_t st, const float* part = nullptr, int n_part = 0, int chan = 0,
+                             const float* mean_tab = nullptr) {
     const long long total = R * C;
     const long long n_rg = R / rows_per_stat;
     if (vec && rows_per_stat * C < (1ll << 32) && n_rg <= 65535) {
@@ -517,19 +543,19 @@ static int launch_norm_apply(const TX* x, const float* gamma, const float* beta,
         bx = bx > cap ? cap : (bx < 1 ? 1 : bx);
         const dim3 g2((unsigned)bx, (unsigned)n_rg), b2(256);
         const size_t lds = part ? sizeof(float) * 2 * n_groups : 0;
-        if (d2s_W > 0) hipLaunchKernelGGL((norm_apply_rows_kernel<true, TX, TY>), g2, b2, lds, st, x, gamma, beta, stats, rows_per_stat, C, cpg, n_groups, eps, relu, y, d2s_H, d2s_W, xs, part, n_part, stats, chan);
-        else hipLaunchKernelGGL((norm_apply_rows_kernel<false, TX, TY>), g2, b2, lds, st, x, gamma, beta, stats, rows_per_stat, C, cpg, n_groups, eps, relu, y, 0, 0, (TY*)nullptr, part, n_part, stats, chan);
+        if (d2s_W > 0) hipLaunchKernelGGL((norm_apply_rows_kernel<true, TX, TY>), g2, b2, lds, st, x, gamma, beta, stats, rows_per_stat, C, cpg, n_groups, eps, relu, y, d2s_H, d2s_W, xs, part, n_part, stats, chan, mean_tab);
+        else hipLaunchKernelGGL((norm_apply_rows_kernel<false, TX, TY>), g2, b2, lds, st, x, gamma, beta, stats, rows_per_stat, C, cpg, n_groups, eps, relu, y, 0, 0, (TY*)nullptr, part, n_part, stats, chan, mean_tab);
         return check_launch("norm_apply_rows_kernel");
     }
     long long nb = (total / 4 + 255) / 256;
     nb = nb > 4096 ? 4096 : (nb < 1 ? 1 : nb);
     const dim3 g((unsigned)nb), b(256);
     if (d2s_W > 0) {
-        if (vec) hipLaunchKernelGGL((norm_apply_kernel<true, true, TX, TY>), g, b, 0, st, x, gamma, beta, stats, total, rows_per_stat, C, cpg, n_groups, eps, relu, y, d2s_H, d2s_W, xs);
-        else hipLaunchKernelGGL((norm_apply_kernel<false, true, TX, TY>), g, b, 0, st, x, gamma, beta, stats, total, rows_per_stat, C, cpg, n_groups, eps, relu, y, d2s_H, d2s_W, xs);
+        if (vec) hipLaunchKernelGGL((norm_apply_kernel<true, true, TX, TY>), g, b, 0, st, x, gamma, beta, stats, total, rows_per_stat, C, cpg, n_groups, eps, relu, y, d2s_H, d2s_W, xs, mean_tab);
+        else hipLaunchKernelGGL((norm_apply_kernel<false, true, TX, TY>), g, b, 0, st, x, gamma, beta, stats, total, rows_per_stat, C, cpg, n_groups, eps, relu, y, d2s_H, d2s_W, xs, mean_tab);
     } else {
-        if (vec) hipLaunchKernelGGL((norm_apply_kernel<true, false, TX, TY>), g, b, 0, st, x, gamma, beta, stats, total, rows_per_stat, C, cpg, n_groups, eps, relu, y, 0, 0, (TY*)nullptr);
-        else hipLaunchKernelGGL((norm_apply_kernel<false, false, TX, TY>), g, b, 0, st, x, gamma, beta, stats, total, rows_per_stat, C, cpg, n_groups, eps, relu, y, 0, 0, (TY*)nullptr);
+        if (vec) hipLaunchKernelGGL((norm_apply_kernel<true, false, TX, TY>), g, b, 0, st, x, gamma, beta, stats, total, rows_per_stat, C, cpg, n_groups, eps, relu, y, 0, 0, (TY*)nullptr, mean_tab);
+        else hipLaunchKernelGGL((norm_apply_kernel<false, false, TX, TY>), g, b, 0, st, x, gamma, beta, stats, total, rows_per_stat, C, cpg, n_groups, eps, relu, y, 0, 0, (TY*)nullptr, mean_tab);
     }
     return check_launch("norm_apply_kernel");
 }
@@ -556,21 +582,37 @@ static int launch_norm(const TX* x, const float* gamma, const float* beta, long 
     // normalisation, 36 per D-step; its ticket-fused attempt needed a device-scope fence per workgroup and lost).
     if (scratch && vec && grid.x <= CSLGAN_NORM_PARTIAL_BLOCKS && rows_per_stat * C < (1ll << 32) && n_row_groups <= 65535 &&
         2 * (size_t)n_groups * sizeof(float) <= 32768) {
-        hipLaunchKernelGGL((norm_stats_kernel<true, true, TX>), grid, block, 2 * lds, st, x, rows_per_stat, C, cpg, n_groups, (int)rpb, stats, scratch, n_stats);
+        hipLaunchKernelGGL((norm_stats_kernel<true, true, TX>), grid, block, 2 * lds, st, x, rows_per_stat, C, cpg, n_groups, (int)rpb, stats, scratch, n_stats, (const float*)nullptr);
         const int rc1 = check_launch("norm_stats_kernel");
         if (rc1) return rc1;
         return launch_norm_apply(x, gamma, beta, R, rows_per_stat, C, cpg, n_groups, eps, relu, stats, y, d2s_H, d2s_W, xs, vec, st, scratch, (int)grid.x);
     }
     if (int rc = zero_floats(stats, (size_t)2 * n_stats, st)) return rc;
-    if (vec) hipLaunchKernelGGL((norm_stats_kernel<true, false, TX>), grid, block, 2 * lds, st, x, rows_per_stat, C, cpg, n_groups, (int)rpb, stats, (float*)nullptr, n_stats);
-    else hipLaunchKernelGGL((norm_stats_kernel<false, false, TX>), grid, block, 2 * lds, st, x, rows_per_stat, C, cpg, n_groups, (int)rpb, stats, (float*)nullptr, n_stats);
-    int rc = check_launch("norm_stats_kernel");
+    const dim3 fgrid((unsigned)((n_stats + 127) / 128)), fblock(128);
+    const float* shift = nullptr;
+    int rc;
+    if (vec) hipLaunchKernelGGL((norm_stats_kernel<true, false, TX>), grid, block, 2 * lds, st, x, rows_per_stat, C, cpg, n_groups, (int)rpb, stats, (float*)nullptr, n_stats, shift);
+    else hipLaunchKernelGGL((norm_stats_kernel<false, false, TX>), grid, block, 2 * lds, st, x, rows_per_stat, C, cpg, n_groups, (int)rpb, stats, (float*)nullptr, n_stats, shift);
+    rc = check_launch("norm_stats_kernel");
     if (rc) return rc;
-    hipLaunchKernelGGL(norm_stats_finalize_kernel<TX>, dim3((unsigned)((n_stats + 127) / 128)), dim3(128), 0, st, x, rows_per_stat, C, cpg,
-                       n_groups, n_stats, stats);
+    if (scratch) {
+        // The routes with global atomics (more than CSLGAN_NORM_PARTIAL_BLOCKS workgroups per statistic, or the scalar kernels; the
+        // training step's GroupNorms take neither) buy the variance back with a second pass: the first pass's mean_s (n_stats floats
+        // at the head of scratch) becomes the shift, so S2 - S1^2/n no longer cancels by 1 + ((k - mean)/sigma)^2.  One more read
+        // of x: a quarter on top of the three passes (statistics, apply's read and write) the route costs anyway.
+        hipLaunchKernelGGL(norm_stats_finalize_kernel<TX>, fgrid, fblock, 0, st, x, rows_per_stat, C, cpg, n_groups, n_stats, stats, shift, scratch, 1);
+        rc = check_launch("norm_stats_finalize_kernel");
+        if (rc) return rc;
+        shift = scratch;
+        if (vec) hipLaunchKernelGGL((norm_stats_kernel<true, false, TX>), grid, block, 2 * lds, st, x, rows_per_stat, C, cpg, n_groups, (int)rpb, stats, (float*)nullptr, n_stats, shift);
+        else hipLaunchKernelGGL((norm_stats_kernel<false, false, TX>), grid, block, 2 * lds, st, x, rows_per_stat, C, cpg, n_groups, (int)rpb, stats, (float*)nullptr, n_stats, shift);
+        rc = check_launch("norm_stats_kernel");
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(norm_stats_finalize_kernel<TX>, fgrid, fblock, 0, st, x, rows_per_stat, C, cpg, n_groups, n_stats, stats, shift, scratch, 0);
     rc = check_launch("norm_stats_finalize_kernel");
     if (rc) return rc;
-    return launch_norm_apply(x, gamma, beta, R, rows_per_stat, C, cpg, n_groups, eps, relu, stats, y, d2s_H, d2s_W, xs, vec, st);
+    return launch_norm_apply(x, gamma, beta, R, rows_per_stat, C, cpg, n_groups, eps, relu, stats, y, d2s_H, d2s_W, xs, vec, st, nullptr, 0, 0, scratch);
 }
 
 // d2s_W > 0 asks for the depth-to-space output layout: rows are (n, h, w) with w fastest, H = rows_per_image / d2s_W

@@ -1119,6 +1119,8 @@ def norm_act_bwd(x, dy, y, gamma, stats, rows_per_stat, groups, eps, relu):
     """Backward of groupnorm_act / batchnorm_act: returns (dx, dgamma, dbeta)."""
     for t, n in ((x, "x"), (dy, "dy"), (gamma, "gamma"), (stats, "stats")):
         _chk(t, n)
+    if relu and y is not None:      # (a missing y is the library's error)
+        _chk(y, "y")
     Cc = x.shape[-1]
     rows = x.numel() // Cc
     L = _lib.lib()

@@ -414,7 +414,8 @@ int cslgan_fold_channels4_f32(const float* in, int64_t rows, int C, int unfold, 
  * scratch (nullable; ABI v5 meaning): caller workspace of 2*N*groups*CSLGAN_NORM_PARTIAL_BLOCKS floats (no initialisation needed)
  * for per-workgroup partial statistics: the normalisation then runs as TWO launches (statistics, apply — the apply kernel adds the
  * partials in its prologue and publishes the final pairs to stats_ws) instead of four (zero, statistics with atomics, finalize,
- * apply).  One scratch must not be shared by launches on different streams. */
+ * apply).  The routes with global atomics (more than CSLGAN_NORM_PARTIAL_BLOCKS workgroups per statistic, or the scalar
+ * kernels) use scratch too: its first N*groups floats carry the means of a first statistics pass, the shift of a second one.  One scratch must not be shared by launches on different streams. */
 #define CSLGAN_NORM_PARTIAL_BLOCKS 64
 /* The apply half of cslgan_groupnorm_act_f32 on statistics a conv epilogue left behind (cslgan_conv_t.gn_part): part holds
  * n_part = HW/64 (sum, centred sum of squares) pairs per image and group; everything else as cslgan_groupnorm_act_f32
