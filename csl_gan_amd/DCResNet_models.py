@@ -10,7 +10,8 @@ MI355X-first differences, all exact re-associations of the reference arithmetic:
     tensor ps[c',2h+i,2w+j] = x[4c'+2i+j,h,w] repeated four times.  The device path therefore never builds `up`: the
     normalisation kernel writes ps directly and the conv runs on ps with its filter summed over the four channel groups
     (ops.fold_channels4) — a quarter of the reference's multiply-adds for these layers;
-  * the 1x1 shortcut's result is added in the epilogue of the block's last conv;
+  * the 1x1 shortcut's result is added in the epilogue of the block's last conv; in a frozen forward the shortcut itself is
+    computed by the kernel that applies bn1 and shuffles (ops.groupnorm_apply_shortcut);
   * bias, LeakyReLU(0.2) / tanh are conv-kernel epilogues; GroupNorm/BatchNorm+ReLU is one op.
 """
 import torch
@@ -122,8 +123,18 @@ class ResBlockUp(nn.Module):
         if x.shape[-1] % 4:
             raise NotImplementedError("ResBlockUp on HIP needs in_ch %% 4 == 0 (got %d)" % x.shape[-1])
         fuse = _gn_fusable(x)
-        a_ps, x_ps = self.bn1.forward_shuffled(x, part=x_part) if x_part is not None else self.bn1.forward_shuffled(x)
-        s = self.shortcut.forward_shuffled(x_ps)        # 1x1 conv over the C/4 shuffled channels, full resolution
+        sc = self.shortcut.conv
+        if (fuse and isinstance(self.bn1, HipGroupNormAct) and sc.kernel_size == (1, 1) and sc.act == ops.ACT_NONE and sc._bpc is None
+                and ops.gn_shortcut_ok(x, sc.out_channels, x_part)):
+            # frozen forward on the previous block's statistics: apply, shuffle and shortcut in one launch — the raw shuffled x,
+            # which only the shortcut would read, is never written (csrc/gn_shortcut.hip)
+            w = sc.weight.permute(0, 2, 3, 1).contiguous()
+            a_ps, s = ops.groupnorm_apply_shortcut(x, self.bn1.weight.detach(), self.bn1.bias.detach(), self.bn1.num_groups, x_part,
+                                                   ops.fold_channels4(w.detach(), wkey=sc._wkey(w)),
+                                                   None if sc.bias is None else sc.bias.detach(), eps=self.bn1.eps, relu=self.bn1.relu)
+        else:
+            a_ps, x_ps = self.bn1.forward_shuffled(x, part=x_part) if x_part is not None else self.bn1.forward_shuffled(x)
+            s = self.shortcut.forward_shuffled(x_ps)    # 1x1 conv over the C/4 shuffled channels, full resolution
         affine = None
         if fuse and isinstance(self.bn2, HipGroupNormAct):
             with ops.gn_partials(self.bn2.num_groups) as cell:

@@ -22,7 +22,7 @@ EXPORTS = [
     "cslgan_conv2d_wgrad_scaled_f32", "cslgan_conv2d_wgrad_blocks_f32", "cslgan_conv2d_wgrad_sqnorm_gram_f32", "cslgan_conv2d_wgrad_skinny_f32", "cslgan_conv2d_s2_fwd_f32",
     "cslgan_conv2d_dgrad_x3_f32", "cslgan_conv2d_s2_fwd_x3_f32", "cslgan_u8_to_f32_nhwc", "cslgan_split_filter_x3_f32",
     "cslgan_depth_to_space_f32", "cslgan_fold_channels4_f32",
-    "cslgan_bias_grad_grouped_f32", "cslgan_act_bwd_f32", "cslgan_groupnorm_act_f32", "cslgan_groupnorm_apply_parts_f32", "cslgan_groupnorm_affine_parts_f32", "cslgan_batchnorm_act_f32", "cslgan_batchnorm_eval_act_f32",
+    "cslgan_bias_grad_grouped_f32", "cslgan_act_bwd_f32", "cslgan_groupnorm_act_f32", "cslgan_groupnorm_apply_parts_f32", "cslgan_groupnorm_apply_parts_shortcut_f32", "cslgan_groupnorm_affine_parts_f32", "cslgan_batchnorm_act_f32", "cslgan_batchnorm_eval_act_f32",
     "cslgan_norm_act_bwd_f32", "cslgan_norm_bwd_ws_floats",
     "cslgan_adam_step_f32", "cslgan_adam_step_dev_f32", "cslgan_adam_multi_f32",
     "cslgan_adaptive_clip_f32", "cslgan_segment_means_f32", "cslgan_segment_means_bwd_f32", "cslgan_dstep_stats_f32", "cslgan_grad_log_stats_f32",
@@ -122,6 +122,7 @@ def lib():
         "cslgan_groupnorm_act_f32": [vp, vp, vp, i32, i32, i32, i32, f32, i32, vp, vp, i32, vp, vp, vp],
         "cslgan_groupnorm_affine_parts_f32": [vp, i32, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp],
         "cslgan_groupnorm_apply_parts_f32": [vp, vp, vp, i32, i32, i32, i32, f32, i32, vp, i32, vp, vp, i32, vp, vp],
+        "cslgan_groupnorm_apply_parts_shortcut_f32": [vp, vp, vp, i32, i32, i32, i32, f32, i32, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp],
         "cslgan_batchnorm_act_f32": [vp, vp, vp, i64, i32, f32, i32, f32, vp, vp, vp, vp, i64, i32, vp, vp, vp],
         "cslgan_batchnorm_eval_act_f32": [vp, vp, vp, vp, vp, i64, i32, f32, i32, vp, vp, i64, i32, vp, vp],
         "cslgan_adam_step_f32": [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, vp],

@@ -37,7 +37,8 @@ __global__ __launch_bounds__(256) void gram_sqnorm_kernel(const GramParams p) {
     constexpr int ROWS = TILES == 1 ? 128 : 64;      // LDS rows per buffer: 4 K-chunks x 32 pixels, or 1 chunk x 64 pixels
     constexpr int LPT = ROWS * 8 / 256;              // float4 loads per thread per iteration
     __shared__ __attribute__((aligned(16))) float As[2][ROWS * GR_LD];
-    __shared__ float s_red[TILES == 1 ? 2 * 1024 : 4];
+    __shared__ float s_red[4];
+    static_assert(TILES != 1 || 2 * ROWS * GR_LD >= 4 * 2048, "the staging buffers hold the four wavefronts' partial matrices");
 
     const int tid = threadIdx.x;
     const int b = blockIdx.x;
@@ -141,18 +142,23 @@ __global__ __launch_bounds__(256) void gram_sqnorm_kernel(const GramParams p) {
 
     float prod = 0.f;
     if (TILES == 1) {
-        // add the four wavefronts' partial Gram matrices, then multiply them entry by entry
-        for (int i = tid; i < 2 * 1024; i += 256) s_red[i] = 0.f;
-        __syncthreads();
+        // add the four wavefronts' partial Gram matrices in wavefront order, then multiply them entry by entry.  Each wavefront
+        // leaves its two matrices in its own 2048 floats of the staging buffers (the loop's last reads are behind the barrier
+        // above): LDS float atomics into one matrix added them in the order the scheduler chose, so two launches on the same
+        // sample could differ in the last bits.
+        float* red = &As[0][0];
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
             const int row = (v & 3) + 8 * (v >> 2) + 4 * h;
-            atomicAdd(&s_red[row * 32 + r], acc1[v]);
-            atomicAdd(&s_red[1024 + row * 32 + r], acc2[v]);
+            red[wid * 2048 + row * 32 + r] = acc1[v];
+            red[wid * 2048 + 1024 + row * 32 + r] = acc2[v];
         }
         __syncthreads();
-        for (int i = tid; i < 1024; i += 256) prod = fmaf(s_red[i], s_red[1024 + i], prod);
-        __syncthreads();
+        for (int i = tid; i < 1024; i += 256) {
+            const float g1 = ((red[i] + red[2048 + i]) + red[4096 + i]) + red[6144 + i];
+            const float g2 = ((red[1024 + i] + red[3072 + i]) + red[5120 + i]) + red[7168 + i];
+            prod = fmaf(g1, g2, prod);
+        }
         const float tot = block_sum_256(prod, s_red);
         if (tid == 0) atomicAdd(p.sq + b, p.alpha2 * tot);
     } else {

@@ -4,6 +4,7 @@
 // nn.GroupNorm + F.relu DCResNet_models.py:55-57,63-67,101-102; torch.optim.Adam.step train.py:76,484.
 #include "common.h"
 #include "device_prims.h"
+#include "gn_apply.h"
 
 namespace cslgan {
 
@@ -262,25 +263,8 @@ __global__ __launch_bounds__(256) void norm_apply_rows_kernel(const TX* __restri
         // row group's n_part slots here (2 * n_groups threads, n_part loads each), finish them in LDS, and let the row group's first
         // workgroup publish the final (sum x, centred sum of squares) pairs for whoever reads the statistics later (the backward).
         extern __shared__ float s_st[];               // [2 * n_groups]: (mean, centred sum of squares)
-        for (int i = threadIdx.x; chan && i < n_groups; i += 256) {
-            // chan: the partials come from a conv epilogue (cslgan_conv_t.gn_part): per slot the sum of its cnt / n_part values and
-            // their sum of squares about the slot's own mean — combined exactly: M2 = sum_b M2_b + n_b (mean_b - mean)^2
-            float sum = 0.f;
-            for (int b = 0; b < n_part; ++b) sum += part[((sr * n_part + b) * n_groups + i) * 2];
-            const float nb = cnt / (float)n_part, mean_all = sum / cnt;
-            float css = 0.f;
-            for (int b = 0; b < n_part; ++b) {
-                const float* q = part + ((sr * n_part + b) * n_groups + i) * 2;
-                const float dm = q[0] / nb - mean_all;
-                css += q[1] + nb * dm * dm;
-            }
-            s_st[2 * i] = mean_all;
-            s_st[2 * i + 1] = css;
-            if (stats_out && blockIdx.x == 0) {
-                stats_out[2 * (sr * n_groups + i)] = sum;
-                stats_out[2 * (sr * n_groups + i) + 1] = css;
-            }
-        }
+        // chan: the partials come from a conv epilogue (cslgan_conv_t.gn_part) and are combined exactly (gn_apply.h)
+        if (chan) gn_combine_chan(part, sr, n_part, n_groups, cnt, s_st, stats_out, blockIdx.x == 0);
         for (int i = threadIdx.x; !chan && i < n_groups; i += 256) {
             float S1 = 0.f, S2 = 0.f;
             for (int b = 0; b < n_part; ++b) {
@@ -302,9 +286,7 @@ __global__ __launch_bounds__(256) void norm_apply_rows_kernel(const TX* __restri
         __syncthreads();
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const int g = (c + e) / cpg;
-            mean[e] = s_st[2 * g];
-            rstd[e] = rsqrtf(s_st[2 * g + 1] * inv_cnt + eps);
+            gn_group_stat(s_st, (c + e) / cpg, inv_cnt, eps, mean[e], rstd[e]);
         }
     } else {
 #pragma unroll
@@ -327,10 +309,7 @@ __global__ __launch_bounds__(256) void norm_apply_rows_kernel(const TX* __restri
         const float in[4] = {v.x, v.y, v.z, v.w};
         float o[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float t = (in[e] - mean[e]) * rstd[e] * ga[e] + be[e];
-            o[e] = (relu && t < 0.f) ? 0.f : t;
-        }
+        for (int e = 0; e < 4; ++e) o[e] = gn_apply(in[e], mean[e], rstd[e], ga[e], be[e], relu);
         if (D2S) {
             const unsigned rl = i >> lg;              // row within the group
             const int Cq = C >> 2, cq = c >> 2;

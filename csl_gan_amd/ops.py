@@ -1902,6 +1902,45 @@ def groupnorm_act(x, gamma, beta, groups, eps=1e-5, relu=True, return_stats=Fals
     return (out, ws) if return_stats else out
 
 
+_GN_SHORTCUT_FUSE = True   # ResBlockUp's bn1 apply, shuffle and 1x1 shortcut conv in one launch (tests switch it off to compare)
+
+
+def gn_shortcut_ok(x, K, part):
+    """Does groupnorm_apply_shortcut take this block?  (csrc/gn_shortcut.hip: C/4 in {32, 64, 128}, K a multiple of 64, the
+    statistics of a conv epilogue.)"""
+    if not (_GN_SHORTCUT_FUSE and part is not None and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
+        return False
+    N, H, W, Cc = x.shape
+    return Cc in (128, 256, 512) and K >= 64 and K % 64 == 0 and N <= 65535 and H * W == 64 * part[1] and 4 * H * W * K < 2 ** 31
+
+
+def groupnorm_apply_shortcut(x, gamma, beta, groups, part, wf, bias=None, eps=1e-5, relu=True, return_stats=False):
+    """(a_ps, s) of ResBlockUp from one read of x[N,H,W,C]: a_ps[N,2H,2W,C/4] = depth_to_space(act(groupnorm(x))) exactly as
+    groupnorm_act(d2s=True, part=part) writes it, and s[N,2H,2W,K] = conv1x1(depth_to_space(x), wf[K,1,1,C/4]) + bias — the raw
+    shuffled x never reaches HBM.  part: the conv-epilogue statistics of x (gn_partials); wf: the folded shortcut filter."""
+    _chk(x, "x"); _chk(gamma, "gamma"); _chk(beta, "beta"); _chk(wf, "wf")
+    N, H, W, Cc = x.shape
+    K = wf.shape[0]
+    if wf.numel() != K * (Cc // 4):
+        raise RuntimeError("groupnorm_apply_shortcut: wf must be [K, 1, 1, C/4] = [%d, 1, 1, %d]" % (K, Cc // 4))
+    if bias is not None:
+        _chk(bias, "bias")
+        if bias.numel() != K:
+            raise RuntimeError("groupnorm_apply_shortcut: bias must have K = %d elements" % K)
+    pt, n_part = part
+    a_ps = torch.empty((N, 2 * H, 2 * W, Cc // 4), device=x.device, dtype=torch.float32)
+    s = torch.empty((N, 2 * H, 2 * W, K), device=x.device, dtype=torch.float32)
+    ws = torch.empty(2 * N * groups, device=x.device, dtype=torch.float32)
+    rows = 4 * N * H * W
+    # timed as the shortcut conv it replaces: the reference runs it over four identical channel groups
+    _timed("groupnorm_apply_shortcut", 2.0 * rows * K * Cc, 4.0 * (2 * N * H * W * Cc + wf.numel() + rows * K),
+           lambda: check(_lib.lib().cslgan_groupnorm_apply_parts_shortcut_f32(
+               _p(x), _p(gamma), _p(beta), N, H * W, Cc, groups, float(eps), 1 if relu else 0, _p(pt), n_part, _p(ws), _p(a_ps), W,
+               _p(wf), _p(bias), K, _p(s), _stream()), "groupnorm_apply_parts_shortcut"),
+           exec_flop=2.0 * rows * K * (Cc // 4), tag=lambda: "N%d %dx%d C%d K%d" % (N, H, W, Cc, K))
+    return (a_ps, s, ws) if return_stats else (a_ps, s)
+
+
 def batchnorm_act(x, gamma, beta, running_mean=None, running_var=None, momentum=0.1, eps=1e-5, relu=True, return_stats=False,
                   d2s=False, want_raw=False):
     """Training-mode BatchNorm (+ReLU) over all leading dims of NHWC x; updates the running stats in place.

@@ -430,6 +430,17 @@ int cslgan_groupnorm_apply_parts_f32(const float* x, const float* gamma, const f
 int cslgan_groupnorm_act_f32(const float* x, const float* gamma, const float* beta, int N, int HW, int C,
                              int groups, float eps, int relu, float* stats_ws, float* y, int d2s_W, float* x_shuffled,
                              float* scratch, void* stream);
+/* cslgan_groupnorm_apply_parts_f32 with d2s_W > 0 and ResBlockUp's 1x1 shortcut conv in ONE launch (csrc/gn_shortcut.hip; a new
+ * entry under ABI v7: no existing entry or struct changes):
+ * y receives the shuffled activation exactly as the apply entry writes it, stats_ws the final pairs, and instead of the raw
+ * x_shuffled (never written) the kernel leaves the conv that would have read it,
+ *   s[n][2h+i][2w+j][k] = bias[k] + sum_c' wf[k][c'] * x[n][h][w][4c'+2i+j]
+ * wf[K][C/4]: the shortcut filter folded over the four channel groups (cslgan_fold_channels4_f32); bias[K] nullable.
+ * Needs C / 4 in {32, 64, 128}, K % 64 == 0, HW == 64 * n_part (n_part <= CSLGAN_NORM_PARTIAL_BLOCKS), d2s_W dividing HW,
+ * N <= 65535, 4 * HW * K < 2^31 and x, y, wf, s aligned to 16 bytes; anything else is an error before any launch. */
+int cslgan_groupnorm_apply_parts_shortcut_f32(const float* x, const float* gamma, const float* beta, int N, int HW, int C, int groups,
+                                              float eps, int relu, const float* part, int n_part, float* stats_ws, float* y,
+                                              int d2s_W, const float* wf, const float* bias, int K, float* s, void* stream);
 
 /* Training-mode BatchNorm2d (+ optional ReLU) on NHWC x[rows][C], rows = N*H*W: batch statistics per channel,
  * running_mean / running_var (nullable pair) updated with `momentum` and the unbiased variance — the bn=True
