@@ -14,14 +14,17 @@ MI355X-first differences, all exact re-associations of the reference arithmetic:
     computed by the kernel that applies bn1 and shuffles (ops.groupnorm_apply_shortcut);
   * bias, LeakyReLU(0.2) / tanh are conv-kernel epilogues; GroupNorm/BatchNorm+ReLU is one op.
 """
+import contextlib
+
 import torch
 import torch.nn.functional as F
 from torch import nn
 
 from . import functional as HF
 from . import ops
+from . import nn as hnn
 from .models import Discriminator, Generator
-from .nn import HipConv2d, HipGroupNormAct, HipLinear
+from .nn import HipConv2d, HipGroupNormAct, HipLinear, _BatchNormAct
 
 
 class UpsampleConv(nn.Module):
@@ -43,59 +46,30 @@ class UpsampleConv(nn.Module):
         return self.conv(F.pixel_shuffle(torch.cat([x, x, x, x], 1), 2))
 
 
-class _BatchNormAct(nn.BatchNorm2d):
-    """BatchNorm2d + ReLU for the bn=True generator of the non-per-sample modes (init_util.py:46): batch statistics and the
-    running-stat update run on cslgan_batchnorm_act_f32, the backward on cslgan_norm_act_bwd_f32; eval mode (running
-    statistics: the sampling path train.py:298-308, gensamples.py:26-41) on cslgan_batchnorm_eval_act_f32."""
-
-    def _train_stats(self):
-        return self.training or self.running_mean is None
-
-    def forward_nhwc(self, x, d2s=False):
-        from . import nn as hnn
-        if hnn._mask_recorder is not None:          # parity-test hook (csl_gan_amd.nn.ActivationMaskRecorder): two-launch form
-            y = hnn._record_mask(self, self._forward_nhwc(x, False))
-            return (HF.DepthToSpace.apply(y), HF.DepthToSpace.apply(x)) if d2s else y
-        return self._forward_nhwc(x, d2s)
-
-    def _forward_nhwc(self, x, d2s):
-        g, b = self.weight, self.bias
-        if not self._train_stats():
-            if torch.is_grad_enabled() and (x.requires_grad or g.requires_grad):
-                raise NotImplementedError("eval-mode BatchNorm on HIP is inference-only (no backward)")
-            return ops.batchnorm_eval_act(x, g.detach(), b.detach(), self.running_mean, self.running_var, eps=self.eps, relu=True,
-                                          d2s=d2s, want_raw=d2s)
-        if self.num_batches_tracked is not None:
-            self.num_batches_tracked += 1
-        if torch.is_grad_enabled() and (x.requires_grad or g.requires_grad):
-            y = HF.NormAct.apply(x, g, b, 0, self.eps, True, self.running_mean, self.running_var, self.momentum)
-            return (HF.DepthToSpace.apply(y), HF.DepthToSpace.apply(x)) if d2s else y
-        return ops.batchnorm_act(x, g.detach(), b.detach(), self.running_mean, self.running_var, momentum=self.momentum,
-                                 eps=self.eps, relu=True, d2s=d2s, want_raw=d2s)
-
-    def forward_shuffled(self, x):
-        return self.forward_nhwc(x, d2s=True)
-
-    def forward(self, x):
-        if x.is_cuda:
-            return HF.nchw_view(self.forward_nhwc(HF.nhwc(x)))
-        return F.relu(super().forward(x))
-
-
 def _gn_fusable(x):
     """GroupNorm statistics may come from the producing conv's epilogue: a frozen fp32 device forward with no recorder attached."""
-    from . import nn as hnn
     return (not torch.is_grad_enabled()) and x.is_cuda and x.dtype == torch.float32 and not ops.storage_bf16() and hnn._mask_recorder is None
 
 
-def _norm_as_affine(norm, x, part, conv):
-    """GroupNorm(+ReLU) `norm` of x folded into the staging of `conv` (the only consumer): (scale, shift, relu) tables from the
-    statistics x's producer left (ops.groupnorm_affine), or None when the statistics or the conv's route are not there."""
-    if part is None or not ops.in_affine_ok(x, conv.weight.permute(0, 2, 3, 1), conv.stride[0], conv.padding[0]):
-        return None
-    N, H, W, C = x.shape
-    sc, sh = ops.groupnorm_affine(part, norm.weight.detach(), norm.bias.detach(), norm.num_groups, norm.eps, N, H * W, C)
-    return sc, sh, bool(norm.relu)
+class _NoParts:
+    part = None
+
+
+def _parts_for(fuse, norm):
+    """`with _parts_for(fuse, norm) as cell:` around the conv that feeds `norm`: in a frozen forward that conv leaves GroupNorm's
+    partial statistics of its output in cell.part (ops.gn_partials); otherwise, and when its route cannot, cell.part is None."""
+    return ops.gn_partials(norm.num_groups) if fuse and isinstance(norm, HipGroupNormAct) else contextlib.nullcontext(_NoParts)
+
+
+def _norm_then_conv(norm, x, part, conv, **conv_kw):
+    """conv(act(norm(x))), `conv` being the only consumer.  With statistics of x at hand (part) and a conv route that takes them
+    (ops.in_affine_ok), GroupNorm(+ReLU) rides in the conv's staging as per-(image, channel) (scale, shift) tables
+    (ops.groupnorm_affine) and conv reads the raw x; else the norm is a launch of its own (on `part`, if there is one)."""
+    if part is not None and ops.in_affine_ok(x, conv.weight.permute(0, 2, 3, 1), conv.stride[0], conv.padding[0]):
+        N, H, W, C = x.shape
+        sc, sh = ops.groupnorm_affine(part, norm.weight.detach(), norm.bias.detach(), norm.num_groups, norm.eps, N, H * W, C)
+        return conv.forward_nhwc(x, in_affine=(sc, sh, bool(norm.relu)), **conv_kw)
+    return conv.forward_nhwc(norm.forward_nhwc(x, part=part), **conv_kw)
 
 
 def _norm_act(bn, ch):
@@ -123,31 +97,27 @@ class ResBlockUp(nn.Module):
         if x.shape[-1] % 4:
             raise NotImplementedError("ResBlockUp on HIP needs in_ch %% 4 == 0 (got %d)" % x.shape[-1])
         fuse = _gn_fusable(x)
+        # 1. bn1 + shortcut.  A frozen forward on the previous block's statistics applies, shuffles and runs the 1x1 shortcut in one
+        # launch: the raw shuffled x, which only the shortcut would read, is never written (csrc/gn_shortcut.hip).  Else bn1 writes
+        # both shuffled tensors and the shortcut is a 1x1 conv over the C/4 shuffled channels at full resolution
         sc = self.shortcut.conv
-        if (fuse and isinstance(self.bn1, HipGroupNormAct) and sc.kernel_size == (1, 1) and sc.act == ops.ACT_NONE and sc._bpc is None
-                and ops.gn_shortcut_ok(x, sc.out_channels, x_part)):
-            # frozen forward on the previous block's statistics: apply, shuffle and shortcut in one launch — the raw shuffled x,
-            # which only the shortcut would read, is never written (csrc/gn_shortcut.hip)
+        one_launch = (fuse and isinstance(self.bn1, HipGroupNormAct) and sc.kernel_size == (1, 1) and sc.act == ops.ACT_NONE
+                      and sc._bpc is None and ops.gn_shortcut_ok(x, sc.out_channels, x_part))
+        if one_launch:
             w = sc.weight.permute(0, 2, 3, 1).contiguous()
             a_ps, s = ops.groupnorm_apply_shortcut(x, self.bn1.weight.detach(), self.bn1.bias.detach(), self.bn1.num_groups, x_part,
                                                    ops.fold_channels4(w.detach(), wkey=sc._wkey(w)),
                                                    None if sc.bias is None else sc.bias.detach(), eps=self.bn1.eps, relu=self.bn1.relu)
         else:
-            a_ps, x_ps = self.bn1.forward_shuffled(x, part=x_part) if x_part is not None else self.bn1.forward_shuffled(x)
-            s = self.shortcut.forward_shuffled(x_ps)    # 1x1 conv over the C/4 shuffled channels, full resolution
-        affine = None
-        if fuse and isinstance(self.bn2, HipGroupNormAct):
-            with ops.gn_partials(self.bn2.num_groups) as cell:
-                o = self.convUp.forward_shuffled(a_ps)
-            affine = _norm_as_affine(self.bn2, o, cell.part, self.conv)
-            h = o if affine is not None else self.bn2.forward_nhwc(o, part=cell.part)
-        else:
-            h = self.bn2.forward_nhwc(self.convUp.forward_shuffled(a_ps))
-        if fuse and isinstance(next_norm, HipGroupNormAct):
-            with ops.gn_partials(next_norm.num_groups) as cell:
-                out = self.conv.forward_nhwc(h, residual=s, in_affine=affine)
-            return out, cell.part
-        return self.conv.forward_nhwc(h, residual=s, in_affine=affine), None
+            a_ps, x_ps = self.bn1.forward_shuffled(x, part=x_part)
+            s = self.shortcut.forward_shuffled(x_ps)
+        # 2. convUp, which leaves bn2's statistics
+        with _parts_for(fuse, self.bn2) as cell:
+            o = self.convUp.forward_shuffled(a_ps)
+        # 3. bn2 and the last conv (the shortcut added in its epilogue), which leaves the statistics for the next norm
+        with _parts_for(fuse, next_norm) as nxt:
+            out = _norm_then_conv(self.bn2, o, cell.part, self.conv, residual=s)
+        return out, nxt.part
 
     def forward(self, x):
         if x.is_cuda:
@@ -179,11 +149,7 @@ class DCResNetGenerator(Generator):
         for i, blk in enumerate(self.blocks):           # each block leaves the statistics the NEXT normalisation needs (frozen forward)
             nxt = self.blocks[i + 1].bn1 if i + 1 < len(self.blocks) else self.bn
             x, part = blk.forward_nhwc_parts(x, part, nxt)
-        affine = _norm_as_affine(self.bn, x, part, self.convOut) if part is not None else None
-        if affine is not None:                          # the last normalisation rides in the output conv's staging
-            return HF.nchw_view(self.convOut.forward_nhwc(x, in_affine=affine, out=out))
-        h = self.bn.forward_nhwc(x, part=part) if part is not None else self.bn.forward_nhwc(x)
-        return HF.nchw_view(self.convOut.forward_nhwc(h))
+        return HF.nchw_view(_norm_then_conv(self.bn, x, part, self.convOut, out=out))
 
     def loss(self, d_output, device):
         return -torch.mean(d_output)

@@ -12,6 +12,8 @@ recovered from the OUTPUT (slope > 0 keeps the sign), so no pre-activation tenso
 """
 from __future__ import annotations
 
+from typing import NamedTuple, Optional
+
 import torch
 from torch.autograd import Function
 
@@ -166,54 +168,64 @@ def _dense_group(N: int, tiles: int = 1) -> int:
     return 1
 
 
+class ConvOpts(NamedTuple):
+    """What Conv, ConvPerSample, Dgrad and Wgrad take besides tensors: one argument, so a new option lengthens no call and no backward."""
+    stride: int = 1; pad: int = 0; act: int = ops.ACT_NONE
+    wkey: object = None               # the owning layer's cache token (ops.repack_cache)
+    alg_scale: float = 1.0; wversion: object = None       # Conv: see ops.conv2d_fwd
+    bpc: object = None                # backprop clipping (csl_gan_amd.backprop_clip): per-sample clip of the pre-activation gradient
+    in_mask: bool = False; out_masked: bool = False       # fused activation masks (HipConv2d.forward_nhwc)
+    out_dtype: Optional[torch.dtype] = None               # of the result; None follows the input (torch.bfloat16: ops.set_storage_dtype)
+    sink: object = None; pass_idx: int = 0                # ConvPerSample: the engine's collector of this layer, and which pass this is
+    hw: tuple = None; rs: tuple = None                    # Dgrad: (H, W) of the conv's input; Wgrad: (R, S) of its filter
+
+
+def _preact_grad(gy, y, o, differentiable):
+    """gy, the gradient of a conv's activated output y, taken back through the activation and the backprop clip (contiguous).
+    differentiable: as autograd nodes (Conv: the double backward runs through them), else on the kernels directly."""
+    gz = gy if differentiable else gy.contiguous()
+    if o.out_masked:
+        pass                # the consumer's data-gradient epilogue already applied this layer's LeakyReLU slope pattern
+    elif o.act in _SLOPE:
+        # y.detach(): the slope pattern has zero derivative, so the double backward must not see an edge from this node back
+        # into the forward graph.  With the edge, autograd.grad(penalty, params) (train.py:427) walked the whole first-order
+        # forward again with zero-filled gradients — a wasted data-gradient chain per step (0.53 ms of 13.6 at bs=128).
+        gz = ActBwd.apply(gz, y.detach(), _SLOPE[o.act]) if differentiable else ops.act_bwd(gz, y, _SLOPE[o.act])
+    elif o.act == ops.ACT_TANH:
+        gz = gz * (1 - y * y)
+    gz = gz.contiguous()
+    return gz if o.bpc is None else o.bpc.clip_grad(gz)
+
+
 class Conv(Function):
     @staticmethod
-    def forward(ctx, x, w, b, stride, pad, act, residual, wkey=None, alg_scale=1.0, wversion=None, bpc=None, in_mask=False,
-                out_masked=False, out_dtype=None):
-        """out_dtype: torch.bfloat16 stores y as bfloat16 (ops.set_storage_dtype); None follows x's element type."""
-        y = ops.conv2d_fwd(x, w, b, stride=stride, pad=pad, residual=residual, act=act, wkey=wkey, alg_scale=alg_scale, wversion=wversion,
-                           out_dtype=out_dtype)
+    def forward(ctx, x, w, b, residual, o=ConvOpts()):
+        y = ops.conv2d_fwd(x, w, b, stride=o.stride, pad=o.pad, residual=residual, act=o.act, wkey=o.wkey, alg_scale=o.alg_scale,
+                           wversion=o.wversion, out_dtype=o.out_dtype)
         ctx.set_materialize_grads(False)      # an output nobody differentiates reaches backward as None, not as a zero tensor
-        ctx.in_mask, ctx.out_masked = in_mask, out_masked
-        ctx.bpc = bpc              # backprop clipping (csl_gan_amd.backprop_clip): per-sample clip of the pre-activation gradient
         # the owning layer's cache token lets ops reuse repacked filters while the parameter is unchanged; a derived filter
         # (wversion given) must not be cached by the backward, whose caches key on w's own version counter
-        ctx.wkey = wkey if wversion is None else None
-        ctx.cfg = (stride, pad, act)
-        ctx.has_res = residual is not None
+        ctx.o = o if o.wversion is None else o._replace(wkey=None)
         ctx.input_only = _INPUT_GRADS_ONLY
-        ctx.save_for_backward(x, w, y if act != ops.ACT_NONE else None)
+        ctx.save_for_backward(x, w, y if o.act != ops.ACT_NONE else None)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         if gy is None:
-            return (None,) * 14
+            return None, None, None, None, None
         x, w, y = ctx.saved_tensors
-        stride, pad, act = ctx.cfg
-        gz = gy
-        if ctx.out_masked:
-            pass            # the consumer's data-gradient epilogue already applied this layer's LeakyReLU slope pattern
-        elif act in _SLOPE:
-            # y.detach(): the slope pattern has zero derivative, so the double backward must not see an edge from this node back
-            # into the forward graph.  With the edge, autograd.grad(penalty, params) (train.py:427) walked the whole first-order
-            # forward again with zero-filled gradients — a wasted data-gradient chain per step (0.53 ms of 13.6 at bs=128).
-            gz = ActBwd.apply(gy, y.detach(), _SLOPE[act])
-        elif act == ops.ACT_TANH:
-            gz = gy * (1 - y * y)
-        gz = gz.contiguous()
-        if ctx.bpc is not None:
-            gz = ctx.bpc.clip_grad(gz)
+        o = ctx.o
+        gz = _preact_grad(gy, y, o, True)
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
-            gx = Dgrad.apply(gz, w, x.shape[1], x.shape[2], stride, pad, ctx.wkey, x.detach() if ctx.in_mask else None, x.dtype)
+            gx = Dgrad.apply(gz, w, x.detach() if o.in_mask else None, ConvOpts(o.stride, o.pad, wkey=o.wkey, out_dtype=x.dtype, hw=x.shape[1:3]))
         if ctx.needs_input_grad[1] and not ctx.input_only:
-            gw = Wgrad.apply(gz, x, w.shape[1], w.shape[2], stride, pad, ctx.in_mask)
+            gw = Wgrad.apply(gz, x, ConvOpts(o.stride, o.pad, in_mask=o.in_mask, rs=w.shape[1:3]))
         if ctx.needs_input_grad[2] and not ctx.input_only:
             gb = BiasGrad.apply(gz)
         # the residual is added before the activation (ResBlockUp's "o + s", DCResNet_models.py:38): its gradient is gz
-        gres = gz if (ctx.has_res and ctx.needs_input_grad[6]) else None
-        return gx, gw, gb, None, None, None, gres, None, None, None, None, None, None, None
+        return gx, gw, gb, (gz if ctx.needs_input_grad[3] else None), None
 
 
 class DepthToSpace(Function):
@@ -289,67 +301,64 @@ class NormAct(Function):
 
 class Dgrad(Function):
     @staticmethod
-    def forward(ctx, gy, w, H, W, stride, pad, wkey=None, mask=None, out_dtype=None):
-        """mask (optional, the conv's own input when that is a LeakyReLU(0.2) output): gx *= lrelu'(mask) in the kernel's epilogue.
-        out_dtype: element type of gx = that of the conv's input x (bf16-stored activations get bf16 gradients)."""
+    def forward(ctx, gy, w, mask, o):
+        """mask (optional, the conv's own input when that is a LeakyReLU(0.2) output): gx *= lrelu'(mask) in the kernel's epilogue."""
         ctx.set_materialize_grads(False)
-        ctx.cfg = (H, W, stride, pad)
-        ctx.wkey = wkey
+        ctx.o = o
         ctx.save_for_backward(gy, w, mask)
-        return ops.conv2d_dgrad(gy, w, (H, W), stride=stride, pad=pad, wkey=wkey, mask=mask, out_dtype=out_dtype)
+        return ops.conv2d_dgrad(gy, w, o.hw, stride=o.stride, pad=o.pad, wkey=o.wkey, mask=mask, out_dtype=o.out_dtype)
 
     @staticmethod
     def backward(ctx, ggx):
         if ggx is None:
-            return (None,) * 9
+            return None, None, None, None
         gy, w, mask = ctx.saved_tensors
-        H, W, stride, pad = ctx.cfg
+        o = ctx.o
         ggx = ggx.contiguous()
         if mask is not None:        # the epilogue's pointwise factor, applied to the incoming cotangent first (it is linear)
             ggx = ActBwd.apply(ggx, mask, 0.2)
         g_gy = g_w = None
         if ctx.needs_input_grad[0]:
-            g_gy = Conv.apply(ggx, w, None, stride, pad, ops.ACT_NONE, None, ctx.wkey, 1.0, None, None, False, False, gy.dtype)
+            g_gy = Conv.apply(ggx, w, None, None, ConvOpts(o.stride, o.pad, wkey=o.wkey, out_dtype=gy.dtype))
         if ctx.needs_input_grad[1]:
             ps = _PS_SINK
             param = None if ps is None else ps.by_ptr.get(w.data_ptr())
             if param is not None:
                 with torch.no_grad():
                     K, R, S, Cc = w.shape
-                    rows = ops.conv2d_wgrad_grouped(gy.contiguous(), ggx, R, S, stride=stride, pad=pad, group=1, alpha=1.0)
+                    rows = ops.conv2d_wgrad_grouped(gy.contiguous(), ggx, R, S, stride=o.stride, pad=o.pad, group=1, alpha=1.0)
                     ps.sink(param, rows.reshape(rows.shape[0], -1))
             else:
-                g_w = Wgrad.apply(gy, ggx, w.shape[1], w.shape[2], stride, pad)
-        return g_gy, g_w, None, None, None, None, None, None, None
+                g_w = Wgrad.apply(gy, ggx, ConvOpts(o.stride, o.pad, rs=w.shape[1:3]))
+        return g_gy, g_w, None, None
 
 
 class Wgrad(Function):
     """Dense weight gradient: grouped slabs on the MFMA kernel, then a column sum."""
 
     @staticmethod
-    def forward(ctx, gy, x, R, S, stride, pad, in_mask=False):
-        """in_mask: x is a LeakyReLU(0.2) output whose producer relies on its consumers to apply the slope pattern
+    def forward(ctx, gy, x, o):
+        """o.in_mask: x is a LeakyReLU(0.2) output whose producer relies on its consumers to apply the slope pattern
         (fused_act_masks): the gradient this node sends to x (immediate sensitivity differentiates weight gradients with respect
         to the inputs) must carry it too."""
         ctx.set_materialize_grads(False)
-        ctx.in_mask = in_mask
-        ctx.cfg = (R, S, stride, pad)
+        ctx.o = o
         ctx.save_for_backward(gy, x)
-        return ops.conv2d_wgrad_dense(gy, x, R, S, stride=stride, pad=pad)
+        return ops.conv2d_wgrad_dense(gy, x, *o.rs, stride=o.stride, pad=o.pad)
 
     @staticmethod
     def backward(ctx, ggw):
         if ggw is None:
-            return (None,) * 7
+            return None, None, None
         gy, x = ctx.saved_tensors
-        R, S, stride, pad = ctx.cfg
+        o = ctx.o
         ggw = ggw.contiguous()
         g_gy = g_x = None
         if ctx.needs_input_grad[0]:
-            g_gy = Conv.apply(x, ggw, None, stride, pad, ops.ACT_NONE, None, None, 1.0, None, None, False, False, gy.dtype)
+            g_gy = Conv.apply(x, ggw, None, None, ConvOpts(o.stride, o.pad, out_dtype=gy.dtype))
         if ctx.needs_input_grad[1]:
-            g_x = Dgrad.apply(gy, ggw, x.shape[1], x.shape[2], stride, pad, None, x.detach() if ctx.in_mask else None, x.dtype)
-        return g_gy, g_x, None, None, None, None, None
+            g_x = Dgrad.apply(gy, ggw, x.detach() if o.in_mask else None, ConvOpts(o.stride, o.pad, out_dtype=x.dtype, hw=x.shape[1:3]))
+        return g_gy, g_x, None
 
 
 class ConvPerSample(Function):
@@ -357,37 +366,26 @@ class ConvPerSample(Function):
     store (the Opacus-hook replacement, train.py:373,387) and returns only the data gradient."""
 
     @staticmethod
-    def forward(ctx, x, w, b, stride, pad, act, sink, pass_idx, wkey=None, bpc=None, in_mask=False, out_masked=False, out_dtype=None):
-        stored = x.dtype == torch.bfloat16 or out_dtype == torch.bfloat16       # the bf16 filter copy is cached per parameter version
-        y = ops.conv2d_fwd(x, w, b, stride=stride, pad=pad, act=act, wkey=wkey if stored else None, out_dtype=out_dtype)
-        ctx.wkey, ctx.bpc = wkey, bpc
-        ctx.in_mask, ctx.out_masked = in_mask, out_masked
-        ctx.cfg = (stride, pad, act)
-        ctx.sink, ctx.pass_idx = sink, pass_idx
+    def forward(ctx, x, w, b, o):
+        stored = x.dtype == torch.bfloat16 or o.out_dtype == torch.bfloat16       # the bf16 filter copy is cached per parameter version
+        y = ops.conv2d_fwd(x, w, b, stride=o.stride, pad=o.pad, act=o.act, wkey=o.wkey if stored else None, out_dtype=o.out_dtype)
+        ctx.o = o
         ctx.has_bias = b is not None
-        ctx.save_for_backward(x, w, y if act != ops.ACT_NONE else None)
+        ctx.save_for_backward(x, w, y if o.act != ops.ACT_NONE else None)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         x, w, y = ctx.saved_tensors
-        stride, pad, act = ctx.cfg
+        o = ctx.o
         with torch.no_grad():
-            gz = gy.contiguous()
-            if ctx.out_masked:
-                pass        # already multiplied by this layer's slope pattern in the consumer's data-gradient epilogue
-            elif act in _SLOPE:
-                gz = ops.act_bwd(gz, y, _SLOPE[act])
-            elif act == ops.ACT_TANH:
-                gz = gz * (1 - y * y)
-            if ctx.bpc is not None:
-                gz = ctx.bpc.clip_grad(gz)
-            ctx.sink.collect(ctx.pass_idx, gz, x, w.shape[1], w.shape[2], stride, pad, ctx.has_bias)
+            gz = _preact_grad(gy, y, o, False)
+            o.sink.collect(o.pass_idx, gz, x, w.shape[1], w.shape[2], o.stride, o.pad, ctx.has_bias)
             gx = None
             if ctx.needs_input_grad[0]:
-                gx = ops.conv2d_dgrad(gz, w, (x.shape[1], x.shape[2]), stride=stride, pad=pad, wkey=ctx.wkey,
-                                      mask=x if ctx.in_mask else None, out_dtype=x.dtype)
-        return gx, None, None, None, None, None, None, None, None, None, None, None, None
+                gx = ops.conv2d_dgrad(gz, w, (x.shape[1], x.shape[2]), stride=o.stride, pad=o.pad, wkey=o.wkey,
+                                      mask=x if o.in_mask else None, out_dtype=x.dtype)
+        return gx, None, None, None
 
 
 class RowL2Norm(Function):

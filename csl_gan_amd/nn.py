@@ -81,9 +81,22 @@ class _PerSampleMixin:
     _sink = None  # set by the engine (csl_gan_amd.engine.PrivacyEngine)
     _bpc = None   # set by csl_gan_amd.backprop_clip.BackpropClipper: per-sample input / output-gradient clip of this layer
 
-    def _per_sample_active(self):
-        s = self._sink
-        return s is not None and s.enabled and torch.is_grad_enabled()
+    def _wkey(self, w):
+        # only a zero-copy view of the parameter shares its version counter; a re-laid-out copy must not be cached
+        return self._wtoken if w.data_ptr() == self.weight.data_ptr() else None
+
+    def _conv(self, x, w, residual, o):
+        """The layer's conv node: ConvPerSample while the engine's sink collects (its backward hands this layer's per-sample
+        gradients to the sink; there is no such node with a residual), else Conv."""
+        sink = self._sink
+        if sink is not None and sink.enabled and torch.is_grad_enabled() and residual is None:
+            return HF.ConvPerSample.apply(x, w, self.bias, o._replace(sink=sink.collector(self), pass_idx=sink.next_pass(self)))
+        return HF.Conv.apply(x, w, self.bias, residual, o)
+
+
+def _differentiated(x, *params):
+    """Will autograd ask for a backward through an op on x with these parameters?"""
+    return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
 
 
 class HipConv2d(nn.Conv2d, _PerSampleMixin):
@@ -122,13 +135,8 @@ class HipConv2d(nn.Conv2d, _PerSampleMixin):
         im, om = bool(in_mask), bool(out_masked) and self.act == ops.ACT_LRELU02
         if (im or om) and bpc is not None:
             raise RuntimeError("activation-backward fusion and backprop clipping cannot be combined on one layer")
-        if self._per_sample_active() and residual is None:
-            sink = self._sink
-            y = HF.ConvPerSample.apply(x, w, self.bias, self.stride[0], self.padding[0], self.act, sink.collector(self), sink.next_pass(self),
-                                       self._wkey(w), bpc, im, om, out_dtype)
-        else:
-            y = HF.Conv.apply(x, w, self.bias, self.stride[0], self.padding[0], self.act, residual, self._wkey(w), 1.0, None, bpc, im, om,
-                              out_dtype)
+        y = self._conv(x, w, residual, HF.ConvOpts(self.stride[0], self.padding[0], self.act, self._wkey(w), bpc=bpc, in_mask=im,
+                                                   out_masked=om, out_dtype=out_dtype))
         if _shape_log is not None:
             _shape_log[self] = ((x.shape[3], x.shape[1], x.shape[2]), (y.shape[3], y.shape[1], y.shape[2]))
         return _record_mask(self, y, self.act)
@@ -137,19 +145,15 @@ class HipConv2d(nn.Conv2d, _PerSampleMixin):
         """UpsampleConv's conv (DCResNet_models.py:16) on the depth-to-space tensor x_ps[N,2H,2W,C/4]: the reference convolves
         four identical channel groups, i.e. x_ps with the filter summed over the groups (a quarter of the MACs)."""
         w = self.weight.permute(0, 2, 3, 1).contiguous()
-        if torch.is_grad_enabled() and w.requires_grad:
+        if torch.is_grad_enabled() and w.requires_grad:     # not _differentiated: a backward to x alone still reads the cached fold
             wf = HF.FoldChannels4.apply(w)
-            return HF.Conv.apply(x_ps, wf, self.bias, 1, self.padding[0], self.act, None, None, 4.0)
+            return HF.Conv.apply(x_ps, wf, self.bias, None, HF.ConvOpts(1, self.padding[0], self.act, alg_scale=4.0))
         wk = self._wkey(w)
         wf = ops.fold_channels4(w.detach(), wkey=wk)
         # wf is derived from the parameter (its own version counter is always 0, and a later fold may reuse its address): caches
         # downstream of it are keyed on the PARAMETER's version under a token of their own
-        return HF.Conv.apply(x_ps, wf, self.bias, 1, self.padding[0], self.act, None, None if wk is None else (wk, "fold4"), 4.0,
-                             VersionRef(self.weight))
-
-    def _wkey(self, w):
-        # only a zero-copy view of the parameter shares its version counter; a re-laid-out copy must not be cached
-        return self._wtoken if w.data_ptr() == self.weight.data_ptr() else None
+        return HF.Conv.apply(x_ps, wf, self.bias, None, HF.ConvOpts(1, self.padding[0], self.act, None if wk is None else (wk, "fold4"), 4.0,
+                                                                    VersionRef(self.weight)))
 
     def forward(self, x):
         if not x.is_cuda:
@@ -193,13 +197,7 @@ class HipLinear(nn.Linear, _PerSampleMixin):
             x = bpc.clip_input(x)
         x4 = x.contiguous().reshape(B, 1, 1, self.in_features)
         w4 = self.weight.reshape(self.out_features, 1, 1, self.in_features)
-        wkey = self._wtoken if w4.data_ptr() == self.weight.data_ptr() else None
-        im, om = bool(in_mask) and bpc is None, False
-        if self._per_sample_active():
-            sink = self._sink
-            y = HF.ConvPerSample.apply(x4, w4, self.bias, 1, 0, self.act, sink.collector(self), sink.next_pass(self), wkey, bpc, im, om)
-        else:
-            y = HF.Conv.apply(x4, w4, self.bias, 1, 0, self.act, None, wkey, 1.0, None, bpc, im, om)
+        y = self._conv(x4, w4, None, HF.ConvOpts(1, 0, self.act, self._wkey(w4), bpc=bpc, in_mask=bool(in_mask) and bpc is None))
         return _record_mask(self, y.reshape(B, self.out_features), self.act)
 
 
@@ -211,37 +209,84 @@ class HipGroupNormAct(nn.GroupNorm):
         super().__init__(groups, channels)
         self.relu = relu
 
+    def _forward(self, x, d2s, part):
+        stored = ops.storage_bf16()     # --storage_dtype bf16: a frozen generator keeps its activations bfloat16 in HBM from here on
+        if _differentiated(x, self.weight):
+            route = "autograd"          # train_G: stays fp32
+        elif d2s and _mask_recorder is not None:
+            route = "recorder"          # two launches: the recorder wants the activation before the shuffle
+        elif part is not None and not stored and x.dtype == torch.float32:
+            route = "parts"             # the statistics the producing conv's epilogue left: the apply launch alone
+        else:
+            route = "own"               # its own statistics pass
+        fused = d2s and route in ("parts", "own")      # the kernel writes the shuffled activation and the shuffled x itself
+        raw = x
+        if route == "autograd":
+            y = HF.NormAct.apply(x, self.weight, self.bias, self.num_groups, self.eps, self.relu, None, None, 0.0)
+        else:
+            if route == "recorder" and stored and x.dtype == torch.float32:
+                raw = ops.cast_bf16(x)  # what the fused kernel writes for the shortcut in the bf16 storage mode
+            y = ops.groupnorm_act(x, self.weight.detach(), self.bias.detach(), self.num_groups, eps=self.eps, relu=self.relu, d2s=fused,
+                                  want_raw=fused, out_dtype=torch.bfloat16 if stored else None, part=part if route == "parts" else None)
+        if fused:
+            return y
+        if self.relu:
+            y = _record_mask(self, y)
+        return (HF.DepthToSpace.apply(y), HF.DepthToSpace.apply(raw)) if d2s else y
+
     def forward_nhwc(self, x, part=None):
         """part: (partials, slots per image) left by the conv that produced x (ops.gn_partials) — inference only."""
-        if torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad):
-            y = HF.NormAct.apply(x, self.weight, self.bias, self.num_groups, self.eps, self.relu, None, None, 0.0)
-        elif part is not None and not ops.storage_bf16() and x.dtype == torch.float32:
-            y = ops.groupnorm_act(x, self.weight.detach(), self.bias.detach(), self.num_groups, eps=self.eps, relu=self.relu, part=part)
-        else:
-            # --storage_dtype bf16: the frozen generator of a D-step keeps its activations in HBM as bfloat16 from here on (the convs
-            # answer bf16 inputs in kind); a differentiated forward (train_G) stays fp32
-            y = ops.groupnorm_act(x, self.weight.detach(), self.bias.detach(), self.num_groups, eps=self.eps, relu=self.relu,
-                                  out_dtype=torch.bfloat16 if ops.storage_bf16() else None)
-        return _record_mask(self, y) if self.relu else y
+        return self._forward(x, False, part)
 
     def forward_shuffled(self, x, part=None):
         """(depth_to_space(act(norm(x))), depth_to_space(x)) — the inputs of ResBlockUp's convUp and shortcut."""
-        if (torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad)) or _mask_recorder is not None:
-            raw = x
-            if ops.storage_bf16() and x.dtype == torch.float32 and not (torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad)):
-                raw = ops.cast_bf16(x)        # what the fused kernel writes for the shortcut in the bf16 storage mode
-            return HF.DepthToSpace.apply(self.forward_nhwc(x)), HF.DepthToSpace.apply(raw)
-        if part is not None and not ops.storage_bf16() and x.dtype == torch.float32:
-            return ops.groupnorm_act(x, self.weight.detach(), self.bias.detach(), self.num_groups, eps=self.eps, relu=self.relu,
-                                     d2s=True, want_raw=True, part=part)
-        return ops.groupnorm_act(x, self.weight.detach(), self.bias.detach(), self.num_groups, eps=self.eps, relu=self.relu,
-                                 d2s=True, want_raw=True, out_dtype=torch.bfloat16 if ops.storage_bf16() else None)
+        return self._forward(x, True, part)
 
     def forward(self, x):
         if not x.is_cuda:
             y = super().forward(x)
             return F.relu(y) if self.relu else y
         return HF.nchw_view(self.forward_nhwc(HF.nhwc(x)))
+
+
+class _BatchNormAct(nn.BatchNorm2d):
+    """BatchNorm2d + ReLU for the bn=True generator of the non-per-sample modes (init_util.py:46): batch statistics and the
+    running-stat update run on cslgan_batchnorm_act_f32, the backward on cslgan_norm_act_bwd_f32; eval mode (running
+    statistics: the sampling path train.py:298-308, gensamples.py:26-41) on cslgan_batchnorm_eval_act_f32.
+    Same two device methods as HipGroupNormAct; `part` is accepted and ignored (batch statistics span the images)."""
+
+    def _forward(self, x, d2s):
+        g, b, diff = self.weight, self.bias, _differentiated(x, self.weight)
+        train = self.training or self.running_mean is None
+        fused = d2s and not diff and _mask_recorder is None       # else (autograd, parity-test recorder) the shuffles are launches of their own
+        if not train:
+            if diff:
+                raise NotImplementedError("eval-mode BatchNorm on HIP is inference-only (no backward)")
+            y = ops.batchnorm_eval_act(x, g.detach(), b.detach(), self.running_mean, self.running_var, eps=self.eps, relu=True,
+                                       d2s=fused, want_raw=fused)
+        else:
+            if self.num_batches_tracked is not None:
+                self.num_batches_tracked += 1
+            if diff:
+                y = HF.NormAct.apply(x, g, b, 0, self.eps, True, self.running_mean, self.running_var, self.momentum)
+            else:
+                y = ops.batchnorm_act(x, g.detach(), b.detach(), self.running_mean, self.running_var, momentum=self.momentum,
+                                      eps=self.eps, relu=True, d2s=fused, want_raw=fused)
+        if fused:
+            return y
+        y = _record_mask(self, y)
+        return (HF.DepthToSpace.apply(y), HF.DepthToSpace.apply(x)) if d2s else y
+
+    def forward_nhwc(self, x, part=None):
+        return self._forward(x, False)
+
+    def forward_shuffled(self, x, part=None):
+        return self._forward(x, True)
+
+    def forward(self, x):
+        if x.is_cuda:
+            return HF.nchw_view(self.forward_nhwc(HF.nhwc(x)))
+        return F.relu(super().forward(x))
 
 
 def _act_cpu(y, act):

@@ -1842,16 +1842,18 @@ def act_bwd(g, y, slope):
 
 
 def _d2s_out(x, d2s, want_raw, dtype=torch.float32):
-    N, H, W, Cc = x.shape
+    """(y, xs, dW, rpi) of a normalisation: the output, x's own shuffled copy (want_raw) or None, and what tells the kernels to write
+    depth-to-space shuffled — the row width and the rows per image of x (0, 0: plain)."""
     if not d2s:
         if want_raw:
             raise RuntimeError("want_raw needs d2s=True")
-        return torch.empty_like(x, dtype=dtype), None, 0
+        return torch.empty_like(x, dtype=dtype), None, 0, 0
+    N, H, W, Cc = x.shape
     if Cc % 4:
         raise RuntimeError("depth-to-space output needs C %% 4 == 0 (C=%d)" % Cc)
     shp = (N, 2 * H, 2 * W, Cc // 4)
     y = torch.empty(shp, device=x.device, dtype=dtype)
-    return y, (torch.empty(shp, device=x.device, dtype=dtype) if want_raw else None), W
+    return y, (torch.empty(shp, device=x.device, dtype=dtype) if want_raw else None), W, H * W
 
 
 _norm_scratch = {}
@@ -1876,28 +1878,23 @@ def groupnorm_act(x, gamma, beta, groups, eps=1e-5, relu=True, return_stats=Fals
     """GroupNorm(+ReLU).  d2s=True: the output is written depth-to-space shuffled ([N,2H,2W,C/4], see depth_to_space);
     want_raw=True additionally returns the raw x in that layout (one read of x feeds ResBlockUp's convUp and shortcut).
     out_dtype torch.bfloat16 (or a bfloat16 x): bf16-stored outputs (set_storage_dtype), fp32 statistics and arithmetic."""
-    if x.dtype == torch.bfloat16 or out_dtype == torch.bfloat16:
-        _chk(x, "x", allow_bf16=True); _chk(gamma, "gamma"); _chk(beta, "beta")
-        N, H, W, Cc = x.shape
-        y, xs, dW = _d2s_out(x, d2s, want_raw, torch.bfloat16)
-        ws = torch.empty(2 * N * groups, device=x.device, dtype=torch.float32)
-        check(_lib.lib().cslgan_groupnorm_act_bf16s(_p(x), 1 if x.dtype == torch.bfloat16 else 0, _p(gamma), _p(beta), N, H * W, Cc, groups,
-                                                    float(eps), 1 if relu else 0, _p(ws), _p(y), dW, _p(xs), _stream()), "groupnorm_act_bf16s")
-        out = (y, xs) if want_raw else y
-        return (out, ws) if return_stats else out
-    _chk(x, "x"); _chk(gamma, "gamma"); _chk(beta, "beta")
+    stored = x.dtype == torch.bfloat16 or out_dtype == torch.bfloat16
+    _chk(x, "x", allow_bf16=stored); _chk(gamma, "gamma"); _chk(beta, "beta")
     N, H, W, Cc = x.shape
-    y, xs, dW = _d2s_out(x, d2s, want_raw)
+    y, xs, dW, _ = _d2s_out(x, d2s, want_raw, torch.bfloat16 if stored else torch.float32)
     ws = torch.empty(2 * N * groups, device=x.device, dtype=torch.float32)
-    if part is not None:        # statistics left by the producing conv's epilogue (gn_partials): the apply launch alone
+    lib = _lib.lib()
+    if stored:
+        check(lib.cslgan_groupnorm_act_bf16s(_p(x), 1 if x.dtype == torch.bfloat16 else 0, _p(gamma), _p(beta), N, H * W, Cc, groups,
+                                             float(eps), 1 if relu else 0, _p(ws), _p(y), dW, _p(xs), _stream()), "groupnorm_act_bf16s")
+    elif part is not None:      # statistics left by the producing conv's epilogue (gn_partials): the apply launch alone
         pt, n_part = part
-        check(_lib.lib().cslgan_groupnorm_apply_parts_f32(_p(x), _p(gamma), _p(beta), N, H * W, Cc, groups, float(eps), 1 if relu else 0,
-                                                          _p(pt), n_part, _p(ws), _p(y), dW, _p(xs), _stream()), "groupnorm_apply_parts")
-        out = (y, xs) if want_raw else y
-        return (out, ws) if return_stats else out
-    sc = _scratch(x.device, 2 * N * groups)
-    check(_lib.lib().cslgan_groupnorm_act_f32(_p(x), _p(gamma), _p(beta), N, H * W, Cc, groups, float(eps), 1 if relu else 0,
-                                              _p(ws), _p(y), dW, _p(xs), _p(sc), _stream()), "groupnorm_act")
+        check(lib.cslgan_groupnorm_apply_parts_f32(_p(x), _p(gamma), _p(beta), N, H * W, Cc, groups, float(eps), 1 if relu else 0,
+                                                   _p(pt), n_part, _p(ws), _p(y), dW, _p(xs), _stream()), "groupnorm_apply_parts")
+    else:
+        sc = _scratch(x.device, 2 * N * groups)
+        check(lib.cslgan_groupnorm_act_f32(_p(x), _p(gamma), _p(beta), N, H * W, Cc, groups, float(eps), 1 if relu else 0,
+                                           _p(ws), _p(y), dW, _p(xs), _p(sc), _stream()), "groupnorm_act")
     out = (y, xs) if want_raw else y
     return (out, ws) if return_stats else out
 
@@ -1948,11 +1945,7 @@ def batchnorm_act(x, gamma, beta, running_mean=None, running_var=None, momentum=
     _chk(x, "x"); _chk(gamma, "gamma"); _chk(beta, "beta")
     Cc = x.shape[-1]
     rows = x.numel() // Cc
-    if d2s:
-        y, xs, dW = _d2s_out(x, d2s, want_raw)
-        rpi = x.shape[1] * x.shape[2]
-    else:
-        y, xs, dW, rpi = torch.empty_like(x), None, 0, 0
+    y, xs, dW, rpi = _d2s_out(x, d2s, d2s and want_raw)
     ws = torch.empty(2 * Cc, device=x.device, dtype=torch.float32)
     check(_lib.lib().cslgan_batchnorm_act_f32(_p(x), _p(gamma), _p(beta), rows, Cc, float(eps), 1 if relu else 0, float(momentum),
                                               _p(running_mean), _p(running_var), _p(ws), _p(y), rpi, dW, _p(xs),
@@ -1967,11 +1960,7 @@ def batchnorm_eval_act(x, gamma, beta, running_mean, running_var, eps=1e-5, relu
         _chk(t, n)
     Cc = x.shape[-1]
     rows = x.numel() // Cc
-    if d2s:
-        y, xs, dW = _d2s_out(x, d2s, want_raw)
-        rpi = x.shape[1] * x.shape[2]
-    else:
-        y, xs, dW, rpi = torch.empty_like(x), None, 0, 0
+    y, xs, dW, rpi = _d2s_out(x, d2s, d2s and want_raw)
     ws = torch.empty(2 * Cc, device=x.device, dtype=torch.float32)
     check(_lib.lib().cslgan_batchnorm_eval_act_f32(_p(x), _p(gamma), _p(beta), _p(running_mean), _p(running_var), rows, Cc, float(eps),
                                                    1 if relu else 0, _p(ws), _p(y), rpi, dW, _p(xs), _stream()), "batchnorm_eval_act")

@@ -341,8 +341,8 @@ def test_conv_autograd_closed_under_bf16_storage():
     def run_hip():
         xd = _nhwc(x).requires_grad_(True)
         a, b = _krsc(w1).requires_grad_(True), _krsc(w2).requires_grad_(True)
-        h = HF.Conv.apply(xd, a, None, 2, 2, ops.ACT_NONE, None, None, 1.0, None, None, False, False, torch.bfloat16)
-        y = HF.Conv.apply(h, b, None, 2, 2, ops.ACT_NONE, None, None, 1.0, None, None, False, False, torch.bfloat16)
+        h = HF.Conv.apply(xd, a, None, None, HF.ConvOpts(2, 2, out_dtype=torch.bfloat16))
+        y = HF.Conv.apply(h, b, None, None, HF.ConvOpts(2, 2, out_dtype=torch.bfloat16))
         assert h.dtype == torch.bfloat16 and y.dtype == torch.bfloat16
         (gx,) = torch.autograd.grad(y.float().sum(), xd, create_graph=True)
         assert gx.dtype == torch.float32
