@@ -27,8 +27,16 @@ same byte rows: one hidden ReLU layer per class, `objective_mlp_host_bytes` / `p
 per-class, per-feature moments, which on bytes are integers — `class_moments_host_bytes` THE definition, equalled exactly by
 cslgan_class_moments_u8 — and one derivation of the tables on the host for both paths (`gnb_tables`, `bnb_tables`), so a host fit
 and a device fit are the same bits; `jll_host_bytes` is the float64 model of cslgan_nb_score_gauss_u8 / _bern_u8 (csrc/nb_kernels.hip).
+
+`Trees` is DecisionTreeClassifier() and RandomForestClassifier(n_estimators=100) of downstream.py:69-74, one-vs-rest, on
+the same byte rows: a threshold is a byte and a node's statistic a 256-bin integer histogram per feature, so the fit is integer-exact
+— `best_split_host_bytes` THE definition of the split search, equalled in every integer and in the score's bits by
+cslgan_tree_best_split_u8 (csrc/tree_kernels.hip), `tree_apply_host_bytes` that of cslgan_tree_apply_u8 — and one level loop in torch for
+both paths, so a host fit and a device fit are the same trees.
 """
 from __future__ import annotations
+
+import contextlib
 
 import numpy as np
 import torch
@@ -640,3 +648,297 @@ def auroc(P, y):
         pos, neg = P[hot[:, k], k], P[~hot[:, k], k]
         out["per_class"].append(_auc(conv(pos), conv(neg)) if pos.numel() and neg.numel() else float("nan"))
     return out
+
+
+# ---- decision trees and forests on cache bytes --------------------------------------------------------------------------
+
+TREE_KINDS = ("dt", "rf")
+TREE_SEED_TAG = 0x7472656573706C74   # include/cslgan.h "decision trees": xor-ed into the seed of the feature-mask stream
+TREE_COUNTER_TAG = 0x74726565        # word 3 of every counter of that stream
+TREE_MAX_ROWS = 1 << 24
+TREE_LAUNCH_TILES = 1 << 20          # (segment, 16-feature tile) pairs of one split-search call: 40 MiB of workspace at most
+_TREE_HOST_BLOCK = 1 << 22           # entries of a host model's sort block (rows x features)
+
+
+def tree_mask_threshold(max_features, D):
+    """The 32-bit threshold of the keyed feature mask: floor(max_features / D 2^32); 0 — every feature — when max_features >= D."""
+    mf, D = int(max_features), int(D)
+    if mf < 1:
+        raise ValueError("max_features must be >= 1, got %r" % (max_features,))
+    return 0 if mf >= D else (mf << 32) // D
+
+
+def tree_feature_mask(seed, tree, node, D, mask_thr):
+    """bool [D]: feature j is a candidate at node `node` of tree `tree` iff mask_thr == 0 or word 0 of Philox4x32-10 at counter
+    (j, node, tree, TREE_COUNTER_TAG) under the key seed ^ TREE_SEED_TAG is below mask_thr — the host form of the device's mask."""
+    if int(mask_thr) == 0:
+        return np.ones(int(D), dtype=bool)
+    key = (int(seed) ^ TREE_SEED_TAG) & 0xFFFFFFFFFFFFFFFF
+    w = audit.philox4x32_10(np.arange(int(D), dtype=np.uint64), int(node) & 0xFFFFFFFF, int(tree) & 0xFFFFFFFF, TREE_COUNTER_TAG,
+                            key & 0xFFFFFFFF, key >> 32)[0]
+    return w < np.uint64(int(mask_thr))
+
+
+def _best_split_node(Xs, w, wt, cols):
+    """(j, v, v_hi, nL, pL, score) of one node on the host: Xs [n, D] uint8 rows of weight w >= 1 (int64), wt = w t, over the candidate
+    features `cols` (ascending).  Sorting a feature's bytes puts the candidates at the places where the sorted byte changes; the
+    cumulative sums there are (nL, pL).  In blocks of features; a later block wins only with a strictly larger score."""
+    n_rows = Xs.shape[0]
+    best = (-1, -1, -1, 0, 0, -1.0)
+    if n_rows < 2 or len(cols) == 0:
+        return best
+    n, p = int(w.sum()), int(wt.sum())
+    step = max(1, _TREE_HOST_BLOCK // n_rows)
+    for c0 in range(0, len(cols), step):
+        cc = cols[c0:c0 + step]
+        A = np.ascontiguousarray(Xs[:, cc].T)                        # [c, n]: a feature's bytes lie together
+        order = np.argsort(A, axis=1, kind="stable")
+        vs = np.take_along_axis(A, order, 1)
+        edge = vs[:, :-1] != vs[:, 1:]                               # [c, n - 1]: a candidate between sorted places i and i + 1
+        if not edge.any():
+            continue
+        nL, pL = np.cumsum(w[order], 1)[:, :-1], np.cumsum(wt[order], 1)[:, :-1]
+        nR, pR = n - nL, p - pL                                      # every w >= 1: nL >= 1 and nR >= 1 at every place
+        s = (pL * pL).astype(np.float64) / nL.astype(np.float64) + (pR * pR).astype(np.float64) / nR.astype(np.float64)
+        s = np.where(edge, s, -1.0)                                  # the first maximum is the smallest j, then the smallest v
+        ci, i = divmod(int(np.argmax(s)), n_rows - 1)
+        if s[ci, i] > best[5]:
+            best = (int(cc[ci]), int(vs[ci, i]), int(vs[ci, i + 1]), int(nL[ci, i]), int(pL[ci, i]), float(s[ci, i]))
+    return best
+
+
+def best_split_host_bytes(Xu8, labels, rows, seg_off, seg_class, seg_wrow=None, weights=None, seg_key=None, mask_thr=0, seed=0):
+    """(out int32 [S, 7] = (j, v, v_hi, nL, pL, n, p), score int64 [S]: the bits of the float64 score), CPU tensors — THE definition of the
+    split search (include/cslgan.h "decision trees" has the arguments).  Segment s is the rows rows[seg_off[s] ..
+    seg_off[s + 1]) of X with the targets t = [label == seg_class[s]] and the weights weights[seg_wrow[s]] (1 without; a row of
+    weight 0 is not there).  A candidate (j, v): byte v <= 254 present, nL = sum w [b <= v] >= 1, nR >= 1, feature j let through by
+    tree_feature_mask(seed, *seg_key[s], D, mask_thr); score fl(pL pL / nL) + fl(pR pR / nR) in float64, the products exact integers
+    converted once.  The largest score wins, ties to the smallest j, then the smallest v; v_hi is the next larger byte present.
+    No valid candidate: (-1, -1, -1, 0, 0, n, p) and score 0."""
+    X = _check_row_size(_bytes_rows(Xu8)).cpu().numpy()
+    N, D = X.shape
+    if not 1 <= N < TREE_MAX_ROWS:
+        raise ValueError("need 1 <= N < 2^24 rows, got %d" % N)
+    tonp = lambda a: (a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)).astype(np.int64)
+    y, rows, seg_off, seg_class = tonp(labels).reshape(-1), tonp(rows).reshape(-1), tonp(seg_off).reshape(-1), tonp(seg_class).reshape(-1)
+    S = len(seg_class)
+    if len(y) != N or len(seg_off) != S + 1:
+        raise ValueError("need labels [N] and seg_off [S + 1], got %d labels for %d rows and %d offsets for %d segments" % (len(y), N, len(seg_off), S))
+    if (weights is None) != (seg_wrow is None):
+        raise ValueError("weights and seg_wrow go together")
+    if int(mask_thr) and seg_key is None:
+        raise ValueError("a feature mask needs seg_key = (seg_tree, seg_node)")
+    W = None if weights is None else tonp(weights)
+    wrow = None if seg_wrow is None else tonp(seg_wrow).reshape(-1)
+    key = None if seg_key is None else (tonp(seg_key[0]).reshape(-1), tonp(seg_key[1]).reshape(-1))
+    out = np.zeros((S, 7), dtype=np.int32)
+    score = np.zeros(S, dtype=np.float64)
+    every = np.arange(D)
+    for s in range(S):
+        r = rows[seg_off[s]:seg_off[s + 1]]
+        w = np.ones(len(r), dtype=np.int64) if W is None or wrow[s] < 0 else W[wrow[s]][r]
+        r, w = r[w > 0], w[w > 0]
+        wt = w * (y[r] == seg_class[s])
+        n, p = int(w.sum()), int(wt.sum())
+        if n >= 1 << 31:
+            raise ValueError("the weights of segment %d add up to %d; the counters take less than 2^31" % (s, n))
+        cols = every if int(mask_thr) == 0 else np.nonzero(tree_feature_mask(seed, key[0][s], key[1][s], D, mask_thr))[0]
+        j, v, vh, nL, pL, sc = _best_split_node(X[r], w, wt, cols)
+        out[s] = (j, v, vh, nL, pL, n, p)
+        score[s] = sc if j >= 0 else 0.0
+    return torch.from_numpy(out), torch.from_numpy(score.view(np.int64).copy())
+
+
+def tree_tables(coef):
+    """(feature, threshold, child int32 [Q], tree_off int32 [T + 1]) numpy views of node tables coef [Q, 6] = (tree, feature, threshold,
+    first child, n, p) sorted by (tree, node): what the apply entries take."""
+    c = (coef.detach().cpu().numpy() if torch.is_tensor(coef) else np.asarray(coef)).astype(np.int32)
+    T = int(c[:, 0].max()) + 1
+    off = np.concatenate([[0], np.cumsum(np.bincount(c[:, 0], minlength=T))]).astype(np.int32)
+    return np.ascontiguousarray(c[:, 1]), np.ascontiguousarray(c[:, 2]), np.ascontiguousarray(c[:, 3]), off
+
+
+def tree_apply_host_bytes(Xu8, feature, threshold, child, tree_off):
+    """leaf int32 [T, M], a CPU tensor: the tree-local number of the leaf each row of Xu8 reaches — from the root, left (child) when
+    byte <= threshold, right (child + 1) otherwise, until feature == -1.  A walk that leaves its tree's table, or a child that does not
+    lie behind its parent, gives -1 (the device's rule for a malformed table)."""
+    X = _bytes_rows(Xu8).cpu().numpy()
+    f, t, c, off = (np.asarray(a).astype(np.int64).reshape(-1) for a in (feature, threshold, child, tree_off))
+    M, D, T = X.shape[0], X.shape[1], len(off) - 1
+    leaf = np.full((T, M), -1, dtype=np.int32)
+    ar = np.arange(M)
+    for k in range(T):
+        q0, nq = int(off[k]), int(off[k + 1] - off[k])
+        if nq < 1 or q0 < 0 or q0 + nq > len(f):
+            continue
+        node, live = np.zeros(M, dtype=np.int64), np.ones(M, dtype=bool)
+        for _ in range(nq):
+            if not live.any():
+                break
+            fi = f[q0 + node]
+            done = live & (fi < 0)
+            leaf[k, done] = node[done]
+            live &= fi >= 0
+            ci = c[q0 + node]
+            live &= (fi < D) & (ci > node) & (ci + 1 < nq)
+            b = X[ar, np.where(live, fi, 0)]
+            node = np.where(live, ci + (b > t[q0 + node]), node)
+    return torch.from_numpy(leaf)
+
+
+class Trees:
+    """`Trees(n_classes, kind).fit_bytes(Xu8, y)` then `.apply_bytes(Xu8)`, `.predict_proba_bytes(Xu8)`: kind "dt" is
+    OneVsRestClassifier(DecisionTreeClassifier()) and "rf" OneVsRestClassifier(RandomForestClassifier(n_trees)) of downstream.py:69-74,
+    grown on the uint8 rows themselves by the definition of DESIGN.md §6m — exact histogram splits, Gini, ties to the smallest
+    (feature, byte), nodes numbered level by level.  Class k has n_trees trees (one for dt), tree number k n_trees + b.
+
+    rf: tree b weighs the rows by the multiplicities of N draws with replacement from numpy's default_rng([seed, b]) (drawn on the
+    host, shared by the K classes), and at node q feature j is a candidate iff tree_feature_mask(seed, b, q, D, thr)[j] with
+    thr = tree_mask_threshold(max_features, D); max_features defaults to max(1, floor(sqrt(D))).  Two deviations from Breiman /
+    scikit-learn: the subset is drawn per feature, so its size is binomial(D, max_features / D), not fixed; and a node whose subset
+    holds no valid split becomes a leaf, where scikit-learn keeps drawing features until it has found one.
+
+    Rows on a HIP device select ops.tree_best_split_u8 / ops.tree_apply_u8, anything else best_split_host_bytes /
+    tree_apply_host_bytes — the same integers and score bits, so `coef` is the same on both paths.  The level loop around the split
+    search is one piece of torch code that runs where the rows are.
+    `coef`: the node tables, int32 [Q, 6] on the CPU = (tree, feature or -1, threshold, first child or -1, n, p) sorted by (tree, node).
+    fit_bytes returns the report {"kind", "n_per_class", "nodes", "leaves", "depth" (per tree), "levels" (split-search levels)}."""
+
+    def __init__(self, n_classes, kind="dt", n_trees=100, max_features=None, max_depth=0, min_samples_split=2, seed=0):
+        self.K = _check_classes(n_classes)
+        if kind not in TREE_KINDS:
+            raise ValueError("kind must be one of %s, got %r" % (TREE_KINDS, kind))
+        self.kind = kind
+        self.B = 1 if kind == "dt" else int(n_trees)
+        if not 1 <= self.B <= 4095:
+            raise ValueError("n_trees must lie in 1 .. 4095, got %r" % (n_trees,))
+        if max_features is not None and int(max_features) < 1:
+            raise ValueError("max_features must be >= 1, got %r" % (max_features,))
+        self.max_features = None if max_features is None else int(max_features)
+        self.max_depth, self.min_samples_split, self.seed = int(max_depth), int(min_samples_split), int(seed)
+        if self.max_depth < 0:
+            raise ValueError("max_depth must be >= 0 (0: unlimited), got %r" % (max_depth,))
+        if self.min_samples_split < 2:
+            raise ValueError("min_samples_split must be >= 2, got %r" % (min_samples_split,))
+        if not 0 <= self.seed < 2 ** 63:
+            raise ValueError("seed must lie in 0 .. 2^63 - 1, got %r" % (seed,))
+        self.coef, self.report = None, None
+
+    def bootstrap_weights(self, N):
+        """int32 [n_trees, N]: row b holds the multiplicities of N draws with replacement from default_rng([seed, b])."""
+        return np.stack([np.bincount(np.random.default_rng([self.seed, b]).integers(0, N, N), minlength=N) for b in range(self.B)]).astype(np.int32)
+
+    def mask_threshold(self, D):
+        if self.kind == "dt":
+            return 0
+        return tree_mask_threshold(max(1, int(np.sqrt(D))) if self.max_features is None else self.max_features, D)
+
+    def _search(self, X, lab, rows, seg_off, seg_tree, seg_node, W, thr):
+        """The split search of one level, in calls of at most TREE_LAUNCH_TILES (segment, tile) pairs: int64 numpy [S, 7]."""
+        S, D, B = len(seg_tree), X.shape[1], self.B
+        per = max(1, TREE_LAUNCH_TILES // ((D + 15) // 16))
+        outs = []
+        for s0 in range(0, S, per):
+            s1 = min(S, s0 + per)
+            dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(X.device)
+            args = (dev(seg_off[s0:s1 + 1]), dev(seg_tree[s0:s1] // B))
+            kw = dict(seg_wrow=None if W is None else dev(seg_tree[s0:s1] % B), weights=W,
+                      seg_key=(dev(seg_tree[s0:s1] % B), dev(seg_node[s0:s1])), mask_thr=thr, seed=self.seed)
+            if X.is_cuda:
+                out, _ = ops.tree_best_split_u8(X, lab, self.K, rows, *args, **kw)
+            else:
+                out, _ = best_split_host_bytes(X, lab, rows, *args, **kw)
+            outs.append(out.cpu().numpy().astype(np.int64))
+        return np.concatenate(outs, 0)
+
+    def fit_bytes(self, Xu8, y, weights=None, mask_thr=None):
+        """Grow the K n_trees trees.  weights (int [n_trees, N], >= 0) replaces the bootstrap multiplicities (dt: the unit weights) and
+        mask_thr the feature-mask threshold — what the tests use to tie rf to dt."""
+        X, y = _check_row_size(_bytes_rows(Xu8)).contiguous(), torch.as_tensor(y)
+        _check_rows(self.K, X, y)
+        N, D = X.shape
+        if not N < TREE_MAX_ROWS:
+            raise ValueError("need fewer than 2^24 rows, got %d" % N)
+        K, B, dev = self.K, self.B, X.device
+        T = K * B
+        thr = self.mask_threshold(D) if mask_thr is None else int(mask_thr)
+        Wn = weights if weights is not None else (self.bootstrap_weights(N) if self.kind == "rf" else None)
+        if Wn is not None:
+            Wn = np.ascontiguousarray(np.asarray(Wn), dtype=np.int64).reshape(B, N)
+            if (Wn < 0).any() or int(Wn.sum(1).max()) >= 1 << 31 or int(Wn.sum(1).min()) < 1:
+                raise ValueError("weights must be >= 0 and add up to 1 .. 2^31 - 1 per tree")
+        with torch.cuda.device(dev) if X.is_cuda else contextlib.nullcontext():
+            lab = y.to(dev).reshape(-1).to(torch.int32).contiguous()
+            W = None if Wn is None else torch.from_numpy(Wn.astype(np.int32)).to(dev)
+            # the roots: per tree the rows of weight >= 1, in row order; trees in the order k B + b
+            per_b = [np.arange(N) if Wn is None else np.nonzero(Wn[b])[0] for b in range(B)]
+            rows = torch.from_numpy(np.concatenate(per_b * K).astype(np.int32)).to(dev)
+            sizes = np.array([len(r) for r in per_b] * K, dtype=np.int64)
+            seg_tree, seg_node = np.arange(T, dtype=np.int64), np.zeros(T, dtype=np.int64)
+            next_node = np.ones(T, dtype=np.int64)
+            depth = np.zeros(T, dtype=np.int64)
+            records, level = [], 0
+            while len(seg_tree):
+                S = len(seg_tree)
+                seg_off = np.concatenate([[0], np.cumsum(sizes)])
+                o = self._search(X, lab, rows, seg_off, seg_tree, seg_node, W, thr)
+                j, v, vh, n, p = o[:, 0], o[:, 1], o[:, 2], o[:, 5], o[:, 6]
+                split = ~((p == 0) | (p == n) | (n < self.min_samples_split) | (j < 0))
+                if self.max_depth and level >= self.max_depth:
+                    split[:] = False
+                # children: per tree the next free numbers, in the order of the parents, left before right
+                rank = np.cumsum(split) - split                                          # among all splitting segments
+                first = np.searchsorted(seg_tree, seg_tree, side="left")                 # the tree's first segment of this level
+                child = np.where(split, next_node[seg_tree] + 2 * (rank - rank[first]), -1)
+                next_node += 2 * np.bincount(seg_tree[split], minlength=T)
+                depth[seg_tree] = level
+                records.append(np.stack([seg_tree, seg_node, np.where(split, j, -1), np.where(split, (v + vh) // 2, 0), child, n, p], 1))
+                level += 1
+                if not split.any():
+                    break
+                # the next level's segments: gather the chosen byte per row, stable sort by (segment, side)
+                seg_of_row = torch.repeat_interleave(torch.arange(S, device=dev), torch.from_numpy(sizes).to(dev))
+                keep = torch.from_numpy(split).to(dev)[seg_of_row]
+                r, sg = rows[keep], seg_of_row[keep]
+                byte = X[r.long(), torch.from_numpy(np.where(split, j, 0)).to(dev)[sg]]
+                side = (byte.to(torch.int64) > torch.from_numpy(v).to(dev)[sg]).to(torch.int64)
+                key = 2 * torch.from_numpy(rank).to(dev)[sg] + side
+                rows = r[torch.sort(key, stable=True).indices].contiguous()
+                n_split = int(split.sum())
+                sizes = torch.bincount(key, minlength=2 * n_split).cpu().numpy().astype(np.int64)
+                seg_tree = np.repeat(seg_tree[split], 2)
+                seg_node = np.stack([child[split], child[split] + 1], 1).reshape(-1)
+        rec = np.concatenate(records, 0)
+        rec = rec[np.lexsort((rec[:, 1], rec[:, 0]))]
+        self.coef = torch.from_numpy(np.ascontiguousarray(rec[:, [0, 2, 3, 4, 5, 6]]).astype(np.int32))
+        counts = np.bincount(y.detach().cpu().numpy().astype(np.int64).reshape(-1), minlength=K)
+        self.report = {"kind": self.kind, "n_per_class": [int(c) for c in counts[:K]], "nodes": [int(c) for c in next_node],
+                       "leaves": [int(c) for c in np.bincount(rec[rec[:, 2] < 0, 0], minlength=T)], "depth": [int(c) for c in depth], "levels": level}
+        return self.report
+
+    def apply_bytes(self, Xu8):
+        """leaf int32 [K n_trees, M] on the CPU: ops.tree_apply_u8 for rows on a HIP device, tree_apply_host_bytes elsewhere."""
+        if self.coef is None:
+            raise RuntimeError("fit first")
+        X = _check_row_size(_bytes_rows(Xu8))
+        tabs = tree_tables(self.coef)
+        if not X.is_cuda:
+            return tree_apply_host_bytes(X, *tabs)
+        with torch.cuda.device(X.device):
+            return ops.tree_apply_u8(X.contiguous(), *(torch.from_numpy(t).to(X.device) for t in tabs)).cpu()
+
+    def predict_proba_bytes(self, Xu8):
+        """P [M, K] float64 on the CPU: the mean over the class's trees, added in tree order, of the reached leaf's p / n — computed
+        here, on the host, from the integer leaf tables for both paths."""
+        leaf = self.apply_bytes(Xu8).numpy().astype(np.int64)
+        c = self.coef.numpy().astype(np.int64)
+        off = tree_tables(self.coef)[3].astype(np.int64)
+        value = c[:, 5].astype(np.float64) / c[:, 4].astype(np.float64)
+        P = np.zeros((leaf.shape[1], self.K), dtype=np.float64)
+        for k in range(self.K):
+            for b in range(self.B):
+                t = k * self.B + b
+                P[:, k] += value[off[t] + leaf[t]]
+            P[:, k] /= float(self.B)
+        return torch.from_numpy(P)
+

@@ -1687,6 +1687,84 @@ def nb_score_bern_u8(Xtest, delta, binarize=0, out=None):
     return out
 
 
+def _chk_i32(t, name, what, numel=None):
+    if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or (numel is not None and t.numel() != numel):
+        raise RuntimeError("%s: %s must be a contiguous int32 device tensor%s" % (what, name, "" if numel is None else " of %d entries" % numel))
+    return t
+
+
+def tree_best_split_ws_bytes(S, D):
+    """Workspace of tree_best_split_u8 in bytes (0: a shape one launch does not take; split the segments over several calls)."""
+    return int(_lib.lib().cslgan_tree_best_split_ws_bytes(int(S), int(D)))
+
+
+def tree_best_split_u8(X, labels, n_classes, rows, seg_off, seg_class, seg_wrow=None, weights=None, seg_key=None, mask_thr=0, seed=0, out=None, ws=None):
+    """(out int32 [S, 7] = (j, v, v_hi, nL, pL, n, p), score int64 [S]: the bits of the float64 score) of the best split of S segments of
+    rows of X [N, D] uint8 (include/cslgan.h "decision trees"): rows int32 [R] row indices, seg_off int32 [S + 1], seg_class int32 [S];
+    weights int32 [B, N] with seg_wrow int32 [S] (-1: weight 1) or neither; seg_key = (seg_tree, seg_node), int32 [S] each, with
+    mask_thr in 1 .. 2^32 - 1 for the keyed feature mask (0: every feature).  out: such a pair to write into; ws: a uint8 device tensor
+    of at least tree_best_split_ws_bytes(S, D) bytes; both allocated when absent.  Exact: csl_gan_amd.classify.best_split_host_bytes
+    is the host model, equalled in every integer and in the score's bits."""
+    what = "tree_best_split_u8"
+    _chk_bytes(X, "X")
+    if X.dim() != 2:
+        raise RuntimeError("%s: need X [N, D], got %s" % (what, tuple(X.shape)))
+    N, D, K = X.shape[0], X.shape[1], int(n_classes)
+    _chk_i32(labels, "labels", what, N)
+    _chk_i32(rows, "rows", what)
+    S = _chk_i32(seg_class, "seg_class", what).numel()
+    _chk_i32(seg_off, "seg_off", what, S + 1)
+    if (weights is None) != (seg_wrow is None):
+        raise RuntimeError("%s: weights and seg_wrow go together" % what)
+    B = 0
+    if weights is not None:
+        if weights.dim() != 2 or weights.shape[1] != N:
+            raise RuntimeError("%s: need weights [B, %d], got %s" % (what, N, tuple(weights.shape)))
+        B = _chk_i32(weights, "weights", what).shape[0]
+        _chk_i32(seg_wrow, "seg_wrow", what, S)
+    mask_thr, seed = int(mask_thr), int(seed)
+    if not 0 <= mask_thr < 2 ** 32 or not 0 <= seed < 2 ** 64:
+        raise RuntimeError("%s: need 0 <= mask_thr < 2^32 and 0 <= seed < 2^64, got %d and %d" % (what, mask_thr, seed))
+    if mask_thr and seg_key is None:
+        raise RuntimeError("%s: a feature mask needs seg_key = (seg_tree, seg_node)" % what)
+    tree, node = (None, None) if seg_key is None else (_chk_i32(seg_key[0], "seg_tree", what, S), _chk_i32(seg_key[1], "seg_node", what, S))
+    if out is None:
+        out = (torch.empty((S, 7), device=X.device, dtype=torch.int32), torch.empty(S, device=X.device, dtype=torch.int64))
+    _chk_i32(out[0], "out[0]", what, 7 * S)
+    if not out[1].is_cuda or out[1].dtype != torch.int64 or not out[1].is_contiguous() or out[1].numel() != S:
+        raise RuntimeError("%s: out[1] must be a contiguous int64 device tensor of %d entries" % (what, S))
+    need = tree_best_split_ws_bytes(S, D)
+    if need == 0:
+        raise RuntimeError("%s: S = %d segments of D = %d features is outside 1 <= S, 1 <= D <= 65536, S ceil(D / 16) < 2^31" % (what, S, D))
+    if ws is None:
+        ws = torch.empty(need, device=X.device, dtype=torch.uint8)
+    elif not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need:
+        raise RuntimeError("%s: ws must be a contiguous uint8 device tensor of at least %d bytes" % (what, need))
+    check(_lib.lib().cslgan_tree_best_split_u8(_p(X), _p(labels), _p(weights), B, N, D, K, _p(rows), rows.numel(), _p(seg_off), _p(seg_class), _p(seg_wrow),
+                                               _p(tree), _p(node), S, mask_thr, seed, _p(out[0]), _p(out[1]), _p(ws), ws.numel(), _stream()), what)
+    return out
+
+
+def tree_apply_u8(Xtest, feature, threshold, child, tree_off, out=None):
+    """leaf int32 [T, M]: the tree-local leaf number of every row of uint8 Xtest [M, D] under T trees given as flat int32 node tables
+    feature, threshold, child [Q] and tree_off [T + 1] (include/cslgan.h "decision trees"); -1 where a table is malformed.
+    csl_gan_amd.classify.tree_apply_host_bytes is the host model."""
+    what = "tree_apply_u8"
+    _chk_bytes(Xtest, "Xtest")
+    if Xtest.dim() != 2:
+        raise RuntimeError("%s: need Xtest [M, D], got %s" % (what, tuple(Xtest.shape)))
+    M, D = Xtest.shape
+    Q = _chk_i32(feature, "feature", what).numel()
+    _chk_i32(threshold, "threshold", what, Q)
+    _chk_i32(child, "child", what, Q)
+    T = _chk_i32(tree_off, "tree_off", what).numel() - 1
+    if out is None:
+        out = torch.empty((max(T, 0), M), device=Xtest.device, dtype=torch.int32)
+    _chk_i32(out, "out", what, max(T, 0) * M)
+    check(_lib.lib().cslgan_tree_apply_u8(_p(Xtest), M, D, _p(feature), _p(threshold), _p(child), _p(tree_off), T, Q, _p(out), _stream()), what)
+    return out
+
+
 def nn_padded_dim(D):
     """Row pitch of the prepared operands of nn_min: D rounded up to the kernel's K tile (0: a D outside 1 .. 65536)."""
     return int(_lib.lib().cslgan_nn_padded_dim(int(D)))

@@ -1,6 +1,7 @@
 """Are the samples any use?  `python -m csl_gan_amd.tstr --syn_cache out/syn [more ...] --test_cache out/test
 [--train_cache out/train --baseline] [-d cuda:0] [--gtol_rel G] [--max_iter 2000] [--values_dir DIR]
-[--classifier {lr,mlp,gnb,bnb} --hidden 100 --alpha 1.0 --seed 0 --var_smoothing 1e-9 --nb_alpha 0.01 --binarize 0]
+[--classifier {lr,mlp,gnb,bnb,dt,rf} --hidden 100 --alpha 1.0 --seed 0 --var_smoothing 1e-9 --nb_alpha 0.01 --binarize 0
+--n_trees 100 --max_features 0 --max_depth 0 --min_samples_split 2]
 [--save --outputs_dir outputs/ --name tstr]`.
 
 Train on synthetic, test on real: per labelled synthetic cache (what `gensamples --cache` of a conditional generator
@@ -23,6 +24,13 @@ gives exact integer moments and the model follows in closed form, the same bits 
 "classifier", "fit" (the class counts; eps for gnb) and the parameters used instead of "solver"; AUROC ranks the log-odds (the
 posteriors saturate to exactly 0 and 1), accuracy is the argmax of the joint log-likelihood; --values_dir keeps P (float64
 posteriors), J (the joint log-likelihood) and U (NaiveBayes.coef).  A flag of another classifier is ignored.
+
+--classifier dt / rf fit the reference's two tree classifiers (csl_gan_amd.classify.Trees): per class a fully grown
+decision tree, or a forest of --n_trees trees on bootstrap weights with about --max_features candidate features per node (0: sqrt of
+the row size), both drawn from --seed; --max_depth (0: unlimited) and --min_samples_split bound the growth.  The splits are exact
+integer histograms of the bytes: the trees, hence every figure, are the same bits with -d cpu and on a device.  The figures carry
+"classifier", "fit" (class counts; nodes, leaves and depth per tree; levels) and the parameters; P is the mean leaf frequency over the
+class's trees; --values_dir keeps P and U (the node tables, Trees.coef).
 """
 import argparse
 import sys
@@ -43,14 +51,18 @@ def build_parser():
     ap.add_argument("--baseline", default=False, action="store_true", help="also fit on the training set itself")
     ap.add_argument("--gtol_rel", type=float, default=None, help="a class has converged when max|gradient| <= gtol_rel * n")
     ap.add_argument("--max_iter", type=int, default=None, help="L-BFGS iterations per class (default: 2000 for lr, 200 for mlp)")
-    ap.add_argument("--classifier", type=str, default="lr", choices=["lr", "mlp", "gnb", "bnb"],
-                    help="one-vs-rest logistic regression or MLP, Gaussian or Bernoulli naive Bayes")
+    ap.add_argument("--classifier", type=str, default="lr", choices=["lr", "mlp", "gnb", "bnb", "dt", "rf"],
+                    help="one-vs-rest logistic regression or MLP, Gaussian or Bernoulli naive Bayes, decision tree or random forest")
     ap.add_argument("--hidden", type=int, default=100, help="mlp: hidden ReLU units per class, 1 .. %d" % classify.MAX_HIDDEN)
     ap.add_argument("--alpha", type=float, default=1.0, help="mlp: L2 penalty on the weights, >= 0")
-    ap.add_argument("--seed", type=int, default=0, help="mlp: seed of the initial point")
+    ap.add_argument("--seed", type=int, default=0, help="mlp: seed of the initial point; rf: seed of the bootstrap draws and feature masks")
     ap.add_argument("--var_smoothing", type=float, default=1e-9, help="gnb: share of the largest feature variance added to every variance, >= 0")
     ap.add_argument("--nb_alpha", type=float, default=0.01, help="bnb: additive smoothing of the counts, > 0")
     ap.add_argument("--binarize", type=int, default=0, help="bnb: the feature is [byte > binarize], 0 .. 254")
+    ap.add_argument("--n_trees", type=int, default=100, help="rf: trees per class, 1 .. 4095")
+    ap.add_argument("--max_features", type=int, default=0, help="rf: expected number of candidate features per node (0: sqrt of the row size)")
+    ap.add_argument("--max_depth", type=int, default=0, help="dt, rf: depth at which every node is a leaf (0: unlimited)")
+    ap.add_argument("--min_samples_split", type=int, default=2, help="dt, rf: a node of fewer (weighted) rows is a leaf, >= 2")
     return ap
 
 
@@ -73,13 +85,24 @@ def _scores(stats, a, acc):
     return stats
 
 
-def fit_and_score(train_x, train_y, K, test_x, test_y, device, gtol_rel=None, max_iter=2000, mlp=None, nb=None):
+def fit_and_score(train_x, train_y, K, test_x, test_y, device, gtol_rel=None, max_iter=2000, mlp=None, nb=None, trees=None):
     """One fit on bytes train_x [n, D] (numpy) and its figures on test_x (a uint8 tensor already on `device`): (stats, values), values
     the arrays --values_dir keeps ("P", "U"; "J" as well for naive Bayes).  The estimator: nb = {"kind": "gnb", "var_smoothing"} or
     {"kind": "bnb", "alpha", "binarize"} for classify.NaiveBayes; else mlp = {"hidden", "alpha", "seed"} for classify.OvrMlp; else the
-    logistic regression.  The parameters are part of the stats."""
+    logistic regression; trees = {"kind": "dt" | "rf", "n_trees", "max_features", "max_depth", "min_samples_split", "seed"} comes before all
+    of them, for classify.Trees.  The parameters are part of the stats."""
     stats = {"n_train": int(len(train_y)), "n_test": int(len(test_y)), "classes": int(K)}
     X = torch.from_numpy(train_x).to(device)
+    if trees is not None:
+        clf = classify.Trees(K, **trees)
+        report = clf.fit_bytes(X, torch.from_numpy(train_y))
+        del X
+        P = clf.predict_proba_bytes(test_x)
+        _scores(stats, classify.auroc(P.to(test_x.device), test_y), classify.accuracy(P, test_y))     # on a device the rank counts are the device's
+        stats.update({"classifier": trees["kind"], "fit": report, "max_depth": clf.max_depth, "min_samples_split": clf.min_samples_split})
+        if trees["kind"] == "rf":
+            stats.update({"n_trees": clf.B, "max_features": clf.max_features or max(1, int(np.sqrt(train_x.shape[1]))), "seed": clf.seed})
+        return stats, {"P": P.numpy(), "U": clf.coef.numpy()}
     if nb is not None:
         clf = classify.NaiveBayes(K, **nb)
         report = clf.fit_bytes(X, torch.from_numpy(train_y))
@@ -117,6 +140,18 @@ def main(argv=None):
         raise SystemExit("--nb_alpha %r: the smoothing must be a finite number > 0" % a.nb_alpha)
     if not 0 <= a.binarize <= 254:
         raise SystemExit("--binarize %d: a byte threshold, 0 .. 254" % a.binarize)
+    if not 1 <= a.n_trees <= 4095:
+        raise SystemExit("--n_trees %d: a forest takes 1 .. 4095 trees per class" % a.n_trees)
+    if a.max_features < 0:
+        raise SystemExit("--max_features %d: the expected number of candidate features, >= 1 (0: sqrt of the row size)" % a.max_features)
+    if a.max_depth < 0:
+        raise SystemExit("--max_depth %d: must be >= 0 (0: unlimited)" % a.max_depth)
+    if a.min_samples_split < 2:
+        raise SystemExit("--min_samples_split %d: must be >= 2" % a.min_samples_split)
+    if a.classifier in ("dt", "rf") and not 0 <= a.seed < 2 ** 63:
+        raise SystemExit("--seed %d: the trees take 0 .. 2^63 - 1" % a.seed)
+    trees = {"kind": a.classifier, "n_trees": a.n_trees, "max_features": a.max_features or None, "max_depth": a.max_depth,
+             "min_samples_split": a.min_samples_split, "seed": a.seed} if a.classifier in ("dt", "rf") else None
     mlp = {"hidden": a.hidden, "alpha": a.alpha, "seed": a.seed} if a.classifier == "mlp" else None
     nb = {"gnb": {"kind": "gnb", "var_smoothing": a.var_smoothing}, "bnb": {"kind": "bnb", "alpha": a.nb_alpha, "binarize": a.binarize}}.get(a.classifier)
     max_iter = a.max_iter if a.max_iter is not None else (2000 if mlp is None else 200)
@@ -141,13 +176,17 @@ def main(argv=None):
     stats, values = {}, {}
     for lab, _, c in sets:
         x, y = cache_rows(c)
-        m, vals = fit_and_score(x, y, classes[lab], test_x, test_yt, device, a.gtol_rel, max_iter, mlp, nb)
+        m, vals = fit_and_score(x, y, classes[lab], test_x, test_yt, device, a.gtol_rel, max_iter, mlp, nb, trees)
         stats[lab] = m
         values.update({lab + "_" + k: v for k, v in vals.items()})
         print("%s: fitted on %d rows, scored %d: AUROC %.6f, accuracy %.4f (%d / %d)" % (
             lab, m["n_train"], m["n_test"], m["auroc_micro"], m["accuracy"], m["accuracy_hits"], m["n_test"]))
         print("   per class: %s" % " ".join("%.4f" % v for v in m["auroc_per_class"]))
-        if nb is None:
+        if trees is not None:
+            f = m["fit"]
+            print("   fit: rows per class %s  trees %d  nodes %d  leaves %d  depth <= %d  levels %d" % (
+                f["n_per_class"], len(f["nodes"]), sum(f["nodes"]), sum(f["leaves"]), max(f["depth"]), f["levels"]))
+        elif nb is None:
             print(classify.solver_line(m["solver"]))
         else:
             print("   fit: rows per class %s%s" % (m["fit"]["n_per_class"], "  eps %.6g" % m["fit"]["eps"] if "eps" in m["fit"] else ""))

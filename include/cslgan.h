@@ -677,6 +677,46 @@ int cslgan_class_moments_u8(const void* X, const int32_t* labels, int64_t N, int
 int cslgan_nb_score_gauss_u8(const void* Xtest, const float* m, const float* w, int64_t M, int D, int K, float* S, void* stream);
 int cslgan_nb_score_bern_u8(const void* Xtest, const float* delta, int64_t M, int D, int K, int binarize, float* S, void* stream);
 
+/* ---- decision trees on cache bytes (tree_kernels.hip; csl_gan_amd.tstr --classifier dt / rf; backward-compatible
+ * additions, ABI stays 7).  OneVsRestClassifier(DecisionTreeClassifier()) and (RandomForestClassifier()) of downstream.py:69-74 on the
+ * bytes themselves: a threshold is one of 255 byte values and a node's sufficient statistic a 256-bin integer histogram per feature, so
+ * the fit is integer-exact.  X / Xtest: uint8 [N, D] row-major, base 16-byte aligned, 1 <= D <= 65536, rows need not be aligned; no
+ * byte beyond X + N D is read.  2 <= K <= 16, 1 <= N < 2^24, 1 <= M < 2^31.  Both entries validate on the host before any launch (null
+ * pointers, D, K, N / M, S, T, Q, the workspace size, alignment), never allocate and never synchronise.
+ *
+ * cslgan_tree_best_split_u8 — the split search of one tree level.  rows: int32 [R] row indices into X, grouped into S segments,
+ * segment s being rows[seg_off[s] .. seg_off[s + 1]) (seg_off: int32 [S + 1], non-decreasing, within 0 .. R): the rows of one open node
+ * of one tree.  Per segment: seg_class[s], the class k whose one-vs-rest targets t_i = [labels[i] == k] the node counts (a label outside
+ * 0 .. K-1 is negative for every class); seg_wrow[s], the row of weights (int32 [n_wrows, N], w >= 0) that holds its row weights, or
+ * -1 for w = 1 (weights == NULL: w = 1 everywhere, seg_wrow may be NULL); and, when mask_thr != 0, its mask key (seg_tree[s],
+ * seg_node[s]).  The weights of a segment's rows must add up to less than 2^31; a row of weight 0 is not there.
+ *   With n = sum w, p = sum w t over the segment, a candidate is (feature j, byte v), v in 0 .. 254 present in the segment, with
+ * nL = sum w [b_ij <= v] >= 1 and nR = n - nL >= 1; its score is s = fl(pL pL / nL) + fl(pR pR / nR) in float64 — the products exact
+ * integers converted once, two IEEE divisions, one addition, nothing fused.  Feature j is a candidate feature iff mask_thr == 0 or
+ * word 0 of Philox4x32-10(counter (j, seg_node, seg_tree, 0x74726565), key = seed ^ 0x7472656573706C74) < mask_thr.  The segment's
+ * result is the candidate of the largest s, ties to the smallest j, then the smallest v:
+ *     out[s] = (j, v, v_hi, nL, pL, n, p)   int32 [S, 7],  v_hi the next larger byte present;   score[s] = the bits of s   int64 [S]
+ * and (-1, -1, -1, 0, 0, n, p) with score 0 where no candidate is valid.  Every entry of out and score is written.  EXACT: equal to
+ * csl_gan_amd.classify.best_split_host_bytes in every output and in the bits of the score, the same on every call.
+ *   A workgroup owns a (segment, tile of 16 features) pair, builds the tile's 256-bin (n, p) histograms in LDS with 64-bit LDS atomics
+ * (n in the low half, p in the high half: sum w < 2^31 keeps both from wrapping, one bin may hold it all), scans them and writes one
+ * candidate per (segment, tile) into ws; a second kernel reduces the tiles with the tie rule.  No global histogram exists.
+ * ws: cslgan_tree_best_split_ws_bytes(S, D) bytes, 8-byte aligned (0: S < 1, D outside 1 .. 65536, or S ceil(D / 16) >= 2^31 — split the
+ * level into several calls then).
+ *
+ * cslgan_tree_apply_u8 — leaf[t][i], int32 [T, M]: the tree-local number of the leaf that row i of Xtest reaches in tree t.  The T trees
+ * are flat tables of Q nodes in all, tree t being the nodes tree_off[t] .. tree_off[t + 1] - 1 (int32 [T + 1]) with its root first:
+ * feature[q] (-1: a leaf), threshold[q], child[q] (the tree-local number of the left child; the right one follows it; children lie
+ * behind their parent).  A row goes left when its byte <= threshold.  A table that breaks these rules gives leaf -1 for the rows that
+ * meet the broken node; nothing outside the tables or Xtest is read.  1 <= T <= 65535. */
+int64_t cslgan_tree_best_split_ws_bytes(int64_t S, int D);
+int cslgan_tree_best_split_u8(const void* X, const int32_t* labels, const int32_t* weights, int n_wrows, int64_t N, int D, int K, const int32_t* rows,
+                              int64_t R, const int32_t* seg_off, const int32_t* seg_class, const int32_t* seg_wrow, const int32_t* seg_tree,
+                              const int32_t* seg_node, int64_t S, uint32_t mask_thr, uint64_t seed, int32_t* out, int64_t* score, void* ws,
+                              int64_t ws_bytes, void* stream);
+int cslgan_tree_apply_u8(const void* Xtest, int64_t M, int D, const int32_t* feature, const int32_t* threshold, const int32_t* child,
+                         const int32_t* tree_off, int T, int64_t Q, int32_t* leaf, void* stream);
+
 /* ---- Nearest-neighbour audit (nn_kernels.hip; backward-compatible additions, ABI stays 7) -----------------------------------------
  * Exact nearest neighbour of every row of Q [nq, D] among the rows of R [nr, D], both uint8, D = H W C with 1 <= D <= 65536
  * (so 255^2 D < 2^32):
