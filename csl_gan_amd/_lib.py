@@ -38,6 +38,7 @@ EXPORTS = [
     "cslgan_ovr_mlp_u8_ws_floats", "cslgan_ovr_mlp_eval_u8", "cslgan_ovr_mlp_proba_u8",
     "cslgan_class_moments_u8", "cslgan_nb_score_gauss_u8", "cslgan_nb_score_bern_u8",
     "cslgan_tree_best_split_ws_bytes", "cslgan_tree_best_split_u8", "cslgan_tree_apply_u8",
+    "cslgan_boost_stump_ws_bytes", "cslgan_boost_stump_u8",
     "cslgan_nn_padded_dim", "cslgan_nn_prepare_u8", "cslgan_nn_min_i8", "cslgan_nn_count_i8",
     "cslgan_nn_kth_workspace_bytes", "cslgan_nn_kth_i8", "cslgan_nn_count_radius_i8",
 ]
@@ -171,6 +172,7 @@ def lib():
         "cslgan_nb_score_bern_u8": [vp, vp, i64, i32, i32, i32, vp, vp],
         "cslgan_tree_best_split_u8": [vp, vp, vp, i32, i64, i32, i32, vp, i64, vp, vp, vp, vp, vp, i64, C.c_uint32, u64, vp, vp, vp, i64, vp],
         "cslgan_tree_apply_u8": [vp, i64, i32, vp, vp, vp, vp, i32, i64, vp, vp],
+        "cslgan_boost_stump_u8": [vp, vp, vp, i64, i32, i32, vp, vp, vp, i64, vp],
         "cslgan_nn_padded_dim": [i32],
         "cslgan_nn_prepare_u8": [vp, i64, i32, i32, vp, vp, vp],
         "cslgan_nn_min_i8": [vp, vp, i64, vp, vp, i64, i32, i64, vp, vp],
@@ -192,6 +194,8 @@ def lib():
     L.cslgan_ovr_mlp_u8_ws_floats.restype = C.c_int64
     L.cslgan_tree_best_split_ws_bytes.argtypes = [i64, i32]
     L.cslgan_tree_best_split_ws_bytes.restype = C.c_int64
+    L.cslgan_boost_stump_ws_bytes.argtypes = [i32, i32]
+    L.cslgan_boost_stump_ws_bytes.restype = C.c_int64
     L.cslgan_nn_kth_workspace_bytes.argtypes = [i64, i64, i32]
     L.cslgan_nn_kth_workspace_bytes.restype = C.c_int64
     if L.cslgan_version() != ABI_VERSION:

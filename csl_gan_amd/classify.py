@@ -33,10 +33,16 @@ the same byte rows: a threshold is a byte and a node's statistic a 256-bin integ
 — `best_split_host_bytes` THE definition of the split search, equalled in every integer and in the score's bits by
 cslgan_tree_best_split_u8 (csrc/tree_kernels.hip), `tree_apply_host_bytes` that of cslgan_tree_apply_u8 — and one level loop in torch for
 both paths, so a host fit and a device fit are the same trees.
+
+`AdaBoost` is AdaBoostClassifier() of downstream.py:79-80, one-vs-rest, on the same byte rows: rounds of depth-1 trees
+under fixed-point row weights 0 .. 2^28, so every sum of a round is an exact integer — `boost_stump_host_bytes` THE definition of the
+stump search, equalled in every integer and in the score's bits by cslgan_boost_stump_u8 (csrc/boost_kernels.hip) — and one round loop
+in torch for both paths; the stumps score test rows through the tree apply path.
 """
 from __future__ import annotations
 
 import contextlib
+import math
 
 import numpy as np
 import torch
@@ -942,3 +948,216 @@ class Trees:
             P[:, k] /= float(self.B)
         return torch.from_numpy(P)
 
+
+
+# ---- boosted stumps on cache bytes ----------------------------------------------------------------------------------------
+
+BOOST_W1 = 1 << 28                   # the largest fixed-point row weight (include/cslgan.h "boosted stumps")
+BOOST_MAX_ROUNDS = 4095              # K n_rounds stumps go through the tree apply path as trees: at most 65535
+_BOOST_APPLY_ENTRIES = 1 << 24       # (stump, test row) pairs of one apply call
+_BOOST_SORT_ROWS = 64                # the host model sorts a feature's bytes up to this many rows and builds its histograms beyond
+
+
+def boost_stump_host_bytes(Xu8, labels, weights, K):
+    """(out int64 [K, 7] = (j, v, v_hi, nL, pL, n, p), score int64 [K]: the bits of the float64 score), CPU tensors — THE definition of
+    the stump search of a boosting round (include/cslgan.h "boosted stumps").  Class k has the targets t = [label == k]
+    and the weights weights[k] (int [K, N], 0 .. BOOST_W1; a row of weight 0 is not there).  A candidate (j, v): byte v <= 254 present
+    among the rows of weight > 0, nL = sum w [b <= v] >= 1, nR = n - nL >= 1; score (a a) / fl(nL) + (c c) / fl(nR) with a = fl(pL),
+    c = fl(p - pL), five float64 operations rounded once each (every integer is below 2^52: the conversions are exact).  The largest
+    score wins, ties to the smallest j, then the smallest v; v_hi is the next larger byte present.  No valid candidate:
+    (-1, -1, -1, 0, 0, n, p) and score 0.
+    Two ways to the same integers: a few rows are sorted per feature (the candidates lie where the sorted byte changes), more rows go
+    into 256-bin histograms — np.bincount with float64 weights, every partial sum an integer below 2^53, so the sums are exact."""
+    X = _check_row_size(_bytes_rows(Xu8)).cpu().numpy()
+    N, D = X.shape
+    K = _check_classes(K)
+    if not 1 <= N < TREE_MAX_ROWS:
+        raise ValueError("need 1 <= N < 2^24 rows, got %d" % N)
+    tonp = lambda a: (a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)).astype(np.int64)
+    y, W = tonp(labels).reshape(-1), tonp(weights)
+    if len(y) != N or W.shape != (K, N):
+        raise ValueError("need labels [N] and weights [K, N], got %d labels and weights %s for %d rows, %d classes" % (len(y), W.shape, N, K))
+    if (W < 0).any() or (W > BOOST_W1).any():
+        raise ValueError("weights must lie in 0 .. 2^28")
+    out = np.zeros((K, 7), dtype=np.int64)
+    score = np.zeros(K, dtype=np.float64)
+    for k in range(K):
+        live = W[k] > 0
+        w = W[k][live].astype(np.float64)
+        wt = w * (y[live] == k)
+        n, p = int(w.sum()), int(wt.sum())
+        out[k] = (-1, -1, -1, 0, 0, n, p)
+        n_rows = int(live.sum())
+        if n_rows < 2:
+            continue
+        Xs = X[live]
+        best = -1.0
+        few = n_rows <= _BOOST_SORT_ROWS
+        step = max(1, _TREE_HOST_BLOCK // (n_rows if few else 256))
+        for c0 in range(0, D, step):
+            c = min(step, D - c0)
+            if few:                                                  # (nL, pL) where a feature's sorted bytes change
+                A = np.ascontiguousarray(Xs[:, c0:c0 + c].T)
+                order = np.argsort(A, axis=1, kind="stable")
+                vs = np.take_along_axis(A, order, 1)
+                valid = vs[:, :-1] != vs[:, 1:]
+                nL, pL = np.cumsum(w[order].astype(np.int64), 1)[:, :-1], np.cumsum(wt[order].astype(np.int64), 1)[:, :-1]
+            else:                                                    # (nL, pL) at every byte of a feature's 256-bin histograms
+                idx = (Xs[:, c0:c0 + c].astype(np.int64) + 256 * np.arange(c)[None, :]).reshape(-1)
+                hn = np.bincount(idx, weights=np.repeat(w, c), minlength=256 * c).reshape(c, 256).astype(np.int64)
+                hp = np.bincount(idx, weights=np.repeat(wt, c), minlength=256 * c).reshape(c, 256).astype(np.int64)
+                nL, pL = np.cumsum(hn, 1), np.cumsum(hp, 1)
+                valid = (hn > 0) & (nL < n)
+            if not valid.any():
+                continue
+            a, b = pL.astype(np.float64), (p - pL).astype(np.float64)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                s = (a * a) / nL.astype(np.float64) + (b * b) / (n - nL).astype(np.float64)
+            s = np.where(valid, s, -1.0)                             # the first maximum is the smallest j, then the smallest v
+            ci, i = divmod(int(np.argmax(s)), s.shape[1])
+            if s[ci, i] > best:
+                best = float(s[ci, i])
+                v, vh = (int(vs[ci, i]), int(vs[ci, i + 1])) if few else (i, i + 1 + int(np.nonzero(hn[ci, i + 1:])[0][0]))
+                out[k, :5] = (c0 + ci, v, vh, int(nL[ci, i]), int(pL[ci, i]))
+        score[k] = best if out[k, 0] >= 0 else 0.0
+    return torch.from_numpy(out), torch.from_numpy(score.view(np.int64).copy())
+
+
+class AdaBoost:
+    """`AdaBoost(n_classes, n_rounds, learning_rate).fit_bytes(Xu8, y)` then `.decision_bytes(Xu8)`, `.predict_proba_bytes(Xu8)`:
+    OneVsRestClassifier(AdaBoostClassifier()) of downstream.py:79-80 on the uint8 rows themselves by the definition of DESIGN.md §6n —
+    per class up to n_rounds stumps (depth-1 trees with exact byte thresholds), SAMME for two classes, under fixed-point row weights
+    0 .. 2^28 whose largest is 2^28 after every round.  A round: the stump (boost_stump_host_bytes), its weighted error e (an exact
+    int64); e == 0 keeps it with alpha 1 and stops the class, 2 e >= n discards it and stops; else alpha = learning_rate log((n - e) / e),
+    the missed rows are multiplied by exp(alpha) and all by 2^28 / the largest, rounded down.
+
+    Rows on a HIP device select ops.boost_stump_u8 / ops.tree_apply_u8, anything else boost_stump_host_bytes / tree_apply_host_bytes —
+    the same integers, so `coef` and P are the same bits on both paths.  Everything around the stump search — the predictions on the
+    training rows, e, the largest weight, the reweighting — is one piece of torch int64 / float64 code that runs where the rows are;
+    alpha and exp(alpha) are computed on the host for both paths.
+    `coef`: float64 [Q, 7] on the CPU = (class, round, feature or -1, threshold, left prediction, right prediction, alpha) sorted by
+    (class, round); a stump without a split has feature -1 and two equal predictions.  fit_bytes returns the report {"kind": "ab",
+    "n_per_class", "rounds", "alpha_sum", "first_err"}, the last three per class (first_err: e / n of the first round)."""
+
+    def __init__(self, n_classes, n_rounds=50, learning_rate=1.0):
+        self.K = _check_classes(n_classes)
+        self.n_rounds, self.learning_rate = int(n_rounds), float(learning_rate)
+        if not 1 <= self.n_rounds <= BOOST_MAX_ROUNDS or self.n_rounds != n_rounds:
+            raise ValueError("n_rounds must lie in 1 .. %d, got %r" % (BOOST_MAX_ROUNDS, n_rounds))
+        if not 0 < self.learning_rate < float("inf"):
+            raise ValueError("learning_rate must be a finite number > 0, got %r" % (learning_rate,))
+        self.coef, self.report = None, None
+
+    def fit_bytes(self, Xu8, y, on_round=None):
+        """on_round(round, weights int32 [K, N]) is called after every round with the weights of the next one (a stopped class: zeros)."""
+        X, y = _check_row_size(_bytes_rows(Xu8)).contiguous(), torch.as_tensor(y).reshape(-1)
+        N, D = X.shape
+        K, dev = self.K, X.device
+        if y.numel() != N or not 1 <= N < TREE_MAX_ROWS:
+            raise ValueError("need X [N, D] and y [N] with 1 <= N < 2^24, got %s and %s" % (tuple(X.shape), tuple(y.shape)))
+        counts = np.bincount(np.clip(y.cpu().numpy().astype(np.int64), -1, K) + 1, minlength=K + 2)[1:K + 1]      # labels outside: no class
+        if (counts == 0).any():
+            raise ValueError("every class 0 .. %d needs a training sample; counts: %s" % (K - 1, counts.tolist()))
+        records = [[] for _ in range(K)]
+        first_err = [0.0] * K
+        with torch.cuda.device(dev) if X.is_cuda else contextlib.nullcontext():
+            lab = y.to(dev).to(torch.int32).contiguous()
+            T = lab[None, :] == torch.arange(K, device=dev, dtype=torch.int32)[:, None]          # [K, N]
+            w = torch.full((K, N), BOOST_W1, dtype=torch.int32, device=dev)
+            active = np.ones(K, dtype=bool)
+            todev = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(dev).to(dt)
+            ws = torch.empty(ops.boost_stump_ws_bytes(K, D), device=dev, dtype=torch.uint8) if X.is_cuda else None
+            for rnd in range(self.n_rounds):
+                if X.is_cuda:
+                    out, _ = ops.boost_stump_u8(X, lab, K, w, ws=ws)
+                else:
+                    out, _ = boost_stump_host_bytes(X, lab, w, K)
+                o = out.cpu().numpy()
+                j, v, vh, nL, pL, n, p = (o[:, i] for i in range(7))
+                thr = np.where(j >= 0, (v + vh) // 2, 0)
+                left = np.where(j >= 0, 2 * pL > nL, 2 * p > n)                                 # a tie predicts negative
+                right = np.where(j >= 0, 2 * (p - pL) > n - nL, 2 * p > n)
+                byte = X[:, todev(np.maximum(j, 0), torch.int64)].t().to(torch.int64)           # [K, N]
+                h = torch.where(byte > todev(thr, torch.int64)[:, None], todev(right, torch.bool)[:, None], todev(left, torch.bool)[:, None])
+                miss = h != T
+                e = (w.to(torch.int64) * miss).sum(1).cpu().numpy()
+                mult = np.ones(K, dtype=np.float64)
+                for k in np.nonzero(active)[0]:
+                    ek, nk = int(e[k]), int(n[k])
+                    if rnd == 0:
+                        first_err[k] = ek / nk
+                    if ek == 0:
+                        alpha, active[k] = 1.0, False
+                    elif 2 * ek >= nk:
+                        active[k] = False
+                        continue
+                    else:
+                        alpha = self.learning_rate * math.log(float(nk - ek) / float(ek))
+                        mult[k] = math.exp(alpha)
+                    records[k].append((float(k), float(rnd), float(j[k]), float(thr[k]), float(left[k]), float(right[k]), float(alpha)))
+                # u = w (m where missed), the largest becomes 2^28: one multiplication, one division, an exact scaling, floor
+                u = w.to(torch.float64) * torch.where(miss, todev(mult, torch.float64)[:, None], torch.ones((), dtype=torch.float64, device=dev))
+                umax = u.max(1, keepdim=True)[0]
+                keep = todev(active, torch.bool)[:, None]
+                scaled = torch.floor(u / torch.where(keep, umax, torch.ones_like(umax)) * float(BOOST_W1))
+                w = torch.where(keep, scaled, torch.zeros_like(scaled)).to(torch.int32)
+                if on_round is not None:
+                    on_round(rnd, w)
+                if not active.any():
+                    break
+        rec = [r for k in range(K) for r in records[k]]
+        self.coef = torch.tensor(rec, dtype=torch.float64).reshape(-1, 7)
+        self.report = {"kind": "ab", "n_per_class": [int(c) for c in counts], "rounds": [len(r) for r in records],
+                       "alpha_sum": [float(sum(q[6] for q in r)) for r in records], "first_err": [float(f) for f in first_err]}
+        return self.report
+
+    def stump_tables(self):
+        """(feature, threshold, child int32 [Q'], tree_off int32 [Q + 1]): the Q stumps as trees for the tree apply path — a split is a
+        3-node tree (left leaf 1, right leaf 2), a stump without one a single node (leaf 0)."""
+        c = self.coef.numpy()
+        f, t, ch, off = [], [], [], [0]
+        for q in range(len(c)):
+            if c[q, 2] >= 0:
+                f += [int(c[q, 2]), -1, -1]; t += [int(c[q, 3]), 0, 0]; ch += [1, -1, -1]
+            else:
+                f += [-1]; t += [0]; ch += [-1]
+            off.append(len(f))
+        return tuple(np.array(a, dtype=np.int32) for a in (f, t, ch, off))
+
+    def decision_bytes(self, Xu8):
+        """F [M, K] float64 on the CPU: F_k = sum_m alpha_m sigma_m / sum_m alpha_m, sigma = +-1 the stump's prediction, added in round
+        order on the host from the integer leaf numbers of the tree apply path, for both paths; 0 for a class without a stump."""
+        if self.coef is None:
+            raise RuntimeError("fit first")
+        X = _check_row_size(_bytes_rows(Xu8))
+        M = X.shape[0]
+        c = self.coef.numpy()
+        F = np.zeros((M, self.K), dtype=np.float64)
+        if len(c) == 0:
+            return torch.from_numpy(F)
+        tabs = self.stump_tables()
+        if X.is_cuda:
+            X = X.contiguous()
+            dtabs = [torch.from_numpy(t).to(X.device) for t in tabs]
+        step = max(1, _BOOST_APPLY_ENTRIES // len(c))
+        for m0 in range(0, M, step):
+            xb = X[m0:m0 + step]
+            if X.is_cuda:
+                with torch.cuda.device(X.device):
+                    leaf = ops.tree_apply_u8(xb, *dtabs).cpu().numpy()
+            else:
+                leaf = tree_apply_host_bytes(xb, *tabs).numpy()
+            for q in range(len(c)):
+                sigma = np.where(np.where(leaf[q] == 2, c[q, 5], c[q, 4]) > 0, 1.0, -1.0)
+                F[m0:m0 + step, int(c[q, 0])] += c[q, 6] * sigma
+        for k in range(self.K):
+            tot = 0.0
+            for a in c[c[:, 0] == k, 6]:
+                tot += float(a)
+            if tot > 0:
+                F[:, k] /= tot
+        return torch.from_numpy(F)
+
+    def predict_proba_bytes(self, Xu8):
+        """P [M, K] float64 on the CPU: 1 / (1 + exp(-2 F)), column 1 of scikit-learn's AdaBoostClassifier.predict_proba per class."""
+        return torch.from_numpy(1.0 / (1.0 + np.exp(-2.0 * self.decision_bytes(Xu8).numpy())))

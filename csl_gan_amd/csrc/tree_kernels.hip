@@ -26,6 +26,7 @@
 // is range-checked against the tree's node count and the walk is bounded by that count, so a malformed table ends in leaf -1, not
 // in a stray read or an endless loop.
 #include "ovr_rows.h"
+#include "tree_best.h"
 
 namespace cslgan {
 
@@ -39,30 +40,7 @@ constexpr uint32_t TR_COUNTER_TAG = 0x74726565u;          // word 3 of every cou
 constexpr unsigned long long TR_SEED_TAG = 0x7472656573706C74ull;      // xor-ed into the seed ("treesplt")
 constexpr int TR_REC = 8;                // int32 words of a tile record: j, v, v_hi, nL, pL, n, p, unused
 
-struct TreeBest {
-    double s;                            // -1: no candidate (a score is >= 0)
-    int j, v, vh;
-    unsigned nL, pL;
-};
-
-// a before b: the larger score, then the smaller feature, then the smaller byte
-__device__ __forceinline__ bool tree_better(double as, int aj, int av, double bs, int bj, int bv) {
-    return as > bs || (as == bs && (aj < bj || (aj == bj && av < bv)));
-}
-
-__device__ __forceinline__ void tree_wave_best(TreeBest& b) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        TreeBest t;
-        t.s = __shfl_xor(b.s, o, 64);
-        t.j = __shfl_xor(b.j, o, 64);
-        t.v = __shfl_xor(b.v, o, 64);
-        t.vh = __shfl_xor(b.vh, o, 64);
-        t.nL = __shfl_xor(b.nL, o, 64);
-        t.pL = __shfl_xor(b.pL, o, 64);
-        if (tree_better(t.s, t.j, t.v, b.s, b.j, b.v)) b = t;
-    }
-}
+using TreeBest = TreeBestT<unsigned>;    // tree_best.h: the record, tree_better and tree_wave_best, shared with boost_kernels.hip
 
 template <bool AL>
 __global__ __launch_bounds__(TR_THREADS) void tree_split_tile_kernel(

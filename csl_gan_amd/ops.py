@@ -1765,6 +1765,42 @@ def tree_apply_u8(Xtest, feature, threshold, child, tree_off, out=None):
     return out
 
 
+def boost_stump_ws_bytes(n_classes, D):
+    """Workspace of boost_stump_u8 in bytes (0: n_classes outside 2 .. 16 or D outside 1 .. 65536)."""
+    return int(_lib.lib().cslgan_boost_stump_ws_bytes(int(n_classes), int(D)))
+
+
+def boost_stump_u8(X, labels, n_classes, weights, out=None, ws=None):
+    """(out int64 [K, 7] = (j, v, v_hi, nL, pL, n, p), score int64 [K]: the bits of the float64 score) of the best stump of each of the K
+    one-vs-rest classes on all rows of X [N, D] uint8 under the fixed-point weights int32 [K, N], 0 .. 2^28 (include/cslgan.h "boosted
+    stumps"; a weight outside the range is clamped).  out: such a pair to write into; ws: a uint8 device tensor of at least
+    boost_stump_ws_bytes(K, D) bytes; both allocated when absent.  Exact: csl_gan_amd.classify.boost_stump_host_bytes is the host
+    model, equalled in every integer and in the score's bits."""
+    what = "boost_stump_u8"
+    _chk_bytes(X, "X")
+    if X.dim() != 2:
+        raise RuntimeError("%s: need X [N, D], got %s" % (what, tuple(X.shape)))
+    N, D, K = X.shape[0], X.shape[1], int(n_classes)
+    _chk_i32(labels, "labels", what, N)
+    if weights.dim() != 2 or tuple(weights.shape) != (K, N):
+        raise RuntimeError("%s: need weights [%d, %d], got %s" % (what, K, N, tuple(weights.shape)))
+    _chk_i32(weights, "weights", what)
+    need = boost_stump_ws_bytes(K, D)
+    if need == 0:
+        raise RuntimeError("%s: K = %d classes of D = %d features is outside 2 <= K <= 16, 1 <= D <= 65536" % (what, K, D))
+    if out is None:
+        out = (torch.empty((K, 7), device=X.device, dtype=torch.int64), torch.empty(K, device=X.device, dtype=torch.int64))
+    for t, name, numel in ((out[0], "out[0]", 7 * K), (out[1], "out[1]", K)):
+        if not t.is_cuda or t.dtype != torch.int64 or not t.is_contiguous() or t.numel() != numel:
+            raise RuntimeError("%s: %s must be a contiguous int64 device tensor of %d entries" % (what, name, numel))
+    if ws is None:
+        ws = torch.empty(need, device=X.device, dtype=torch.uint8)
+    elif not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need:
+        raise RuntimeError("%s: ws must be a contiguous uint8 device tensor of at least %d bytes" % (what, need))
+    check(_lib.lib().cslgan_boost_stump_u8(_p(X), _p(labels), _p(weights), N, D, K, _p(out[0]), _p(out[1]), _p(ws), ws.numel(), _stream()), what)
+    return out
+
+
 def nn_padded_dim(D):
     """Row pitch of the prepared operands of nn_min: D rounded up to the kernel's K tile (0: a D outside 1 .. 65536)."""
     return int(_lib.lib().cslgan_nn_padded_dim(int(D)))

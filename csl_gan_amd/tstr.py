@@ -1,7 +1,7 @@
 """Are the samples any use?  `python -m csl_gan_amd.tstr --syn_cache out/syn [more ...] --test_cache out/test
 [--train_cache out/train --baseline] [-d cuda:0] [--gtol_rel G] [--max_iter 2000] [--values_dir DIR]
-[--classifier {lr,mlp,gnb,bnb,dt,rf} --hidden 100 --alpha 1.0 --seed 0 --var_smoothing 1e-9 --nb_alpha 0.01 --binarize 0
---n_trees 100 --max_features 0 --max_depth 0 --min_samples_split 2]
+[--classifier {lr,mlp,gnb,bnb,dt,rf,ab} --hidden 100 --alpha 1.0 --seed 0 --var_smoothing 1e-9 --nb_alpha 0.01 --binarize 0
+--n_trees 100 --max_features 0 --max_depth 0 --min_samples_split 2 --n_rounds 50 --learning_rate 1.0]
 [--save --outputs_dir outputs/ --name tstr]`.
 
 Train on synthetic, test on real: per labelled synthetic cache (what `gensamples --cache` of a conditional generator
@@ -31,6 +31,12 @@ the row size), both drawn from --seed; --max_depth (0: unlimited) and --min_samp
 integer histograms of the bytes: the trees, hence every figure, are the same bits with -d cpu and on a device.  The figures carry
 "classifier", "fit" (class counts; nodes, leaves and depth per tree; levels) and the parameters; P is the mean leaf frequency over the
 class's trees; --values_dir keeps P and U (the node tables, Trees.coef).
+
+--classifier ab fits the reference's AdaBoost classifier (csl_gan_amd.classify.AdaBoost): per class up to --n_rounds
+stumps, SAMME with --learning_rate, under fixed-point row weights, so every sum of a round is an exact integer and the stumps, hence
+every figure, are the same bits with -d cpu and on a device.  The figures carry "classifier", "fit" (class counts; rounds kept, the sum
+of the stump weights and the first round's error per class), "n_rounds" and "learning_rate"; P is 1 / (1 + exp(-2 F)) of the
+normalised vote F; --values_dir keeps P and U (the stump table, AdaBoost.coef).
 """
 import argparse
 import sys
@@ -51,8 +57,8 @@ def build_parser():
     ap.add_argument("--baseline", default=False, action="store_true", help="also fit on the training set itself")
     ap.add_argument("--gtol_rel", type=float, default=None, help="a class has converged when max|gradient| <= gtol_rel * n")
     ap.add_argument("--max_iter", type=int, default=None, help="L-BFGS iterations per class (default: 2000 for lr, 200 for mlp)")
-    ap.add_argument("--classifier", type=str, default="lr", choices=["lr", "mlp", "gnb", "bnb", "dt", "rf"],
-                    help="one-vs-rest logistic regression or MLP, Gaussian or Bernoulli naive Bayes, decision tree or random forest")
+    ap.add_argument("--classifier", type=str, default="lr", choices=["lr", "mlp", "gnb", "bnb", "dt", "rf", "ab"],
+                    help="one-vs-rest logistic regression or MLP, Gaussian or Bernoulli naive Bayes, decision tree or random forest, AdaBoost of stumps")
     ap.add_argument("--hidden", type=int, default=100, help="mlp: hidden ReLU units per class, 1 .. %d" % classify.MAX_HIDDEN)
     ap.add_argument("--alpha", type=float, default=1.0, help="mlp: L2 penalty on the weights, >= 0")
     ap.add_argument("--seed", type=int, default=0, help="mlp: seed of the initial point; rf: seed of the bootstrap draws and feature masks")
@@ -63,6 +69,8 @@ def build_parser():
     ap.add_argument("--max_features", type=int, default=0, help="rf: expected number of candidate features per node (0: sqrt of the row size)")
     ap.add_argument("--max_depth", type=int, default=0, help="dt, rf: depth at which every node is a leaf (0: unlimited)")
     ap.add_argument("--min_samples_split", type=int, default=2, help="dt, rf: a node of fewer (weighted) rows is a leaf, >= 2")
+    ap.add_argument("--n_rounds", type=int, default=50, help="ab: boosting rounds (stumps) per class, 1 .. %d" % classify.BOOST_MAX_ROUNDS)
+    ap.add_argument("--learning_rate", type=float, default=1.0, help="ab: the factor on every stump's weight, > 0")
     return ap
 
 
@@ -85,14 +93,23 @@ def _scores(stats, a, acc):
     return stats
 
 
-def fit_and_score(train_x, train_y, K, test_x, test_y, device, gtol_rel=None, max_iter=2000, mlp=None, nb=None, trees=None):
+def fit_and_score(train_x, train_y, K, test_x, test_y, device, gtol_rel=None, max_iter=2000, mlp=None, nb=None, trees=None, boost=None):
     """One fit on bytes train_x [n, D] (numpy) and its figures on test_x (a uint8 tensor already on `device`): (stats, values), values
     the arrays --values_dir keeps ("P", "U"; "J" as well for naive Bayes).  The estimator: nb = {"kind": "gnb", "var_smoothing"} or
     {"kind": "bnb", "alpha", "binarize"} for classify.NaiveBayes; else mlp = {"hidden", "alpha", "seed"} for classify.OvrMlp; else the
     logistic regression; trees = {"kind": "dt" | "rf", "n_trees", "max_features", "max_depth", "min_samples_split", "seed"} comes before all
-    of them, for classify.Trees.  The parameters are part of the stats."""
+    of them, for classify.Trees, and boost = {"n_rounds", "learning_rate"} before those, for classify.AdaBoost.  The parameters are part
+    of the stats."""
     stats = {"n_train": int(len(train_y)), "n_test": int(len(test_y)), "classes": int(K)}
     X = torch.from_numpy(train_x).to(device)
+    if boost is not None:
+        clf = classify.AdaBoost(K, **boost)
+        report = clf.fit_bytes(X, torch.from_numpy(train_y))
+        del X
+        P = clf.predict_proba_bytes(test_x)
+        _scores(stats, classify.auroc(P.to(test_x.device), test_y), classify.accuracy(P, test_y))     # on a device the rank counts are the device's
+        stats.update({"classifier": "ab", "fit": report, "n_rounds": clf.n_rounds, "learning_rate": clf.learning_rate})
+        return stats, {"P": P.numpy(), "U": clf.coef.numpy()}
     if trees is not None:
         clf = classify.Trees(K, **trees)
         report = clf.fit_bytes(X, torch.from_numpy(train_y))
@@ -150,6 +167,11 @@ def main(argv=None):
         raise SystemExit("--min_samples_split %d: must be >= 2" % a.min_samples_split)
     if a.classifier in ("dt", "rf") and not 0 <= a.seed < 2 ** 63:
         raise SystemExit("--seed %d: the trees take 0 .. 2^63 - 1" % a.seed)
+    if not 1 <= a.n_rounds <= classify.BOOST_MAX_ROUNDS:
+        raise SystemExit("--n_rounds %d: boosting takes 1 .. %d rounds per class" % (a.n_rounds, classify.BOOST_MAX_ROUNDS))
+    if not 0 < a.learning_rate < float("inf"):
+        raise SystemExit("--learning_rate %r: must be a finite number > 0" % a.learning_rate)
+    boost = {"n_rounds": a.n_rounds, "learning_rate": a.learning_rate} if a.classifier == "ab" else None
     trees = {"kind": a.classifier, "n_trees": a.n_trees, "max_features": a.max_features or None, "max_depth": a.max_depth,
              "min_samples_split": a.min_samples_split, "seed": a.seed} if a.classifier in ("dt", "rf") else None
     mlp = {"hidden": a.hidden, "alpha": a.alpha, "seed": a.seed} if a.classifier == "mlp" else None
@@ -176,13 +198,16 @@ def main(argv=None):
     stats, values = {}, {}
     for lab, _, c in sets:
         x, y = cache_rows(c)
-        m, vals = fit_and_score(x, y, classes[lab], test_x, test_yt, device, a.gtol_rel, max_iter, mlp, nb, trees)
+        m, vals = fit_and_score(x, y, classes[lab], test_x, test_yt, device, a.gtol_rel, max_iter, mlp, nb, trees, boost)
         stats[lab] = m
         values.update({lab + "_" + k: v for k, v in vals.items()})
         print("%s: fitted on %d rows, scored %d: AUROC %.6f, accuracy %.4f (%d / %d)" % (
             lab, m["n_train"], m["n_test"], m["auroc_micro"], m["accuracy"], m["accuracy_hits"], m["n_test"]))
         print("   per class: %s" % " ".join("%.4f" % v for v in m["auroc_per_class"]))
-        if trees is not None:
+        if boost is not None:
+            f = m["fit"]
+            print("   fit: rows per class %s  rounds per class %s  stumps %d" % (f["n_per_class"], f["rounds"], sum(f["rounds"])))
+        elif trees is not None:
             f = m["fit"]
             print("   fit: rows per class %s  trees %d  nodes %d  leaves %d  depth <= %d  levels %d" % (
                 f["n_per_class"], len(f["nodes"]), sum(f["nodes"]), sum(f["leaves"]), max(f["depth"]), f["levels"]))

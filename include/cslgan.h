@@ -717,6 +717,31 @@ int cslgan_tree_best_split_u8(const void* X, const int32_t* labels, const int32_
 int cslgan_tree_apply_u8(const void* Xtest, int64_t M, int D, const int32_t* feature, const int32_t* threshold, const int32_t* child,
                          const int32_t* tree_off, int T, int64_t Q, int32_t* leaf, void* stream);
 
+/* ---- boosted stumps on cache bytes (boost_kernels.hip; csl_gan_amd.tstr --classifier ab; backward-compatible additions,
+ * ABI stays 7).  OneVsRestClassifier(AdaBoostClassifier()) of downstream.py:79-80: rounds of depth-1 trees under row weights that are
+ * rewritten every round.  The weights are fixed-point integers 0 .. W1 = 2^28, so every sum is an exact integer below 2^52 and the
+ * search is the same bits on the host and on a device.
+ *
+ * cslgan_boost_stump_u8 — the stump search of one round, all K classes over all N rows in one launch.  X: uint8 [N, D] row-major, base
+ * 16-byte aligned, rows need not be aligned, no byte beyond X + N D is read; labels: int32 [N], class k counts t_i = [labels[i] == k]
+ * (a label outside 0 .. K-1 is negative for every class); weights: int32 [K, N], row k the weights of class k — a weight outside
+ * 0 .. 2^28 is clamped into that range, a row of weight 0 is not there.  2 <= K <= 16, 1 <= D <= 65536, 1 <= N < 2^24.
+ *   With n = sum w, p = sum w t, a candidate is (feature j, byte v), v in 0 .. 254 present among the rows of weight > 0, with
+ * nL = sum w [b_ij <= v] >= 1 and nR = n - nL >= 1; its score is s = (a a) / fl(nL) + (c c) / fl(nR), a = fl(pL), c = fl(p - pL), in
+ * float64 — the conversions are exact, each of the five operations is rounded once, nothing is fused.  The largest s wins, ties to the
+ * smallest j, then the smallest v:
+ *     out[k] = (j, v, v_hi, nL, pL, n, p)   int64 [K, 7],  v_hi the next larger byte present;   score[k] = the bits of s   int64 [K]
+ * and (-1, -1, -1, 0, 0, n, p) with score 0 where no candidate is valid.  Every entry of out and score is written.  EXACT: equal to
+ * csl_gan_amd.classify.boost_stump_host_bytes in every output and in the bits of the score, the same on every call.
+ *   A workgroup owns a (class, tile of 16 features) pair — the K workgroups of a tile are neighbours in the grid — and builds per feature
+ * two 256-bin histograms of 64-bit LDS counters, the weights of the negative and of the positive rows: one 64-bit LDS atomic per byte.
+ * It scans them and writes one candidate into ws; a second kernel reduces the tiles with the tie rule.
+ * ws: cslgan_boost_stump_ws_bytes(K, D) = 64 K ceil(D / 16) bytes, 8-byte aligned (0: K or D out of range).  The entry validates on the
+ * host before any launch (null pointers, N, D, K, the workspace size, alignment), never allocates and never synchronises. */
+int64_t cslgan_boost_stump_ws_bytes(int K, int D);
+int cslgan_boost_stump_u8(const void* X, const int32_t* labels, const int32_t* weights /* [K, N] */, int64_t N, int D, int K,
+                          int64_t* out /* [K, 7] */, int64_t* score /* [K] */, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- Nearest-neighbour audit (nn_kernels.hip; backward-compatible additions, ABI stays 7) -----------------------------------------
  * Exact nearest neighbour of every row of Q [nq, D] among the rows of R [nr, D], both uint8, D = H W C with 1 <= D <= 65536
  * (so 255^2 D < 2^32):

@@ -1,0 +1,123 @@
+"""The device path of csl_gan_amd.classify.AdaBoost (-m gpu): cslgan_boost_stump_u8 against its host model — every
+integer and the bits of every score — the device fit against the host fit on the three problems of tests/test_tstr.py, and the command
+line on cuda:0 against -d cpu.  Every comparison is exact."""
+import functools
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from test_tstr import PROBLEMS, make, make_caches
+
+pytestmark = pytest.mark.gpu
+
+W1 = 1 << 28
+SHAPES = [(1, 1, 2), (2, 1, 2), (17, 5, 3), (257, 930, 10), (300, 1040, 2), (100, 12288, 2), (20, 65536, 16)]
+
+
+def _dev(a, dtype=np.int32):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).cuda()
+
+
+def _check_stump(X, y, K, W):
+    """One launch against the host model; the outputs are handed over filled with -1; a second call returns the same bits.  Returns
+    the host's (out, score) as numpy."""
+    from csl_gan_amd import _lib, classify, ops
+    ho, hs = classify.boost_stump_host_bytes(X, y, W, K)
+    args = (_dev(X, np.uint8), _dev(y), K, _dev(W))
+    out = (torch.full((K, 7), -1, dtype=torch.int64, device="cuda"), torch.full((K,), -1, dtype=torch.int64, device="cuda"))
+    got = ops.boost_stump_u8(*args, out=out)
+    assert got[0] is out[0] and got[1] is out[1] and _lib.lib().cslgan_last_kernel() == b"boost_stump_tile_kernel"
+    go, gs = out[0].cpu().numpy(), out[1].cpu().numpy()
+    bad = np.nonzero((go != ho.numpy()).any(1) | (gs != hs.numpy()))[0]
+    assert len(bad) == 0, "classes %s: device %s, host %s" % (bad[:5], go[bad[:5]].tolist(), ho.numpy()[bad[:5]].tolist())
+    again = ops.boost_stump_u8(*args)
+    assert np.array_equal(again[0].cpu().numpy(), go) and np.array_equal(again[1].cpu().numpy(), gs)
+    return go, gs
+
+
+@pytest.mark.parametrize("N,D,K", SHAPES)
+def test_stump_search_equals_the_host_model(N, D, K):
+    """Per shape: unit weights; random weights in 0 .. 2^28 with zeros among them; the same with one class whose weights are all 0.
+    Coarse bytes (multiples of 32) on half of the columns make equal scores in different features and tiles common."""
+    rng = np.random.default_rng(N + D)
+    X = rng.integers(0, 256, (N, D)).astype(np.uint8)
+    X[:, ::2] = X[:, ::2] // 32 * 32
+    y = rng.integers(0, K, N)
+    go, _ = _check_stump(X, y, K, np.full((K, N), W1))
+    assert (go[:, 5] == N * W1).all() and np.array_equal(go[:, 6], np.bincount(y, minlength=K) * W1)
+    W = rng.integers(0, W1 + 1, (K, N)) * (rng.random((K, N)) < 0.8)
+    W[:, 0] = W1
+    go, _ = _check_stump(X, y, K, W)
+    assert np.array_equal(go[:, 5], W.sum(1))
+    W[K - 1] = 0
+    go, gs = _check_stump(X, y, K, W)
+    assert go[K - 1].tolist() == [-1, -1, -1, 0, 0, 0, 0] and gs[K - 1] == 0
+
+
+def test_counters_take_two_to_the_52():
+    """70 000 rows of weight 2^28 and 8 bytes, every byte of the positive class 255: one bin holds about 2^44, and pL pL exceeds 2^64."""
+    rng = np.random.default_rng(2)
+    N = 70000
+    y = (rng.random(N) < 0.95).astype(np.int64)
+    X = np.where(y[:, None] == 1, 255, rng.integers(0, 255, (N, 8))).astype(np.uint8)
+    go, gs = _check_stump(X, y, 2, np.full((2, N), W1))
+    p = int(y.sum())
+    assert p * W1 > 2 ** 44 and float(p * W1) ** 2 > 2.0 ** 64
+    assert go[1].tolist()[3:] == [(N - p) * W1, 0, N * W1, p * W1] and go[1, 2] == 255 and gs.view(np.float64)[1] == float(p * W1)
+    assert go[0].tolist()[3:] == [(N - p) * W1, (N - p) * W1, N * W1, (N - p) * W1]           # the same stump seen from the other class
+
+
+def test_duplicate_columns_in_different_tiles_and_labels_outside_the_classes():
+    rng = np.random.default_rng(3)
+    N, D = 400, 100
+    y = rng.integers(-3, 6, N)                                                       # K = 3: labels -3 .. -1 and 3 .. 5 belong to no class
+    X = rng.integers(0, 256, (N, D)).astype(np.uint8)
+    X[:, 70] = np.where(y == 1, 180, 60) + rng.integers(0, 20, N)                    # the best feature of class 1 ...
+    X[:, 35] = X[:, 70]                                                              # ... twice, in tiles 2 and 4: the smaller j wins
+    X[:, 99] = X[:, 70]
+    W = rng.integers(1, W1 + 1, (3, N))
+    go, _ = _check_stump(X, y, 3, W)
+    assert go[1, 0] == 35 and go[:, 6].tolist() == [int(W[k][y == k].sum()) for k in range(3)]
+    go, _ = _check_stump(X[:, 36:], y, 3, W)                                         # rows of 64 bytes: the aligned loader
+    assert go[1, 0] == 34
+
+
+@functools.lru_cache(maxsize=None)
+def _host_boost(i):
+    """(fitted host classifier, report, P on the held-out rows, train (x, y), held-out x) of PROBLEMS[i]; computed once, left unchanged."""
+    from csl_gan_amd import classify
+    N, H, W, C, K, M = PROBLEMS[i]
+    x, y = make(N, H, W, C, K, 1)
+    xt, _ = make(M, H, W, C, K, 2)
+    clf = classify.AdaBoost(K, n_rounds=8)
+    rep = clf.fit_bytes(x, y)
+    return clf, rep, clf.predict_proba_bytes(xt).numpy(), (x, y), xt
+
+
+@pytest.mark.parametrize("i", range(len(PROBLEMS)))
+def test_device_fit_equals_the_host_fit(i):
+    """coef, P and the report: the stump search, and torch's float64 division and floor of the reweighting on the device."""
+    from csl_gan_amd import classify
+    host, rep, P, (x, y), xt = _host_boost(i)
+    clf = classify.AdaBoost(PROBLEMS[i][4], n_rounds=8)
+    rep_d = clf.fit_bytes(torch.from_numpy(x).cuda(), torch.from_numpy(y))
+    assert rep_d == rep and sum(rep["rounds"]) > PROBLEMS[i][4]                      # more than one round: the reweighting ran
+    assert clf.coef.device.type == "cpu" and np.array_equal(clf.coef.numpy().view(np.uint64), host.coef.numpy().view(np.uint64))
+    Pd = clf.predict_proba_bytes(torch.from_numpy(xt).cuda()).numpy()
+    assert np.array_equal(Pd.view(np.uint64), P.view(np.uint64))
+
+
+def test_cli_on_the_device_agrees_with_the_cpu(tmp_path):
+    from csl_gan_amd import tstr
+    c = make_caches(tmp_path)
+    res = {}
+    for dev in ("cpu", "cuda:0"):
+        vals = str(tmp_path / ("vals_" + dev[:3]))
+        res[dev] = (tstr.main(["--syn_cache", c["syn"][0], "--test_cache", c["test"][0], "-d", dev, "--values_dir", vals, "--classifier", "ab",
+                               "--n_rounds", "10"]), vals)
+    assert res["cpu"][0] == res["cuda:0"][0] and res["cpu"][0]["syn"]["classifier"] == "ab"
+    for name in ("syn_P.npy", "syn_U.npy"):
+        a, b = (np.load(os.path.join(res[d][1], name)) for d in ("cpu", "cuda:0"))
+        assert a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8)), name
