@@ -664,6 +664,7 @@ TREE_COUNTER_TAG = 0x74726565        # word 3 of every counter of that stream
 TREE_MAX_ROWS = 1 << 24
 TREE_LAUNCH_TILES = 1 << 20          # (segment, 16-feature tile) pairs of one split-search call: 40 MiB of workspace at most
 _TREE_HOST_BLOCK = 1 << 22           # entries of a host model's sort block (rows x features)
+_HOST_SORT_ROWS = 64                 # a host search sorts a feature's bytes up to this many rows and builds its histograms beyond
 
 
 def tree_mask_threshold(max_features, D):
@@ -685,31 +686,46 @@ def tree_feature_mask(seed, tree, node, D, mask_thr):
     return w < np.uint64(int(mask_thr))
 
 
-def _best_split_node(Xs, w, wt, cols):
-    """(j, v, v_hi, nL, pL, score) of one node on the host: Xs [n, D] uint8 rows of weight w >= 1 (int64), wt = w t, over the candidate
-    features `cols` (ascending).  Sorting a feature's bytes puts the candidates at the places where the sorted byte changes; the
-    cumulative sums there are (nL, pL).  In blocks of features; a later block wins only with a strictly larger score."""
+def _best_byte_split(Xs, w, wt, cols):
+    """(j, v, v_hi, nL, pL, score) of one node on the host — the one search behind best_split_host_bytes and boost_stump_host_bytes:
+    Xs [n, D] uint8 rows of weight w >= 1 (int64), wt = w t, over the candidate features `cols` (ascending); (-1, -1, -1, 0, 0, -1.0)
+    without a candidate.  Two ways to the same integers: up to _HOST_SORT_ROWS rows are sorted per feature (the candidates lie where
+    the sorted byte changes, the cumulative sums there are (nL, pL)), more rows go into 256-bin histograms — np.bincount with float64
+    weights, every partial sum an integer below 2^53, so the sums are exact.  The score is (a a) / fl(nL) + (c c) / fl(nR) with
+    a = fl(pL), c = fl(p - pL): five float64 operations rounded once each.  In blocks of features; the first maximum of a block is
+    the smallest j, then the smallest v, and a later block wins only with a strictly larger score."""
     n_rows = Xs.shape[0]
     best = (-1, -1, -1, 0, 0, -1.0)
     if n_rows < 2 or len(cols) == 0:
         return best
     n, p = int(w.sum()), int(wt.sum())
-    step = max(1, _TREE_HOST_BLOCK // n_rows)
+    few = n_rows <= _HOST_SORT_ROWS
+    step = max(1, _TREE_HOST_BLOCK // (n_rows if few else 256))
     for c0 in range(0, len(cols), step):
         cc = cols[c0:c0 + step]
-        A = np.ascontiguousarray(Xs[:, cc].T)                        # [c, n]: a feature's bytes lie together
-        order = np.argsort(A, axis=1, kind="stable")
-        vs = np.take_along_axis(A, order, 1)
-        edge = vs[:, :-1] != vs[:, 1:]                               # [c, n - 1]: a candidate between sorted places i and i + 1
-        if not edge.any():
+        if few:
+            A = np.ascontiguousarray(Xs[:, cc].T)                    # [c, n]: a feature's bytes lie together
+            order = np.argsort(A, axis=1, kind="stable")
+            vs = np.take_along_axis(A, order, 1)
+            valid = vs[:, :-1] != vs[:, 1:]                          # [c, n - 1]: a candidate between sorted places i and i + 1
+            nL, pL = np.cumsum(w[order], 1)[:, :-1], np.cumsum(wt[order], 1)[:, :-1]
+        else:
+            c = len(cc)
+            idx = (Xs[:, cc].astype(np.int64) + 256 * np.arange(c)[None, :]).reshape(-1)
+            hn = np.bincount(idx, weights=np.repeat(w.astype(np.float64), c), minlength=256 * c).reshape(c, 256).astype(np.int64)
+            hp = np.bincount(idx, weights=np.repeat(wt.astype(np.float64), c), minlength=256 * c).reshape(c, 256).astype(np.int64)
+            nL, pL = np.cumsum(hn, 1), np.cumsum(hp, 1)
+            valid = (hn > 0) & (nL < n)
+        if not valid.any():
             continue
-        nL, pL = np.cumsum(w[order], 1)[:, :-1], np.cumsum(wt[order], 1)[:, :-1]
-        nR, pR = n - nL, p - pL                                      # every w >= 1: nL >= 1 and nR >= 1 at every place
-        s = (pL * pL).astype(np.float64) / nL.astype(np.float64) + (pR * pR).astype(np.float64) / nR.astype(np.float64)
-        s = np.where(edge, s, -1.0)                                  # the first maximum is the smallest j, then the smallest v
-        ci, i = divmod(int(np.argmax(s)), n_rows - 1)
+        a, b = pL.astype(np.float64), (p - pL).astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            s = (a * a) / nL.astype(np.float64) + (b * b) / (n - nL).astype(np.float64)
+        s = np.where(valid, s, -1.0)
+        ci, i = divmod(int(np.argmax(s)), s.shape[1])
         if s[ci, i] > best[5]:
-            best = (int(cc[ci]), int(vs[ci, i]), int(vs[ci, i + 1]), int(nL[ci, i]), int(pL[ci, i]), float(s[ci, i]))
+            v, vh = (int(vs[ci, i]), int(vs[ci, i + 1])) if few else (i, i + 1 + int(np.nonzero(hn[ci, i + 1:])[0][0]))
+            best = (int(cc[ci]), v, vh, int(nL[ci, i]), int(pL[ci, i]), float(s[ci, i]))
     return best
 
 
@@ -719,7 +735,8 @@ def best_split_host_bytes(Xu8, labels, rows, seg_off, seg_class, seg_wrow=None, 
     seg_off[s + 1]) of X with the targets t = [label == seg_class[s]] and the weights weights[seg_wrow[s]] (1 without; a row of
     weight 0 is not there).  A candidate (j, v): byte v <= 254 present, nL = sum w [b <= v] >= 1, nR >= 1, feature j let through by
     tree_feature_mask(seed, *seg_key[s], D, mask_thr); score fl(pL pL / nL) + fl(pR pR / nR) in float64, the products exact integers
-    converted once.  The largest score wins, ties to the smallest j, then the smallest v; v_hi is the next larger byte present.
+    converted once — computed as boost_stump_host_bytes' (a a) / fl(nL) + (c c) / fl(nR), the same bits: the counts are below 2^31, so
+    the factors convert exactly and the product of the two is the exact integer rounded once.  The largest score wins, ties to the smallest j, then the smallest v; v_hi is the next larger byte present.
     No valid candidate: (-1, -1, -1, 0, 0, n, p) and score 0."""
     X = _check_row_size(_bytes_rows(Xu8)).cpu().numpy()
     N, D = X.shape
@@ -749,7 +766,7 @@ def best_split_host_bytes(Xu8, labels, rows, seg_off, seg_class, seg_wrow=None, 
         if n >= 1 << 31:
             raise ValueError("the weights of segment %d add up to %d; the counters take less than 2^31" % (s, n))
         cols = every if int(mask_thr) == 0 else np.nonzero(tree_feature_mask(seed, key[0][s], key[1][s], D, mask_thr))[0]
-        j, v, vh, nL, pL, sc = _best_split_node(X[r], w, wt, cols)
+        j, v, vh, nL, pL, sc = _best_byte_split(X[r], w, wt, cols)
         out[s] = (j, v, vh, nL, pL, n, p)
         score[s] = sc if j >= 0 else 0.0
     return torch.from_numpy(out), torch.from_numpy(score.view(np.int64).copy())
@@ -955,7 +972,6 @@ class Trees:
 BOOST_W1 = 1 << 28                   # the largest fixed-point row weight (include/cslgan.h "boosted stumps")
 BOOST_MAX_ROUNDS = 4095              # K n_rounds stumps go through the tree apply path as trees: at most 65535
 _BOOST_APPLY_ENTRIES = 1 << 24       # (stump, test row) pairs of one apply call
-_BOOST_SORT_ROWS = 64                # the host model sorts a feature's bytes up to this many rows and builds its histograms beyond
 
 
 def boost_stump_host_bytes(Xu8, labels, weights, K):
@@ -966,8 +982,8 @@ def boost_stump_host_bytes(Xu8, labels, weights, K):
     c = fl(p - pL), five float64 operations rounded once each (every integer is below 2^52: the conversions are exact).  The largest
     score wins, ties to the smallest j, then the smallest v; v_hi is the next larger byte present.  No valid candidate:
     (-1, -1, -1, 0, 0, n, p) and score 0.
-    Two ways to the same integers: a few rows are sorted per feature (the candidates lie where the sorted byte changes), more rows go
-    into 256-bin histograms — np.bincount with float64 weights, every partial sum an integer below 2^53, so the sums are exact."""
+    The search is best_split_host_bytes' (_best_byte_split); for counts below 2^32 its form of the score, the exact integer pL pL
+    converted once, rounds the same real number once and gives the same bits."""
     X = _check_row_size(_bytes_rows(Xu8)).cpu().numpy()
     N, D = X.shape
     K = _check_classes(K)
@@ -981,45 +997,14 @@ def boost_stump_host_bytes(Xu8, labels, weights, K):
         raise ValueError("weights must lie in 0 .. 2^28")
     out = np.zeros((K, 7), dtype=np.int64)
     score = np.zeros(K, dtype=np.float64)
+    every = np.arange(D)
     for k in range(K):
         live = W[k] > 0
-        w = W[k][live].astype(np.float64)
+        w = W[k][live]
         wt = w * (y[live] == k)
-        n, p = int(w.sum()), int(wt.sum())
-        out[k] = (-1, -1, -1, 0, 0, n, p)
-        n_rows = int(live.sum())
-        if n_rows < 2:
-            continue
-        Xs = X[live]
-        best = -1.0
-        few = n_rows <= _BOOST_SORT_ROWS
-        step = max(1, _TREE_HOST_BLOCK // (n_rows if few else 256))
-        for c0 in range(0, D, step):
-            c = min(step, D - c0)
-            if few:                                                  # (nL, pL) where a feature's sorted bytes change
-                A = np.ascontiguousarray(Xs[:, c0:c0 + c].T)
-                order = np.argsort(A, axis=1, kind="stable")
-                vs = np.take_along_axis(A, order, 1)
-                valid = vs[:, :-1] != vs[:, 1:]
-                nL, pL = np.cumsum(w[order].astype(np.int64), 1)[:, :-1], np.cumsum(wt[order].astype(np.int64), 1)[:, :-1]
-            else:                                                    # (nL, pL) at every byte of a feature's 256-bin histograms
-                idx = (Xs[:, c0:c0 + c].astype(np.int64) + 256 * np.arange(c)[None, :]).reshape(-1)
-                hn = np.bincount(idx, weights=np.repeat(w, c), minlength=256 * c).reshape(c, 256).astype(np.int64)
-                hp = np.bincount(idx, weights=np.repeat(wt, c), minlength=256 * c).reshape(c, 256).astype(np.int64)
-                nL, pL = np.cumsum(hn, 1), np.cumsum(hp, 1)
-                valid = (hn > 0) & (nL < n)
-            if not valid.any():
-                continue
-            a, b = pL.astype(np.float64), (p - pL).astype(np.float64)
-            with np.errstate(divide="ignore", invalid="ignore"):
-                s = (a * a) / nL.astype(np.float64) + (b * b) / (n - nL).astype(np.float64)
-            s = np.where(valid, s, -1.0)                             # the first maximum is the smallest j, then the smallest v
-            ci, i = divmod(int(np.argmax(s)), s.shape[1])
-            if s[ci, i] > best:
-                best = float(s[ci, i])
-                v, vh = (int(vs[ci, i]), int(vs[ci, i + 1])) if few else (i, i + 1 + int(np.nonzero(hn[ci, i + 1:])[0][0]))
-                out[k, :5] = (c0 + ci, v, vh, int(nL[ci, i]), int(pL[ci, i]))
-        score[k] = best if out[k, 0] >= 0 else 0.0
+        j, v, vh, nL, pL, sc = _best_byte_split(X[live], w, wt, every)
+        out[k] = (j, v, vh, nL, pL, int(w.sum()), int(wt.sum()))
+        score[k] = sc if j >= 0 else 0.0
     return torch.from_numpy(out), torch.from_numpy(score.view(np.int64).copy())
 
 

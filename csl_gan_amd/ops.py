@@ -1486,8 +1486,7 @@ def _ovr_eval_outputs(what, X, labels, U, out_loss, out_grad):
     """What the three ovr_*_eval wrappers share once X [N, D] and U [P, K] have their shapes: labels must be N int32 entries on the
     device, and (out_loss [K], out_grad like U) are checked, or allocated when absent."""
     N, K = X.shape[0], U.shape[1]
-    if not labels.is_cuda or labels.dtype != torch.int32 or labels.numel() != N or not labels.is_contiguous():
-        raise RuntimeError("%s: labels must be a contiguous int32 device tensor of %d entries" % (what, N))
+    _chk_i32(labels, "labels", what, N)
     if out_loss is None:
         out_loss = torch.empty(K, device=X.device, dtype=torch.float32)
     elif _chk(out_loss, "out_loss").numel() != K:
@@ -1635,12 +1634,9 @@ def class_moments_u8(X, labels, n_classes, binarize=0, out=None):
     number of rows with b > binarize of X [N, D] uint8 with int32 labels [N] (include/cslgan.h "naive Bayes"): one pass over X, exact,
     the same integers in every schedule.  out: such a dict to write into (whatever it holds is overwritten); allocated when absent.
     csl_gan_amd.classify.class_moments_host_bytes is the host model."""
-    _chk_bytes(X, "X")
-    if X.dim() != 2:
-        raise RuntimeError("class_moments_u8: need X [N, D], got %s" % (tuple(X.shape),))
-    N, D, K = X.shape[0], X.shape[1], int(n_classes)
-    if not labels.is_cuda or labels.dtype != torch.int32 or labels.numel() != N or not labels.is_contiguous():
-        raise RuntimeError("class_moments_u8: labels must be a contiguous int32 device tensor of %d entries" % N)
+    N, D = _byte_rows(X, "class_moments_u8")
+    K = int(n_classes)
+    _chk_i32(labels, "labels", "class_moments_u8", N)
     shapes = {"n": (K,), "s1": (K, D), "s2": (K, D), "cnt": (K, D)}
     if out is None:
         out = {k: torch.empty(s, device=X.device, dtype=torch.int64) for k, s in shapes.items()}
@@ -1693,6 +1689,31 @@ def _chk_i32(t, name, what, numel=None):
     return t
 
 
+def _byte_rows(X, what, name="X", rows="N"):
+    """(rows, D) of X [rows, D], contiguous device bytes."""
+    _chk_bytes(X, name)
+    if X.dim() != 2:
+        raise RuntimeError("%s: need %s [%s, D], got %s" % (what, name, rows, tuple(X.shape)))
+    return X.shape
+
+
+def _split_outputs(what, X, S, dtype, out, need, refusal, ws):
+    """What the two split searches share once X [N, D] is checked: the pair (out [S, 7] of dtype, score int64 [S]) and the byte
+    workspace of at least `need` (0: a shape the entry does not take, refused with `refusal`), each checked, or allocated when absent."""
+    if need == 0:
+        raise RuntimeError("%s: %s" % (what, refusal))
+    if out is None:
+        out = (torch.empty((S, 7), device=X.device, dtype=dtype), torch.empty(S, device=X.device, dtype=torch.int64))
+    for t, name, dt, numel in ((out[0], "out[0]", dtype, 7 * S), (out[1], "out[1]", torch.int64, S)):
+        if not t.is_cuda or t.dtype != dt or not t.is_contiguous() or t.numel() != numel:
+            raise RuntimeError("%s: %s must be a contiguous %s device tensor of %d entries" % (what, name, str(dt).replace("torch.", ""), numel))
+    if ws is None:
+        ws = torch.empty(need, device=X.device, dtype=torch.uint8)
+    elif not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need:
+        raise RuntimeError("%s: ws must be a contiguous uint8 device tensor of at least %d bytes" % (what, need))
+    return out, ws
+
+
 def tree_best_split_ws_bytes(S, D):
     """Workspace of tree_best_split_u8 in bytes (0: a shape one launch does not take; split the segments over several calls)."""
     return int(_lib.lib().cslgan_tree_best_split_ws_bytes(int(S), int(D)))
@@ -1706,10 +1727,8 @@ def tree_best_split_u8(X, labels, n_classes, rows, seg_off, seg_class, seg_wrow=
     of at least tree_best_split_ws_bytes(S, D) bytes; both allocated when absent.  Exact: csl_gan_amd.classify.best_split_host_bytes
     is the host model, equalled in every integer and in the score's bits."""
     what = "tree_best_split_u8"
-    _chk_bytes(X, "X")
-    if X.dim() != 2:
-        raise RuntimeError("%s: need X [N, D], got %s" % (what, tuple(X.shape)))
-    N, D, K = X.shape[0], X.shape[1], int(n_classes)
+    N, D = _byte_rows(X, what)
+    K = int(n_classes)
     _chk_i32(labels, "labels", what, N)
     _chk_i32(rows, "rows", what)
     S = _chk_i32(seg_class, "seg_class", what).numel()
@@ -1728,18 +1747,8 @@ def tree_best_split_u8(X, labels, n_classes, rows, seg_off, seg_class, seg_wrow=
     if mask_thr and seg_key is None:
         raise RuntimeError("%s: a feature mask needs seg_key = (seg_tree, seg_node)" % what)
     tree, node = (None, None) if seg_key is None else (_chk_i32(seg_key[0], "seg_tree", what, S), _chk_i32(seg_key[1], "seg_node", what, S))
-    if out is None:
-        out = (torch.empty((S, 7), device=X.device, dtype=torch.int32), torch.empty(S, device=X.device, dtype=torch.int64))
-    _chk_i32(out[0], "out[0]", what, 7 * S)
-    if not out[1].is_cuda or out[1].dtype != torch.int64 or not out[1].is_contiguous() or out[1].numel() != S:
-        raise RuntimeError("%s: out[1] must be a contiguous int64 device tensor of %d entries" % (what, S))
-    need = tree_best_split_ws_bytes(S, D)
-    if need == 0:
-        raise RuntimeError("%s: S = %d segments of D = %d features is outside 1 <= S, 1 <= D <= 65536, S ceil(D / 16) < 2^31" % (what, S, D))
-    if ws is None:
-        ws = torch.empty(need, device=X.device, dtype=torch.uint8)
-    elif not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need:
-        raise RuntimeError("%s: ws must be a contiguous uint8 device tensor of at least %d bytes" % (what, need))
+    out, ws = _split_outputs(what, X, S, torch.int32, out, tree_best_split_ws_bytes(S, D),
+                             "S = %d segments of D = %d features is outside 1 <= S, 1 <= D <= 65536, S ceil(D / 16) < 2^31" % (S, D), ws)
     check(_lib.lib().cslgan_tree_best_split_u8(_p(X), _p(labels), _p(weights), B, N, D, K, _p(rows), rows.numel(), _p(seg_off), _p(seg_class), _p(seg_wrow),
                                                _p(tree), _p(node), S, mask_thr, seed, _p(out[0]), _p(out[1]), _p(ws), ws.numel(), _stream()), what)
     return out
@@ -1750,10 +1759,7 @@ def tree_apply_u8(Xtest, feature, threshold, child, tree_off, out=None):
     feature, threshold, child [Q] and tree_off [T + 1] (include/cslgan.h "decision trees"); -1 where a table is malformed.
     csl_gan_amd.classify.tree_apply_host_bytes is the host model."""
     what = "tree_apply_u8"
-    _chk_bytes(Xtest, "Xtest")
-    if Xtest.dim() != 2:
-        raise RuntimeError("%s: need Xtest [M, D], got %s" % (what, tuple(Xtest.shape)))
-    M, D = Xtest.shape
+    M, D = _byte_rows(Xtest, what, "Xtest", "M")
     Q = _chk_i32(feature, "feature", what).numel()
     _chk_i32(threshold, "threshold", what, Q)
     _chk_i32(child, "child", what, Q)
@@ -1777,26 +1783,14 @@ def boost_stump_u8(X, labels, n_classes, weights, out=None, ws=None):
     boost_stump_ws_bytes(K, D) bytes; both allocated when absent.  Exact: csl_gan_amd.classify.boost_stump_host_bytes is the host
     model, equalled in every integer and in the score's bits."""
     what = "boost_stump_u8"
-    _chk_bytes(X, "X")
-    if X.dim() != 2:
-        raise RuntimeError("%s: need X [N, D], got %s" % (what, tuple(X.shape)))
-    N, D, K = X.shape[0], X.shape[1], int(n_classes)
+    N, D = _byte_rows(X, what)
+    K = int(n_classes)
     _chk_i32(labels, "labels", what, N)
     if weights.dim() != 2 or tuple(weights.shape) != (K, N):
         raise RuntimeError("%s: need weights [%d, %d], got %s" % (what, K, N, tuple(weights.shape)))
     _chk_i32(weights, "weights", what)
-    need = boost_stump_ws_bytes(K, D)
-    if need == 0:
-        raise RuntimeError("%s: K = %d classes of D = %d features is outside 2 <= K <= 16, 1 <= D <= 65536" % (what, K, D))
-    if out is None:
-        out = (torch.empty((K, 7), device=X.device, dtype=torch.int64), torch.empty(K, device=X.device, dtype=torch.int64))
-    for t, name, numel in ((out[0], "out[0]", 7 * K), (out[1], "out[1]", K)):
-        if not t.is_cuda or t.dtype != torch.int64 or not t.is_contiguous() or t.numel() != numel:
-            raise RuntimeError("%s: %s must be a contiguous int64 device tensor of %d entries" % (what, name, numel))
-    if ws is None:
-        ws = torch.empty(need, device=X.device, dtype=torch.uint8)
-    elif not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need:
-        raise RuntimeError("%s: ws must be a contiguous uint8 device tensor of at least %d bytes" % (what, need))
+    out, ws = _split_outputs(what, X, K, torch.int64, out, boost_stump_ws_bytes(K, D),
+                             "K = %d classes of D = %d features is outside 2 <= K <= 16, 1 <= D <= 65536" % (K, D), ws)
     check(_lib.lib().cslgan_boost_stump_u8(_p(X), _p(labels), _p(weights), N, D, K, _p(out[0]), _p(out[1]), _p(ws), ws.numel(), _stream()), what)
     return out
 

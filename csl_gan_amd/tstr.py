@@ -39,6 +39,7 @@ of the stump weights and the first round's error per class), "n_rounds" and "lea
 normalised vote F; --values_dir keeps P and U (the stump table, AdaBoost.coef).
 """
 import argparse
+import collections
 import sys
 
 import numpy as np
@@ -46,6 +47,68 @@ import torch
 
 from . import cache_cli, classify, pipeline
 from .cache_cli import cache_rows  # noqa: F401  (scripts/tstr_bench.py and scripts/mlp_bench.py reach it as tstr.cache_rows)
+
+
+def _proba_scores(clf, test_x):
+    """(what AUROC ranks, what accuracy takes the argmax of, the values kept besides U) of an estimator with predict_proba_bytes.  Where P
+    comes back on the host (dt, rf, ab) it is moved to the test rows' device for the ranks: on a device the rank counts are the device's."""
+    P = clf.predict_proba_bytes(test_x)
+    return P.to(test_x.device), P, {"P": P}
+
+
+def _nb_scores(clf, test_x):
+    """Naive Bayes: AUROC ranks the log-odds (the posteriors saturate to exactly 0 and 1), accuracy is the argmax of J."""
+    J = clf.jll_bytes(test_x)
+    return classify.log_odds(J).to(test_x.device), J, {"P": torch.softmax(J, 1), "J": J}
+
+
+def _max_iter(a, default):
+    return a.max_iter if a.max_iter is not None else default
+
+
+def _trees(K, a):
+    return classify.Trees(K, kind=a.classifier, n_trees=a.n_trees, max_features=a.max_features or None, max_depth=a.max_depth,
+                          min_samples_split=a.min_samples_split, seed=a.seed)
+
+
+def _tree_stats(clf, a, rep, D):
+    return {"classifier": a.classifier, "fit": rep, "max_depth": clf.max_depth, "min_samples_split": clf.min_samples_split}
+
+
+def _nb_line(m):
+    return "   fit: rows per class %s%s" % (m["fit"]["n_per_class"], "  eps %.6g" % m["fit"]["eps"] if "eps" in m["fit"] else "")
+
+
+def _tree_line(m):
+    f = m["fit"]
+    return "   fit: rows per class %s  trees %d  nodes %d  leaves %d  depth <= %d  levels %d" % (
+        f["n_per_class"], len(f["nodes"]), sum(f["nodes"]), sum(f["leaves"]), max(f["depth"]), f["levels"])
+
+
+# One entry per --classifier choice.  build(K, a): the estimator of csl_gan_amd.classify from the parsed arguments a (fit_bytes(X, y)
+# returns its report); scores(clf, test_x): see _proba_scores; stats(clf, a, report, D): the keys the figures carry besides the scores,
+# the report among them, in the order they are written; fit_line(figures): the line printed under the scores.  DESIGN.md §6o.
+Estimator = collections.namedtuple("Estimator", "build scores stats fit_line")
+ESTIMATORS = {
+    "lr": Estimator(lambda K, a: classify.OvrLogReg(K, gtol_rel=a.gtol_rel, max_iter=_max_iter(a, 2000)), _proba_scores,
+                    lambda clf, a, rep, D: {"solver": rep}, lambda m: classify.solver_line(m["solver"])),
+    "mlp": Estimator(lambda K, a: classify.OvrMlp(K, gtol_rel=a.gtol_rel, max_iter=_max_iter(a, 200), hidden=a.hidden, alpha=a.alpha, seed=a.seed),
+                     _proba_scores,
+                     lambda clf, a, rep, D: {"solver": rep, "classifier": "mlp", "hidden": int(a.hidden), "alpha": float(a.alpha), "seed": int(a.seed)},
+                     lambda m: classify.solver_line(m["solver"])),
+    "gnb": Estimator(lambda K, a: classify.NaiveBayes(K, kind="gnb", var_smoothing=a.var_smoothing), _nb_scores,
+                     lambda clf, a, rep, D: {"classifier": "gnb", "fit": rep, "var_smoothing": a.var_smoothing}, _nb_line),
+    "bnb": Estimator(lambda K, a: classify.NaiveBayes(K, kind="bnb", alpha=a.nb_alpha, binarize=a.binarize), _nb_scores,
+                     lambda clf, a, rep, D: {"classifier": "bnb", "fit": rep, "alpha": a.nb_alpha, "binarize": a.binarize}, _nb_line),
+    "dt": Estimator(_trees, _proba_scores, _tree_stats, _tree_line),
+    "rf": Estimator(_trees, _proba_scores,
+                    lambda clf, a, rep, D: dict(_tree_stats(clf, a, rep, D), n_trees=clf.B, max_features=clf.max_features or max(1, int(np.sqrt(D))),
+                                                seed=clf.seed), _tree_line),
+    "ab": Estimator(lambda K, a: classify.AdaBoost(K, n_rounds=a.n_rounds, learning_rate=a.learning_rate), _proba_scores,
+                    lambda clf, a, rep, D: {"classifier": "ab", "fit": rep, "n_rounds": clf.n_rounds, "learning_rate": clf.learning_rate},
+                    lambda m: "   fit: rows per class %s  rounds per class %s  stumps %d" % (
+                        m["fit"]["n_per_class"], m["fit"]["rounds"], sum(m["fit"]["rounds"]))),
+}
 
 
 def build_parser():
@@ -57,7 +120,7 @@ def build_parser():
     ap.add_argument("--baseline", default=False, action="store_true", help="also fit on the training set itself")
     ap.add_argument("--gtol_rel", type=float, default=None, help="a class has converged when max|gradient| <= gtol_rel * n")
     ap.add_argument("--max_iter", type=int, default=None, help="L-BFGS iterations per class (default: 2000 for lr, 200 for mlp)")
-    ap.add_argument("--classifier", type=str, default="lr", choices=["lr", "mlp", "gnb", "bnb", "dt", "rf", "ab"],
+    ap.add_argument("--classifier", type=str, default="lr", choices=list(ESTIMATORS),
                     help="one-vs-rest logistic regression or MLP, Gaussian or Bernoulli naive Bayes, decision tree or random forest, AdaBoost of stumps")
     ap.add_argument("--hidden", type=int, default=100, help="mlp: hidden ReLU units per class, 1 .. %d" % classify.MAX_HIDDEN)
     ap.add_argument("--alpha", type=float, default=1.0, help="mlp: L2 penalty on the weights, >= 0")
@@ -88,95 +151,41 @@ def n_classes_of(labels, path):
     return K
 
 
-def _scores(stats, a, acc):
-    stats.update({"auroc_micro": a["micro"], "auroc_per_class": a["per_class"], "accuracy": acc["accuracy"], "accuracy_hits": acc["hits"]})
-    return stats
-
-
-def fit_and_score(train_x, train_y, K, test_x, test_y, device, gtol_rel=None, max_iter=2000, mlp=None, nb=None, trees=None, boost=None):
-    """One fit on bytes train_x [n, D] (numpy) and its figures on test_x (a uint8 tensor already on `device`): (stats, values), values
-    the arrays --values_dir keeps ("P", "U"; "J" as well for naive Bayes).  The estimator: nb = {"kind": "gnb", "var_smoothing"} or
-    {"kind": "bnb", "alpha", "binarize"} for classify.NaiveBayes; else mlp = {"hidden", "alpha", "seed"} for classify.OvrMlp; else the
-    logistic regression; trees = {"kind": "dt" | "rf", "n_trees", "max_features", "max_depth", "min_samples_split", "seed"} comes before all
-    of them, for classify.Trees, and boost = {"n_rounds", "learning_rate"} before those, for classify.AdaBoost.  The parameters are part
-    of the stats."""
+def fit_and_score(est, a, train_x, train_y, K, test_x, test_y, device):
+    """One fit of the estimator est (an entry of ESTIMATORS, built from the parsed arguments a) on bytes train_x [n, D] (numpy) and its
+    figures on test_x (a uint8 tensor already on `device`): (stats, values), values the arrays --values_dir keeps ("P", "U"; "J" as
+    well for naive Bayes).  The parameters are part of the stats."""
     stats = {"n_train": int(len(train_y)), "n_test": int(len(test_y)), "classes": int(K)}
-    X = torch.from_numpy(train_x).to(device)
-    if boost is not None:
-        clf = classify.AdaBoost(K, **boost)
-        report = clf.fit_bytes(X, torch.from_numpy(train_y))
-        del X
-        P = clf.predict_proba_bytes(test_x)
-        _scores(stats, classify.auroc(P.to(test_x.device), test_y), classify.accuracy(P, test_y))     # on a device the rank counts are the device's
-        stats.update({"classifier": "ab", "fit": report, "n_rounds": clf.n_rounds, "learning_rate": clf.learning_rate})
-        return stats, {"P": P.numpy(), "U": clf.coef.numpy()}
-    if trees is not None:
-        clf = classify.Trees(K, **trees)
-        report = clf.fit_bytes(X, torch.from_numpy(train_y))
-        del X
-        P = clf.predict_proba_bytes(test_x)
-        _scores(stats, classify.auroc(P.to(test_x.device), test_y), classify.accuracy(P, test_y))     # on a device the rank counts are the device's
-        stats.update({"classifier": trees["kind"], "fit": report, "max_depth": clf.max_depth, "min_samples_split": clf.min_samples_split})
-        if trees["kind"] == "rf":
-            stats.update({"n_trees": clf.B, "max_features": clf.max_features or max(1, int(np.sqrt(train_x.shape[1]))), "seed": clf.seed})
-        return stats, {"P": P.numpy(), "U": clf.coef.numpy()}
-    if nb is not None:
-        clf = classify.NaiveBayes(K, **nb)
-        report = clf.fit_bytes(X, torch.from_numpy(train_y))
-        del X
-        J = clf.jll_bytes(test_x)
-        L = classify.log_odds(J).to(test_x.device)                   # on a device the rank counts are the device's
-        _scores(stats, classify.auroc(L, test_y), classify.accuracy(J, test_y))
-        stats.update({"classifier": nb["kind"], "fit": report}, **{k: v for k, v in nb.items() if k != "kind"})
-        return stats, {"P": torch.softmax(J, 1).numpy(), "J": J.numpy(), "U": clf.coef.numpy()}
-    if mlp is None:
-        clf = classify.OvrLogReg(K, gtol_rel=gtol_rel, max_iter=max_iter)
-    else:
-        clf = classify.OvrMlp(K, gtol_rel=gtol_rel, max_iter=max_iter, **mlp)
-    report = clf.fit_bytes(X, torch.from_numpy(train_y))
-    del X
-    P = clf.predict_proba_bytes(test_x)
-    _scores(stats, classify.auroc(P, test_y), classify.accuracy(P, test_y))
-    stats["solver"] = report
-    if mlp is not None:
-        stats.update({"classifier": "mlp", "hidden": int(mlp["hidden"]), "alpha": float(mlp["alpha"]), "seed": int(mlp["seed"])})
-    return stats, {"P": P.cpu().numpy(), "U": clf.coef.cpu().numpy()}
+    clf = est.build(K, a)
+    report = clf.fit_bytes(torch.from_numpy(train_x).to(device), torch.from_numpy(train_y))
+    rank, top, values = est.scores(clf, test_x)
+    au, acc = classify.auroc(rank, test_y), classify.accuracy(top, test_y)
+    stats.update({"auroc_micro": au["micro"], "auroc_per_class": au["per_class"], "accuracy": acc["accuracy"], "accuracy_hits": acc["hits"]})
+    stats.update(est.stats(clf, a, report, train_x.shape[1]))
+    return stats, {k: v.cpu().numpy() for k, v in dict(values, U=clf.coef).items()}
 
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
     if a.baseline and not a.train_cache:
         raise SystemExit("--baseline fits on the training set: give --train_cache")
-    if not 1 <= a.hidden <= classify.MAX_HIDDEN:
-        raise SystemExit("--hidden %d: the MLP takes 1 .. %d hidden units per class" % (a.hidden, classify.MAX_HIDDEN))
-    if not 0 <= a.alpha < float("inf"):
-        raise SystemExit("--alpha %r: the penalty must be a finite number >= 0" % a.alpha)
-    if not 0 <= a.var_smoothing < float("inf"):
-        raise SystemExit("--var_smoothing %r: must be a finite number >= 0" % a.var_smoothing)
-    if not 0 < a.nb_alpha < float("inf"):
-        raise SystemExit("--nb_alpha %r: the smoothing must be a finite number > 0" % a.nb_alpha)
-    if not 0 <= a.binarize <= 254:
-        raise SystemExit("--binarize %d: a byte threshold, 0 .. 254" % a.binarize)
-    if not 1 <= a.n_trees <= 4095:
-        raise SystemExit("--n_trees %d: a forest takes 1 .. 4095 trees per class" % a.n_trees)
-    if a.max_features < 0:
-        raise SystemExit("--max_features %d: the expected number of candidate features, >= 1 (0: sqrt of the row size)" % a.max_features)
-    if a.max_depth < 0:
-        raise SystemExit("--max_depth %d: must be >= 0 (0: unlimited)" % a.max_depth)
-    if a.min_samples_split < 2:
-        raise SystemExit("--min_samples_split %d: must be >= 2" % a.min_samples_split)
-    if a.classifier in ("dt", "rf") and not 0 <= a.seed < 2 ** 63:
-        raise SystemExit("--seed %d: the trees take 0 .. 2^63 - 1" % a.seed)
-    if not 1 <= a.n_rounds <= classify.BOOST_MAX_ROUNDS:
-        raise SystemExit("--n_rounds %d: boosting takes 1 .. %d rounds per class" % (a.n_rounds, classify.BOOST_MAX_ROUNDS))
-    if not 0 < a.learning_rate < float("inf"):
-        raise SystemExit("--learning_rate %r: must be a finite number > 0" % a.learning_rate)
-    boost = {"n_rounds": a.n_rounds, "learning_rate": a.learning_rate} if a.classifier == "ab" else None
-    trees = {"kind": a.classifier, "n_trees": a.n_trees, "max_features": a.max_features or None, "max_depth": a.max_depth,
-             "min_samples_split": a.min_samples_split, "seed": a.seed} if a.classifier in ("dt", "rf") else None
-    mlp = {"hidden": a.hidden, "alpha": a.alpha, "seed": a.seed} if a.classifier == "mlp" else None
-    nb = {"gnb": {"kind": "gnb", "var_smoothing": a.var_smoothing}, "bnb": {"kind": "bnb", "alpha": a.nb_alpha, "binarize": a.binarize}}.get(a.classifier)
-    max_iter = a.max_iter if a.max_iter is not None else (2000 if mlp is None else 200)
+    inf = float("inf")
+    for flag, ok, msg in (          # every flag is checked whichever classifier is chosen; only --seed is the trees' alone
+            ("hidden", 1 <= a.hidden <= classify.MAX_HIDDEN, "--hidden %%d: the MLP takes 1 .. %d hidden units per class" % classify.MAX_HIDDEN),
+            ("alpha", 0 <= a.alpha < inf, "--alpha %r: the penalty must be a finite number >= 0"),
+            ("var_smoothing", 0 <= a.var_smoothing < inf, "--var_smoothing %r: must be a finite number >= 0"),
+            ("nb_alpha", 0 < a.nb_alpha < inf, "--nb_alpha %r: the smoothing must be a finite number > 0"),
+            ("binarize", 0 <= a.binarize <= 254, "--binarize %d: a byte threshold, 0 .. 254"),
+            ("n_trees", 1 <= a.n_trees <= 4095, "--n_trees %d: a forest takes 1 .. 4095 trees per class"),
+            ("max_features", a.max_features >= 0, "--max_features %d: the expected number of candidate features, >= 1 (0: sqrt of the row size)"),
+            ("max_depth", a.max_depth >= 0, "--max_depth %d: must be >= 0 (0: unlimited)"),
+            ("min_samples_split", a.min_samples_split >= 2, "--min_samples_split %d: must be >= 2"),
+            ("seed", a.classifier not in ("dt", "rf") or 0 <= a.seed < 2 ** 63, "--seed %d: the trees take 0 .. 2^63 - 1"),
+            ("n_rounds", 1 <= a.n_rounds <= classify.BOOST_MAX_ROUNDS, "--n_rounds %%d: boosting takes 1 .. %d rounds per class" % classify.BOOST_MAX_ROUNDS),
+            ("learning_rate", 0 < a.learning_rate < inf, "--learning_rate %r: must be a finite number > 0")):
+        if not ok:
+            raise SystemExit(msg % getattr(a, flag))
+    est = ESTIMATORS[a.classifier]
     test = pipeline.CachedImages(a.test_cache)
     extra = [("baseline_train", a.train_cache, pipeline.CachedImages(a.train_cache))] if a.baseline else []
     sets = cache_cli.open_syn_caches(a.syn_cache, test, a.test_cache, [(p, c) for _, p, c in extra]) + extra
@@ -198,23 +207,13 @@ def main(argv=None):
     stats, values = {}, {}
     for lab, _, c in sets:
         x, y = cache_rows(c)
-        m, vals = fit_and_score(x, y, classes[lab], test_x, test_yt, device, a.gtol_rel, max_iter, mlp, nb, trees, boost)
+        m, vals = fit_and_score(est, a, x, y, classes[lab], test_x, test_yt, device)
         stats[lab] = m
         values.update({lab + "_" + k: v for k, v in vals.items()})
         print("%s: fitted on %d rows, scored %d: AUROC %.6f, accuracy %.4f (%d / %d)" % (
             lab, m["n_train"], m["n_test"], m["auroc_micro"], m["accuracy"], m["accuracy_hits"], m["n_test"]))
         print("   per class: %s" % " ".join("%.4f" % v for v in m["auroc_per_class"]))
-        if boost is not None:
-            f = m["fit"]
-            print("   fit: rows per class %s  rounds per class %s  stumps %d" % (f["n_per_class"], f["rounds"], sum(f["rounds"])))
-        elif trees is not None:
-            f = m["fit"]
-            print("   fit: rows per class %s  trees %d  nodes %d  leaves %d  depth <= %d  levels %d" % (
-                f["n_per_class"], len(f["nodes"]), sum(f["nodes"]), sum(f["leaves"]), max(f["depth"]), f["levels"]))
-        elif nb is None:
-            print(classify.solver_line(m["solver"]))
-        else:
-            print("   fit: rows per class %s%s" % (m["fit"]["n_per_class"], "  eps %.6g" % m["fit"]["eps"] if "eps" in m["fit"] else ""))
+        print(est.fit_line(m))
     cache_cli.save_values(a.values_dir, values)
     return cache_cli.report(a, stats)
 

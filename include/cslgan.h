@@ -692,7 +692,9 @@ int cslgan_nb_score_bern_u8(const void* Xtest, const float* delta, int64_t M, in
  * seg_node[s]).  The weights of a segment's rows must add up to less than 2^31; a row of weight 0 is not there.
  *   With n = sum w, p = sum w t over the segment, a candidate is (feature j, byte v), v in 0 .. 254 present in the segment, with
  * nL = sum w [b_ij <= v] >= 1 and nR = n - nL >= 1; its score is s = fl(pL pL / nL) + fl(pR pR / nR) in float64 — the products exact
- * integers converted once, two IEEE divisions, one addition, nothing fused.  Feature j is a candidate feature iff mask_thr == 0 or
+ * integers converted once, two IEEE divisions, one addition, nothing fused (computed by the score routine of the boosted stumps below,
+ * (a a) / fl(nL) + (c c) / fl(nR) on the converted counts: below 2^32 they convert exactly and both forms round the exact product once —
+ * the same bits).  Feature j is a candidate feature iff mask_thr == 0 or
  * word 0 of Philox4x32-10(counter (j, seg_node, seg_tree, 0x74726565), key = seed ^ 0x7472656573706C74) < mask_thr.  The segment's
  * result is the candidate of the largest s, ties to the smallest j, then the smallest v:
  *     out[s] = (j, v, v_hi, nL, pL, n, p)   int32 [S, 7],  v_hi the next larger byte present;   score[s] = the bits of s   int64 [S]
@@ -700,7 +702,8 @@ int cslgan_nb_score_bern_u8(const void* Xtest, const float* delta, int64_t M, in
  * csl_gan_amd.classify.best_split_host_bytes in every output and in the bits of the score, the same on every call.
  *   A workgroup owns a (segment, tile of 16 features) pair, builds the tile's 256-bin (n, p) histograms in LDS with 64-bit LDS atomics
  * (n in the low half, p in the high half: sum w < 2^31 keeps both from wrapping, one bin may hold it all), scans them and writes one
- * candidate per (segment, tile) into ws; a second kernel reduces the tiles with the tie rule.  No global histogram exists.
+ * candidate per (segment, tile) into ws; a second kernel reduces the tiles with the tie rule.  No global histogram exists.  The
+ * histogram scatter, the scan, the score and the reductions are byte_split.h's, shared with cslgan_boost_stump_u8.
  * ws: cslgan_tree_best_split_ws_bytes(S, D) bytes, 8-byte aligned (0: S < 1, D outside 1 .. 65536, or S ceil(D / 16) >= 2^31 — split the
  * level into several calls then).
  *
@@ -735,7 +738,8 @@ int cslgan_tree_apply_u8(const void* Xtest, int64_t M, int D, const int32_t* fea
  * csl_gan_amd.classify.boost_stump_host_bytes in every output and in the bits of the score, the same on every call.
  *   A workgroup owns a (class, tile of 16 features) pair — the K workgroups of a tile are neighbours in the grid — and builds per feature
  * two 256-bin histograms of 64-bit LDS counters, the weights of the negative and of the positive rows: one 64-bit LDS atomic per byte.
- * It scans them and writes one candidate into ws; a second kernel reduces the tiles with the tie rule.
+ * It scans them and writes one candidate into ws; a second kernel reduces the tiles with the tie rule — the frame and the score routine of
+ * cslgan_tree_best_split_u8 (byte_split.h), on 64-bit counts: with every weight 1 a class's result equals that entry's on all rows.
  * ws: cslgan_boost_stump_ws_bytes(K, D) = 64 K ceil(D / 16) bytes, 8-byte aligned (0: K or D out of range).  The entry validates on the
  * host before any launch (null pointers, N, D, K, the workspace size, alignment), never allocates and never synchronises. */
 int64_t cslgan_boost_stump_ws_bytes(int K, int D);

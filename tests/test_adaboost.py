@@ -99,6 +99,24 @@ def test_host_stump_equals_brute_force(N, D):
             assert want[0] != 1                                      # the duplicate of column 0 never wins
 
 
+@pytest.mark.parametrize("n_live", [64, 65])
+def test_host_stump_at_the_switch_from_sorting_to_histograms(n_live):
+    """Exactly 64 and 65 rows of weight > 0 (the switch counts those), 12 more of weight 0: the last size that is sorted and the first
+    that goes into histograms, against the definition in every integer and the bits of the score."""
+    from csl_gan_amd import classify
+    rng = np.random.default_rng(n_live)
+    N = n_live + 12
+    X = (rng.integers(0, 256, (N, 6)) // 16 * 16).astype(np.uint8)
+    y = rng.integers(0, 2, N)
+    W = rng.integers(1, W1 + 1, (2, N))
+    W[:, rng.choice(N, 12, replace=False)] = 0
+    assert ((W > 0).sum(1) == n_live).all()
+    out, score = classify.boost_stump_host_bytes(X, y, W, 2)
+    for k in range(2):
+        want, sbits = brute_stump(X, y == k, W[k])
+        assert tuple(int(a) for a in out[k]) == want and int(score[k]) == sbits, k
+
+
 def test_hand_made_cases():
     y = np.array([0, 0, 1, 1])
     col = lambda *b: np.array(b, dtype=np.uint8)[:, None]

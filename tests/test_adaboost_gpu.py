@@ -56,6 +56,24 @@ def test_stump_search_equals_the_host_model(N, D, K):
     assert go[K - 1].tolist() == [-1, -1, -1, 0, 0, 0, 0] and gs[K - 1] == 0
 
 
+@pytest.mark.parametrize("N,D,K", [(17, 5, 3), (300, 1040, 2)])
+def test_the_stump_search_and_the_tree_search_are_one(N, D, K):
+    """Every weight 1 against the root of every class (all rows, unit weights, no mask) in cslgan_tree_best_split_u8: the two kernels
+    share one frame and one score routine, so all seven integers and the score bits agree.  (17, 5, 3): the partial tile of D < 16;
+    (300, 1040, 2): the aligned loader and 65 tiles, so the reduction's loop over the tiles wraps."""
+    from csl_gan_amd import ops
+    rng = np.random.default_rng(N + D)
+    X = rng.integers(0, 256, (N, D)).astype(np.uint8)
+    X[:, ::2] = X[:, ::2] // 32 * 32
+    y = rng.integers(0, K, N)
+    Xd, yd = _dev(X, np.uint8), _dev(y)
+    bo, bs = ops.boost_stump_u8(Xd, yd, K, _dev(np.ones((K, N))))
+    to, ts = ops.tree_best_split_u8(Xd, yd, K, _dev(np.tile(np.arange(N), K)), _dev(np.arange(K + 1) * N), _dev(np.arange(K)))
+    assert to.dtype == torch.int32 and bo.dtype == torch.int64 and (bo[:, 0] >= 0).all()
+    assert np.array_equal(to.cpu().numpy().astype(np.int64), bo.cpu().numpy()), (to.tolist(), bo.tolist())
+    assert np.array_equal(ts.cpu().numpy(), bs.cpu().numpy())
+
+
 def test_counters_take_two_to_the_52():
     """70 000 rows of weight 2^28 and 8 bytes, every byte of the positive class 255: one bin holds about 2^44, and pL pL exceeds 2^64."""
     rng = np.random.default_rng(2)

@@ -104,6 +104,34 @@ def test_weights_equal_repeated_rows_and_zero_weight_rows_are_absent():
         split1(X, np.array([0, 1, 1, 1]), w=[2 ** 30, 2 ** 30, 1, 1])
 
 
+@pytest.mark.parametrize("n_live", [64, 65])
+def test_host_search_agrees_on_both_sides_of_its_switch(n_live):
+    """64 rows are the last that the host search sorts, 65 the first that go into 256-bin histograms.  On both sides, with unit weights
+    and with weights 1 .. 4 on n_live rows among 10 rows of weight 0, best_split_host_bytes is the maximum of brute_scores (the
+    definition on the repeated rows) with ties to the smallest (j, v): every integer and the bits of the score."""
+    rng = np.random.default_rng(n_live)
+    for weighted in (False, True):
+        N = n_live + (10 if weighted else 0)
+        X = (rng.integers(0, 256, (N, 7)) // 16 * 16).astype(np.uint8)
+        X[:, 3] = X[:, 2]                                                            # a duplicate column: the smaller j
+        y = rng.integers(0, 2, N)
+        w = np.ones(N, dtype=np.int64)
+        if weighted:
+            w = rng.integers(1, 5, N)
+            w[rng.choice(N, 10, replace=False)] = 0
+        assert int((w > 0).sum()) == n_live
+        rep = np.repeat(np.arange(N), w)
+        Xr, yr = X[rep], y[rep]
+        sc = brute_scores(Xr, yr)
+        top = max(sc.values())
+        j, v = min(k for k, s in sc.items() if s == top)
+        left = Xr[:, j] <= v
+        want = (j, v, int(Xr[~left, j].min()), int(left.sum()), int(yr[left].sum()), len(yr), int(yr.sum()))
+        got, s = split1(X, y, w=w if weighted else None)
+        assert got == want and j != 3, (weighted, got, want)
+        assert np.float64(s).view(np.int64) == np.float64(top).view(np.int64), (weighted, s, top)
+
+
 def test_labels_outside_the_classes_are_negative_for_every_class():
     rng = np.random.default_rng(4)
     X = rng.integers(0, 256, (60, 7)).astype(np.uint8)

@@ -220,6 +220,28 @@ def test_cli_refusals(caches, tmp_path):
         tstr.main(["--syn_cache", syn, "--test_cache", test, "--baseline", "--train_cache", os.path.join(d, "uncond")])
 
 
+_SCORES = {"n_train", "n_test", "classes", "auroc_micro", "auroc_per_class", "accuracy", "accuracy_hits"}
+STATS_KEYS = {"lr": _SCORES | {"solver"},
+              "mlp": _SCORES | {"solver", "classifier", "hidden", "alpha", "seed"},
+              "gnb": _SCORES | {"classifier", "fit", "var_smoothing"},
+              "bnb": _SCORES | {"classifier", "fit", "alpha", "binarize"},
+              "dt": _SCORES | {"classifier", "fit", "max_depth", "min_samples_split"},
+              "rf": _SCORES | {"classifier", "fit", "max_depth", "min_samples_split", "n_trees", "max_features", "seed"},
+              "ab": _SCORES | {"classifier", "fit", "n_rounds", "learning_rate"}}
+
+
+def test_every_classifier_runs_through_the_table(caches):
+    """The parser offers the table's keys, and every choice runs end to end and reports exactly the keys written down above."""
+    from csl_gan_amd import tstr
+    choices = [act.choices for act in tstr.build_parser()._actions if act.dest == "classifier"][0]
+    assert list(choices) == list(tstr.ESTIMATORS) == list(STATS_KEYS)
+    for k, keys in STATS_KEYS.items():
+        res = tstr.main(["--syn_cache", caches["syn"][0], "--test_cache", caches["test"][0], "-d", "cpu", "--classifier", k, "--max_iter", "3",
+                         "--hidden", "4", "--n_trees", "2", "--n_rounds", "3"])
+        assert list(res) == ["syn"] and set(res["syn"]) == keys, k
+        assert res["syn"].get("classifier", "lr") == k
+
+
 # ---- the C-ABI entries validate on the host -----------------------------------------------------------------------------------------
 
 def test_abi_entries_reject_bad_arguments_without_a_device():
