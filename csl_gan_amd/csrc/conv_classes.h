@@ -1,9 +1,25 @@
-// Host-side geometry shared by the conv entry points: how a cslgan_conv_t becomes tap tables and tap classes (igemm.h: KcClass).
+// Host-side geometry shared by the conv entry points: their argument check and how a cslgan_conv_t becomes tap tables and tap classes
+// (igemm.h: KcClass).
 // Plain functions over the existing structs; nothing here runs on the device.
 #pragma once
+#include "common.h"
 #include "igemm.h"
 
 namespace cslgan {
+
+// Argument check of every conv entry; `who` prefixes the messages.  check_compute: cslgan_conv_t.compute must name a compute mode
+// (the bf16-stored entries never read it and accept any value).
+inline int check_conv(const cslgan_conv_t* c, const char* who, bool check_compute) {
+    CSLGAN_REQUIRE(c->N > 0 && c->H > 0 && c->W > 0 && c->C > 0 && c->K > 0 && c->R > 0 && c->S > 0 && c->stride > 0 && c->pad >= 0,
+                   "%s: non-positive dimension", who);
+    CSLGAN_REQUIRE(c->R * c->S <= IG_MAX_TAPS, "%s: %dx%d filter has more than %d taps", who, c->R, c->S, IG_MAX_TAPS);
+    CSLGAN_REQUIRE(!check_compute || (c->compute >= CSLGAN_COMPUTE_F32 && c->compute <= CSLGAN_COMPUTE_BF16X3), "%s: unknown cslgan_conv_t.compute %d", who, c->compute);
+    const int P = (c->H + 2 * c->pad - c->R) / c->stride + 1, Q = (c->W + 2 * c->pad - c->S) / c->stride + 1;
+    CSLGAN_REQUIRE(P == c->P && Q == c->Q, "%s: output %dx%d does not match P,Q=%d,%d", who, P, Q, c->P, c->Q);
+    CSLGAN_REQUIRE((long long)c->N * c->P * c->Q * c->K < (1ll << 31) && (long long)c->N * c->H * c->W * c->C < (1ll << 31) &&
+                   (long long)c->K * c->R * c->S * c->C < (1ll << 31), "%s: tensor too large for 32-bit offsets", who);
+    return CSLGAN_OK;
+}
 
 // Tap table of a forward conv (and of a weight gradient, which walks the same window): tap t = kh*S + kw reads the input
 // at offset (kh - pad, kw - pad).  Writes R*S entries; the tables sit in zero-initialised parameter structs.
@@ -46,6 +62,29 @@ inline int build_dgrad_classes(const cslgan_conv_t* c, KcClass* cls, ClassTaps& 
             ++n;
         }
     return n;
+}
+
+// Split-K factor of a weight-gradient launch (McParams, or the bf16-stored MsParams of igemm_mcs.hip; tiles_m / tiles_n set): few
+// workgroups with a long pixel loop (the 3-channel first layer: one 64x75 tile per sample, 1024+ pixels) split the pixels over
+// workgroups that atomically add into the fp32 output, which is zeroed here.  bk: pixels per K tile; only from min_nk K tiles on, and
+// at least tiles_per_split of them per workgroup.
+template <typename P>
+inline int wgrad_plan_split(P& p, int bk, int min_nk, int tiles_per_split, hipStream_t st) {
+    const long long base = (long long)p.n_groups * p.tiles_m * p.tiles_n;
+    const int nk_all = (p.group * p.P * p.Q + bk - 1) / bk;
+    p.ksplit = 1;
+    if (!p.gw || p.out_bf16 || base >= 192 || nk_all < min_nk) return CSLGAN_OK;
+    const long long want = (512 + base - 1) / base, cap = nk_all / tiles_per_split;
+    p.ksplit = (int)(want < cap ? want : cap);
+    if (p.ksplit <= 1) { p.ksplit = 1; return CSLGAN_OK; }
+    return zero_floats((float*)p.gw, (size_t)p.n_groups * p.Kc * p.Ndim, st);
+}
+
+// After a split launch the per-group norms need the completed sums: one pass of the contract norm kernel over the (small) result.
+template <typename P>
+inline int wgrad_split_norms(const P& p, hipStream_t st) {
+    if (p.ksplit <= 1 || !p.sq) return CSLGAN_OK;
+    return sqnorm_rows_accumulate((const float*)p.gw, p.n_groups, (long long)p.Kc * p.Ndim, p.sq, st);
 }
 
 // Range of a class's tap offsets: the halo of a patch is its side plus (max - min) in each direction.

@@ -155,10 +155,16 @@ bool linear_k1_shape(const cslgan_conv_t* c);
 int launch_linear_k1_fwd(const cslgan_conv_t* c, const float* x, const float* w, const float* bias, const float* residual, int act,
                          float* y, hipStream_t st);
 int launch_linear_k1_dgrad(const cslgan_conv_t* c, const float* gy, const float* w, const float* mask, float* gx, hipStream_t st);
+int launch_linear_k1s_fwd(const cslgan_conv_t* c, const void* x, const float* w, const float* bias, int act, float* y, hipStream_t st);      // x bf16
 
 // conv1x1.hip: 1x1 convs with 32 / 64 / 128 input channels as a stream over 128-row tiles
 bool conv1x1_eligible(const cslgan_conv_t* c, const float* x, const float* w, const float* residual);
 int launch_conv1x1(const cslgan_conv_t* c, const float* x, const float* w, const float* bias, int act, float* y, hipStream_t st);
+// ... and on bf16-stored x with 16 / 32 / 64 input channels (wb: the filter rounded to bf16) as a stream over 32-pixel wavefront tiles
+bool conv1x1s_eligible(const cslgan_conv_t* c, const void* residual);
+int launch_conv1x1s(const cslgan_conv_t* c, const void* x, const void* wb, const float* bias, int act, void* y, int y_bf16, hipStream_t st);
+// cast_kernels.hip: out[0..n) = bf16(w[0..n)), the filter copy of the bf16-stored convs (w 16-byte, out 8-byte aligned)
+int round_bf16(const float* w, void* out, long long n, hipStream_t st);
 
 // igemm_kc.hip routes a K-contiguous launch to one of these (each: eligibility test, then the launch)
 bool skinny_eligible(const KcParams& p);        // igemm_skinny.hip: 1..4 output channels on the vector ALU

@@ -26,6 +26,7 @@
 #include "common.h"
 #include "igemm.h"
 #include "kc_frame.h"
+#include "conv_classes.h"
 
 namespace cslgan {
 
@@ -499,19 +500,7 @@ __global__ __launch_bounds__(256, 2) void igemm_mc_bf16_kernel(const McParams p)
 int launch_mc_bf16(McParams& p, bool vecA, bool vecB, hipStream_t st, int nsplit) {
     p.tiles_m = (p.Kc + 127) / 128;
     p.tiles_n = (p.Ndim + 127) / 128;
-    p.ksplit = 1;
-    {
-        const long long base = (long long)p.n_groups * p.tiles_m * p.tiles_n;
-        const int nk_all = (p.group * p.P * p.Q + MCB_BK - 1) / MCB_BK;
-        if (p.gw && !p.out_bf16 && base < 192 && nk_all >= 16) {
-            const long long want = (512 + base - 1) / base, cap = nk_all / 4;
-            p.ksplit = (int)(want < cap ? want : cap);
-            if (p.ksplit < 1) p.ksplit = 1;
-        }
-    }
-    if (p.ksplit > 1) {
-        if (int rc = zero_floats(p.gw, (size_t)p.n_groups * p.Kc * p.Ndim, st)) return rc;
-    }
+    if (int rc = wgrad_plan_split(p, MCB_BK, 16, 4, st)) return rc;
     const long long nb = (long long)p.n_groups * p.tiles_m * p.tiles_n * p.ksplit;
     if (nb > 0x7fffffffll) { set_error("wgrad_bf16: grid too large"); return CSLGAN_ERR_INVALID_ARG; }
     const dim3 grid((unsigned)nb), block(256);
@@ -528,10 +517,8 @@ int launch_mc_bf16(McParams& p, bool vecA, bool vecB, hipStream_t st, int nsplit
         else if (vecB) hipLaunchKernelGGL((igemm_mc_bf16_kernel<128, 128, 2, 2, false, true, 1>), grid, block, 0, st, p);
         else hipLaunchKernelGGL((igemm_mc_bf16_kernel<128, 128, 2, 2, false, false, 1>), grid, block, 0, st, p);
     }
-    int rc = check_launch("igemm_mc_bf16_kernel");
-    if (rc) return rc;
-    if (p.ksplit > 1 && p.sq) rc = sqnorm_rows_accumulate(p.gw, p.n_groups, (long long)p.Kc * p.Ndim, p.sq, st);
-    return rc;
+    if (int rc = check_launch("igemm_mc_bf16_kernel")) return rc;
+    return wgrad_split_norms(p, st);
 }
 
 }  // namespace cslgan

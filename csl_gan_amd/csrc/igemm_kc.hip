@@ -292,30 +292,7 @@ int launch_kc(KcParams& p, hipStream_t st, long long out_elems) {
     long long rows = 0;
     for (int c = 0; c < p.n_cls; ++c) rows += p.cls[c].M;
     if (rows <= 0 || p.Nn <= 0) return CSLGAN_OK;
-    {
-        const long long n_img = p.cls[0].M / ((long long)p.cls[0].OHc * p.cls[0].OWc);
-        const long long a_b = (p.a_bf16 ? 2ll : 4ll) * n_img * p.AH * p.AW * p.AC;
-        long long w_end = 0;
-        for (int c = 0; c < p.n_cls; ++c) {
-            const long long e = (long long)p.cls[c].w_off + (long long)p.Nn * p.cls[c].Kdim;
-            w_end = e > w_end ? e : w_end;
-        }
-        if (a_b >= (long long)BUF_OOB || 4 * w_end >= (long long)BUF_OOB) {
-            set_error("igemm_kc: operand larger than 4 GB");
-            return CSLGAN_ERR_INVALID_ARG;
-        }
-        p.a_bytes = (unsigned)a_b;
-        p.w_bytes = (unsigned)(4 * w_end);
-        // k / AC as umulhi(k, ceil(2^32 / AC)): exact while k < 2^32 / AC
-        long long kmax = 0;
-        for (int c = 0; c < p.n_cls; ++c) kmax = p.cls[c].Kdim > kmax ? p.cls[c].Kdim : kmax;
-        if (p.AC < 2 || (kmax + IG_BK) * (long long)p.AC >= (1ll << 32)) {
-            if (p.AC == 1 && kmax + IG_BK < (1ll << 31)) p.ac_recip = 0xFFFFFFFFu;   // handled exactly below
-            else { set_error("igemm_kc: K too large for reciprocal division"); return CSLGAN_ERR_INVALID_ARG; }
-        } else {
-            p.ac_recip = (unsigned)(((1ull << 32) + (unsigned long long)p.AC - 1) / (unsigned long long)p.AC);
-        }
-    }
+    if (int rc = kc_operand_ranges(p, p.a_bf16 ? 2 : 4, 4, IG_BK, "igemm_kc", true)) return rc;      // (AC == 1: the kernels take k itself)
     // 1..4 output channels: vector-ALU kernel, fp32 in every compute mode (a 32-wide MFMA tile would be 29/32 padding)
     if (!p.acc_classes && skinny_eligible(p)) {
         if (p.gn_part) { set_error("conv2d_fwd: gn_part is not produced by the 1..4-output-channel kernel"); return CSLGAN_ERR_INVALID_ARG; }
@@ -343,19 +320,6 @@ int launch_kc(KcParams& p, hipStream_t st, long long out_elems) {
     if (kc_tiles_for(p, 128, 128) >= KC_T128) return launch_kc_tile<128, 128, 2, 2>(p, vecA, vecB, st, out_elems);
     if (kc_tiles_for(p, 64, 128) >= t64) return launch_kc_tile<64, 128, 1, 4>(p, vecA, vecB, st, out_elems);
     return launch_kc_tile<64, 64, 2, 2>(p, vecA, vecB, st, out_elems);
-}
-
-static int check_conv(const cslgan_conv_t* c, const char* who) {
-    CSLGAN_REQUIRE(c->N > 0 && c->H > 0 && c->W > 0 && c->C > 0 && c->K > 0 && c->R > 0 && c->S > 0 && c->stride > 0 && c->pad >= 0,
-                   "%s: non-positive dimension", who);
-    CSLGAN_REQUIRE(c->R * c->S <= IG_MAX_TAPS, "%s: %dx%d filter has more than %d taps", who, c->R, c->S, IG_MAX_TAPS);
-    CSLGAN_REQUIRE(c->compute >= CSLGAN_COMPUTE_F32 && c->compute <= CSLGAN_COMPUTE_BF16X3, "%s: unknown cslgan_conv_t.compute %d", who, c->compute);
-    const int VH = c->H, VW = c->W;
-    const int P = (VH + 2 * c->pad - c->R) / c->stride + 1, Q = (VW + 2 * c->pad - c->S) / c->stride + 1;
-    CSLGAN_REQUIRE(P == c->P && Q == c->Q, "%s: output %dx%d does not match P,Q=%d,%d", who, P, Q, c->P, c->Q);
-    CSLGAN_REQUIRE((long long)c->N * c->P * c->Q * c->K < (1ll << 31) && (long long)c->N * VH * VW * c->C < (1ll << 31) &&
-                   (long long)c->K * c->R * c->S * c->C < (1ll << 31), "%s: tensor too large for 32-bit offsets", who);
-    return CSLGAN_OK;
 }
 
 }  // namespace cslgan
@@ -399,7 +363,7 @@ int cslgan_conv2d_fwd_x3_f32(const cslgan_conv_t* c, const float* x, const float
 static int conv2d_fwd_impl(const cslgan_conv_t* c, const float* x, const float* w, const void* w3, const float* bias,
                            const float* residual, int act, float* y, void* stream, int x_bf16) {
     CSLGAN_REQUIRE(c && x && w && y, "conv2d_fwd: null argument");
-    int rc = check_conv(c, "conv2d_fwd");
+    int rc = check_conv(c, "conv2d_fwd", true);
     if (rc) return rc;
     CSLGAN_REQUIRE(act >= 0 && act <= 3, "conv2d_fwd: unknown activation %d", act);
     if (c->in_scale) {      // the input affine map is applied by the halo kernel's and the 1..4-output kernel's staging only
@@ -463,7 +427,7 @@ int cslgan_conv2d_s2_fwd_x3_f32(const cslgan_conv_t* c, const float* x, const fl
 static int conv2d_s2_fwd_impl(const cslgan_conv_t* c, const float* x, const float* w, float* wcls_ws, void* w3_ws, int repack,
                               const float* bias, int act, float* y, void* stream) {
     CSLGAN_REQUIRE(c && x && w && wcls_ws && y, "conv2d_s2_fwd: null argument");
-    int rc = check_conv(c, "conv2d_s2_fwd");
+    int rc = check_conv(c, "conv2d_s2_fwd", true);
     if (rc) return rc;
     CSLGAN_REQUIRE(c->stride == 2 && c->R == c->S, "conv2d_s2_fwd: needs stride 2 and a square filter");
     CSLGAN_REQUIRE(act >= 0 && act <= 3, "conv2d_s2_fwd: unknown activation %d", act);
@@ -558,7 +522,7 @@ int cslgan_conv2d_dgrad_skinny_bf16in(const cslgan_conv_t* c, const void* gy_bf1
 static int conv2d_dgrad_impl(const cslgan_conv_t* c, const float* gy, const float* w, float* wt_ws, int repack,
                              const float* mask, float* gx, void* stream, int gy_bf16, void* w3_ws) {
     CSLGAN_REQUIRE(c && gy && w && wt_ws && gx, "conv2d_dgrad: null argument");
-    int rc = check_conv(c, "conv2d_dgrad");
+    int rc = check_conv(c, "conv2d_dgrad", true);
     if (rc) return rc;
     CSLGAN_REQUIRE(c->stride >= 1 && c->stride <= 2, "conv2d_dgrad: stride %d unsupported", c->stride);
     if (!gy_bf16 && linear_k1_shape(c) && aligned16(w) && aligned16(gx) && (!mask || aligned16(mask)))      // gx[n,:] = gy[n] * w: no repack needed

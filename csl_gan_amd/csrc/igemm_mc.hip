@@ -286,26 +286,59 @@ __global__ __launch_bounds__(256) void bias_grad_grouped_vec_kernel(const float*
     }
 }
 
+// gb[g][k] = alpha * sum over the group's pixels of gy[., k] (bf16 gy, fp32 sums); K % 8 == 0, K <= 2048, 256 % (K/8) == 0
+__global__ __launch_bounds__(256) void bias_grad_bf16_kernel(const unsigned short* __restrict__ gy, int PQ, int K, int group, float alpha,
+                                                             float* __restrict__ gb, float* __restrict__ sq) {
+    extern __shared__ float s_part[];            // [K]
+    __shared__ float red[4];
+    const int tid = threadIdx.x;
+    const int c8n = K >> 3, c8 = tid % c8n, sl = tid / c8n, nsl = 256 / c8n;
+    const int g = blockIdx.x;
+    const long long npix = (long long)group * PQ;
+    const unsigned short* base = gy + (long long)g * npix * K + 8 * c8;
+    for (int i = tid; i < K; i += 256) s_part[i] = 0.f;
+    __syncthreads();
+    float acc[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) acc[q] = 0.f;
+    long long px = sl;
+    for (; px + 3 * nsl < npix; px += 4 * nsl) {
+        uint4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const uint4*>(base + (px + u * nsl) * K);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const unsigned d[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { acc[2 * q] += bf_lo(d[q]); acc[2 * q + 1] += bf_hi(d[q]); }
+        }
+    }
+    for (; px < npix; px += nsl) {
+        const uint4 v = *reinterpret_cast<const uint4*>(base + px * K);
+        const unsigned d[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { acc[2 * q] += bf_lo(d[q]); acc[2 * q + 1] += bf_hi(d[q]); }
+    }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) atomicAdd(&s_part[8 * c8 + q], acc[q]);
+    __syncthreads();
+    float ss = 0.f;
+    for (int k = tid; k < K; k += 256) {
+        const float v = alpha * s_part[k];
+        if (gb) gb[(long long)g * K + k] = v;
+        ss = fmaf(v, v, ss);
+    }
+    if (sq) {
+        const float tot = block_sum_256(ss, red);
+        if (tid == 0) atomicAdd(sq + g, tot);
+    }
+}
+
 template <int BM, int BN, int WM, int WN>
 static int launch_mc_tile(McParams& p, bool vecA, bool vecB, hipStream_t st) {
     p.tiles_m = (p.Kc + BM - 1) / BM;
     p.tiles_n = (p.Ndim + BN - 1) / BN;
-    // few workgroups with a long pixel loop (the 3-channel first layer: one 64x75 tile per sample, 1024+ pixels):
-    // split the pixels over workgroups that atomically add into the zeroed fp32 output
-    p.ksplit = 1;
-    {
-        const long long base = (long long)p.n_groups * p.tiles_m * p.tiles_n;
-        const int nk_all = (p.group * p.P * p.Q + MC_BK - 1) / MC_BK;
-        if (p.gw && !p.out_bf16 && base < 192 && nk_all >= 32) {
-            long long want = (512 + base - 1) / base;
-            const long long cap = nk_all / 8;
-            p.ksplit = (int)(want < cap ? want : cap);
-            if (p.ksplit < 1) p.ksplit = 1;
-        }
-    }
-    if (p.ksplit > 1) {
-        if (int rc = zero_floats(p.gw, (size_t)p.n_groups * p.Kc * p.Ndim, st)) return rc;
-    }
+    if (int rc = wgrad_plan_split(p, MC_BK, 32, 8, st)) return rc;
     const long long nb = (long long)p.n_groups * p.tiles_m * p.tiles_n * p.ksplit;
     if (nb > 0x7fffffffll) { set_error("wgrad: grid too large"); return CSLGAN_ERR_INVALID_ARG; }
     const dim3 grid((unsigned)nb), block(256);
@@ -314,13 +347,8 @@ static int launch_mc_tile(McParams& p, bool vecA, bool vecB, hipStream_t st) {
     else if (vecA) hipLaunchKernelGGL((igemm_mc_kernel<BM, BN, WM, WN, true, false>), grid, block, 0, st, p);
     else if (vecB) hipLaunchKernelGGL((igemm_mc_kernel<BM, BN, WM, WN, false, true>), grid, block, 0, st, p);
     else hipLaunchKernelGGL((igemm_mc_kernel<BM, BN, WM, WN, false, false>), grid, block, 0, st, p);
-    int rc = check_launch("igemm_mc_kernel");
-    if (rc) return rc;
-    if (p.ksplit > 1 && p.sq) {
-        // the per-group norm needs the completed sums: one pass of the contract norm kernel over the (small) result
-        rc = sqnorm_rows_accumulate(p.gw, p.n_groups, (long long)p.Kc * p.Ndim, p.sq, st);
-    }
-    return rc;
+    if (int rc = check_launch("igemm_mc_kernel")) return rc;
+    return wgrad_split_norms(p, st);
 }
 
 }  // namespace cslgan
@@ -403,6 +431,15 @@ int cslgan_bias_grad_grouped_f32(const float* gy, int N, int PQ, int K, int grou
     hipLaunchKernelGGL(bias_grad_grouped_kernel, dim3((unsigned)((K + 63) / 64), (unsigned)(N / group)), dim3(256), 0,
                        (hipStream_t)stream, gy, PQ, K, group, alpha, gb, sq);
     return check_launch("bias_grad_grouped_kernel");
+}
+
+int cslgan_bias_grad_grouped_bf16(const void* gy, int N, int PQ, int K, int group, float alpha, float* gb, float* sq, void* stream) {
+    CSLGAN_REQUIRE(gy && (gb || sq), "bias_grad_bf16: null argument");
+    CSLGAN_REQUIRE(N > 0 && PQ > 0 && K > 0 && group >= 1 && N % group == 0, "bias_grad_bf16: bad sizes");
+    CSLGAN_REQUIRE(K % 8 == 0 && K <= 2048 && 256 % (K / 8) == 0 && aligned16(gy), "bias_grad_bf16: K must be a multiple of 8 with 256 %% (K/8) == 0");
+    hipLaunchKernelGGL(bias_grad_bf16_kernel, dim3((unsigned)(N / group)), dim3(256), sizeof(float) * K, (hipStream_t)stream,
+                       reinterpret_cast<const unsigned short*>(gy), PQ, K, group, alpha, gb, sq);
+    return check_launch("bias_grad_bf16_kernel");
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // The frame shared by the K-contiguous implicit-GEMM kernels: where a gather workgroup sits (igemm_kc_kernel,
 // igemm_kc_bf16_kernel), the row-offset staging (those two and igemm_halo_kernel), the accumulator store (igemm_kc_kernel,
-// igemm_halo_kernel), plus the host-side tile planning of the two gather kernels.  The kernels keep their own loaders, LDS layouts and inner products.
+// igemm_halo_kernel), plus the host-side operand ranges and tile planning of the gather kernels (the bf16-stored launchers of
+// igemm_bf16s.hip included).  The kernels keep their own loaders, LDS layouts and inner products.
 #pragma once
 #include "common.h"
 #include "device_prims.h"
@@ -125,9 +126,32 @@ inline long long kc_tiles_for(const KcParams& p, int BM, int BN) {
     return tm * ((p.Nn + BN - 1) / BN);
 }
 
-// Tile grid of a gather launch: tile0 per class, tiles_m / tiles_n and the split-K factor; zeroes the output when K is split.
-// out_elems: floats of the output tensor, or 0 to forbid splitting.  The grid is tiles_m * tiles_n * ksplit workgroups.
-inline int kc_plan_tiles(KcParams& p, int BM, int BN, long long out_elems, hipStream_t st) {
+// (Templates on the parameter struct: KcParams or the bf16-stored KsParams of igemm_bf16s.hip, which share these fields.)
+// Byte ranges of both operands for the buffer descriptors and the reciprocal the loaders divide k by: k / AC as umulhi(k, ceil(2^32 / AC)),
+// exact while k < 2^32 / AC.  a_es / w_es: bytes per element of a / the filter matrices; bk: the kernel's K tile (k runs up to Kdim + bk);
+// who prefixes the messages; ac1_exact: the caller's loaders take k itself when AC == 1, where no reciprocal fits 32 bits.
+template <typename P>
+inline int kc_operand_ranges(P& p, int a_es, int w_es, int bk, const char* who, bool ac1_exact = false) {
+    const long long n_img = p.cls[0].M / ((long long)p.cls[0].OHc * p.cls[0].OWc);
+    const long long a_b = (long long)a_es * n_img * p.AH * p.AW * p.AC;
+    long long w_end = 0, kmax = 0;
+    for (int c = 0; c < p.n_cls; ++c) {
+        const long long e = (long long)p.cls[c].w_off + (long long)p.Nn * p.cls[c].Kdim;
+        w_end = e > w_end ? e : w_end;
+        kmax = p.cls[c].Kdim > kmax ? p.cls[c].Kdim : kmax;
+    }
+    CSLGAN_REQUIRE(a_b < (long long)BUF_OOB && w_es * w_end < (long long)BUF_OOB, "%s: operand larger than 4 GB", who);
+    p.a_bytes = (unsigned)a_b;
+    p.w_bytes = (unsigned)(w_es * w_end);
+    if (ac1_exact && p.AC == 1 && kmax + bk < (1ll << 31)) { p.ac_recip = 0xFFFFFFFFu; return CSLGAN_OK; }
+    CSLGAN_REQUIRE(p.AC >= 2 && (kmax + bk) * (long long)p.AC < (1ll << 32), "%s: K too large for reciprocal division", who);
+    p.ac_recip = (unsigned)(((1ull << 32) + (unsigned long long)p.AC - 1) / (unsigned long long)p.AC);
+    return CSLGAN_OK;
+}
+
+// Tile grid of a K-contiguous launch: tile0 per class, tiles_m and tiles_n.  Returns the number of tiles.
+template <typename P>
+inline long long kc_assign_tiles(P& p, int BM, int BN) {
     int tm = 0;
     for (int c = 0; c < p.n_cls; ++c) {
         p.cls[c].tile0 = tm;
@@ -135,7 +159,13 @@ inline int kc_plan_tiles(KcParams& p, int BM, int BN, long long out_elems, hipSt
     }
     p.tiles_m = tm;
     p.tiles_n = (p.Nn + BN - 1) / BN;
-    const int tiles = p.tiles_m * p.tiles_n;
+    return (long long)p.tiles_m * p.tiles_n;
+}
+
+// kc_assign_tiles and the split-K factor of a gather launch; zeroes the output when K is split.
+// out_elems: floats of the output tensor, or 0 to forbid splitting.  The grid is tiles_m * tiles_n * ksplit workgroups.
+inline int kc_plan_tiles(KcParams& p, int BM, int BN, long long out_elems, hipStream_t st) {
+    const int tiles = (int)kc_assign_tiles(p, BM, BN);
     // split K only for purely linear epilogues and launches that would leave most CUs idle
     p.ksplit = 1;
     int nk_max = 0;
@@ -152,14 +182,17 @@ inline int kc_plan_tiles(KcParams& p, int BM, int BN, long long out_elems, hipSt
     return CSLGAN_OK;
 }
 
-// Gather launches enumerate 8x8 patches where the class grid allows it; vecA / vecB: 16-byte loads of a / the filter are legal.
+// Gather launches enumerate 8x8 patches where the class grid allows it ...
+template <typename P>
+inline void kc_mark_patches(P& p) {
+    for (KcClass* k = p.cls; k < p.cls + p.n_cls; ++k) k->patch = (k->T > 1 && k->OHc % 8 == 0 && k->OWc % 8 == 0) ? 1 : 0;
+}
+
+// ... and vecA / vecB: 16-byte loads of a / the filter are legal.
 inline void kc_mark_patches_and_vec(KcParams& p, bool& vecA, bool& vecB) {
+    kc_mark_patches(p);
     bool kd4 = true;
-    for (int c = 0; c < p.n_cls; ++c) {
-        KcClass& k = p.cls[c];
-        k.patch = (k.T > 1 && k.OHc % 8 == 0 && k.OWc % 8 == 0) ? 1 : 0;
-        kd4 = kd4 && (k.Kdim % 4 == 0) && (k.w_off % 4 == 0);
-    }
+    for (int c = 0; c < p.n_cls; ++c) kd4 = kd4 && (p.cls[c].Kdim % 4 == 0) && (p.cls[c].w_off % 4 == 0);
     vecA = (p.AC % 4 == 0) && aligned16(p.a);
     vecB = kd4 && aligned16(p.w);
 }

@@ -145,7 +145,7 @@ _storage_bf16 = False
 
 def set_storage_dtype(name):
     """Element type of the ACTIVATIONS and ACTIVATION GRADIENTS between the critic's conv layers in HBM (BASELINE configs[4],
-    csrc/igemm_bf16s.hip):
+    csrc/igemm_bf16s.hip, csrc/igemm_mcs.hip):
       "fp32"  the default: every tensor is fp32;
       "bf16"  the critic's conv layers write bfloat16 outputs; every conv / data-gradient / weight-gradient call whose activation
               operands are bfloat16 runs on the bf16-stored kernels (bf16 filter copies cached per parameter version, fp32

@@ -23,7 +23,7 @@ Additions of this build (all optional, none changes a reference default):
                        Gram norms are computed in fp32) is replaced by --materialize private — unless the activations are also STORED as
                        bfloat16 (--storage_dtype bf16), where the Gram norms are the norms of the stored values' gradients
   --storage_dtype T    element type of the critic's activations and activation gradients in HBM: fp32 (default) or bf16 (needs
-                       --compute_dtype bf16: bf16-stored kernels of csrc/igemm_bf16s.hip, bf16 filter copies, fp32 accumulation,
+                       --compute_dtype bf16: bf16-stored kernels of csrc/igemm_bf16s.hip and igemm_mcs.hip, bf16 filter copies, fp32 accumulation,
                        fp32 weight gradients / norms / clip / noise / Adam; BASELINE.json configs[4])
   --hip_graph B        (default True) record the DP D-step (dp_mode=gc, full batches, one process) once in a HIP graph and replay it
                        (trainer.GraphedDStep): no per-launch host work, and the step's second stream (gradient-penalty branch)

@@ -129,6 +129,14 @@ CASES = {
     "kcs_dgrad_s2": _dgrad(4, 32, 32, 64, 64, 5, stride=2, bf16s=True),
     "kcs_dgrad_s1": _dgrad(4, 16, 16, 64, 64, 3, bf16s=True),
     "mcs_wgrad": _wgrad(8, 8, 8, 64, 64, 3, bf16s=True),
+    # ---- bf16-stored gather kernel above 64 filters: 128x128 tiles from 256 row blocks x column tiles on (48 channels: not the 1x1 stream) --
+    "kcs_t128_at": _fwd(256, 8, 16, 48, 128, 1, bf16s=True),             # 32768 rows = 256 row blocks of 128, one column tile
+    "kcs_t128_below": _fwd(255, 8, 16, 48, 128, 1, bf16s=True),
+    # ---- the critic's head on bf16 features (fp32 loss cotangent) and the clip-weighted weight gradient ------------------------------
+    "linear_k1s_fwd": _fwd(8, 1, 1, 256, 1, 1, bf16s=True),
+    "linear_k1s_dgrad": _dgrad(8, 1, 1, 256, 1, 1, bf16s=True, gy_f32=True),
+    "linear_k1s_wgrad": _wgrad(8, 1, 1, 256, 1, 1, group=2, bf16s=True, gy_f32=True),
+    "mcs_wgrad_scaled": _wgrad(8, 8, 8, 64, 64, 3, group=2, bf16s=True, row_scale=True),     # 8x8 output: a 64-pixel K tile per sample
 }
 
 
@@ -137,7 +145,9 @@ def run_case(case, seed=0, epilogue=False, act=None):
 
     epilogue: forward cases also pass a random bias and the activation `act` (main() passes 1 + case index % 3, so the three
     activations alternate over the cases; default 1 + seed % 3); data-gradient cases pass a random mask.  No residual: it changes routes (and an
-    activation keeps K from being split, so those launches hash reproducibly)."""
+    activation keeps K from being split, so those launches hash reproducibly).
+    Optional case keys: gy_f32 (the output gradient stays fp32 in a bf16s case: the head's loss cotangent; a data gradient then asks
+    for a bf16 result), row_scale (a weight gradient gets random [N] fp32 per-sample weights)."""
     import torch
     from csl_gan_amd import _lib, ops
 
@@ -146,6 +156,9 @@ def run_case(case, seed=0, epilogue=False, act=None):
     def rnd(*shape):
         t = torch.randn(*shape, generator=g).cuda()
         return ops.cast_bf16(t) if case["bf16s"] else t
+
+    def rnd_gy(*shape):
+        return torch.randn(*shape, generator=g).cuda() if case.get("gy_f32") else rnd(*shape)
 
     op = case["op"]
     N, H, W, Cc = case["N"], case["H"], case["W"], case["C"]
@@ -160,9 +173,12 @@ def run_case(case, seed=0, epilogue=False, act=None):
                 out = ops.conv2d_fwd(rnd(N, H, W, Cc), w, stride=stride, pad=pad, **extra)
             elif op == "dgrad":
                 extra = dict(mask=rnd(N, H, W, Cc)) if epilogue else {}
-                out = ops.conv2d_dgrad(rnd(N, P, Q, K), w, (H, W), stride=stride, pad=pad, **extra)
+                if case.get("gy_f32"):
+                    extra["out_dtype"] = torch.bfloat16
+                out = ops.conv2d_dgrad(rnd_gy(N, P, Q, K), w, (H, W), stride=stride, pad=pad, **extra)
             elif op == "wgrad":
-                out = ops.conv2d_wgrad_grouped(rnd(N, P, Q, K), rnd(N, H, W, Cc), R, R, stride=stride, pad=pad, group=case["group"])
+                extra = dict(row_scale=torch.rand(N, generator=g).cuda()) if case.get("row_scale") else {}
+                out = ops.conv2d_wgrad_grouped(rnd_gy(N, P, Q, K), rnd(N, H, W, Cc), R, R, stride=stride, pad=pad, group=case["group"], **extra)
             elif op == "gram":
                 out = ops.conv2d_wgrad_sqnorm_gram(rnd(N, P, Q, K), rnd(N, H, W, Cc), R, R, stride=stride, pad=pad)
             else:

@@ -69,7 +69,7 @@ def test_invalid_arguments_fail_loudly_without_gpu(built_lib):
 
 
 def test_bf16_storage_entries_validate_their_arguments(built_lib):
-    """csrc/igemm_bf16s.hip and the bf16 forms of the first-layer / vector-ALU / normalisation kernels (round 3): shapes they do not
+    """csrc/igemm_bf16s.hip, csrc/igemm_mcs.hip and the bf16 forms of the first-layer / vector-ALU / normalisation kernels (round 3): shapes they do not
     take are refused on the host, before any launch."""
     from csl_gan_amd import _lib
     L = _lib.lib()

@@ -1,4 +1,4 @@
-"""bf16 STORAGE path (-m gpu; csrc/igemm_bf16s.hip, `--storage_dtype bf16`, BASELINE.json configs[4]).
+"""bf16 STORAGE path (-m gpu; csrc/igemm_bf16s.hip, csrc/igemm_mcs.hip, `--storage_dtype bf16`, BASELINE.json configs[4]).
 
 Kernel level: every bf16-stored entry against plain PyTorch fp32 math on the SAME bf16-rounded operands (the kernels multiply
 bf16 values exactly and accumulate in fp32, so only the summation order differs: 1e-4 of scale for fp32 outputs; a bf16 output

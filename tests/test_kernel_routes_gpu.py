@@ -36,7 +36,7 @@ _PAIRS = [("kc_t128_at", "kc_t128_below"), ("kc_t64_at", "kc_t64_below"), ("kc_t
           ("s2_halo_wide_at", "s2_halo_wide_below"), ("x3_quad_at", "x3_quad_below"), ("x3_quad_bf16_at", "x3_quad_bf16_below"),
           ("x3_quad_dgrad_at", "x3_quad_dgrad_below"), ("halo_quad_at", "halo_quad_below"), ("halo_pair_at", "halo_pair_below"),
           ("x3_wide_at", "x3_wide_below"), ("x3_wide_x3_at", "x3_wide_x3_below"), ("mc_wide64_at", "mc_wide64_below"),
-          ("mc_wide64_at", "mc_wide64_ndim_below"),
+          ("mc_wide64_at", "mc_wide64_ndim_below"), ("kcs_t128_at", "kcs_t128_below"),
           # shape rules: the default route against its ineligible neighbour
           ("c3_fwd", "c3_fwd_padded_rgb"), ("c3_wgrad", "c3_wgrad_padded_rgb"), ("conv1x1_c32", "conv1x1_c48"), ("conv1x1s_c32", "conv1x1s_c48"),
           ("linear_k1_fwd", "linear_k1_fwd_c128"), ("linear_k1_dgrad", "linear_k1_dgrad_c128"), ("skinny_k3", "skinny_k3_c32"),
