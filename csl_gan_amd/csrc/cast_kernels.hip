@@ -1,6 +1,7 @@
-// Streams over bf16-stored tensors (the storage mode of igemm_bf16s.hip): fp32 <-> bfloat16 casts, round_bf16 (the fp32 master filter
-// rounded once per parameter version for the bf16-stored convs, cached by the caller) and the activation backward, whose fp32 form is in
-// pointwise_kernels.hip (full).  gfx950 only.  Replaces (reference file:line): F.leaky_relu's backward DCResNet_models.py:132 (autograd).
+// Casts and the activation backward.  Streams over bf16-stored tensors (the storage mode of igemm_bf16s.hip): fp32 <-> bfloat16 casts and
+// round_bf16 (the fp32 master filter rounded once per parameter version for the bf16-stored convs, cached by the caller); the activation
+// backward in its fp32 and its bf16 form.  gfx950 only.  Replaces (reference file:line): F.leaky_relu's backward DCResNet_models.py:132
+// (autograd).
 #include "common.h"
 #include "device_prims.h"
 #include "igemm.h"
@@ -28,6 +29,27 @@ __global__ void widen_bf16_kernel(const unsigned short* __restrict__ in, float* 
 static unsigned stream_blocks(long long n_items) {
     long long nb = (n_items + 255) / 256;
     return (unsigned)(nb > 4096 ? 4096 : (nb < 1 ? 1 : nb));
+}
+
+__global__ void act_bwd_kernel(const float* __restrict__ g, const float* __restrict__ y, long long n, float slope,
+                               float* __restrict__ out, int vec) {
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    if (vec) {
+        const long long n4 = n >> 2;
+        const float4* g4 = reinterpret_cast<const float4*>(g);
+        const float4* y4 = reinterpret_cast<const float4*>(y);
+        float4* o4 = reinterpret_cast<float4*>(out);
+        for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+            const float4 a = g4[i], b = y4[i];
+            o4[i] = make_float4(b.x > 0.f ? a.x : slope * a.x, b.y > 0.f ? a.y : slope * a.y,
+                                b.z > 0.f ? a.z : slope * a.z, b.w > 0.f ? a.w : slope * a.w);
+        }
+        for (long long i = (n4 << 2) + (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+            out[i] = y[i] > 0.f ? g[i] : slope * g[i];
+    } else {
+        for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+            out[i] = y[i] > 0.f ? g[i] : slope * g[i];
+    }
 }
 
 // out = g * (y > 0 ? 1 : slope): LeakyReLU / ReLU backward from the OUTPUT's sign, 8 values per lane
@@ -71,6 +93,15 @@ int cslgan_cast_bf16_f32(const void* in, float* out, int64_t n, void* stream) {
     if (n == 0) return CSLGAN_OK;
     hipLaunchKernelGGL(widen_bf16_kernel, dim3(stream_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const unsigned short*>(in), out, (long long)n);
     return check_launch("widen_bf16_kernel");
+}
+
+int cslgan_act_bwd_f32(const float* g, const float* y, int64_t n, float slope, float* out, void* stream) {
+    CSLGAN_REQUIRE(g && y && out, "act_bwd: null argument");
+    CSLGAN_REQUIRE(n >= 0, "act_bwd: n < 0");
+    if (n == 0) return CSLGAN_OK;
+    const int vec = aligned16(g) && aligned16(y) && aligned16(out);
+    hipLaunchKernelGGL(act_bwd_kernel, dim3(grid_for(n, 4)), dim3(256), 0, (hipStream_t)stream, g, y, (long long)n, slope, out, vec);
+    return check_launch("act_bwd_kernel");
 }
 
 int cslgan_act_bwd_bf16(const void* g, const void* y, int64_t n, float slope, void* out, void* stream) {

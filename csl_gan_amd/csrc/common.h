@@ -60,4 +60,13 @@ inline bool aligned_to(const void* p, unsigned bytes) { return (reinterpret_cast
 int zero_floats(float* p, size_t n_floats, hipStream_t st);
 __device__ __forceinline__ bool aligned16_dev(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// 256-thread workgroups of a grid-stride stream over n elements, per_thread each: at most 2048.  The bf16 streams
+// (stream_blocks, cast_kernels.hip) and the norm apply launch (norm_kernels.hip) size theirs with a cap of 4096; the three stay apart.
+inline unsigned grid_for(long long n, int per_thread = 1) {
+    long long b = (n / per_thread + 255) / 256;
+    if (b > 2048) b = 2048;
+    if (b < 1) b = 1;
+    return (unsigned)b;
+}
+
 }  // namespace cslgan

@@ -1,5 +1,5 @@
 // Device primitives shared by every HIP kernel of libcslgan_hip.so (gfx950 only): vector types, range-checked buffer
-// loads, the two bfloat16 rounding forms, the three-piece fp32 split and the epilogue pieces.  Included after common.h.
+// loads, the two bfloat16 rounding forms, the three-piece fp32 split, depth-to-space addressing and the epilogue pieces.  Included after common.h.
 // One definition each: a fix made here reaches every kernel.
 #pragma once
 #include "common.h"
@@ -93,6 +93,20 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
         k1 += 0xBB67AE85u;
     }
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+// ---- depth-to-space addressing ----------------------------------------------------------------------------------------------
+// Depth-to-space addressing of UpsampleConv (DCResNet_models.py:13-15): cat([x]*4, dim=1) + pixel_shuffle(2) gives
+// up[c][2h+i][2w+j] = x[(4c+2i+j) mod C][h][w], i.e. for C % 4 == 0 the C output channels are the C/4 channels of the
+// plain depth-to-space tensor  ps[n][2h+i][2w+j][c'] = x[n][h][w][4c'+2i+j]  repeated four times (the conv that follows
+// runs on ps with its filter summed over the four channel groups, cslgan_fold_channels4_f32).  Element (row r, channel
+// 4c'+p) of x[N*H*W][C] lands at ps offset d2s_offset(r, p) + c'.
+__device__ __forceinline__ long long d2s_offset(long long r, int p, int H, int W, int Cq) {
+    const int w = (int)(r % W);
+    const long long t = r / W;
+    const int h = (int)(t % H);
+    const long long n = t / H;
+    return ((n * 2 * H + 2 * h + (p >> 1)) * 2 * W + 2 * w + (p & 1)) * Cq;
 }
 
 // ---- epilogue pieces --------------------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-// The GroupNorm apply arithmetic shared by norm_apply_rows_kernel (pointwise_kernels.hip) and gn_shortcut_kernel (gn_shortcut.hip):
+// The GroupNorm apply arithmetic shared by norm_apply_rows_kernel (norm_kernels.hip) and gn_shortcut_kernel (gn_shortcut.hip):
 // both compile these expressions, so the two routes of ResBlockUp's bn1 give the same bits.
 #pragma once
 #include "common.h"

@@ -1,33 +1,12 @@
-// Pointwise / normalisation kernels (HBM-bound, 16-byte accesses where alignment allows).  gfx950.
-//
-// Replaces (reference file:line): F.leaky_relu backward DCResNet_models.py:132 (autograd);
-// nn.GroupNorm + F.relu DCResNet_models.py:55-57,63-67,101-102; torch.optim.Adam.step train.py:76,484.
+// The normalisation family over NHWC data (HBM-bound, 16-byte accesses where alignment allows): GroupNorm / BatchNorm statistics, apply
+// (+ReLU, + the depth-to-space output of UpsampleConv), eval-mode and running BatchNorm statistics, the consumers of the conv
+// epilogue's partial statistics, and the backward.  gfx950 only.
+// Replaces (reference file:line): nn.GroupNorm + F.relu DCResNet_models.py:55-57,63-67,101-102 and their autograd backward.
 #include "common.h"
 #include "device_prims.h"
 #include "gn_apply.h"
 
 namespace cslgan {
-
-__global__ void act_bwd_kernel(const float* __restrict__ g, const float* __restrict__ y, long long n, float slope,
-                               float* __restrict__ out, int vec) {
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    if (vec) {
-        const long long n4 = n >> 2;
-        const float4* g4 = reinterpret_cast<const float4*>(g);
-        const float4* y4 = reinterpret_cast<const float4*>(y);
-        float4* o4 = reinterpret_cast<float4*>(out);
-        for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-            const float4 a = g4[i], b = y4[i];
-            o4[i] = make_float4(b.x > 0.f ? a.x : slope * a.x, b.y > 0.f ? a.y : slope * a.y,
-                                b.z > 0.f ? a.z : slope * a.z, b.w > 0.f ? a.w : slope * a.w);
-        }
-        for (long long i = (n4 << 2) + (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-            out[i] = y[i] > 0.f ? g[i] : slope * g[i];
-    } else {
-        for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-            out[i] = y[i] > 0.f ? g[i] : slope * g[i];
-    }
-}
 
 // ---- normalisation statistics over NHWC data ------------------------------------------------
 // x is [R][C] (R = N*H*W rows).  A statistic s covers `rows_per_stat` consecutive rows and `cpg`
@@ -50,10 +29,6 @@ __global__ void act_bwd_kernel(const float* __restrict__ g, const float* __restr
 // global atomic per channel per block.
 constexpr int NS_ROWS_MIN = 64;   // rows per block, lower bound (the launch picks a multiple: ~1024 blocks in all)
 
-// PART: `final_stats` is the partials array [row group][workgroup of the row group][group][2] (see launch_norm): every workgroup
-// leaves its own (S1, S2) pairs there and the apply kernel adds them — no zeroed accumulator, no atomics, no finalize launch.
-// (Round 3's attempt to finish the statistics in the LAST workgroup of a row group behind a ticket needed a device-scope fence in
-// every workgroup and made this kernel 5x slower, DESIGN §4.11; it is gone.)
 // Element access for the normalisation kernels: fp32 tensors, or bfloat16-stored activations (csrc/igemm_bf16s.hip's storage mode;
 // statistics and arithmetic are fp32 either way, a bf16 output is rounded to nearest even).
 typedef unsigned short bf16_t;
@@ -71,6 +46,10 @@ __device__ __forceinline__ void st4(bf16_t* p, long long i, float a, float b, fl
     *reinterpret_cast<uint2*>(p + i) = make_uint2(rne_bf16(a) | (rne_bf16(b) << 16), rne_bf16(c) | (rne_bf16(d) << 16));
 }
 
+// PART: `final_stats` is the partials array [row group][workgroup of the row group][group][2] (see launch_norm): every workgroup
+// leaves its own (S1, S2) pairs there and the apply kernel adds them — no zeroed accumulator, no atomics, no finalize launch.
+// (Round 3's attempt to finish the statistics in the LAST workgroup of a row group behind a ticket needed a device-scope fence in
+// every workgroup and made this kernel 5x slower, DESIGN §4.11; it is gone.)
 template <bool VEC, bool PART, typename TX>
 __global__ __launch_bounds__(256) void norm_stats_kernel(const TX* __restrict__ x, long long rows_per_stat, int C, int cpg,
                                                          int n_groups, int rows_per_block, float* __restrict__ stats,
@@ -164,19 +143,6 @@ __global__ void norm_stats_finalize_kernel(const TX* __restrict__ x, long long r
     if (css < 0.f) css = 0.f;
     stats[2 * s] = (k + m1) * cnt;      // sum x
     stats[2 * s + 1] = css;
-}
-
-// Depth-to-space addressing of UpsampleConv (DCResNet_models.py:13-15): cat([x]*4, dim=1) + pixel_shuffle(2) gives
-// up[c][2h+i][2w+j] = x[(4c+2i+j) mod C][h][w], i.e. for C % 4 == 0 the C output channels are the C/4 channels of the
-// plain depth-to-space tensor  ps[n][2h+i][2w+j][c'] = x[n][h][w][4c'+2i+j]  repeated four times (the conv that follows
-// runs on ps with its filter summed over the four channel groups, cslgan_fold_channels4_f32).  Element (row r, channel
-// 4c'+p) of x[N*H*W][C] lands at ps offset d2s_offset(r, p) + c'.
-__device__ __forceinline__ long long d2s_offset(long long r, int p, int H, int W, int Cq) {
-    const int w = (int)(r % W);
-    const long long t = r / W;
-    const int h = (int)(t % H);
-    const long long n = t / H;
-    return ((n * 2 * H + 2 * h + (p >> 1)) * 2 * W + 2 * w + (p & 1)) * Cq;
 }
 
 // y = act((x - mean_s) * rstd_s * gamma[c] + beta[c])
@@ -333,49 +299,6 @@ __global__ __launch_bounds__(256) void norm_apply_rows_kernel(const TX* __restri
     }
 }
 
-// ps[n][2h+i][2w+j][c'] = x[n][h][w][4c'+2i+j]  (INVERSE: x from ps — the backward of the forward and vice versa)
-template <bool INVERSE>
-__global__ void depth_to_space_kernel(const float* __restrict__ in, long long rows, int H, int W, int C, float* __restrict__ out) {
-    const int Cq = C >> 2;
-    const long long n4 = rows * Cq;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
-        const long long r = i / Cq;
-        const int cq = (int)(i - r * Cq);
-        if (INVERSE) {
-            float v[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = in[d2s_offset(r, e, H, W, Cq) + cq];
-            reinterpret_cast<float4*>(out)[i] = make_float4(v[0], v[1], v[2], v[3]);
-        } else {
-            const float4 v = reinterpret_cast<const float4*>(in)[i];
-            const float a[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) out[d2s_offset(r, e, H, W, Cq) + cq] = a[e];
-        }
-    }
-}
-
-// The conv after the depth-to-space sees four identical channel groups, so it equals a conv over C/4 channels with
-//   wf[row][c'] = sum_q w[row][c' + q*C/4]      (row = (k, r, s) of a KRSC filter)
-// UNFOLD is its transpose (the gradient of w from the gradient of wf): gw[row][c' + q*C/4] = gwf[row][c'].
-template <bool UNFOLD>
-__global__ void fold_channels4_kernel(const float* __restrict__ in, long long rows, int C, float* __restrict__ out) {
-    const int Cq = C >> 2;
-    const long long n = rows * Cq;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const long long r = i / Cq;
-        const int cq = (int)(i - r * Cq);
-        if (UNFOLD) {
-            const float v = in[i];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) out[r * C + q * Cq + cq] = v;
-        } else {
-            const float* b = in + r * C + cq;
-            out[i] = (b[0] + b[Cq]) + (b[2 * Cq] + b[3 * Cq]);
-        }
-    }
-}
-
 // eval-mode BatchNorm: the (sum, centred sum of squares) pair norm_apply_kernel consumes, from the running statistics
 __global__ void bn_eval_stats_kernel(const float* __restrict__ rm, const float* __restrict__ rv, int C, float cnt,
                                      float* __restrict__ stats) {
@@ -509,89 +432,96 @@ __global__ void bn_running_kernel(const float* __restrict__ stats, int C, float 
     rv[c] = (1.f - momentum) * rv[c] + momentum * var_unb;
 }
 
+// ---- host frame: one normalisation call as its entry describes it, filled once, read by launch_norm and launch_norm_apply -------------
 template <typename TX, typename TY>
-static int launch_norm_apply(const TX* x, const float* gamma, const float* beta, long long R, long long rows_per_stat, int C,
-                             int cpg, int n_groups, float eps, int relu, float* stats, TY* y, int d2s_H, int d2s_W,
-                             TY* xs, bool vec, hipStream_t st, const float* part = nullptr, int n_part = 0, int chan = 0,
-                             const float* mean_tab = nullptr) {
-    const long long total = R * C;
-    const long long n_rg = R / rows_per_stat;
-    if (vec && rows_per_stat * C < (1ll << 32) && n_rg <= 65535) {
-        long long bx = (rows_per_stat * C / 4 + 255) / 256;
+struct NormCall {
+    const TX* x;
+    const float *gamma, *beta;
+    long long R, rows_per_stat;        // rows in all; rows of one statistic (divides R)
+    int C, cpg, n_groups;
+    float eps;
+    int relu;
+    float* stats;                      // [R / rows_per_stat][n_groups][2]
+    TY* y;
+    int d2s_H, d2s_W;                  // d2s_W > 0: y (and xs, the raw input, when given) in the depth-to-space layout; else both 0
+    TY* xs;
+    hipStream_t st;
+};
+
+// about 1024 workgroups in all, each with at least NS_ROWS_MIN rows: fewer, longer blocks mean fewer global atomics
+static long long norm_rows_per_block(long long rows) {
+    const long long rpb = (rows / 1024 + NS_ROWS_MIN - 1) / NS_ROWS_MIN * NS_ROWS_MIN;
+    return rpb < NS_ROWS_MIN ? NS_ROWS_MIN : (rpb > 4096 ? 4096 : rpb);
+}
+
+// The channel half of "the 16-byte kernels are legal": a row is whole float4s and 256 threads hold whole rows of them.
+static bool norm_vec_channels(int C) { return (C % 4 == 0) && ((C / 4) <= 256) && (256 % (C / 4) == 0); }
+
+static bool norm_vec_ok(const void* x, const void* y, const void* xs, int C, int cpg) {
+    return norm_vec_channels(C) && (cpg % 4 == 0 || 4 % cpg == 0) && aligned16(x) && aligned16(y) && (!xs || aligned16(xs));
+}
+
+template <typename TX, typename TY>
+static int launch_norm_apply(const NormCall<TX, TY>& c, bool vec, const float* part = nullptr, int n_part = 0, int chan = 0, const float* mean_tab = nullptr) {
+    const long long total = c.R * c.C;
+    const long long n_rg = c.R / c.rows_per_stat;
+    const bool d2s = c.d2s_W > 0;
+    if (vec && c.rows_per_stat * c.C < (1ll << 32) && n_rg <= 65535) {
+        long long bx = (c.rows_per_stat * c.C / 4 + 255) / 256;
         const long long cap = (4096 + n_rg - 1) / n_rg;                 // about 4096 workgroups in all
         bx = bx > cap ? cap : (bx < 1 ? 1 : bx);
-        const dim3 g2((unsigned)bx, (unsigned)n_rg), b2(256);
-        const size_t lds = part ? sizeof(float) * 2 * n_groups : 0;
-        if (d2s_W > 0) hipLaunchKernelGGL((norm_apply_rows_kernel<true, TX, TY>), g2, b2, lds, st, x, gamma, beta, stats, rows_per_stat, C, cpg, n_groups, eps, relu, y, d2s_H, d2s_W, xs, part, n_part, stats, chan, mean_tab);
-        else hipLaunchKernelGGL((norm_apply_rows_kernel<false, TX, TY>), g2, b2, lds, st, x, gamma, beta, stats, rows_per_stat, C, cpg, n_groups, eps, relu, y, 0, 0, (TY*)nullptr, part, n_part, stats, chan, mean_tab);
+        const size_t lds = part ? sizeof(float) * 2 * c.n_groups : 0;
+        const auto k = d2s ? norm_apply_rows_kernel<true, TX, TY> : norm_apply_rows_kernel<false, TX, TY>;
+        hipLaunchKernelGGL(k, dim3((unsigned)bx, (unsigned)n_rg), dim3(256), lds, c.st, c.x, c.gamma, c.beta, c.stats, c.rows_per_stat, c.C, c.cpg,
+                           c.n_groups, c.eps, c.relu, c.y, c.d2s_H, c.d2s_W, c.xs, part, n_part, c.stats, chan, mean_tab);
         return check_launch("norm_apply_rows_kernel");
     }
     long long nb = (total / 4 + 255) / 256;
     nb = nb > 4096 ? 4096 : (nb < 1 ? 1 : nb);
-    const dim3 g((unsigned)nb), b(256);
-    if (d2s_W > 0) {
-        if (vec) hipLaunchKernelGGL((norm_apply_kernel<true, true, TX, TY>), g, b, 0, st, x, gamma, beta, stats, total, rows_per_stat, C, cpg, n_groups, eps, relu, y, d2s_H, d2s_W, xs, mean_tab);
-        else hipLaunchKernelGGL((norm_apply_kernel<false, true, TX, TY>), g, b, 0, st, x, gamma, beta, stats, total, rows_per_stat, C, cpg, n_groups, eps, relu, y, d2s_H, d2s_W, xs, mean_tab);
-    } else {
-        if (vec) hipLaunchKernelGGL((norm_apply_kernel<true, false, TX, TY>), g, b, 0, st, x, gamma, beta, stats, total, rows_per_stat, C, cpg, n_groups, eps, relu, y, 0, 0, (TY*)nullptr, mean_tab);
-        else hipLaunchKernelGGL((norm_apply_kernel<false, false, TX, TY>), g, b, 0, st, x, gamma, beta, stats, total, rows_per_stat, C, cpg, n_groups, eps, relu, y, 0, 0, (TY*)nullptr, mean_tab);
-    }
+    const auto k = d2s ? (vec ? norm_apply_kernel<true, true, TX, TY> : norm_apply_kernel<false, true, TX, TY>)
+                       : (vec ? norm_apply_kernel<true, false, TX, TY> : norm_apply_kernel<false, false, TX, TY>);
+    hipLaunchKernelGGL(k, dim3((unsigned)nb), dim3(256), 0, c.st, c.x, c.gamma, c.beta, c.stats, total, c.rows_per_stat, c.C, c.cpg, c.n_groups, c.eps, c.relu, c.y, c.d2s_H, c.d2s_W, c.xs, mean_tab);
     return check_launch("norm_apply_kernel");
 }
 
-static bool norm_vec_ok(const void* x, const void* y, const void* xs, int C, int cpg) {
-    return (C % 4 == 0) && ((C / 4) <= 256) && (256 % (C / 4) == 0) && (cpg % 4 == 0 || 4 % cpg == 0) && aligned16(x) && aligned16(y) &&
-           (!xs || aligned16(xs));
-}
-
 template <typename TX, typename TY>
-static int launch_norm(const TX* x, const float* gamma, const float* beta, long long R, long long rows_per_stat, int C, int cpg,
-                       int n_groups, float eps, int relu, float* stats, TY* y, int d2s_H, int d2s_W, TY* xs, hipStream_t st,
-                       float* scratch = nullptr) {
-    const long long n_row_groups = R / rows_per_stat;
-    const long long n_stats = n_row_groups * n_groups;
-    const bool vec = norm_vec_ok(x, y, xs, C, cpg);
-    // about 1024 workgroups in all, each with at least NS_ROWS_MIN rows: fewer, longer blocks mean fewer global atomics
-    long long rpb = (rows_per_stat * n_row_groups / 1024 + NS_ROWS_MIN - 1) / NS_ROWS_MIN * NS_ROWS_MIN;
-    rpb = rpb < NS_ROWS_MIN ? NS_ROWS_MIN : (rpb > 4096 ? 4096 : rpb);
-    const dim3 grid((unsigned)((rows_per_stat + rpb - 1) / rpb), (unsigned)n_row_groups), block(256);
-    const size_t lds = sizeof(float) * C;
-    // Two-launch form: per-workgroup partial statistics into `scratch` (2 * n_stats * grid.x floats, grid.x <= CSLGAN_NORM_PARTIAL_BLOCKS),
-    // summed by the apply kernel's prologue — no zeroed accumulator, no global atomics, no finalize launch (round 3: four launches per
-    // normalisation, 36 per D-step; its ticket-fused attempt needed a device-scope fence per workgroup and lost).
-    if (scratch && vec && grid.x <= CSLGAN_NORM_PARTIAL_BLOCKS && rows_per_stat * C < (1ll << 32) && n_row_groups <= 65535 &&
-        2 * (size_t)n_groups * sizeof(float) <= 32768) {
-        hipLaunchKernelGGL((norm_stats_kernel<true, true, TX>), grid, block, 2 * lds, st, x, rows_per_stat, C, cpg, n_groups, (int)rpb, stats, scratch, n_stats, (const float*)nullptr);
-        const int rc1 = check_launch("norm_stats_kernel");
-        if (rc1) return rc1;
-        return launch_norm_apply(x, gamma, beta, R, rows_per_stat, C, cpg, n_groups, eps, relu, stats, y, d2s_H, d2s_W, xs, vec, st, scratch, (int)grid.x);
+static int launch_norm(const NormCall<TX, TY>& c, float* scratch = nullptr) {
+    const long long n_row_groups = c.R / c.rows_per_stat;
+    const long long n_stats = n_row_groups * c.n_groups;
+    const bool vec = norm_vec_ok(c.x, c.y, c.xs, c.C, c.cpg);
+    const long long rpb = norm_rows_per_block(c.R);
+    const dim3 grid((unsigned)((c.rows_per_stat + rpb - 1) / rpb), (unsigned)n_row_groups), block(256);
+    const size_t lds = sizeof(float) * 2 * c.C;
+    // Two-launch form (PART, above norm_stats_kernel): per-workgroup partial statistics into `scratch` (2 * n_stats * grid.x floats,
+    // grid.x <= CSLGAN_NORM_PARTIAL_BLOCKS), summed by the apply kernel's prologue; round 3 took four launches per normalisation, 36 per D-step.
+    if (scratch && vec && grid.x <= CSLGAN_NORM_PARTIAL_BLOCKS && c.rows_per_stat * c.C < (1ll << 32) && n_row_groups <= 65535 && 2 * (size_t)c.n_groups * sizeof(float) <= 32768) {
+        hipLaunchKernelGGL((norm_stats_kernel<true, true, TX>), grid, block, lds, c.st, c.x, c.rows_per_stat, c.C, c.cpg, c.n_groups, (int)rpb, c.stats, scratch, n_stats, (const float*)nullptr);
+        if (int rc = check_launch("norm_stats_kernel")) return rc;
+        return launch_norm_apply(c, vec, scratch, (int)grid.x);
     }
-    if (int rc = zero_floats(stats, (size_t)2 * n_stats, st)) return rc;
-    const dim3 fgrid((unsigned)((n_stats + 127) / 128)), fblock(128);
-    const float* shift = nullptr;
-    int rc;
-    if (vec) hipLaunchKernelGGL((norm_stats_kernel<true, false, TX>), grid, block, 2 * lds, st, x, rows_per_stat, C, cpg, n_groups, (int)rpb, stats, (float*)nullptr, n_stats, shift);
-    else hipLaunchKernelGGL((norm_stats_kernel<false, false, TX>), grid, block, 2 * lds, st, x, rows_per_stat, C, cpg, n_groups, (int)rpb, stats, (float*)nullptr, n_stats, shift);
-    rc = check_launch("norm_stats_kernel");
-    if (rc) return rc;
+    if (int rc = zero_floats(c.stats, (size_t)2 * n_stats, c.st)) return rc;
+    // one pass of the statistics with global atomics about `shift` (nullptr: the statistic's first element); then the finalize kernel
+    const auto stats_pass = [&](const float* shift) {
+        const auto k = vec ? norm_stats_kernel<true, false, TX> : norm_stats_kernel<false, false, TX>;
+        hipLaunchKernelGGL(k, grid, block, lds, c.st, c.x, c.rows_per_stat, c.C, c.cpg, c.n_groups, (int)rpb, c.stats, (float*)nullptr, n_stats, shift);
+        return check_launch("norm_stats_kernel");
+    };
+    const auto finalize = [&](const float* shift, int first_pass) {
+        hipLaunchKernelGGL(norm_stats_finalize_kernel<TX>, dim3((unsigned)((n_stats + 127) / 128)), dim3(128), 0, c.st, c.x, c.rows_per_stat, c.C,
+                           c.cpg, c.n_groups, n_stats, c.stats, shift, scratch, first_pass);
+        return check_launch("norm_stats_finalize_kernel");
+    };
+    if (int rc = stats_pass(nullptr)) return rc;
     if (scratch) {
         // The routes with global atomics (more than CSLGAN_NORM_PARTIAL_BLOCKS workgroups per statistic, or the scalar kernels; the
         // training step's GroupNorms take neither) buy the variance back with a second pass: the first pass's mean_s (n_stats floats
         // at the head of scratch) becomes the shift, so S2 - S1^2/n no longer cancels by 1 + ((k - mean)/sigma)^2.  One more read
         // of x: a quarter on top of the three passes (statistics, apply's read and write) the route costs anyway.
-        hipLaunchKernelGGL(norm_stats_finalize_kernel<TX>, fgrid, fblock, 0, st, x, rows_per_stat, C, cpg, n_groups, n_stats, stats, shift, scratch, 1);
-        rc = check_launch("norm_stats_finalize_kernel");
-        if (rc) return rc;
-        shift = scratch;
-        if (vec) hipLaunchKernelGGL((norm_stats_kernel<true, false, TX>), grid, block, 2 * lds, st, x, rows_per_stat, C, cpg, n_groups, (int)rpb, stats, (float*)nullptr, n_stats, shift);
-        else hipLaunchKernelGGL((norm_stats_kernel<false, false, TX>), grid, block, 2 * lds, st, x, rows_per_stat, C, cpg, n_groups, (int)rpb, stats, (float*)nullptr, n_stats, shift);
-        rc = check_launch("norm_stats_kernel");
-        if (rc) return rc;
+        if (int rc = finalize(nullptr, 1)) return rc;
+        if (int rc = stats_pass(scratch)) return rc;
     }
-    hipLaunchKernelGGL(norm_stats_finalize_kernel<TX>, fgrid, fblock, 0, st, x, rows_per_stat, C, cpg, n_groups, n_stats, stats, shift, scratch, 0);
-    rc = check_launch("norm_stats_finalize_kernel");
-    if (rc) return rc;
-    return launch_norm_apply(x, gamma, beta, R, rows_per_stat, C, cpg, n_groups, eps, relu, stats, y, d2s_H, d2s_W, xs, vec, st, nullptr, 0, 0, scratch);
+    if (int rc = finalize(scratch, 0)) return rc;
+    return launch_norm_apply(c, vec, nullptr, 0, 0, scratch);
 }
 
 // d2s_W > 0 asks for the depth-to-space output layout: rows are (n, h, w) with w fastest, H = rows_per_image / d2s_W
@@ -607,43 +537,25 @@ static int check_d2s(long long rows_per_image, int C, int d2s_W, const void* xs,
     return CSLGAN_OK;
 }
 
-__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                            long long n, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        float gi = g[i];
-        const float pi = p[i];
-        if (wd != 0.f) gi = fmaf(wd, pi, gi);
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        m[i] = mi;
-        v[i] = vi;
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        p[i] = pi - (lr / bc1) * (mi / denom);
-    }
+// The argument checks of the GroupNorm entries under the entry's message prefix `who`; n_part (nullable): of an entry that consumes partials.
+static int check_groupnorm(const char* who, bool pointers, int N, int HW, int C, int groups, const int* n_part, int d2s_W, const void* xs, int* H_out) {
+    CSLGAN_REQUIRE(pointers, "%s: null argument", who);
+    CSLGAN_REQUIRE(N > 0 && HW > 0 && C > 0 && groups > 0 && C % groups == 0, "%s: C=%d not divisible by groups=%d", who, C, groups);
+    if (n_part)
+        CSLGAN_REQUIRE(N <= 65535 && C <= 8192 && *n_part >= 1 && *n_part <= CSLGAN_NORM_PARTIAL_BLOCKS && HW == 64 * *n_part,
+                       "%s: needs HW == 64 * n_part <= %d * 64", who, CSLGAN_NORM_PARTIAL_BLOCKS);
+    else
+        CSLGAN_REQUIRE(N <= 65535 && C <= 8192, "%s: N or C too large", who);
+    return check_d2s(HW, C, d2s_W, xs, H_out);
 }
 
-__global__ void adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                long long n, float lr, float b1, float b2, float eps, float wd, const int* __restrict__ step_dev) {
-    const float st = (float)(*step_dev);
-    const float bc1 = 1.f - powf(b1, st), bc2_sqrt = sqrtf(1.f - powf(b2, st));
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        float gi = g[i];
-        const float pi = p[i];
-        if (wd != 0.f) gi = fmaf(wd, pi, gi);
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        m[i] = mi;
-        v[i] = vi;
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        p[i] = pi - (lr / bc1) * (mi / denom);
-    }
-}
-
-static unsigned grid_for(long long n, int per_thread = 1) {
-    long long b = (n / per_thread + 255) / 256;
-    if (b > 2048) b = 2048;
-    if (b < 1) b = 1;
-    return (unsigned)b;
+// The same for the BatchNorm entries; running_pair: running_mean and running_var are both given or both absent.
+static int check_batchnorm(const char* who, bool pointers, long long rows, int C, bool running_pair, long long rows_per_image, int d2s_W, const void* xs, int* H_out) {
+    CSLGAN_REQUIRE(pointers, "%s: null argument", who);
+    CSLGAN_REQUIRE(rows > 0 && C > 0 && C <= 8192, "%s: bad sizes", who);
+    CSLGAN_REQUIRE(running_pair, "%s: running_mean/var must both be given or both null", who);
+    CSLGAN_REQUIRE(d2s_W == 0 || (rows_per_image > 0 && rows % rows_per_image == 0), "%s: rows_per_image must divide rows", who);
+    return check_d2s(rows_per_image, C, d2s_W, xs, H_out);
 }
 
 }  // namespace cslgan
@@ -652,25 +564,11 @@ using namespace cslgan;
 
 extern "C" {
 
-int cslgan_act_bwd_f32(const float* g, const float* y, int64_t n, float slope, float* out, void* stream) {
-    CSLGAN_REQUIRE(g && y && out, "act_bwd: null argument");
-    CSLGAN_REQUIRE(n >= 0, "act_bwd: n < 0");
-    if (n == 0) return CSLGAN_OK;
-    const int vec = aligned16(g) && aligned16(y) && aligned16(out);
-    hipLaunchKernelGGL(act_bwd_kernel, dim3(grid_for(n, 4)), dim3(256), 0, (hipStream_t)stream, g, y, (long long)n, slope, out, vec);
-    return check_launch("act_bwd_kernel");
-}
-
 int cslgan_groupnorm_act_f32(const float* x, const float* gamma, const float* beta, int N, int HW, int C, int groups,
                              float eps, int relu, float* stats_ws, float* y, int d2s_W, float* x_shuffled, float* scratch, void* stream) {
-    CSLGAN_REQUIRE(x && gamma && beta && stats_ws && y, "groupnorm: null argument");
-    CSLGAN_REQUIRE(N > 0 && HW > 0 && C > 0 && groups > 0 && C % groups == 0, "groupnorm: C=%d not divisible by groups=%d", C, groups);
-    CSLGAN_REQUIRE(N <= 65535 && C <= 8192, "groupnorm: N or C too large");
     int H = 0;
-    int rc = check_d2s(HW, C, d2s_W, x_shuffled, &H);
-    if (rc) return rc;
-    return launch_norm(x, gamma, beta, (long long)N * HW, HW, C, C / groups, groups, eps, relu, stats_ws, y, H, d2s_W, x_shuffled,
-                       (hipStream_t)stream, scratch);
+    if (int rc = check_groupnorm("groupnorm", x && gamma && beta && stats_ws && y, N, HW, C, groups, nullptr, d2s_W, x_shuffled, &H)) return rc;
+    return launch_norm(NormCall<float, float>{x, gamma, beta, (long long)N * HW, HW, C, C / groups, groups, eps, relu, stats_ws, y, H, d2s_W, x_shuffled, (hipStream_t)stream}, scratch);
 }
 
 // (scale, shift) of every (image, channel) from the conv-epilogue partials: one workgroup per image.  The n_part (<= 64) pairs of
@@ -734,166 +632,47 @@ int cslgan_groupnorm_affine_parts_f32(const float* part, int n_part, const float
 // The apply half on statistics left by a conv epilogue (include/cslgan.h: cslgan_conv_t.gn_part).
 int cslgan_groupnorm_apply_parts_f32(const float* x, const float* gamma, const float* beta, int N, int HW, int C, int groups, float eps, int relu,
                                      const float* part, int n_part, float* stats_ws, float* y, int d2s_W, float* x_shuffled, void* stream) {
-    CSLGAN_REQUIRE(x && gamma && beta && stats_ws && y && part, "groupnorm_apply_parts: null argument");
-    CSLGAN_REQUIRE(N > 0 && HW > 0 && C > 0 && groups > 0 && C % groups == 0, "groupnorm_apply_parts: C=%d not divisible by groups=%d", C, groups);
-    CSLGAN_REQUIRE(N <= 65535 && C <= 8192 && n_part >= 1 && n_part <= CSLGAN_NORM_PARTIAL_BLOCKS && HW == 64 * n_part,
-                   "groupnorm_apply_parts: needs HW == 64 * n_part <= %d * 64", CSLGAN_NORM_PARTIAL_BLOCKS);
     int H = 0;
-    int rc = check_d2s(HW, C, d2s_W, x_shuffled, &H);
-    if (rc) return rc;
+    if (int rc = check_groupnorm("groupnorm_apply_parts", x && gamma && beta && stats_ws && y && part, N, HW, C, groups, &n_part, d2s_W, x_shuffled, &H)) return rc;
     CSLGAN_REQUIRE(norm_vec_ok(x, y, x_shuffled, C, C / groups) && (long long)HW * C < (1ll << 32) && 2 * (size_t)groups * sizeof(float) <= 32768,
                    "groupnorm_apply_parts: shape not taken by the row-walking apply kernel");
-    return launch_norm_apply(x, gamma, beta, (long long)N * HW, HW, C, C / groups, groups, eps, relu, stats_ws, y, H, d2s_W, x_shuffled, true,
-                             (hipStream_t)stream, part, n_part, 1);
+    return launch_norm_apply(NormCall<float, float>{x, gamma, beta, (long long)N * HW, HW, C, C / groups, groups, eps, relu, stats_ws, y, H, d2s_W,
+                                                    x_shuffled, (hipStream_t)stream}, true, part, n_part, 1);
 }
 
 // GroupNorm (+ReLU) at the head of the bf16-stored chain (csrc/igemm_bf16s.hip): x fp32 or bfloat16, y (and x_shuffled) bfloat16;
 // statistics and arithmetic in fp32 exactly as cslgan_groupnorm_act_f32.
 int cslgan_groupnorm_act_bf16s(const void* x, int x_bf16, const float* gamma, const float* beta, int N, int HW, int C, int groups,
                                float eps, int relu, float* stats_ws, void* y_bf16, int d2s_W, void* x_shuffled_bf16, void* stream) {
-    CSLGAN_REQUIRE(x && gamma && beta && stats_ws && y_bf16, "groupnorm_bf16s: null argument");
-    CSLGAN_REQUIRE(N > 0 && HW > 0 && C > 0 && groups > 0 && C % groups == 0, "groupnorm_bf16s: C=%d not divisible by groups=%d", C, groups);
-    CSLGAN_REQUIRE(N <= 65535 && C <= 8192, "groupnorm_bf16s: N or C too large");
     int H = 0;
-    int rc = check_d2s(HW, C, d2s_W, x_shuffled_bf16, &H);
-    if (rc) return rc;
-    bf16_t* y = reinterpret_cast<bf16_t*>(y_bf16);
-    bf16_t* xs = reinterpret_cast<bf16_t*>(x_shuffled_bf16);
-    if (x_bf16)
-        return launch_norm(reinterpret_cast<const bf16_t*>(x), gamma, beta, (long long)N * HW, HW, C, C / groups, groups, eps, relu, stats_ws, y, H,
-                           d2s_W, xs, (hipStream_t)stream);
-    return launch_norm(reinterpret_cast<const float*>(x), gamma, beta, (long long)N * HW, HW, C, C / groups, groups, eps, relu, stats_ws, y, H, d2s_W,
-                       xs, (hipStream_t)stream);
+    if (int rc = check_groupnorm("groupnorm_bf16s", x && gamma && beta && stats_ws && y_bf16, N, HW, C, groups, nullptr, d2s_W, x_shuffled_bf16, &H)) return rc;
+    const NormCall<float, bf16_t> c{reinterpret_cast<const float*>(x), gamma, beta, (long long)N * HW, HW, C, C / groups, groups, eps, relu, stats_ws,
+                                    reinterpret_cast<bf16_t*>(y_bf16), H, d2s_W, reinterpret_cast<bf16_t*>(x_shuffled_bf16), (hipStream_t)stream};
+    if (!x_bf16) return launch_norm(c);
+    return launch_norm(NormCall<bf16_t, bf16_t>{reinterpret_cast<const bf16_t*>(x), c.gamma, c.beta, c.R, c.rows_per_stat, c.C, c.cpg, c.n_groups, c.eps,
+                                                c.relu, c.stats, c.y, c.d2s_H, c.d2s_W, c.xs, c.st});
 }
 
 int cslgan_batchnorm_act_f32(const float* x, const float* gamma, const float* beta, int64_t rows, int C, float eps, int relu,
                              float momentum, float* running_mean, float* running_var, float* stats_ws, float* y,
                              int64_t rows_per_image, int d2s_W, float* x_shuffled, float* scratch, void* stream) {
-    CSLGAN_REQUIRE(x && gamma && beta && stats_ws && y, "batchnorm: null argument");
-    CSLGAN_REQUIRE(rows > 0 && C > 0 && C <= 8192, "batchnorm: bad sizes");
-    CSLGAN_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "batchnorm: running_mean/var must both be given or both null");
     int H = 0;
-    CSLGAN_REQUIRE(d2s_W == 0 || (rows_per_image > 0 && rows % rows_per_image == 0), "batchnorm: rows_per_image must divide rows");
-    int rc = check_d2s(rows_per_image, C, d2s_W, x_shuffled, &H);
-    if (rc) return rc;
-    rc = launch_norm(x, gamma, beta, rows, rows, C, 1, C, eps, relu, stats_ws, y, H, d2s_W, x_shuffled, (hipStream_t)stream, scratch);
-    if (rc) return rc;
-    if (running_mean) {
-        hipLaunchKernelGGL(bn_running_kernel, dim3((unsigned)((C + 127) / 128)), dim3(128), 0, (hipStream_t)stream, stats_ws, C,
-                           (float)rows, momentum, running_mean, running_var);
-        return check_launch("bn_running_kernel");
-    }
-    return CSLGAN_OK;
+    if (int rc = check_batchnorm("batchnorm", x && gamma && beta && stats_ws && y, rows, C, (running_mean == nullptr) == (running_var == nullptr), rows_per_image, d2s_W, x_shuffled, &H)) return rc;
+    if (int rc = launch_norm(NormCall<float, float>{x, gamma, beta, rows, rows, C, 1, C, eps, relu, stats_ws, y, H, d2s_W, x_shuffled, (hipStream_t)stream}, scratch)) return rc;
+    if (!running_mean) return CSLGAN_OK;
+    hipLaunchKernelGGL(bn_running_kernel, dim3((unsigned)((C + 127) / 128)), dim3(128), 0, (hipStream_t)stream, stats_ws, C, (float)rows, momentum, running_mean, running_var);
+    return check_launch("bn_running_kernel");
 }
 
 int cslgan_batchnorm_eval_act_f32(const float* x, const float* gamma, const float* beta, const float* running_mean,
                                   const float* running_var, int64_t rows, int C, float eps, int relu, float* stats_ws, float* y,
                                   int64_t rows_per_image, int d2s_W, float* x_shuffled, void* stream) {
-    CSLGAN_REQUIRE(x && gamma && beta && running_mean && running_var && stats_ws && y, "batchnorm_eval: null argument");
-    CSLGAN_REQUIRE(rows > 0 && C > 0 && C <= 8192, "batchnorm_eval: bad sizes");
-    CSLGAN_REQUIRE(d2s_W == 0 || (rows_per_image > 0 && rows % rows_per_image == 0), "batchnorm_eval: rows_per_image must divide rows");
     int H = 0;
-    int rc = check_d2s(rows_per_image, C, d2s_W, x_shuffled, &H);
-    if (rc) return rc;
+    if (int rc = check_batchnorm("batchnorm_eval", x && gamma && beta && running_mean && running_var && stats_ws && y, rows, C, true, rows_per_image, d2s_W, x_shuffled, &H)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(bn_eval_stats_kernel, dim3((unsigned)((C + 127) / 128)), dim3(128), 0, st, running_mean, running_var, C,
-                       (float)rows, stats_ws);
-    rc = check_launch("bn_eval_stats_kernel");
-    if (rc) return rc;
-    return launch_norm_apply(x, gamma, beta, rows, rows, C, 1, C, eps, relu, stats_ws, y, H, d2s_W, x_shuffled,
-                             norm_vec_ok(x, y, x_shuffled, C, 1), st);
-}
-
-// ---- input pipeline (round 4): uint8 NHWC image rows -> normalised fp32 NHWC, with the per-image horizontal flip -------------------
-// out[n][h][w][c] = src[n][h][flip[n] ? W-1-w : w][c] * scale + bias     (datasets.py:41-47: ToTensor, RandomHorizontalFlip, Normalize)
-__global__ void u8_to_f32_nhwc_kernel(const unsigned char* __restrict__ src, const unsigned char* __restrict__ flip, int N, int H, int W, int C,
-                                      float scale, float bias, float* __restrict__ out) {
-    const long long total = (long long)N * H * W * C;
-    const long long per_img = (long long)H * W * C;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const long long n = i / per_img;
-        long long si = i;
-        if (flip && flip[n]) {
-            const long long r = i - n * per_img;
-            const long long row = r / ((long long)W * C);
-            const int wc = (int)(r - row * W * C);
-            const int w = wc / C, c = wc - w * C;
-            si = n * per_img + row * W * C + (long long)(W - 1 - w) * C + c;
-        }
-        out[i] = (float)src[si] * scale + bias;
-    }
-}
-
-int cslgan_u8_to_f32_nhwc(const void* src_u8, const void* flip_u8, int N, int H, int W, int C, float scale, float bias, float* out, void* stream) {
-    CSLGAN_REQUIRE(src_u8 && out, "u8_to_f32_nhwc: null argument");
-    CSLGAN_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0, "u8_to_f32_nhwc: non-positive dimension");
-    const long long total = (long long)N * H * W * C;
-    unsigned nb = (unsigned)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
-    hipLaunchKernelGGL(u8_to_f32_nhwc_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const unsigned char*>(src_u8),
-                       reinterpret_cast<const unsigned char*>(flip_u8), N, H, W, C, scale, bias, out);
-    return check_launch("u8_to_f32_nhwc_kernel");
-}
-
-// ---- the inverse: fp32 images -> uint8 rows of the cache (util.denorm_celeba + util.save_image's quantisation, elementwise) -----------
-//   t = clamp(src * scale + bias, 0, 1);  dst = (uint8) clamp(t * 255 + 0.5, 0, 255)        truncation; NaN -> 0
-// Bit-identical to the host's fp32 expression: every product and sum is rounded on its own (no contraction into an fma, which
-// would skip the product's rounding and can move a value across a (k + 0.5) / 255 boundary), in the host's order.
-__device__ __forceinline__ unsigned quantise_u8(float x, float scale, float bias) {
-#pragma clang fp contract(off)
-    float t = x * scale;
-    t = t + bias;
-    t = fminf(fmaxf(t, 0.f), 1.f);               // fmaxf(NaN, 0) = 0
-    float u = t * 255.f;
-    u = u + 0.5f;
-    u = fminf(fmaxf(u, 0.f), 255.f);
-    return (unsigned)u;
-}
-
-// vec: src 16-byte and dst 4-byte aligned — one float4 load and one packed 4-byte store per thread and step; the n % 4 tail and
-// misaligned slices go element by element.
-__global__ __launch_bounds__(256) void f32_to_u8_kernel(const float* __restrict__ src, long long n, float scale, float bias,
-                                                        unsigned char* __restrict__ dst, int vec) {
-    const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long long)gridDim.x * blockDim.x;
-    long long done = 0;
-    if (vec) {
-        const long long n4 = n >> 2;
-        for (long long i = tid; i < n4; i += nth) {
-            const float4 v = reinterpret_cast<const float4*>(src)[i];
-            reinterpret_cast<unsigned*>(dst)[i] = quantise_u8(v.x, scale, bias) | (quantise_u8(v.y, scale, bias) << 8) |
-                                                  (quantise_u8(v.z, scale, bias) << 16) | (quantise_u8(v.w, scale, bias) << 24);
-        }
-        done = n4 << 2;
-    }
-    for (long long i = done + tid; i < n; i += nth) dst[i] = (unsigned char)quantise_u8(src[i], scale, bias);
-}
-
-int cslgan_f32_to_u8(const float* src, int64_t n, float scale, float bias, void* dst_u8, void* stream) {
-    CSLGAN_REQUIRE(src && dst_u8, "f32_to_u8: null argument");
-    CSLGAN_REQUIRE(n > 0, "f32_to_u8: n=%lld must be positive", (long long)n);
-    const int vec = (aligned16(src) && (reinterpret_cast<uintptr_t>(dst_u8) & 3u) == 0) ? 1 : 0;
-    hipLaunchKernelGGL(f32_to_u8_kernel, dim3(grid_for(n, vec ? 4 : 1)), dim3(256), 0, (hipStream_t)stream, src, (long long)n, scale, bias,
-                       reinterpret_cast<unsigned char*>(dst_u8), vec);
-    return check_launch("f32_to_u8_kernel");
-}
-
-int cslgan_depth_to_space_f32(const float* x, int N, int H, int W, int C, int inverse, float* y, void* stream) {
-    CSLGAN_REQUIRE(x && y, "depth_to_space: null argument");
-    CSLGAN_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "depth_to_space: needs C %% 4 == 0 (C=%d)", C);
-    CSLGAN_REQUIRE(aligned16(inverse ? y : x), "depth_to_space: the [N,H,W,C] tensor must be 16-byte aligned");
-    const long long rows = (long long)N * H * W;
-    const dim3 g(grid_for(rows * (C / 4))), b(256);
-    if (inverse) hipLaunchKernelGGL((depth_to_space_kernel<true>), g, b, 0, (hipStream_t)stream, x, rows, H, W, C, y);
-    else hipLaunchKernelGGL((depth_to_space_kernel<false>), g, b, 0, (hipStream_t)stream, x, rows, H, W, C, y);
-    return check_launch("depth_to_space_kernel");
-}
-
-int cslgan_fold_channels4_f32(const float* in, int64_t rows, int C, int unfold, float* out, void* stream) {
-    CSLGAN_REQUIRE(in && out, "fold_channels4: null argument");
-    CSLGAN_REQUIRE(rows > 0 && C > 0 && C % 4 == 0, "fold_channels4: needs C %% 4 == 0 (C=%d)", C);
-    const dim3 g(grid_for((long long)rows * (C / 4))), b(256);
-    if (unfold) hipLaunchKernelGGL((fold_channels4_kernel<true>), g, b, 0, (hipStream_t)stream, in, (long long)rows, C, out);
-    else hipLaunchKernelGGL((fold_channels4_kernel<false>), g, b, 0, (hipStream_t)stream, in, (long long)rows, C, out);
-    return check_launch("fold_channels4_kernel");
+    hipLaunchKernelGGL(bn_eval_stats_kernel, dim3((unsigned)((C + 127) / 128)), dim3(128), 0, st, running_mean, running_var, C, (float)rows, stats_ws);
+    if (int rc = check_launch("bn_eval_stats_kernel")) return rc;
+    return launch_norm_apply(NormCall<float, float>{x, gamma, beta, rows, rows, C, 1, C, eps, relu, stats_ws, y, H, d2s_W, x_shuffled, st}, norm_vec_ok(x, y, x_shuffled, C, 1));
 }
 
 int cslgan_norm_act_bwd_f32(const float* x, const float* dy, const float* y, const float* gamma, const float* stats,
@@ -901,8 +680,7 @@ int cslgan_norm_act_bwd_f32(const float* x, const float* dy, const float* y, con
                             float* dgamma, float* dbeta, void* stream) {
     CSLGAN_REQUIRE(x && dy && gamma && stats && ws && dx && dgamma && dbeta, "norm_bwd: null argument");
     CSLGAN_REQUIRE(!relu || y, "norm_bwd: relu backward needs the forward output");
-    CSLGAN_REQUIRE(rows > 0 && rows_per_stat > 0 && rows % rows_per_stat == 0 && C > 0 && groups > 0 && C % groups == 0 && C <= 4096,
-                   "norm_bwd: bad sizes");
+    CSLGAN_REQUIRE(rows > 0 && rows_per_stat > 0 && rows % rows_per_stat == 0 && C > 0 && groups > 0 && C % groups == 0 && C <= 4096, "norm_bwd: bad sizes");
     hipStream_t st = (hipStream_t)stream;
     const long long nrg = rows / rows_per_stat;
     CSLGAN_REQUIRE(nrg <= 65535, "norm_bwd: too many row groups");
@@ -910,49 +688,23 @@ int cslgan_norm_act_bwd_f32(const float* x, const float* dy, const float* y, con
     float* ab = ws;                         // [nrg][C][2]
     float* gs = ws + nrg * C * 2;           // [nrg*groups][2]
     if (int rc = zero_floats(ab, (size_t)nrg * C * 2, st)) return rc;
-    const bool vec = (C % 4 == 0) && ((C / 4) <= 256) && (256 % (C / 4) == 0) && aligned16(x) && aligned16(dy) && (!relu || aligned16(y));
-    long long rpb = (rows / 1024 + NS_ROWS_MIN - 1) / NS_ROWS_MIN * NS_ROWS_MIN;
-    rpb = rpb < NS_ROWS_MIN ? NS_ROWS_MIN : (rpb > 4096 ? 4096 : rpb);
+    const bool vec = norm_vec_channels(C) && aligned16(x) && aligned16(dy) && (!relu || aligned16(y));
+    const long long rpb = norm_rows_per_block(rows);
     const dim3 grid((unsigned)((rows_per_stat + rpb - 1) / rpb), (unsigned)nrg), block(256);
-    if (vec) hipLaunchKernelGGL((norm_bwd_stats_kernel<true>), grid, block, sizeof(float) * 2 * C, st, x, dy, y, stats, (long long)rows_per_stat, C, cpg, groups, eps, relu, (int)rpb, ab);
-    else hipLaunchKernelGGL((norm_bwd_stats_kernel<false>), grid, block, sizeof(float) * 2 * C, st, x, dy, y, stats, (long long)rows_per_stat, C, cpg, groups, eps, relu, (int)rpb, ab);
-    int rc = check_launch("norm_bwd_stats_kernel");
-    if (rc) return rc;
+    hipLaunchKernelGGL(vec ? norm_bwd_stats_kernel<true> : norm_bwd_stats_kernel<false>, grid, block, sizeof(float) * 2 * C, st, x, dy, y, stats,
+                       (long long)rows_per_stat, C, cpg, groups, eps, relu, (int)rpb, ab);
+    if (int rc = check_launch("norm_bwd_stats_kernel")) return rc;
     const long long nfin = nrg * groups > C ? nrg * groups : C;
     hipLaunchKernelGGL(norm_bwd_finalize_kernel, dim3((unsigned)((nfin + 127) / 128)), dim3(128), 0, st, ab, gamma, nrg, C, cpg, groups, gs, dgamma, dbeta);
-    rc = check_launch("norm_bwd_finalize_kernel");
-    if (rc) return rc;
+    if (int rc = check_launch("norm_bwd_finalize_kernel")) return rc;
     const long long total = rows * C;
-    hipLaunchKernelGGL(norm_bwd_apply_kernel, dim3(grid_for(total)), dim3(256), 0, st, x, dy, y, gamma, stats, gs, total,
-                       (long long)rows_per_stat, C, cpg, groups, eps, relu, dx);
+    hipLaunchKernelGGL(norm_bwd_apply_kernel, dim3(grid_for(total)), dim3(256), 0, st, x, dy, y, gamma, stats, gs, total, (long long)rows_per_stat, C, cpg, groups, eps, relu, dx);
     return check_launch("norm_bwd_apply_kernel");
 }
 
 int64_t cslgan_norm_bwd_ws_floats(int64_t rows, int64_t rows_per_stat, int C, int groups) {
     const int64_t nrg = rows_per_stat > 0 ? rows / rows_per_stat : 0;
     return nrg * C * 2 + nrg * groups * 2;
-}
-
-int cslgan_adam_step_f32(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps,
-                         float weight_decay, int step, void* stream) {
-    CSLGAN_REQUIRE(p && g && m && v, "adam: null argument");
-    CSLGAN_REQUIRE(n >= 0 && step >= 1, "adam: bad n/step");
-    if (n == 0) return CSLGAN_OK;
-    const double bc1 = 1.0 - pow((double)b1, (double)step);
-    const double bc2 = 1.0 - pow((double)b2, (double)step);
-    hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long long)n, lr, b1, b2,
-                       eps, weight_decay, (float)bc1, (float)sqrt(bc2));
-    return check_launch("adam_kernel");
-}
-
-int cslgan_adam_step_dev_f32(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps,
-                             float weight_decay, const int32_t* step_dev, void* stream) {
-    CSLGAN_REQUIRE(p && g && m && v && step_dev, "adam_dev: null argument");
-    CSLGAN_REQUIRE(n >= 0, "adam_dev: bad n");
-    if (n == 0) return CSLGAN_OK;
-    hipLaunchKernelGGL(adam_dev_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long long)n, lr, b1, b2,
-                       eps, weight_decay, step_dev);
-    return check_launch("adam_dev_kernel");
 }
 
 }  // extern "C"

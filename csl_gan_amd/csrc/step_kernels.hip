@@ -6,7 +6,7 @@
 //   train.py:310-329             update_grad_logging                                -> grad_log_stats
 //   gradient_penalty.py:36       interpolates = alpha * real + (1 - alpha) * fake   -> lerp_rows
 //   gradient_penalty.py:52-54    norms, (norms - 1)^2 [clamped], mean, * weight     -> lipschitz_term (+ backward)
-//   train.py:76,484              torch.optim.Adam.step over all parameter tensors   -> adam_multi
+//   train.py:76,484              torch.optim.Adam.step, all tensors / one tensor     -> adam_multi, adam_step
 #include "common.h"
 
 namespace cslgan {
@@ -257,14 +257,19 @@ __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, 
     p = p - lr_bc1 * (m / denom);
 }
 
-__global__ void adam_multi_kernel(AdamArgs a, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
-                                  const int* __restrict__ step_dev) {
+// lr / bc1 of a launch; step_dev (nullable): a device step counter replaces the bias corrections passed by value (graph replay)
+__device__ __forceinline__ float adam_lr_bc1(float lr, float b1, float b2, float bc1, float& bc2_sqrt, const int* __restrict__ step_dev) {
     if (step_dev) {
         const float st = (float)(*step_dev);
         bc1 = 1.f - powf(b1, st);
         bc2_sqrt = sqrtf(1.f - powf(b2, st));
     }
-    const float lr_bc1 = lr / bc1;
+    return lr / bc1;
+}
+
+__global__ void adam_multi_kernel(AdamArgs a, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
+                                  const int* __restrict__ step_dev) {
+    const float lr_bc1 = adam_lr_bc1(lr, b1, b2, bc1, bc2_sqrt, step_dev);
     int s = 0;
     while (s + 1 < a.n_seg && (int)blockIdx.x >= a.chunk_prefix[s + 1]) ++s;
     const long long base = (long long)((int)blockIdx.x - a.chunk_prefix[s]) * ADAM_CHUNK;
@@ -290,6 +295,15 @@ __global__ void adam_multi_kernel(AdamArgs a, float lr, float b1, float b2, floa
     } else {
         for (long long i = base + threadIdx.x; i < end; i += blockDim.x) adam_one(p[i], g[i], m[i], v[i], lr_bc1, b1, b2, eps, wd, bc2_sqrt);
     }
+}
+
+// One tensor per launch (the two single-tensor entries): a grid-stride walk.
+__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                            long long n, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
+                            const int* __restrict__ step_dev) {
+    const float lr_bc1 = adam_lr_bc1(lr, b1, b2, bc1, bc2_sqrt, step_dev);
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+        adam_one(p[i], g[i], m[i], v[i], lr_bc1, b1, b2, eps, wd, bc2_sqrt);
 }
 
 static int fill_seg_mean(SegMeanArgs& a, int n_seg, const int32_t* sizes, const float* scale) {
@@ -491,6 +505,27 @@ int cslgan_adam_multi_f32(int n_seg, float* const* p, const float* const* g, flo
     hipLaunchKernelGGL(adam_multi_kernel, dim3(tot), dim3(256), 0, (hipStream_t)stream, a, lr, b1, b2, eps, weight_decay, (float)bc1,
                        (float)sqrt(bc2), step_dev);
     return check_launch("adam_multi_kernel");
+}
+
+int cslgan_adam_step_f32(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps,
+                         float weight_decay, int step, void* stream) {
+    CSLGAN_REQUIRE(p && g && m && v, "adam: null argument");
+    CSLGAN_REQUIRE(n >= 0 && step >= 1, "adam: bad n/step");
+    if (n == 0) return CSLGAN_OK;
+    const double bc1 = 1.0 - pow((double)b1, (double)step), bc2 = 1.0 - pow((double)b2, (double)step);
+    hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long long)n, lr, b1, b2,
+                       eps, weight_decay, (float)bc1, (float)sqrt(bc2), (const int*)nullptr);
+    return check_launch("adam_kernel");
+}
+
+int cslgan_adam_step_dev_f32(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps,
+                             float weight_decay, const int32_t* step_dev, void* stream) {
+    CSLGAN_REQUIRE(p && g && m && v && step_dev, "adam_dev: null argument");
+    CSLGAN_REQUIRE(n >= 0, "adam_dev: bad n");
+    if (n == 0) return CSLGAN_OK;
+    hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long long)n, lr, b1, b2,
+                       eps, weight_decay, 1.f, 1.f, step_dev);
+    return check_launch("adam_dev_kernel");
 }
 
 }  // extern "C"

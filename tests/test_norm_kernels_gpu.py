@@ -1,6 +1,6 @@
-"""Edge shapes of the normalisation and layout kernels of csrc/pointwise_kernels.hip (-m gpu): the GroupNorm / BatchNorm forward
-family, its backward, the consumers of the conv epilogue's partial statistics, and the depth-to-space / channel-fold movers, each
-against float64 host arithmetic written out here from the formula the kernel's comment states.  No expected value comes from
+"""Edge shapes of the normalisation kernels of csrc/norm_kernels.hip and the layout kernels of csrc/layout_kernels.hip (-m gpu): the
+GroupNorm / BatchNorm forward family, its backward, the consumers of the conv epilogue's partial statistics, and the depth-to-space /
+channel-fold movers, each against float64 host arithmetic written out here from the formula the kernel's comment states.  No expected value comes from
 csl_gan_amd itself.
 
 Kernel -> case (shape numbers are those of GN_SHAPES / BN_SHAPES below):
@@ -10,7 +10,9 @@ Kernel -> case (shape numbers are those of GN_SHAPES / BN_SHAPES below):
   norm_stats_kernel<false, false, float>  test_groupnorm_forward[3] (cpg 3, tail of 17 rows), [5] (C / 4 > 256), [6] (C 8192: 64 KB of LDS),
                                           test_batchnorm_forward[10] (256 % 3 != 0, 7 blocks), test_groupnorm_unaligned (x or y 4 bytes off)
   norm_stats_kernel<true, false, bf16>    test_groupnorm_bf16[1], [2] (no scratch on the bf16 entry: atomics with 2 and 65 blocks)
-  norm_stats_kernel<false, false, bf16>   not reached here: a bf16 tensor that is 8 bytes off a 16-byte boundary (tests/test_bf16s_gpu.py has C = 96)
+  norm_stats_kernel<false, false, bf16>   test_groupnorm_bf16_routes[(2, 8, 8, 12, 3), x bf16]
+  <float x, bf16 y> of both apply kernels test_groupnorm_bf16_routes[x float32] (no scratch on the bf16 entry: one statistics pass, mean = sum * (1 / n));
+                                          the scalar apply kernel with bf16 x: [(2, 8, 8, 12, 3), x bf16], plain and d2s
   norm_stats_finalize_kernel              every <*, false, *> case above; the float cases run it twice (first pass: the mean as the second pass's shift)
   norm_apply_kernel<false, false>         test_groupnorm_forward[3], [5], [6], test_batchnorm_forward[10], test_groupnorm_unaligned, test_batchnorm_eval[10]
   norm_apply_kernel<false, true>          test_norm_d2s[gn 3], [bn 10] (d2s_offset per element)
@@ -116,7 +118,7 @@ def _within(family, what, got, ref, f32, widen=1.0):
 # ---- the statistics' geometry and the two references ------------------------------------------------------------------------------
 def _view(x, kind, groups):
     """[N, H, W, C] as [row groups, rows per statistic, groups, channels per group]: statistic s = row group * groups + group
-    (pointwise_kernels.hip, "normalisation statistics over NHWC data").  BatchNorm: one row group, a group per channel."""
+    (norm_kernels.hip, "normalisation statistics over NHWC data").  BatchNorm: one row group, a group per channel."""
     N, H, W, Cc = x.shape
     return x.reshape(N, H * W, groups, Cc // groups) if kind == "gn" else x.reshape(1, N * H * W, Cc, 1)
 
@@ -151,7 +153,7 @@ def _apply32(x, gamma, beta, mean, var, kind, groups, relu):
 
 
 def _d2s_np(a):
-    """ps[n][2h+i][2w+j][c'] = x[n][h][w][4c'+2i+j] (the comment above d2s_offset in pointwise_kernels.hip)."""
+    """ps[n][2h+i][2w+j][c'] = x[n][h][w][4c'+2i+j] (the comment above d2s_offset in device_prims.h)."""
     N, H, W, Cc = a.shape
     out = np.empty((N, 2 * H, 2 * W, Cc // 4), dtype=a.dtype)
     for i in range(2):
@@ -367,6 +369,39 @@ def _rne_bf16(a):
     return r.view(np.float32).astype(np.float64)
 
 
+def _check_groupnorm_bf16(what, shape, groups, x_bf16, d2s):
+    """ops.groupnorm_act with a bf16 output on x stored as bf16 (x_bf16) or as float32, under test_groupnorm_bf16's rule; the raw
+    shuffled copy is x rounded to nearest-even bf16 (x itself where it is stored as bf16), bit for bit."""
+    ops = _ops()
+    _, x, gamma, beta = _inputs("gn", shape, groups, "a", "bf16")
+    xb = x.to(torch.bfloat16)
+    if x_bf16:
+        x = xb.float()
+    for relu in (False, True):
+        ref, two, _, _ = _forward_refs(x, gamma, beta, "gn", groups, relu)
+        two = two.numpy().astype(np.float64)
+        if d2s:
+            y, xs = ops.groupnorm_act(_dev(xb if x_bf16 else x), _dev(gamma), _dev(beta), groups, eps=EPS, relu=relu, d2s=True, want_raw=True,
+                                      out_dtype=torch.bfloat16)
+            ref, two = _d2s_np(ref), _d2s_np(two)
+            assert xs.dtype == torch.bfloat16
+            assert np.array_equal(xs.float().cpu().numpy().view(np.uint32), _d2s_np(_rne_bf16(x.numpy()).astype(np.float32)).view(np.uint32))
+        else:
+            y = ops.groupnorm_act(_dev(xb if x_bf16 else x), _dev(gamma), _dev(beta), groups, eps=EPS, relu=relu, out_dtype=torch.bfloat16)
+        assert y.dtype == torch.bfloat16
+        got = _np64(y)
+        e2 = float(np.abs(two - ref).max())
+        bound = 4.0 * e2 + 16.0 * HALF_ULP * max(1.0, float(np.abs(ref).max()))
+        exact = got == _rne_bf16(ref)
+        ok = exact | ((got >= _rne_bf16(ref - bound)) & (got <= _rne_bf16(ref + bound)))
+        used = 1.0 - float(exact.mean())
+        msg = "norm-fig | gn bf16 | %s d2s %d relu %d | %d of %d outside the allowance | two-pass e2 %.3e | bound %.3e | allowance used by %.4f%%" % (
+            what, d2s, relu, int((~ok).sum()), ok.size, e2, bound, 100 * used)
+        print(msg)
+        assert bool(ok.all()), "%s | first offender: ref %.9e, got %.9e" % (msg, ref[~ok][0], got[~ok][0])
+        assert used <= 0.01, msg
+
+
 @pytest.mark.parametrize("d2s", [False, True])
 @pytest.mark.parametrize("shape_no", [1, 2])
 def test_groupnorm_bf16(shape_no, d2s):
@@ -379,33 +414,19 @@ def test_groupnorm_bf16(shape_no, d2s):
     boundary"; for the few outputs with |y| < 2e-3 the bf16 grid is finer than the float32 bound, and a result inside the float32 bound
     can be several (tiny) bf16 steps from the reference's rounding (shape 1 has one output of 3.9e-6: a bf16 step of 3e-8 there, under
     the float32 ulp of the sum that produces it).  On an MI355X 0 - 0.03% of the elements used the allowance."""
-    ops = _ops()
-    shape, groups = GN_SHAPES[shape_no][:4], GN_SHAPES[shape_no][4]
-    _, x, gamma, beta = _inputs("gn", shape, groups, "a", "bf16")
-    xb = x.to(torch.bfloat16)
-    x = xb.float()
-    for relu in (False, True):
-        ref, two, _, _ = _forward_refs(x, gamma, beta, "gn", groups, relu)
-        two = two.numpy().astype(np.float64)
-        if d2s:
-            y, xs = ops.groupnorm_act(_dev(xb), _dev(gamma), _dev(beta), groups, eps=EPS, relu=relu, d2s=True, want_raw=True)
-            ref, two = _d2s_np(ref), _d2s_np(two)
-            assert xs.dtype == torch.bfloat16
-            assert np.array_equal(xs.float().cpu().numpy().view(np.uint32), _d2s_np(x.numpy()).view(np.uint32))
-        else:
-            y = ops.groupnorm_act(_dev(xb), _dev(gamma), _dev(beta), groups, eps=EPS, relu=relu)
-        assert y.dtype == torch.bfloat16
-        got = _np64(y)
-        e2 = float(np.abs(two - ref).max())
-        bound = 4.0 * e2 + 16.0 * HALF_ULP * max(1.0, float(np.abs(ref).max()))
-        exact = got == _rne_bf16(ref)
-        ok = exact | ((got >= _rne_bf16(ref - bound)) & (got <= _rne_bf16(ref + bound)))
-        used = 1.0 - float(exact.mean())
-        msg = "norm-fig | gn bf16 | gn %d d2s %d relu %d | %d of %d outside the allowance | two-pass e2 %.3e | bound %.3e | allowance used by %.4f%%" % (
-            shape_no, d2s, relu, int((~ok).sum()), ok.size, e2, bound, 100 * used)
-        print(msg)
-        assert bool(ok.all()), "%s | first offender: ref %.9e, got %.9e" % (msg, ref[~ok][0], got[~ok][0])
-        assert used <= 0.01, msg
+    _check_groupnorm_bf16("gn %d" % shape_no, GN_SHAPES[shape_no][:4], GN_SHAPES[shape_no][4], True, d2s)
+
+
+BF16_ROUTE_SHAPES = [(2, 8, 8, 8, 2), (2, 8, 8, 12, 3)]
+
+
+@pytest.mark.parametrize("d2s", [False, True])
+@pytest.mark.parametrize("x_bf16", [False, True])
+@pytest.mark.parametrize("case", BF16_ROUTE_SHAPES)
+def test_groupnorm_bf16_routes(case, x_bf16, d2s):
+    """The bf16 entry on the smallest shapes of its two routes, x stored as float32 and as bf16, under test_groupnorm_bf16's rule:
+    C = 8 takes the 16-byte kernels, C = 12 (256 % 3 != 0) the scalar ones."""
+    _check_groupnorm_bf16("%s x_bf16 %d" % (case, x_bf16), case[:4], case[4], x_bf16, d2s)
 
 
 # ---- 5. the consumers of the conv epilogue's partial statistics ----------------------------------------------------------------------
@@ -521,7 +542,7 @@ def _stats32(x, kind, groups):
 
 
 def _bwd64(x, dy, mask, gamma, stats, kind, groups):
-    """The backward's formulas (the comment above norm_bwd_stats_kernel in pointwise_kernels.hip) in float64 numpy, on the statistics
+    """The backward's formulas (the comment above norm_bwd_stats_kernel in norm_kernels.hip) in float64 numpy, on the statistics
     the kernel is handed."""
     v = _view(x.numpy().astype(np.float64), kind, groups)
     gp = _view(dy.numpy().astype(np.float64) * mask, kind, groups)

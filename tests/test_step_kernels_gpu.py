@@ -1,5 +1,5 @@
-"""Edge shapes of the D-step's small kernels (-m gpu): csrc/step_kernels.hip, the row helpers of csrc/clip_kernels.hip and the Adam /
-act_bwd kernels of csrc/pointwise_kernels.hip, each against float64 host arithmetic written out here from the reference line the
+"""Edge shapes of the D-step's small kernels (-m gpu): csrc/step_kernels.hip (the Adam kernels among them), the row helpers of
+csrc/clip_kernels.hip and the act_bwd kernel of csrc/cast_kernels.hip, each against float64 host arithmetic written out here from the reference line the
 kernel's comment cites.  The shapes are the smallest that reach a second loop trip, a second workgroup, the scalar (unaligned or
 len % 4 != 0) branches, the grid caps and rows of exactly zero.  No expected value comes from csl_gan_amd itself.
 
@@ -18,7 +18,7 @@ Kernel -> case:
   row_l2norm_bwd_kernel        test_row_l2norm (66565: five trips under the 64 cap; zero row)
   l2_clip_scale_kernel         test_l2_clip_rows (16388: second trip; 66565; zero row)
   adam_multi_kernel            test_adam_multi (20 tensors: two launches; 4095 / 4096 / 4097 / 8195; g or m 4 bytes off: scalar branch)
-  adam_kernel, adam_dev_kernel test_adam_device_counter (steps 1 .. 4 and 1000, by value and from a device int32)
+  adam_kernel                  test_adam_device_counter (steps 1 .. 4 and 1000, by value and from a device int32)
   act_bwd_kernel               test_act_bwd (g and y 4 bytes off: scalar branch; y == +-0.0)
 """
 import ctypes
