@@ -41,6 +41,7 @@ EXPORTS = [
     "cslgan_boost_stump_ws_bytes", "cslgan_boost_stump_u8",
     "cslgan_nn_padded_dim", "cslgan_nn_prepare_u8", "cslgan_nn_min_i8", "cslgan_nn_count_i8",
     "cslgan_nn_kth_workspace_bytes", "cslgan_nn_kth_i8", "cslgan_nn_count_radius_i8",
+    "cslgan_gram_d2_u8", "cslgan_svc_smo_f64",
 ]
 
 
@@ -179,6 +180,8 @@ def lib():
         "cslgan_nn_count_i8": [vp, vp, i64, vp, vp, i64, i32, vp, i32, vp, vp],
         "cslgan_nn_kth_i8": [vp, vp, i64, vp, vp, i64, i32, i64, i64, i32, vp, vp, i64, vp],
         "cslgan_nn_count_radius_i8": [vp, vp, i64, vp, vp, i64, i32, vp, vp, vp],
+        "cslgan_gram_d2_u8": [vp, vp, i64, i32, vp, i64, vp],
+        "cslgan_svc_smo_f64": [vp, i64, vp, i64, vp, vp, i32, C.c_double, C.c_double, i64, i64, vp, vp, vp, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

@@ -38,6 +38,9 @@ both paths, so a host fit and a device fit are the same trees.
 under fixed-point row weights 0 .. 2^28, so every sum of a round is an exact integer — `boost_stump_host_bytes` THE definition of the
 stump search, equalled in every integer and in the score's bits by cslgan_boost_stump_u8 (csrc/boost_kernels.hip) — and one round loop
 in torch for both paths; the stumps score test rows through the tree apply path.
+
+The linear support-vector classifier of downstream.py:67 lives in csl_gan_amd.svm (`OvrSvc`): it scores through
+`proba_host_bytes` / cslgan_ovr_logreg_proba_u8 here, Platt's sigmoid of a linear score being a logistic model.
 """
 from __future__ import annotations
 

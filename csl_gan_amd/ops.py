@@ -1918,6 +1918,50 @@ def nn_count_radius(q, qn, r, rn, radius, counts):
     return counts
 
 
+SVM_MAX_ROWS = 65536            # include/cslgan.h "linear SVC": the stored matrix of more rows is refused
+
+
+def gram_pitch(n):
+    """Row pitch of the matrix of gram_d2 in entries: n rounded up to 32, so that every row is whole 128-byte lines."""
+    return (int(n) + 31) // 32 * 32
+
+
+def gram_d2(xs, sq, out=None):
+    """d2 [n, gram_pitch(n)] as int32 holding the uint32 bits: the exact squared distance of every pair of the rows that nn_prepare turned
+    into xs [n, Dp] / sq [n] (include/cslgan.h "linear SVC").  The columns n .. pitch - 1 mean nothing.  n <= 65536.
+    csl_gan_amd.svm.gram_d2_host is the host model."""
+    n, _, Dp = _nn_operands("gram_d2", xs, sq, xs, sq, [])
+    if n > SVM_MAX_ROWS:
+        raise RuntimeError("gram_d2: %d rows; the stored matrix takes at most %d (16 GiB)" % (n, SVM_MAX_ROWS))
+    pitch = gram_pitch(n)
+    if out is None:
+        out = torch.empty((n, pitch), device=xs.device, dtype=torch.int32)
+    elif _chk_dev(out, "out", torch.int32, "gram_d2").shape != (n, pitch):
+        raise RuntimeError("gram_d2: out has the shape %s, expected %s" % (tuple(out.shape), (n, pitch)))
+    check(_lib.lib().cslgan_gram_d2_u8(_p(xs), _p(sq), n, Dp, _p(out), pitch, _stream()), "gram_d2")
+    return out
+
+
+def svc_smo(d2, s, y, active, C, tol, chunk, max_iter, alpha, grad, iters, done):
+    """At most `chunk` more SMO iterations on each of the P dual problems over the rows of d2 (gram_d2's matrix; s: int64 [n], the byte
+    rows' squared norms), in place on the state alpha / grad (float64 [P, n], started at 0 / -1), iters (int64 [P]) and done (int32 [P]),
+    both started at 0; y: int8 [P, n] of +1 / -1, active: uint8 [P, n].  The caller repeats the call until every problem is done or has
+    run max_iter iterations.  Equal to csl_gan_amd.svm.smo_host bit for bit."""
+    what = "svc_smo"
+    for t, name, dt in ((d2, "d2", torch.int32), (s, "s", torch.int64), (y, "y", torch.int8), (active, "active", torch.uint8),
+                        (alpha, "alpha", torch.float64), (grad, "grad", torch.float64), (iters, "iters", torch.int64), (done, "done", torch.int32)):
+        _chk_dev(t, name, dt, what)
+    if d2.dim() != 2 or y.dim() != 2:
+        raise RuntimeError("%s: need d2 [n, pitch] and y [P, n], got %s and %s" % (what, tuple(d2.shape), tuple(y.shape)))
+    n, pitch = d2.shape
+    P = y.shape[0]
+    shapes = [tuple(t.shape) for t in (s, y, active, alpha, grad, iters, done)]
+    if shapes != [(n,), (P, n), (P, n), (P, n), (P, n), (P,), (P,)] or pitch != gram_pitch(n):
+        raise RuntimeError("%s: d2 %s with s, y, active, alpha, grad, iters, done of the shapes %s" % (what, tuple(d2.shape), shapes))
+    check(_lib.lib().cslgan_svc_smo_f64(_p(d2), pitch, _p(s), n, _p(y), _p(active), P, float(C), float(tol), int(chunk), int(max_iter),
+                                         _p(alpha), _p(grad), _p(iters), _p(done), _stream()), what)
+
+
 def row_l2norm(t2d):
     _chk(t2d, "t")
     n, L = t2d.shape

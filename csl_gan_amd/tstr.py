@@ -37,6 +37,9 @@ stumps, SAMME with --learning_rate, under fixed-point row weights, so every sum 
 every figure, are the same bits with -d cpu and on a device.  The figures carry "classifier", "fit" (class counts; rounds kept, the sum
 of the stump weights and the first round's error per class), "n_rounds" and "learning_rate"; P is 1 / (1 + exp(-2 F)) of the
 normalised vote F; --values_dir keeps P and U (the stump table, AdaBoost.coef).
+
+The panel's eighth classifier, the linear support-vector machine, has its own command over the same machinery: csl_gan_amd.tstr_svm
+(DESIGN.md §6p), which calls `run` below with its own Estimator.
 """
 import argparse
 import collections
@@ -111,13 +114,24 @@ ESTIMATORS = {
 }
 
 
-def build_parser():
-    ap = argparse.ArgumentParser(description="Train-on-synthetic, test-on-real classifier utility of labelled image caches")
-    cache_cli.add_common_arguments(ap, "tstr", "labelled uint8 image cache(s) of synthetic samples",
+def add_cache_arguments(ap, name):
+    """The arguments of every train-on-synthetic command line (this one and csl_gan_amd.tstr_svm): the common ones under the tool's `name`,
+    --test_cache, --train_cache and --baseline."""
+    cache_cli.add_common_arguments(ap, name, "labelled uint8 image cache(s) of synthetic samples",
                                    "keep the test probabilities and the coefficients as .npy here")
     ap.add_argument("--test_cache", type=str, required=True, help="labelled uint8 image cache of real test images")
     ap.add_argument("--train_cache", type=str, default=None, help="labelled uint8 image cache of the training set (for --baseline)")
     ap.add_argument("--baseline", default=False, action="store_true", help="also fit on the training set itself")
+
+
+def check_cache_arguments(a):
+    if a.baseline and not a.train_cache:
+        raise SystemExit("--baseline fits on the training set: give --train_cache")
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(description="Train-on-synthetic, test-on-real classifier utility of labelled image caches")
+    add_cache_arguments(ap, "tstr")
     ap.add_argument("--gtol_rel", type=float, default=None, help="a class has converged when max|gradient| <= gtol_rel * n")
     ap.add_argument("--max_iter", type=int, default=None, help="L-BFGS iterations per class (default: 2000 for lr, 200 for mlp)")
     ap.add_argument("--classifier", type=str, default="lr", choices=list(ESTIMATORS),
@@ -167,8 +181,7 @@ def fit_and_score(est, a, train_x, train_y, K, test_x, test_y, device):
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
-    if a.baseline and not a.train_cache:
-        raise SystemExit("--baseline fits on the training set: give --train_cache")
+    check_cache_arguments(a)
     inf = float("inf")
     for flag, ok, msg in (          # every flag is checked whichever classifier is chosen; only --seed is the trees' alone
             ("hidden", 1 <= a.hidden <= classify.MAX_HIDDEN, "--hidden %%d: the MLP takes 1 .. %d hidden units per class" % classify.MAX_HIDDEN),
@@ -185,7 +198,13 @@ def main(argv=None):
             ("learning_rate", 0 < a.learning_rate < inf, "--learning_rate %r: must be a finite number > 0")):
         if not ok:
             raise SystemExit(msg % getattr(a, flag))
-    est = ESTIMATORS[a.classifier]
+    return run(a, ESTIMATORS[a.classifier])
+
+
+def run(a, est, check_set=None):
+    """What a train-on-synthetic command line does once its arguments are parsed and checked: open and check the caches, fit the estimator
+    `est` (an Estimator) on every set, score the test cache, print, keep the values and report the figures.  check_set(labels, K, path):
+    the estimator's own refusals of a training set, raised before the first fit."""
     test = pipeline.CachedImages(a.test_cache)
     extra = [("baseline_train", a.train_cache, pipeline.CachedImages(a.train_cache))] if a.baseline else []
     sets = cache_cli.open_syn_caches(a.syn_cache, test, a.test_cache, [(p, c) for _, p, c in extra]) + extra
@@ -200,6 +219,8 @@ def main(argv=None):
         K = classes[lab] = n_classes_of(np.asarray(c.labels, dtype=np.int64).reshape(-1), p)
         if int(test_y.min()) < 0 or int(test_y.max()) >= K:
             raise SystemExit("%s: test labels span %d .. %d; %s has the classes 0 .. %d" % (a.test_cache, int(test_y.min()), int(test_y.max()), p, K - 1))
+        if check_set is not None:
+            check_set(np.asarray(c.labels, dtype=np.int64).reshape(-1), K, p)
 
     device = torch.device(a.device)
     test_x = torch.from_numpy(test_bytes).to(device)       # once, for all fits

@@ -828,6 +828,36 @@ int cslgan_nn_kth_i8(const void* q, const int32_t* qn, int64_t nq, const void* r
 int cslgan_nn_count_radius_i8(const void* q, const int32_t* qn, int64_t nq, const void* r, const int32_t* rn, int64_t nr, int Dp,
                               const uint32_t* radius, uint32_t* counts, void* stream);
 
+/* ---- linear SVC (svm_kernels.hip; csl_gan_amd.svm and csl_gan_amd.tstr_svm; backward-compatible additions, ABI stays 7).
+ * OneVsRestClassifier(SVC(kernel='linear', probability=True)) of downstream.py:67 on byte rows, x = byte / 255: the kernel matrix is
+ *     K_ij = <b_i, b_j> / 65025,   <b_i, b_j> = (s_i + s_j - d2_ij) / 2   an exact integer below 2^53,
+ * s the squared norms of the BYTE rows (int64; not the norms of the shifted rows that nn_prepare_u8 leaves) and d2 the squared distance.
+ *
+ * cslgan_gram_d2_u8 — the stored matrix.  xs / sqnorm: the prepared rows [n, Dp] and norms of cslgan_nn_prepare_u8, taken against
+ * themselves by the tile loop of the nearest-neighbour kernels (nn_tile.h).  out: uint32 [n, pitch], 128-byte aligned, pitch a multiple
+ * of 32 with n <= pitch <= 65536, so every row starts on 128 bytes and is written in whole 128-byte stores; out[i, j] = d2(i, j) for
+ * j < n, the columns n .. pitch - 1 are written with values that mean nothing.  1 <= n <= 65536 (a 16 GiB matrix): a larger set is
+ * refused with a message that says so.  EXACT.
+ *
+ * cslgan_svc_smo_f64 — LIBSVM's SMO on n_problems <= 96 dual problems over the same n rows, one workgroup per problem:
+ *     minimise 1/2 a'Qa - e'a,  0 <= a <= C,  y'a = 0 over the rows of active[p],  Q_ij = y_i y_j K_ij
+ * with y: int8 [P, n] of +1 / -1 and active: uint8 [P, n].  State per problem, kept in global memory between calls: alpha and grad
+ * (float64 [P, n]; the caller starts them at 0 and -1), iters (int64 [P], from 0) and done (int32 [P], from 0).  A call runs at most
+ * `chunk` iterations per problem and never past max_iter in total; it leaves done[p] = 1 where m(a) - M(a) < tol or no pair is left, and
+ * a problem that is done is not touched again.  The caller repeats the call until every problem is done or at max_iter.
+ *   One iteration: i = argmax of -y G over I_up; j = argmin of -b^2 / a over the rows of I_low with b = m + y G > 0, a = K_ii + K_jj -
+ * 2 K_ij (TAU = 1e-12 where a <= 0), second-order selection of Fan, Chen and Lin; LIBSVM's clipped two-variable update; G += (Q_i da_i)
+ * + (Q_j da_j) over ALL rows, the inactive ones included (so y_t (G_t + 1) is the held-out decision value of row t).  Both selections
+ * resolve ties to the lowest row index.  Every operation is a single IEEE float64 operation in the order of csl_gan_amd.svm.smo_host
+ * (no fused multiply-add, IEEE division): alpha, grad and iters equal the host's bit for bit, whatever `chunk` is.
+ * 2 <= n <= 65536; d2 / pitch as written by cslgan_gram_d2_u8; C and tol finite and > 0; chunk >= 1; max_iter >= 0.
+ * Both entries validate on the host before any launch (null pointers, n, Dp, pitch, the problem count, alignment), never allocate and
+ * never synchronise. */
+int cslgan_gram_d2_u8(const void* xs, const int32_t* sqnorm, int64_t n, int Dp, uint32_t* out /* [n, pitch] */, int64_t pitch, void* stream);
+int cslgan_svc_smo_f64(const uint32_t* d2 /* [n, pitch] */, int64_t pitch, const int64_t* s /* [n] */, int64_t n, const int8_t* y /* [P, n] */,
+                       const uint8_t* active /* [P, n] */, int n_problems, double C, double tol, int64_t chunk, int64_t max_iter,
+                       double* alpha /* [P, n] */, double* grad /* [P, n] */, int64_t* iters /* [P] */, int32_t* done /* [P] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
