@@ -42,6 +42,7 @@ EXPORTS = [
     "cslgan_nn_padded_dim", "cslgan_nn_prepare_u8", "cslgan_nn_min_i8", "cslgan_nn_count_i8",
     "cslgan_nn_kth_workspace_bytes", "cslgan_nn_kth_i8", "cslgan_nn_count_radius_i8",
     "cslgan_gram_d2_u8", "cslgan_svc_smo_f64",
+    "cslgan_swd_directions_i8", "cslgan_swd_project_i8", "cslgan_sort_rows_ws_bytes", "cslgan_sort_rows_i32", "cslgan_swd_w1_i64",
 ]
 
 
@@ -182,6 +183,10 @@ def lib():
         "cslgan_nn_count_radius_i8": [vp, vp, i64, vp, vp, i64, i32, vp, vp, vp],
         "cslgan_gram_d2_u8": [vp, vp, i64, i32, vp, i64, vp],
         "cslgan_svc_smo_f64": [vp, i64, vp, i64, vp, vp, i32, C.c_double, C.c_double, i64, i64, vp, vp, vp, vp, vp],
+        "cslgan_swd_directions_i8": [u64, i64, i32, i32, vp, vp],
+        "cslgan_swd_project_i8": [vp, i64, vp, i64, i32, vp, i64, i64, vp],
+        "cslgan_sort_rows_i32": [vp, i64, i64, i64, i32, vp, i64, vp],
+        "cslgan_swd_w1_i64": [vp, i64, i64, vp, i64, i64, i64, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -201,6 +206,8 @@ def lib():
     L.cslgan_boost_stump_ws_bytes.restype = C.c_int64
     L.cslgan_nn_kth_workspace_bytes.argtypes = [i64, i64, i32]
     L.cslgan_nn_kth_workspace_bytes.restype = C.c_int64
+    L.cslgan_sort_rows_ws_bytes.argtypes = [i64, i64]
+    L.cslgan_sort_rows_ws_bytes.restype = C.c_int64
     if L.cslgan_version() != ABI_VERSION:
         raise HipLibraryMissing("libcslgan_hip.so ABI version mismatch")
     _lib = L

@@ -1,6 +1,6 @@
 // The 128 x 128 int8 tile loop of the exact squared-distance kernels (nn_kernels.hip: search, counts, k-th keys; svm_kernels.hip: the
-// stored matrix) and the launch rule of its entries.  Operands are those of nn_prepare_u8_kernel (nn_kernels.hip): int8 rows of pitch
-// Dp, a multiple of NN_KT, with their squared norms.
+// stored matrix; swd_kernels.hip: the stored projection) and the launch rule of its entries.  Operands are those of
+// nn_prepare_u8_kernel (nn_kernels.hip): int8 rows of pitch Dp, a multiple of NN_KT, with their squared norms.
 #pragma once
 #include "common.h"
 #include "device_prims.h"
@@ -38,11 +38,13 @@ struct NNLane {                                                // where a lane s
 // kernel so that they are promoted to registers.  The loop ends behind a barrier, every call done.
 // A kernel that needs a value per COLUMN (nn_count_radius_i8_kernel: the column's radius) passes `per_col(bool live, long long col)`
 // as well, which runs once per column and tile ahead of that column's 32 epilogue calls.
+// RAW = true (swd_kernels.hip: the stored projection) hands the epilogue the accumulator itself, the dot product a.b as the bits of
+// an int32, in place of d2; qn and rn are then never read and may be null.  The default is the loop of the distance kernels.
 struct NNNoColumn {
     __device__ __forceinline__ void operator()(bool, long long) const {}
 };
 
-template <class PerColumn, class Epilogue>
+template <bool RAW = false, class PerColumn, class Epilogue>
 __device__ __forceinline__ void nn_tile_loop(const signed char* __restrict__ q, const int* __restrict__ qn, int nq, const signed char* __restrict__ r,
                                              const int* __restrict__ rn, int nr, int Dp, int tiles_per, int n_col_tiles, PerColumn per_col,
                                              Epilogue epi) {
@@ -59,7 +61,7 @@ __device__ __forceinline__ void nn_tile_loop(const signed char* __restrict__ q, 
     const int nk = Dp / NN_KT;
     const int n_iter = (tile_end - tile_first) * nk;
 
-    if (tid < NN_TM) qn_s[tid] = tid < rows_here ? qn[row0 + tid] : 0;
+    if (!RAW && tid < NN_TM) qn_s[tid] = tid < rows_here ? qn[row0 + tid] : 0;
 
     // range-checked descriptors over the rows that exist: a row past nq / nr reads as zeros (and is masked in the epilogue anyway)
     const __amdgpu_buffer_rsrc_t rq = make_rsrc(q + row0 * (long long)Dp, (unsigned)rows_here * (unsigned)Dp);
@@ -126,13 +128,16 @@ __device__ __forceinline__ void nn_tile_loop(const signed char* __restrict__ q, 
             for (int nt = 0; nt < 2; ++nt) {
                 const long long col = ln.col(ct, nt);
                 const bool live = col < nr;
-                const uint32_t bn = live ? (uint32_t)rn[col] : 0u;
+                const uint32_t bn = (!RAW && live) ? (uint32_t)rn[col] : 0u;
                 per_col(live, col);
 #pragma unroll
                 for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
                     for (int i = 0; i < 16; ++i) {
-                        epi(mt, i, live, col, (uint32_t)qn_s[ln.row(mt, i)] + bn - 2u * (uint32_t)acc[mt][nt][i]);
+                        if (RAW)
+                            epi(mt, i, live, col, (uint32_t)acc[mt][nt][i]);
+                        else
+                            epi(mt, i, live, col, (uint32_t)qn_s[ln.row(mt, i)] + bn - 2u * (uint32_t)acc[mt][nt][i]);
                         acc[mt][nt][i] = 0;
                     }
             }

@@ -1962,6 +1962,99 @@ def svc_smo(d2, s, y, active, C, tol, chunk, max_iter, alpha, grad, iters, done)
                                          _p(alpha), _p(grad), _p(iters), _p(done), _stream()), what)
 
 
+def swd_directions(P, D, seed, device, out=None):
+    """int8 [P, nn_padded_dim(D)] on `device`: the P Rademacher directions of the stream of `seed` (include/cslgan.h "Sliced Wasserstein
+    audit"), +1 / -1 in the columns < D and zero behind them — the shape of nn_prepare's operands.  csl_gan_amd.sliced.directions_host is
+    the host model."""
+    P, D, Dp = int(P), int(D), nn_padded_dim(D)
+    if P < 1 or Dp == 0:
+        raise RuntimeError("swd_directions: need at least one direction of 1 .. 65536 columns, got P = %d, D = %d" % (P, D))
+    if out is None:
+        out = torch.empty((P, Dp), device=device, dtype=torch.int8)
+    elif tuple(_chk_dev(out, "out", torch.int8, "swd_directions").shape) != (P, Dp):
+        raise RuntimeError("swd_directions: out has the shape %s, expected %s" % (tuple(out.shape), (P, Dp)))
+    with torch.cuda.device(out.device):
+        check(_lib.lib().cslgan_swd_directions_i8(int(seed) & 0xFFFFFFFFFFFFFFFF, P, D, Dp, _p(out), _stream()), "swd_directions")
+    return out
+
+
+def swd_project(dirs, xs, Y, col0=0):
+    """Y[p, col0 + i] = dirs[p] . xs[i], in place: dirs int8 [P, Dp] of swd_directions, xs int8 [n, Dp] of nn_prepare, Y int32
+    [P, ld] with ld >= col0 + n.  Nothing else of Y is written.  csl_gan_amd.sliced.project_host is the host model."""
+    what = "swd_project"
+    args = ((dirs, "dirs", torch.int8), (xs, "xs", torch.int8), (Y, "Y", torch.int32))
+    for t, name, dt in args:                            # the types first, wherever the tensor lives (as _nn_operands)
+        if t.dtype != dt:
+            raise RuntimeError("%s: %s must be a contiguous %s tensor" % (what, name, str(dt).replace("torch.", "")))
+    for t, name, dt in args:
+        _chk_dev(t, name, dt, what)
+    if dirs.dim() != 2 or xs.dim() != 2 or Y.dim() != 2 or dirs.shape[1] != xs.shape[1] or Y.shape[0] != dirs.shape[0]:
+        raise RuntimeError("%s: need dirs [P, Dp], xs [n, Dp] and Y [P, ld], got %s, %s and %s" % (what, tuple(dirs.shape), tuple(xs.shape), tuple(Y.shape)))
+    P, Dp = dirs.shape
+    n, ld, col0 = xs.shape[0], Y.shape[1], int(col0)
+    if col0 < 0 or ld < col0 + n:
+        raise RuntimeError("%s: Y has %d columns, col0 + n = %d + %d" % (what, ld, col0, n))
+    check(_lib.lib().cslgan_swd_project_i8(_p(dirs), P, _p(xs), n, Dp, _p(Y), ld, col0, _stream()), what)
+    return Y
+
+
+def sort_rows_ws_bytes(P, n):
+    """Workspace of sort_rows in bytes (0: sizes that the sort refuses)."""
+    return int(_lib.lib().cslgan_sort_rows_ws_bytes(int(P), int(n)))
+
+
+def sort_rows(x, n=None, key_bits=32, ws=None):
+    """The first n (default: all) entries of every row of x, int32 [P, ld] on the device, sorted ascending as signed values, in place;
+    the entries behind n stay.  key_bits < 32 promises values in [-2^(key_bits - 1), 2^(key_bits - 1)) and saves passes.  ws: a uint8
+    device tensor of at least sort_rows_ws_bytes(P, n) bytes, allocated when absent.  Equal to np.sort(axis=1)."""
+    what = "sort_rows"
+    if x.dtype != torch.int32:
+        raise RuntimeError("%s: x must be a contiguous int32 tensor" % what)
+    _chk_dev(x, "x", torch.int32, what)
+    if x.dim() != 2:
+        raise RuntimeError("%s: need x [P, ld], got %s" % (what, tuple(x.shape)))
+    P, ld = x.shape
+    n, key_bits = ld if n is None else int(n), int(key_bits)
+    if not 1 <= n <= ld or not 1 <= key_bits <= 32:
+        raise RuntimeError("%s: n = %d of %d columns, key_bits = %d; need 1 <= n <= ld and 1 <= key_bits <= 32" % (what, n, ld, key_bits))
+    need = sort_rows_ws_bytes(P, n)
+    if need <= 0:
+        raise RuntimeError("%s: %d rows of %d entries are out of range" % (what, P, n))
+    if ws is None:
+        ws = torch.empty(need, device=x.device, dtype=torch.uint8)
+    elif _chk_dev(ws, "ws", torch.uint8, what).numel() < need:
+        raise RuntimeError("%s: ws has %d bytes, need %d" % (what, ws.numel(), need))
+    check(_lib.lib().cslgan_sort_rows_i32(_p(x), P, n, ld, key_bits, _p(ws), ws.numel(), _stream()), what)
+    return x
+
+
+SWD_MAX_CELLS = 2 ** 38         # include/cslgan.h "Sliced Wasserstein audit": Na Nb 2^25 must stay below 2^63
+
+
+def swd_w1(a, na, b, nb, out=None):
+    """int64 [P]: the W1 numerators of the sorted rows a [P, lda] (their first na entries) and b [P, ldb] (first nb), int32 device tensors
+    (include/cslgan.h "Sliced Wasserstein audit").  csl_gan_amd.sliced.w1_numerators_host is the host model."""
+    what = "swd_w1"
+    for t, name in ((a, "a"), (b, "b")):
+        if t.dtype != torch.int32:
+            raise RuntimeError("%s: %s must be a contiguous int32 tensor" % (what, name))
+    for t, name in ((a, "a"), (b, "b")):
+        _chk_dev(t, name, torch.int32, what)
+    if a.dim() != 2 or b.dim() != 2 or a.shape[0] != b.shape[0]:
+        raise RuntimeError("%s: need a [P, lda] and b [P, ldb], got %s and %s" % (what, tuple(a.shape), tuple(b.shape)))
+    P, na, nb = a.shape[0], int(na), int(nb)
+    if not 1 <= na <= a.shape[1] or not 1 <= nb <= b.shape[1]:
+        raise RuntimeError("%s: na = %d of %d columns, nb = %d of %d" % (what, na, a.shape[1], nb, b.shape[1]))
+    if na * nb >= SWD_MAX_CELLS:
+        raise RuntimeError("%s: Na * Nb * 2^25 = %d * %d * 2^25 >= 2^63 overflows the int64 numerator" % (what, na, nb))
+    if out is None:
+        out = torch.empty(P, device=a.device, dtype=torch.int64)
+    elif tuple(_chk_dev(out, "out", torch.int64, what).shape) != (P,):
+        raise RuntimeError("%s: out has the shape %s, expected (%d,)" % (what, tuple(out.shape), P))
+    check(_lib.lib().cslgan_swd_w1_i64(_p(a), a.shape[1], na, _p(b), b.shape[1], nb, P, _p(out), _stream()), what)
+    return out
+
+
 def row_l2norm(t2d):
     _chk(t2d, "t")
     n, L = t2d.shape

@@ -858,6 +858,50 @@ int cslgan_svc_smo_f64(const uint32_t* d2 /* [n, pitch] */, int64_t pitch, const
                        const uint8_t* active /* [P, n] */, int n_problems, double C, double tol, int64_t chunk, int64_t max_iter,
                        double* alpha /* [P, n] */, double* grad /* [P, n] */, int64_t* iters /* [P] */, int32_t* done /* [P] */, void* stream);
 
+/* ---- Sliced Wasserstein audit (swd_kernels.hip; csl_gan_amd.sliced and csl_gan_amd.swd; backward-compatible additions,
+ * ABI stays 7).  Two sets A [Na, D] and B [Nb, D] of uint8 rows, D = H W C with 1 <= D <= 65536, and P directions s_p in {-1, +1}^D:
+ *     y_p(x)  = sum_j s_p[j] (x[j] - 128)                                      an integer, |y| <= 128 D <= 2^23
+ *     num_p   = sum_i sum_j |a[i] - b[j]| * |[i Nb, (i + 1) Nb) n [j Na, (j + 1) Na)|     a, b: the ascending sorted y_p of A and B
+ *     W1_p    = num_p / (Na Nb)                                                the exact 1-D Wasserstein-1 distance, quantile form
+ * and the sliced distance is the mean of W1_p over p divided by sqrt(D), the norm of EVERY direction.  Every num_p is an exact int64
+ * (Na Nb 2^25 < 2^63 is required) and does not depend on tiling, blocking or the device; csl_gan_amd.sliced holds the host models.
+ *
+ * The direction stream: one Philox4x32-10 call gives the 128 signs of the columns 128 b .. 128 b + 127 of direction p, counter
+ * (b, p, 0, 0x73776464 "swdd"), key = seed ^ 0x7377647369676E73 ("swdsigns": low word k0, high word k1).  Bit t of the 128 is bit
+ * t & 31 of output word t >> 5: set is +1, clear is -1.  A direction depends on (seed, p, column) only.
+ *
+ * cslgan_swd_directions_i8 — dirs: int8 [P, Dp], Dp = cslgan_nn_padded_dim(D), 16-byte aligned: +1 / -1 in the columns < D and ZERO in
+ * D .. Dp - 1, the shape of the prepared operands of cslgan_nn_prepare_u8.  1 <= P < 2^31. */
+int cslgan_swd_directions_i8(uint64_t seed, int64_t P, int D, int Dp, void* dirs, void* stream);
+
+/* cslgan_swd_project_i8 — Y[p, col0 + i] = dirs[p] . xs[i] as int32 for p < P, i < n.  dirs: int8 [P, Dp] as above; xs: a prepared block
+ * of cslgan_nn_prepare_u8 with n rows (its norms are not needed); Y: int32 [P, ldy] row-major, so the projections of one direction are
+ * contiguous; col0 lets a walk over blocks of a set fill one matrix.  The P x n x Dp product on v_mfma_i32_32x32x32_i8 through the tile
+ * loop of the nearest-neighbour kernels (nn_tile.h), directions as the row operand, with an epilogue that stores the accumulator: every
+ * element of Y[:, col0 .. col0 + n) has exactly one writer and nothing else of Y is touched.  1 <= P, n < 2^31, ldy >= col0 + n, Dp a
+ * multiple of 64 in 64 .. 65536, dirs / xs 16-byte and Y 4-byte aligned. */
+int cslgan_swd_project_i8(const void* dirs, int64_t P, const void* xs, int64_t n, int Dp, int32_t* Y /* [P, ldy] */, int64_t ldy, int64_t col0,
+                          void* stream);
+
+/* cslgan_sort_rows_i32 — the first n entries of every row of x: int32 [P, ld] are sorted ascending as SIGNED values, in place; the
+ * entries n .. ld - 1 are neither read nor written.  Keys only, so the result is unique.  An LSD radix sort segmented by row: the key is
+ * value + 2^(key_bits - 1) as uint32 — with key_bits = 32 the flipped sign bit; with fewer bits every value must lie in
+ * [-2^(key_bits - 1), 2^(key_bits - 1)), and ceil(key_bits / 8) passes run (the sliced distance needs 25).  A pass is three launches
+ * — histogram per (row, tile of 4096, digit) in LDS, exclusive scan per row, stable scatter — between x and a workspace of the same
+ * size; no kernel waits for another workgroup.  workspace: 16-byte aligned, at least cslgan_sort_rows_ws_bytes(P, n) bytes (0 for
+ * sizes that the sort refuses); nothing of it needs clearing.  1 <= P, n < 2^31, P ceil(n / 4096) < 2^31, ld >= n. */
+int64_t cslgan_sort_rows_ws_bytes(int64_t P, int64_t n);
+int cslgan_sort_rows_i32(int32_t* x /* [P, ld] */, int64_t P, int64_t n, int64_t ld, int key_bits, void* workspace, int64_t workspace_bytes,
+                         void* stream);
+
+/* cslgan_swd_w1_i64 — num[p] = num_p as above from the SORTED rows a: int32 [P, lda] (Na entries each) and b: int32 [P, ldb] (Nb entries).
+ * One workgroup per direction walks the longer row; products and sums in int64, reduced over the lanes and waves of the workgroup,
+ * one plain 8-byte store per direction, no atomics: exact and order-free.  Refused when Na Nb 2^25 >= 2^63 (values within +-2^24
+ * then cannot overflow the sum).  1 <= P, Na, Nb < 2^31, lda >= Na, ldb >= Nb, a / b 4-byte and num 8-byte aligned.
+ * All entries of this section validate on the host before any launch, never allocate and never synchronise. */
+int cslgan_swd_w1_i64(const int32_t* a, int64_t lda, int64_t Na, const int32_t* b, int64_t ldb, int64_t Nb, int64_t P, int64_t* num /* [P] */,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
