@@ -5,8 +5,16 @@
 // 1.8 GFLOP output conv, 5.9 TFLOP/s for the first layer's data gradient).  With N this small the op is a
 // stream over the input: every input value meets only NJ filter values.  One workgroup owns one 8x8 output
 // patch: it stages the patch's (8+range)^2 x 64-channel halo in LDS once, and 16 lanes share each output pixel
-// (4 channels per lane, one ds_read_b128 per tap) with that lane's T x NJ filter float4s held in registers; the
-// 16 partial sums meet in a 4-step butterfly.  Same KcParams classes / epilogue contract as igemm_kc.
+// (4 channels per lane, one ds_read_b128 per tap and pixel); the 16 partial sums meet in a 4-step butterfly.  Same
+// KcParams classes / epilogue contract as igemm_kc.
+//
+// The class's [NJ][T][64] filter slice is the same for every workgroup and every pixel slot: the workgroup fetches it
+// once (NJ float4 per thread, in flight with the halo loads) into LDS, and a lane reads the NJ float4s of a tap from
+// there when the tap's turn comes, for its four pixels at once.  Fetched per lane from global memory and held in
+// T x NJ float4 registers, the 27 filter loads were four fifths of the 64 -> 3 output conv's vector-memory instructions
+// (110 KB per workgroup against 25.6 KB of halo) and the 108 registers held the kernel to three workgroups per CU.
+// The kernel is bound by the instructions it issues, not by its traffic: what is left around the
+// 4 x NJ x T x 4 multiply-adds per lane is kept short - no division per halo slot, one epilogue per lane, DPP adds.
 #include "common.h"
 #include "device_prims.h"
 #include "igemm.h"
@@ -14,16 +22,67 @@
 
 namespace cslgan {
 
-constexpr int SK_MAXT = 9;             // taps per class held in registers
+constexpr int SK_MAXT = 9;             // taps per class
 constexpr int SK_C = 64;               // input channels (16 lanes x float4)
 constexpr int SK_HALO = 12 * 12;
+
+typedef float sk_float2 __attribute__((ext_vector_type(2)));
+
+// One class's filter slice on its way into LDS.  Thread (t = tid / 16, c4 = tid % 16) fetches the NJ float4s of tap t and
+// channels 4 c4 .. 4 c4 + 3 (zero past the class's taps) and stores them interleaved by OUTPUT channel, so that a packed
+// FMA finds the filter values of two outputs in one register pair.  In float4 units, SK_MAXT * 16 * NJ in all:
+//   pair plane q (outputs 2q, 2q + 1), at q * 288:  [(t * 2 + h) * 16 + c4] = (w[2q][c], w[2q+1][c], w[2q][c+1], w[2q+1][c+1]),
+//                                                   c = 4 c4 + 2 h
+//   single plane (output NJ - 1, NJ odd), behind:   [t * 16 + c4] = w[NJ-1][4 c4 .. 4 c4 + 3]
+template <int NJ>
+struct SkFilter {
+    static constexpr int NP = NJ / 2, PLANE2 = SK_MAXT * 2 * 16, SINGLE = NP * PLANE2;
+    float4 r[NJ];
+
+    __device__ __forceinline__ void fetch(const KcParams& p, const KcClass& kk, int tid) {
+        const __amdgpu_buffer_rsrc_t w_rsrc = make_rsrc(p.w + kk.w_off, p.w_bytes - 4u * (unsigned)kk.w_off);
+        const int t = tid >> 4;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+            r[j] = buf_load4(w_rsrc, (t < kk.T && j < p.Nn) ? 4u * (unsigned)(j * kk.Kdim + t * SK_C + (tid & 15) * 4) : BUF_OOB);
+    }
+    __device__ __forceinline__ void store(float4* Ws, int tid) const {
+        const int t = tid >> 4, c4 = tid & 15;
+        if (t < SK_MAXT) {
+#pragma unroll
+            for (int q = 0; q < NP; ++q) {
+                Ws[q * PLANE2 + (t * 2 + 0) * 16 + c4] = make_float4(r[2 * q].x, r[2 * q + 1].x, r[2 * q].y, r[2 * q + 1].y);
+                Ws[q * PLANE2 + (t * 2 + 1) * 16 + c4] = make_float4(r[2 * q].z, r[2 * q + 1].z, r[2 * q].w, r[2 * q + 1].w);
+            }
+            if (NJ & 1) Ws[SINGLE + t * 16 + c4] = r[NJ - 1];
+        }
+    }
+};
+
+// v + the values of lanes ^1 and ^2, then of the mirrored lane of the 8- and of the 16-lane group, each step one add with a DPP
+// operand.  After the first two steps the four lanes of a quad hold one value, so the mirrored lane's is the xor-4 / xor-8
+// partner's: the sum of a 16-lane group in the order of the xor butterfly, bit for bit, without an LDS permute.
+template <int CTRL>
+__device__ __forceinline__ float sk_dpp_add(float v) {
+    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
+}
+__device__ __forceinline__ float sk_sum16(float v) {
+    v = sk_dpp_add<0xB1>(v);       // quad_perm [1, 0, 3, 2]
+    v = sk_dpp_add<0x4E>(v);       // quad_perm [2, 3, 0, 1]
+    v = sk_dpp_add<0x141>(v);      // row_half_mirror
+    return sk_dpp_add<0x140>(v);   // row_mirror
+}
 
 // ALL: the classes of the launch (the four parity classes of a stride-2 data gradient) have the same grid and read the same
 // input patch: one workgroup stages the union halo once and runs the classes one after the other (a quarter of the halo traffic;
 // launch_skinny stores the union extents in every class).
 template <int NJ, bool ALL>
 __global__ __launch_bounds__(256) void igemm_skinny_kernel(const KcParams p) {
-    __shared__ float4 Hs[SK_HALO * 16];
+    // one class's filter slice, then the halo: launch_skinny sizes the block for the launch's largest halo, 256 B per pixel
+    // (the 64 -> 3 output conv: 6.9 KB + 10 x 10 pixels = 32.5 KB, five workgroups per CU)
+    extern __shared__ __attribute__((aligned(16))) float4 sk_lds[];
+    float4* const Ws = sk_lds;
+    float4* const Hs = sk_lds + NJ * SK_MAXT * 16;
 
     const int tid = threadIdx.x;
     const int b = xcd_remap(blockIdx.x, p.tiles_m);
@@ -39,6 +98,9 @@ __global__ __launch_bounds__(256) void igemm_skinny_kernel(const KcParams p) {
     const int img_base = rc0.img * p.AH * p.AW * SK_C;
 
     const __amdgpu_buffer_rsrc_t a_rsrc = make_rsrc(p.a, p.a_bytes);
+    // ---- the first class's filter slice, issued in front of the halo loads and stored behind them ----------
+    SkFilter<NJ> wf;
+    wf.fetch(p, kc, tid);
     // ---- halo: hpix pixels x 16 float4 ------------------------------------------------------------------
     const int cl = tid & 15;
     if (p.a_bf16) {
@@ -78,15 +140,18 @@ __global__ __launch_bounds__(256) void igemm_skinny_kernel(const KcParams p) {
             sc = *reinterpret_cast<const float4*>(p.in_scale + rc0.img * SK_C + cl * 4);
             sh = *reinterpret_cast<const float4*>(p.in_shift + rc0.img * SK_C + cl * 4);
         }
+        // slot j of a thread is halo pixel tid / 16 + 16 j, float4 cl of it: sixteen pixels on are one or two halo rows (HW_ >= 8)
+        int hy = (tid >> 4) / HW_, hx = (tid >> 4) - hy * HW_;
 #pragma unroll
         for (int j = 0; j < HREG; ++j) {
-            const int idx = tid + 256 * j;
-            const int c4 = idx & 15, pix = idx >> 4;
-            const int hy = pix / HW_, hx = pix - hy * HW_;
+            const int pix = (tid >> 4) + 16 * j;
             const int iy = y0 + hy, ix = x0 + hx;
             const bool ok = pix < hpix && (unsigned)iy < (unsigned)p.VH && (unsigned)ix < (unsigned)p.VW;
             okm |= (ok ? 1u : 0u) << j;
-            rh[j] = buf_load4(a_rsrc, ok ? 4u * (unsigned)(img_base + (iy * p.AW + ix) * SK_C + c4 * 4) : BUF_OOB);
+            rh[j] = buf_load4(a_rsrc, ok ? 4u * (unsigned)(img_base + (iy * p.AW + ix) * SK_C + cl * 4) : BUF_OOB);
+            hx += 16;
+            if (hx >= HW_) { hx -= HW_; ++hy; }
+            if (hx >= HW_) { hx -= HW_; ++hy; }
         }
 #pragma unroll
         for (int j = 0; j < HREG; ++j) {
@@ -102,66 +167,92 @@ __global__ __launch_bounds__(256) void igemm_skinny_kernel(const KcParams p) {
             if ((idx >> 4) < hpix) Hs[idx] = rh[j];
         }
     }
+    wf.store(Ws, tid);
     __syncthreads();
 
     const int wid = tid >> 6, pg = (tid & 63) >> 4;
+    const int jo = cl & 3;                                // the output channel this lane stores
     float bv = 0.f;
-    if (p.bias && cl < p.Nn) bv = p.bias[cl];
+    if (p.bias && jo < p.Nn) bv = p.bias[jo];
 #pragma unroll 1
     for (int cc = ALL ? 0 : ci; cc < (ALL ? p.n_cls : ci + 1); ++cc) {
     const KcClass& kk = p.cls[cc];
     const int Tc = kk.T;
-    const __amdgpu_buffer_rsrc_t w_rsrc = make_rsrc(p.w + kk.w_off, p.w_bytes - 4u * (unsigned)kk.w_off);
-    // ---- this lane's filter values: 4 channels x T taps x NJ outputs ------------------------------------
-    float4 wr[SK_MAXT][NJ];
-    int toff[SK_MAXT];
+    // the next class's slice travels under this class's arithmetic; it replaces this one once every lane is through its taps
+    const bool more = ALL && cc + 1 < p.n_cls;
+    if (more) wf.fetch(p, p.cls[cc + 1], tid);
+    // ---- taps outermost: the lane's filter values of a tap (its 4 channels, NJ outputs) come from the slice in LDS once and meet
+    // the lane's four pixels, so only the 4 x NJ sums live across the loop.  Every sum still adds its taps in order, channels
+    // x, y, z, w, one fused multiply-add each: outputs 2q and 2q + 1 of a pixel share a packed FMA (two independent lanes of it)
+    constexpr int NP = SkFilter<NJ>::NP;
+    int base[4], toff[SK_MAXT];
 #pragma unroll
-    for (int t = 0; t < SK_MAXT; ++t) {
-        toff[t] = t < Tc ? (((int)kk.ty[t] - kk.ty_min) * HW_ + ((int)kk.tx[t] - kk.tx_min)) * 16 : 0;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-            wr[t][j] = buf_load4(w_rsrc, (t < Tc && j < p.Nn) ? 4u * (unsigned)(j * kk.Kdim + t * SK_C + cl * 4) : BUF_OOB);
-    }
+    for (int t = 0; t < SK_MAXT; ++t) toff[t] = t < Tc ? (((int)kk.ty[t] - kk.ty_min) * HW_ + ((int)kk.tx[t] - kk.tx_min)) * 16 : 0;
+    sk_float2 acc2[4][NP > 0 ? NP : 1];
+    float acc1[4];
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
         const int q = wid * 16 + it * 4 + pg;            // pixel of the patch: 16 lanes each
-        const int qy = q >> 3, qx = q & 7;
-        const int base = (qy * HW_ + qx) * 16 + cl;
-        float acc[NJ];
+        base[it] = ((q >> 3) * HW_ + (q & 7)) * 16 + cl;
+        acc1[it] = 0.f;
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) acc[j] = 0.f;
+        for (int q2 = 0; q2 < NP; ++q2) acc2[it][q2] = sk_float2{0.f, 0.f};
+    }
 #pragma unroll
-        for (int t = 0; t < SK_MAXT; ++t) {
-            if (t < Tc) {                                 // uniform
-                const float4 a = Hs[base + toff[t]];
+    for (int t = 0; t < SK_MAXT; ++t) {
+        if (t < Tc) {                                     // uniform
+            float4 wp[NP > 0 ? NP : 1][2], ws = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-                for (int j = 0; j < NJ; ++j) {
-                    acc[j] = fmaf(a.x, wr[t][j].x, acc[j]);
-                    acc[j] = fmaf(a.y, wr[t][j].y, acc[j]);
-                    acc[j] = fmaf(a.z, wr[t][j].z, acc[j]);
-                    acc[j] = fmaf(a.w, wr[t][j].w, acc[j]);
+            for (int q2 = 0; q2 < NP; ++q2) {
+                wp[q2][0] = Ws[q2 * SkFilter<NJ>::PLANE2 + (t * 2 + 0) * 16 + cl];
+                wp[q2][1] = Ws[q2 * SkFilter<NJ>::PLANE2 + (t * 2 + 1) * 16 + cl];
+            }
+            if (NJ & 1) ws = Ws[SkFilter<NJ>::SINGLE + t * 16 + cl];
+#pragma unroll
+            for (int it = 0; it < 4; ++it) {
+                const float4 a = Hs[base[it] + toff[t]];
+#pragma unroll
+                for (int q2 = 0; q2 < NP; ++q2) {
+                    acc2[it][q2] = __builtin_elementwise_fma(sk_float2{a.x, a.x}, sk_float2{wp[q2][0].x, wp[q2][0].y}, acc2[it][q2]);
+                    acc2[it][q2] = __builtin_elementwise_fma(sk_float2{a.y, a.y}, sk_float2{wp[q2][0].z, wp[q2][0].w}, acc2[it][q2]);
+                    acc2[it][q2] = __builtin_elementwise_fma(sk_float2{a.z, a.z}, sk_float2{wp[q2][1].x, wp[q2][1].y}, acc2[it][q2]);
+                    acc2[it][q2] = __builtin_elementwise_fma(sk_float2{a.w, a.w}, sk_float2{wp[q2][1].z, wp[q2][1].w}, acc2[it][q2]);
+                }
+                if (NJ & 1) {
+                    // the odd output stays on scalar FMAs: left to itself the compiler pairs it across two PIXELS, whose halo
+                    // values sit in different registers, and pays two moves per packed FMA (the empty asm keeps the sums apart)
+                    acc1[it] = fmaf(a.x, ws.x, acc1[it]); asm("" : "+v"(acc1[it]));
+                    acc1[it] = fmaf(a.y, ws.y, acc1[it]); asm("" : "+v"(acc1[it]));
+                    acc1[it] = fmaf(a.z, ws.z, acc1[it]); asm("" : "+v"(acc1[it]));
+                    acc1[it] = fmaf(a.w, ws.w, acc1[it]); asm("" : "+v"(acc1[it]));
                 }
             }
         }
+    }
+    // ---- the 16 lanes of a pixel add up; then lane cl of the 16 takes output cl % 4 of the lane's pixel cl / 4 through the epilogue
+    float val = 0.f;
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
-            acc[j] += __shfl_xor(acc[j], 1);
-            acc[j] += __shfl_xor(acc[j], 2);
-            acc[j] += __shfl_xor(acc[j], 4);
-            acc[j] += __shfl_xor(acc[j], 8);
+            const float sum = sk_sum16(j < 2 * NP ? ((j & 1) ? acc2[it][j >> 1].y : acc2[it][j >> 1].x) : acc1[it]);
+            val = cl == it * 4 + j ? sum : val;
         }
-        if (cl < p.Nn) {
-            float val = acc[0];
-#pragma unroll
-            for (int j = 1; j < NJ; ++j) val = cl == j ? acc[j] : val;
-            val += bv;
-            const RowCoord rc = {rc0.img, rc0.oy + qy, rc0.ox + qx};
-            const int off = kc_out_offset(p, kk, rc);
-            if (p.res) val += p.res[kc_res_offset(p, kk, rc) + cl];
-            val = apply_act(val, p.act);
-            if (p.mask) val = lrelu_mask(val, p.mask[off + cl]);
-            p.out[off + cl] = val;
-        }
+    }
+    if (jo < p.Nn) {
+        const int q = wid * 16 + (cl >> 2) * 4 + pg;
+        val += bv;
+        const RowCoord rc = {rc0.img, rc0.oy + (q >> 3), rc0.ox + (q & 7)};
+        const int off = kc_out_offset(p, kk, rc);
+        if (p.res) val += p.res[kc_res_offset(p, kk, rc) + jo];
+        val = apply_act(val, p.act);
+        if (p.mask) val = lrelu_mask(val, p.mask[off + jo]);
+        p.out[off + jo] = val;
+    }
+    if (more) {
+        __syncthreads();
+        wf.store(Ws, tid);
+        __syncthreads();
     }
     }
 }
@@ -214,10 +305,12 @@ int launch_skinny(KcParams& p, hipStream_t st) {
     p.tiles_n = 1;
     p.ksplit = 1;
     const dim3 grid((unsigned)tm), block(256);
+    int hmax = 0;                      // LDS block: the filter slice and the largest halo of the launch, 16 float4 per row / pixel
+    for (int c = 0; c < p.n_cls; ++c) hmax = p.cls[c].halo_h * p.cls[c].halo_w > hmax ? p.cls[c].halo_h * p.cls[c].halo_w : hmax;
     note_kernel("igemm_skinny_kernel<%d%s>", p.Nn < 4 ? p.Nn : 4, all ? ",all" : "");
-#define CSL_SKINNY(NJ_)                                                                              \
-    if (all) hipLaunchKernelGGL((igemm_skinny_kernel<NJ_, true>), grid, block, 0, st, p);            \
-    else hipLaunchKernelGGL((igemm_skinny_kernel<NJ_, false>), grid, block, 0, st, p);
+#define CSL_SKINNY(NJ_)                                                                                              \
+    if (all) hipLaunchKernelGGL((igemm_skinny_kernel<NJ_, true>), grid, block, 256u * (NJ_ * SK_MAXT + hmax), st, p);  \
+    else hipLaunchKernelGGL((igemm_skinny_kernel<NJ_, false>), grid, block, 256u * (NJ_ * SK_MAXT + hmax), st, p);
     switch (p.Nn) {
         case 1: CSL_SKINNY(1) break;
         case 2: CSL_SKINNY(2) break;
