@@ -43,6 +43,7 @@ EXPORTS = [
     "cslgan_nn_kth_workspace_bytes", "cslgan_nn_kth_i8", "cslgan_nn_count_radius_i8",
     "cslgan_gram_d2_u8", "cslgan_svc_smo_f64",
     "cslgan_swd_directions_i8", "cslgan_swd_project_i8", "cslgan_sort_rows_ws_bytes", "cslgan_sort_rows_i32", "cslgan_swd_w1_i64",
+    "cslgan_mom_transpose_u8", "cslgan_mom_colsum_i64", "cslgan_mom_gram_i64", "cslgan_mom_mirror_i64",
 ]
 
 
@@ -187,6 +188,10 @@ def lib():
         "cslgan_swd_project_i8": [vp, i64, vp, i64, i32, vp, i64, i64, vp],
         "cslgan_sort_rows_i32": [vp, i64, i64, i64, i32, vp, i64, vp],
         "cslgan_swd_w1_i64": [vp, i64, i64, vp, i64, i64, i64, vp, vp],
+        "cslgan_mom_transpose_u8": [vp, i64, i32, i64, vp, vp],
+        "cslgan_mom_colsum_i64": [vp, i32, i64, vp, vp],
+        "cslgan_mom_gram_i64": [vp, i32, i64, vp, i64, vp],
+        "cslgan_mom_mirror_i64": [vp, i32, i64, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

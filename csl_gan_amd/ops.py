@@ -2055,6 +2055,75 @@ def swd_w1(a, na, b, nb, out=None):
     return out
 
 
+MOM_MAX_ROWS = 65536            # include/cslgan.h "Byte moments": rows of one chunk, the reduction length of the Gram product
+
+
+def mom_padded_rows(n):
+    """Row pitch of the transposed image of mom_transpose: n rounded up to the K tile of the Gram product."""
+    return (int(n) + 63) // 64 * 64
+
+
+def _mom_operands(what, args):
+    """The check that the mom_* wrappers share, as swd_project: the types first, wherever a tensor lives, then device and contiguity."""
+    for t, name, dt in args:
+        if t.dtype != dt:
+            raise RuntimeError("%s: %s must be a contiguous %s tensor" % (what, name, str(dt).replace("torch.", "")))
+    for t, name, dt in args:
+        _chk_dev(t, name, dt, what)
+
+
+def mom_transpose(u8, out=None):
+    """int8 [D, mom_padded_rows(n)]: the transposed image of a uint8 device tensor [n, ...] of D bytes per row, out[j, i] = u8[i, j] - 128
+    and zero in the columns n .. (include/cslgan.h "Byte moments").  n <= 65536."""
+    what = "mom_transpose"
+    _mom_operands(what, [(u8, "u8", torch.uint8)])
+    n = u8.shape[0] if u8.dim() else 0
+    D = u8.numel() // max(n, 1)
+    if not 1 <= n <= MOM_MAX_ROWS or not 1 <= D <= 65536:
+        raise RuntimeError("%s: need 1 .. %d rows of 1 .. 65536 bytes, got %s" % (what, MOM_MAX_ROWS, tuple(u8.shape)))
+    np_ = mom_padded_rows(n)
+    if out is None:
+        out = torch.empty((D, np_), device=u8.device, dtype=torch.int8)
+    else:
+        _mom_operands(what, [(out, "out", torch.int8)])
+        if tuple(out.shape) != (D, np_):
+            raise RuntimeError("%s: out has the shape %s, expected %s" % (what, tuple(out.shape), (D, np_)))
+    check(_lib.lib().cslgan_mom_transpose_u8(_p(u8), n, D, np_, _p(out), _stream()), what)
+    return out
+
+
+def mom_colsum(xt, s1):
+    """s1[j] += sum_i xt[j, i], in place: xt int8 [D, np] of mom_transpose, s1 int64 [D] that the caller zeroed once."""
+    what = "mom_colsum"
+    _mom_operands(what, [(xt, "xt", torch.int8), (s1, "s1", torch.int64)])
+    if xt.dim() != 2 or tuple(s1.shape) != (xt.shape[0],):
+        raise RuntimeError("%s: need xt [D, np] and s1 [D], got %s and %s" % (what, tuple(xt.shape), tuple(s1.shape)))
+    check(_lib.lib().cslgan_mom_colsum_i64(_p(xt), xt.shape[0], xt.shape[1], _p(s1), _stream()), what)
+    return s1
+
+
+def mom_gram(xt, S2):
+    """S2[i, j] += xt[i] . xt[j] on the 128 x 128 tiles on and below the diagonal, in place: xt int8 [D, np] of mom_transpose, S2 int64
+    [D, ld] with ld >= D that the caller zeroed once.  The tiles strictly above the diagonal and the columns D .. are not touched:
+    mom_mirror fills the tiles once, after the last chunk.  csl_gan_amd.moments.byte_moments_host is the host model."""
+    what = "mom_gram"
+    _mom_operands(what, [(xt, "xt", torch.int8), (S2, "S2", torch.int64)])
+    if xt.dim() != 2 or S2.dim() != 2 or S2.shape[0] != xt.shape[0] or S2.shape[1] < xt.shape[0]:
+        raise RuntimeError("%s: need xt [D, np] and S2 [D, ld >= D], got %s and %s" % (what, tuple(xt.shape), tuple(S2.shape)))
+    check(_lib.lib().cslgan_mom_gram_i64(_p(xt), xt.shape[0], xt.shape[1], _p(S2), S2.shape[1], _stream()), what)
+    return S2
+
+
+def mom_mirror(S2):
+    """S2[i, j] = S2[j, i] on the 128 x 128 tiles strictly above the diagonal, in place: S2 int64 [D, ld >= D] of mom_gram."""
+    what = "mom_mirror"
+    _mom_operands(what, [(S2, "S2", torch.int64)])
+    if S2.dim() != 2 or S2.shape[1] < S2.shape[0]:
+        raise RuntimeError("%s: need S2 [D, ld >= D], got %s" % (what, tuple(S2.shape)))
+    check(_lib.lib().cslgan_mom_mirror_i64(_p(S2), S2.shape[0], S2.shape[1], _stream()), what)
+    return S2
+
+
 def row_l2norm(t2d):
     _chk(t2d, "t")
     n, L = t2d.shape

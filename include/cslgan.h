@@ -902,6 +902,40 @@ int cslgan_sort_rows_i32(int32_t* x /* [P, ld] */, int64_t P, int64_t n, int64_t
 int cslgan_swd_w1_i64(const int32_t* a, int64_t lda, int64_t Na, const int32_t* b, int64_t ldb, int64_t Nb, int64_t P, int64_t* num /* [P] */,
                       void* stream);
 
+/* ---- Byte moments (moment_kernels.hip; csl_gan_amd.moments and csl_gan_amd.frechet; backward-compatible additions, ABI
+ * stays 7).  A set of N uint8 rows of D = H W C bytes, 1 <= D <= 65536, and y = x - 128, the shift of cslgan_nn_prepare_u8:
+ *     s1[j]    = sum_n y[n][j]                     int64, |s1| <= N 2^7
+ *     s2[i][j] = sum_n y[n][i] y[n][j]             int64, |s2| <= N 2^14
+ *     M        = N s2 - s1 (x) s1                  an exact int64 on the host for N < 2^24 (N^2 2^14 < 2^62)
+ *     C        = M / (N (N - 1))                   the unbiased covariance, float64 on the host
+ * and the Frechet distance of two sets is |dmu|^2 + tr CA + tr CB - 2 tr (CA^1/2 CB CA^1/2)^1/2 from these integers, on the host in
+ * float64 whoever computed them.  s1 and s2 are exact and do not depend on tiling, blocking, chunking or the device;
+ * csl_gan_amd.moments.byte_moments_host is the host model.  A set is walked in chunks of at most 65536 rows: the Gram product sums over
+ * the rows of the chunk in an int32 accumulator, |acc| <= 65536 * 2^14 = 2^30 < 2^31, and adds it to the int64 matrix.
+ *
+ * cslgan_mom_transpose_u8 — the transposed operand image of a chunk.  x: uint8 [n, D], 1 <= n <= 65536, any D in range, no alignment
+ * asked of x.  xt: int8 [D, np], np = n rounded up to 64, 16-byte aligned: xt[j][i] = x[i][j] - 128 for i < n and ZERO in the columns
+ * n .. np - 1, which therefore add nothing to a sum.  Rows of xt are K-contiguous, the shape the tile loop of nn_tile.h wants.  No byte
+ * beyond x + n D is read and nothing outside [D, np] is written. */
+int cslgan_mom_transpose_u8(const void* x, int64_t n, int D, int64_t np, void* xt /* [D, np] */, void* stream);
+
+/* cslgan_mom_colsum_i64 — s1[j] += sum_i xt[j][i] for j < D.  s1: int64 [D], in/out, zeroed by the caller once.  ONE WRITER PER COLUMN:
+ * one wave sums a row of xt and its first lane adds the total by a plain 8-byte load / add / store; no atomics.  np a multiple of 64
+ * in 64 .. 65536, xt 16-byte and s1 8-byte aligned. */
+int cslgan_mom_colsum_i64(const void* xt, int D, int64_t np, int64_t* s1 /* [D] */, void* stream);
+
+/* cslgan_mom_gram_i64 — S2[i][j] += xt[i] . xt[j] for every element of the 128 x 128 tiles ON AND BELOW the diagonal (tile row
+ * i / 128 >= tile column j / 128; a diagonal tile is written whole).  S2: int64 [D, ld] row-major, ld >= D, in/out, zeroed by the caller
+ * once; successive calls add further chunks of rows.  The D x D x np product on v_mfma_i32_32x32x32_i8 through the tile loop of
+ * nn_tile.h with xt as BOTH operands; the epilogue adds the int32 accumulator by a plain 8-byte load / add / store: every element has one
+ * writer per launch and the launches of one stream are ordered.  THE TILES STRICTLY ABOVE THE DIAGONAL, and the columns D .. ld - 1,
+ * ARE NEITHER READ NOR WRITTEN; cslgan_mom_mirror_i64 fills them once at the end.
+ *
+ * cslgan_mom_mirror_i64 — S2[i][j] = S2[j][i] for every element of the tiles strictly above the diagonal; nothing else is written.
+ * All entries of this section validate on the host before any launch, never allocate and never synchronise. */
+int cslgan_mom_gram_i64(const void* xt, int D, int64_t np, int64_t* S2 /* [D, ld] */, int64_t ld, void* stream);
+int cslgan_mom_mirror_i64(int64_t* S2 /* [D, ld] */, int D, int64_t ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
