@@ -44,6 +44,7 @@ EXPORTS = [
     "cslgan_gram_d2_u8", "cslgan_svc_smo_f64",
     "cslgan_swd_directions_i8", "cslgan_swd_project_i8", "cslgan_sort_rows_ws_bytes", "cslgan_sort_rows_i32", "cslgan_swd_w1_i64",
     "cslgan_mom_transpose_u8", "cslgan_mom_colsum_i64", "cslgan_mom_gram_i64", "cslgan_mom_mirror_i64",
+    "cslgan_tri_hist_u32", "cslgan_mmd_kernel_u32", "cslgan_mmd_partition_sums_i64",
 ]
 
 
@@ -192,6 +193,9 @@ def lib():
         "cslgan_mom_colsum_i64": [vp, i32, i64, vp, vp],
         "cslgan_mom_gram_i64": [vp, i32, i64, vp, i64, vp],
         "cslgan_mom_mirror_i64": [vp, i32, i64, vp],
+        "cslgan_tri_hist_u32": [vp, i64, i64, C.c_uint32, i32, vp, vp],
+        "cslgan_mmd_kernel_u32": [vp, i64, i64, vp, vp, i32, vp],
+        "cslgan_mmd_partition_sums_i64": [vp, i64, i64, vp, i64, i64, vp, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

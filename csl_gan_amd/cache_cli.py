@@ -1,4 +1,4 @@
-"""What the command lines over image caches share (csl_gan_amd.nearest, sample_attack, prdc, swd, frechet, tstr): the arguments every one of them
+"""What the command lines over image caches share (csl_gan_amd.nearest, sample_attack, prdc, swd, frechet, mmd, tstr): the arguments every one of them
 takes, how the synthetic caches are opened, named and checked, and how values and figures are written.  A tool decides what it
 computes and under which names and dtypes it keeps it; how a set gets its name and where the results go is decided here.
 """

@@ -2124,6 +2124,73 @@ def mom_mirror(S2):
     return S2
 
 
+MMD_MAX_B = 7                   # include/cslgan.h "Kernel two-sample test": 7 * 2^28 < 2^31
+MMD_TABLE = 65536               # entries of one exp table
+
+
+def mmd_padded_cols(n):
+    """Row pitch of the partition matrix of mmd_partition_sums: n rounded up to the K stage of 64 columns."""
+    return (int(n) + 63) // 64 * 64
+
+
+def _mmd_matrix(what, d2, extra=()):
+    """The rows n of the stored matrix d2 int32 [n, gram_pitch(n)] of gram_d2, checked together with the entry's further tensors `extra`
+    as (tensor, name, dtype): types first, as _mom_operands."""
+    _mom_operands(what, [(d2, "d2", torch.int32)] + list(extra))
+    if d2.dim() != 2 or d2.shape[1] != gram_pitch(d2.shape[0]):
+        raise RuntimeError("%s: need the matrix of gram_d2, [n, gram_pitch(n)], got %s" % (what, tuple(d2.shape)))
+    return d2.shape[0]
+
+
+def tri_hist(d2, prefix=0, prefix_bits=0, hist=None):
+    """hist[v] += #{i < j < n : the top prefix_bits (0, 8, 16, 24) bits of d2[i, j] equal those of `prefix` and the next 8 bits are v},
+    in place: d2 the matrix of gram_d2 (int32 holding the uint32 bits), hist int64 [256] on the device, zeros when absent
+    (include/cslgan.h "Kernel two-sample test").  csl_gan_amd.kernel_test.tri_hist_host is the host model."""
+    what = "tri_hist"
+    n = _mmd_matrix(what, d2)
+    if hist is None:
+        hist = torch.zeros(256, device=d2.device, dtype=torch.int64)
+    else:
+        _mom_operands(what, [(hist, "hist", torch.int64)])
+        if tuple(hist.shape) != (256,):
+            raise RuntimeError("%s: hist has the shape %s, expected (256,)" % (what, tuple(hist.shape)))
+    check(_lib.lib().cslgan_tri_hist_u32(_p(d2), d2.shape[1], n, int(prefix) & 0xFFFFFFFF, int(prefix_bits), _p(hist), _stream()), what)
+    return hist
+
+
+def mmd_kernel(d2, hi, lo):
+    """d2 rewritten in place as Kq = sum_b rint(2^28 hi[b, d2 >> 16] lo[b, d2 & 65535]), zero on the diagonal: d2 the matrix of gram_d2,
+    hi / lo float64 [B, 65536] on the device, B <= 7.  csl_gan_amd.kernel_test.kernel_matrix_host is the host model, equalled bit for bit."""
+    what = "mmd_kernel"
+    n = _mmd_matrix(what, d2, [(hi, "hi", torch.float64), (lo, "lo", torch.float64)])
+    if hi.dim() != 2 or hi.shape[1] != MMD_TABLE or tuple(lo.shape) != tuple(hi.shape):
+        raise RuntimeError("%s: need hi and lo [B, %d], got %s and %s" % (what, MMD_TABLE, tuple(hi.shape), tuple(lo.shape)))
+    check(_lib.lib().cslgan_mmd_kernel_u32(_p(d2), d2.shape[1], n, _p(hi), _p(lo), hi.shape[0], _stream()), what)
+    return d2
+
+
+def mmd_partition_sums(kq, member, sxx2=None, sxy=None):
+    """(sxx2, sxy) int64 [P], added to in place (zeros when absent): with r[i, p] = sum_j kq[i, j] member[p, j], sxx2[p] += the sum of
+    r[i, p] over the rows i that member[p, i] marks and sxy[p] += the sum over the others.  kq: int32 [n, gram_pitch(n)] holding uint32
+    entries below 2^31; member: int8 [P, mmd_padded_cols(n)].  csl_gan_amd.kernel_test.partition_sums_host is the host model."""
+    what = "mmd_partition_sums"
+    n = _mmd_matrix(what, kq, [(member, "member", torch.int8)])
+    if member.dim() != 2 or member.shape[0] < 1 or member.shape[1] < n:
+        raise RuntimeError("%s: need member [P, ldm >= n = %d], got %s" % (what, n, tuple(member.shape)))
+    P = member.shape[0]
+    outs = []
+    for t, name in ((sxx2, "sxx2"), (sxy, "sxy")):
+        if t is None:
+            t = torch.zeros(P, device=kq.device, dtype=torch.int64)
+        else:
+            _mom_operands(what, [(t, name, torch.int64)])
+            if tuple(t.shape) != (P,):
+                raise RuntimeError("%s: %s has the shape %s, expected (%d,)" % (what, name, tuple(t.shape), P))
+        outs.append(t)
+    check(_lib.lib().cslgan_mmd_partition_sums_i64(_p(kq), kq.shape[1], n, _p(member), member.shape[1], P, _p(outs[0]), _p(outs[1]), _stream()), what)
+    return outs[0], outs[1]
+
+
 def row_l2norm(t2d):
     _chk(t2d, "t")
     n, L = t2d.shape

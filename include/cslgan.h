@@ -936,6 +936,38 @@ int cslgan_mom_colsum_i64(const void* xt, int D, int64_t np, int64_t* s1 /* [D] 
 int cslgan_mom_gram_i64(const void* xt, int D, int64_t np, int64_t* S2 /* [D, ld] */, int64_t ld, void* stream);
 int cslgan_mom_mirror_i64(int64_t* S2 /* [D, ld] */, int D, int64_t ld, void* stream);
 
+/* ---- Kernel two-sample test (mmd_kernels.hip; csl_gan_amd.kernel_test and csl_gan_amd.mmd; backward-compatible
+ * additions, ABI stays 7).  Z: n synthetic rows followed by m real rows, N = n + m <= 65536, and d2 the stored matrix of
+ * cslgan_gram_d2_u8 over Z.  med: the lower median of the entries above the diagonal, an integer; bandwidth b has den_b = 2 med c_b.  The
+ * host builds two float64 tables per bandwidth, hi_b[h] = exp(-65536 h / den_b) and lo_b[l] = exp(-l / den_b), 65536 entries each, and
+ *     Kq[i][j] = sum_b rint(2^28 (hi_b[d2 >> 16] lo_b[d2 & 65535]))   for i != j,     Kq[i][i] = 0:
+ * one IEEE float64 product, one exact scaling, round-half-even, then integers: no transcendental and no fused operation on either path,
+ * so Kq is the same bit for bit on the host and the device; Kq < 2^31 for B <= 7.  For a partition p, member[p][j] != 0 marking its
+ * first side,
+ *     r[i][p] = sum_j Kq[i][j] member[p][j],   sxx2[p] = sum_{i in p} r[i][p],   sxy[p] = sum_{i not in p} r[i][p]
+ * are exact int64 (N (N - 1) 2^31 < 2^63), and the unbiased MMD^2 of every relabelling follows from them and the total of Kq on the host
+ * in Python integers.  csl_gan_amd.kernel_test holds the host model of every entry.  All three validate on the host before any launch,
+ * never allocate and never synchronise; d2 / kq: 128-byte aligned, pitch a multiple of 32 in n .. 65536, 1 <= n <= 65536.
+ *
+ * cslgan_tri_hist_u32 — hist[v] += the number of entries d2[i][j], i < j < n, whose top prefix_bits (0, 8, 16 or 24) bits equal those
+ * of `prefix` and whose next 8 bits are v.  hist: int64 [256], in/out, zeroed by the caller.  Four calls are an exact radix select of
+ * any rank.  Nothing on or below the diagonal and nothing in the columns n .. pitch - 1 is counted. */
+int cslgan_tri_hist_u32(const uint32_t* d2, int64_t pitch, int64_t n, uint32_t prefix, int prefix_bits, int64_t* hist /* [256] */, void* stream);
+
+/* cslgan_mmd_kernel_u32 — rewrites d2 in place as Kq: both triangles, zero on the diagonal.  hi, lo: float64 [B, 65536], 1 <= B <= 7.
+ * The columns n .. pitch - 1 hold anything afterwards. */
+int cslgan_mmd_kernel_u32(uint32_t* d2, int64_t pitch, int64_t n, const double* hi, const double* lo, int B, void* stream);
+
+/* cslgan_mmd_partition_sums_i64 — sxx2[p] += sum_{i : member[p][i] != 0} r[i][p] and sxy[p] += sum_{i : member[p][i] == 0} r[i][p] over
+ * the rows i < n, for p < P.  kq: ANY uint32 matrix with entries below 2^31, not necessarily symmetric, its diagonal as stored.  member:
+ * int8 [P, ldm], 16-byte aligned, ldm a multiple of 64 in n .. 65536; the columns n .. of member and of kq are not used.  sxx2, sxy:
+ * int64 [P], in/out, zeroed by the caller; 1 <= P <= 2^20.  The n x P x n product runs on v_mfma_i32_32x32x32_i8: the four bytes of an
+ * entry, each minus 128, are four int8 limb planes (the A operand, cut while a stage is written to LDS) against member (the B operand,
+ * K-contiguous as stored), int32 accumulators per limb (|acc| <= 2^30), recombined to int64 once per 64-row tile with the correction
+ * 0x80808080 sum_j member[p][j]; the results leave by 64-bit integer atomic adds, exact and so independent of their order. */
+int cslgan_mmd_partition_sums_i64(const uint32_t* kq, int64_t pitch, int64_t n, const int8_t* member /* [P, ldm] */, int64_t ldm, int64_t P,
+                                  int64_t* sxx2 /* [P] */, int64_t* sxy /* [P] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
