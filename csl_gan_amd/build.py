@@ -7,7 +7,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcslgan_hip.so")
 SOURCES = ["clip_kernels.hip", "igemm_kc.hip", "igemm_halo.hip", "igemm_skinny.hip", "igemm_mc.hip", "igemm_wgh.hip", "igemm_bf16.hip", "igemm_x3.hip", "igemm_bf16s.hip", "igemm_mcs.hip", "conv_c3.hip", "linear_k1.hip", "conv1x1.hip", "gn_shortcut.hip", "gram_norm.hip", "norm_kernels.hip", "layout_kernels.hip", "cast_kernels.hip", "step_kernels.hip", "attack_kernels.hip", "logreg_kernels.hip", "mlp_kernels.hip", "nb_kernels.hip", "tree_kernels.hip", "boost_kernels.hip", "nn_kernels.hip", "svm_kernels.hip", "swd_kernels.hip", "moment_kernels.hip", "mmd_kernels.hip"]
-HEADERS = ["common.h", "igemm.h", "conv_classes.h", "device_prims.h", "gn_apply.h", "kc_frame.h", "ovr_rows.h", "byte_split.h", "nn_tile.h", os.path.join("..", "..", "include", "cslgan.h")]
+# every header of csrc/ and the public one: a header left out here means objects that silently do not rebuild
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "cslgan.h")]
 
 
 def _newer_than(target, deps):

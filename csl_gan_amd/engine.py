@@ -21,7 +21,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import accountant, ops
+from . import _lib, accountant, ops
 from .nn import HipConv2d, HipLinear, PerSampleSink
 
 CLIP_EPS = 1e-6
@@ -252,7 +252,7 @@ class _LayerCollector:
         # equal row blocks of a layer the LDS-resident kernel takes: ONE launch for all blocks (three launches of 640 workgroups fill
         # the chip's 512 slots 62 %, one of 1920 fills them 94 %); the blocks' outputs are collected and launched after the loop
         launch = None
-        if (not ghost and 1 < len(blocks) <= 4 and e._gs_dtype == torch.float32 and isinstance(self.layer, nn.Conv2d)
+        if (not ghost and 1 < len(blocks) <= _lib.MAX_WGRAD_BLOCKS and e._gs_dtype == torch.float32 and isinstance(self.layer, nn.Conv2d)
                 and len({blk.n for blk in blocks}) == 1 and ops.wgrad_blocks_eligible(gz.shape, x.shape, R, S, stride)):
             launch = []
         st = _Backward(gz, x, conv, has_bias, ghost, launch)

@@ -14,8 +14,9 @@ import torch
 from . import _lib
 from ._lib import ConvT, SegsT, check
 
-ACT_NONE, ACT_LRELU02, ACT_RELU, ACT_TANH = 0, 1, 2, 3
-COMPUTE_F32, COMPUTE_BF16, COMPUTE_BF16X3 = 0, 1, 2          # cslgan_conv_t.compute (include/cslgan.h)
+# the header's constants, as _lib read them
+ACT_NONE, ACT_LRELU02, ACT_RELU, ACT_TANH = _lib.ACT_NONE, _lib.ACT_LRELU02, _lib.ACT_RELU, _lib.ACT_TANH
+COMPUTE_F32, COMPUTE_BF16, COMPUTE_BF16X3 = _lib.COMPUTE_F32, _lib.COMPUTE_BF16, _lib.COMPUTE_BF16X3          # cslgan_conv_t.compute
 
 _compute = COMPUTE_F32
 _auto = False
@@ -2240,7 +2241,7 @@ def _d2s_out(x, d2s, want_raw, dtype=torch.float32):
 _norm_scratch = {}
 
 
-NORM_PARTIAL_BLOCKS = 64            # include/cslgan.h CSLGAN_NORM_PARTIAL_BLOCKS
+NORM_PARTIAL_BLOCKS = _lib.NORM_PARTIAL_BLOCKS
 
 
 def _scratch(dev, n_stats_floats):

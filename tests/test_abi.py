@@ -1,8 +1,11 @@
 """CPU-side checks of the C-ABI library: it builds for gfx950, loads, and exports every symbol that
-include/cslgan.h declares (no compute calls without a GPU)."""
+include/cslgan.h declares (no compute calls without a GPU); the binding csl_gan_amd._lib derives from that header has the types the
+hand-written tables had, refuses a type it does not know, and its three hand-written structs have the compiler's layout."""
 import ctypes
+import json
 import os
 import re
+import subprocess
 
 import pytest
 
@@ -24,6 +27,141 @@ def test_header_symbols_are_exported(built_lib):
     assert not missing, missing
     from csl_gan_amd import _lib
     assert set(_lib.EXPORTS) == declared
+
+
+with open(os.path.join(ROOT, "include", "cslgan.h")) as _f:
+    HEADER = _f.read()
+STRUCT_POINTERS = ("LP_SegsT", "LP_ConvT", "LP_AdaptiveClipT")
+
+
+def _type_name(t):
+    """A bound type's name, every pointer but the three descriptor pointers as c_void_p (a host array and a device pointer are the
+    same thing to the header)."""
+    name = "None" if t is None else t.__name__
+    return "c_void_p" if name.startswith("LP_") and name not in STRUCT_POINTERS else name
+
+
+def test_bound_signatures_equal_the_record(built_lib):
+    """tests/abi_signatures.json holds restype and argtypes of the 108 entries as the hand-written tables bound them, recorded from
+    the commit BEFORE the binding was derived from the header (pointer names normalised as in _type_name).  It is never re-recorded
+    from later code and later entries are not added to it: it holds the parser to real prototypes."""
+    from csl_gan_amd import _lib
+    with open(os.path.join(ROOT, "tests", "abi_signatures.json")) as f:
+        record = json.load(f)
+    assert len(record) == 108 and set(record) <= set(_lib.EXPORTS)
+    L = _lib.lib()
+    bound = {name: {"restype": _type_name(getattr(L, name).restype), "argtypes": [_type_name(t) for t in getattr(L, name).argtypes or []]}
+             for name in record}
+    assert bound == record
+
+
+@pytest.mark.parametrize("text, bad_type", [
+    ("int cslgan_x(short a, void* stream);", "short"),
+    ("long cslgan_x(int a);", "long"),
+    ("int cslgan_x(const unsigned n, void* stream);", "unsigned"),
+    ("int cslgan_x(cslgan_conv_t p);", "cslgan_conv_t"),
+])
+def test_unknown_type_is_refused(text, bad_type):
+    from csl_gan_amd import _lib
+    with pytest.raises(TypeError) as e:
+        _lib.parse_prototypes("int cslgan_ok(void);\n" + text)
+    assert "cslgan_x" in str(e.value) and "'%s'" % bad_type in str(e.value)
+
+
+def test_parser_takes_split_prototypes_and_arrays():
+    from csl_gan_amd import _lib
+    text = """
+    /* int cslgan_commented_out(int a); */
+    int64_t cslgan_a(const cslgan_conv_t* p,   /* the descriptor */
+                     const int32_t first[],    // host array
+                     float* const* gw, uint32_t u /* by value */, double d,
+                     const uint64_t seed, void* stream);
+    const char *cslgan_b( void );
+    int cslgan_c(const cslgan_segs_t* s, const cslgan_adaptive_clip_t *a, const cslgan_other_t* o, int32_t n, float f, int64_t m);
+    """
+    C = ctypes
+    assert _lib.parse_prototypes(text) == {
+        "cslgan_a": (C.c_int64, [C.POINTER(_lib.ConvT), C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_uint64, C.c_void_p]),
+        "cslgan_b": (C.c_char_p, []),
+        "cslgan_c": (C.c_int, [C.POINTER(_lib.SegsT), C.POINTER(_lib.AdaptiveClipT), C.c_void_p, C.c_int, C.c_float, C.c_int64]),
+    }
+    assert list(_lib.parse_prototypes(text)) == ["cslgan_a", "cslgan_b", "cslgan_c"]
+
+
+def test_missing_header_names_its_path(tmp_path):
+    """A copy of the module with no include/ beside its package fails at import, and says where it looked."""
+    import importlib.util
+    from csl_gan_amd import _lib
+    pkg = tmp_path / "pkg"
+    pkg.mkdir()
+    with open(_lib.__file__) as f:
+        (pkg / "_lib.py").write_text(f.read())
+    spec = importlib.util.spec_from_file_location("_lib_without_header", str(pkg / "_lib.py"))
+    with pytest.raises(FileNotFoundError) as e:
+        spec.loader.exec_module(importlib.util.module_from_spec(spec))
+    assert os.path.join(str(pkg), "..", "include", "cslgan.h") in str(e.value)
+
+
+def _header_int(name):
+    (value,) = re.findall(r"^#define %s (\d+)" % name, HEADER, flags=re.M) or re.findall(r"\b%s = (\d+)" % name, HEADER)
+    return int(value)
+
+
+def test_constants_come_from_the_header():
+    from csl_gan_amd import _lib, ops
+    assert _lib.ABI_VERSION == 7
+    for mod, names in ((_lib, ("ABI_VERSION", "MAX_SEGS", "MAX_CLIP_LAYERS", "MAX_CLIP_JOBS", "MAX_WGRAD_BLOCKS", "NORM_PARTIAL_BLOCKS")),
+                       (ops, ("ACT_NONE", "ACT_LRELU02", "ACT_RELU", "ACT_TANH", "COMPUTE_F32", "COMPUTE_BF16", "COMPUTE_BF16X3",
+                              "NORM_PARTIAL_BLOCKS"))):
+        for name in names:
+            assert getattr(mod, name) == _header_int("CSLGAN_" + name), name
+    # once as literals, so that this is not only one regex checking another
+    assert (_lib.MAX_SEGS, _lib.MAX_CLIP_LAYERS, _lib.MAX_CLIP_JOBS, _lib.MAX_WGRAD_BLOCKS, ops.NORM_PARTIAL_BLOCKS) == (16, 32, 16, 4, 64)
+    assert (ops.ACT_NONE, ops.ACT_LRELU02, ops.ACT_RELU, ops.ACT_TANH) == (0, 1, 2, 3)
+    assert (ops.COMPUTE_F32, ops.COMPUTE_BF16, ops.COMPUTE_BF16X3) == (0, 1, 2)
+
+
+def _struct_fields(c_name):
+    """Field names of a `typedef struct { ... } c_name;` of the header, in order."""
+    (body,) = re.findall(r"typedef struct \{([^}]*)\} %s;" % c_name, re.sub(r"/\*.*?\*/", " ", HEADER, flags=re.S))
+    names = []
+    for decl in body.split(";"):
+        names += [re.findall(r"\w+", d.split("[")[0])[-1] for d in decl.split(",") if d.strip()]
+    return names
+
+
+def test_struct_layouts_equal_the_compilers(tmp_path):
+    """sizeof, and offsetof / size of every field, of the three descriptors as the host compiler lays them out from cslgan.h,
+    against the hand-written ctypes classes (`inp` is C's `in`)."""
+    from csl_gan_amd import _lib
+    structs = {"cslgan_segs_t": _lib.SegsT, "cslgan_conv_t": _lib.ConvT, "cslgan_adaptive_clip_t": _lib.AdaptiveClipT}
+    lines = ["#include <stddef.h>", "#include <stdio.h>", '#include "cslgan.h"', "int main(void) {"]
+    for c_name in structs:
+        lines.append('printf("%s %%zu\\n", sizeof(%s));' % (c_name, c_name))
+        for field in _struct_fields(c_name):
+            lines.append('printf("%s.%s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s*)0)->%s));' % (c_name, field, c_name, field, c_name, field))
+    lines += ["return 0;", "}"]
+    (tmp_path / "layout.c").write_text("\n".join(lines) + "\n")
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    subprocess.run([hipcc, "-x", "c", "-I", os.path.join(ROOT, "include"), str(tmp_path / "layout.c"), "-o", str(tmp_path / "layout")],
+                   check=True, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    compiled = subprocess.run([str(tmp_path / "layout")], check=True, stdout=subprocess.PIPE).stdout.decode().splitlines()
+    bound = []
+    for c_name, cls in structs.items():
+        bound.append("%s %d" % (c_name, ctypes.sizeof(cls)))
+        for name, _ in cls._fields_:
+            f = getattr(cls, name)
+            bound.append("%s.%s %d %d" % (c_name, "in" if name == "inp" else name, f.offset, f.size))
+    assert bound == compiled
+    assert [ctypes.sizeof(c) for c in structs.values()] == [784, 96, 1104]
+
+
+def test_build_lists_every_source_and_header():
+    from csl_gan_amd import build
+    csrc = os.listdir(os.path.join(ROOT, "csl_gan_amd", "csrc"))
+    assert set(build.SOURCES) == {f for f in csrc if f.endswith(".hip")} and len(set(build.SOURCES)) == len(build.SOURCES)
+    assert {f for f in csrc if f.endswith(".h")} <= set(build.HEADERS)
+    assert all(os.path.exists(os.path.join(build.CSRC, h)) for h in build.HEADERS)
 
 
 def test_library_loads_and_reports_version(built_lib):
